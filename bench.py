@@ -515,6 +515,35 @@ def forced_group_overhead(args, argv, plain_ms):
 
 
 # ---------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write {name: tensor} as path/<name>.npy (float32; float64 stays float64) so that two builds run with the
+    same arguments can be compared output for output.  Past `budget` bytes in all, every array of more than 1024
+    elements keeps the same share of them, at positions drawn by a fixed seed (sorted, so the same for every run).  Returns
+    {name: [shape, elements written]}."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    whole = 1024                            # (arrays this small -- the loss -- are always written whole)
+    total = sum(a.nbytes for a in host.values())
+    keep = min(1.0, (budget - whole * 8 * len(host)) / float(max(total, 1)))
+    rs = np.random.RandomState(seed)
+    out = {}
+    for name, a in host.items():
+        flat = a.reshape(-1)
+        if keep < 1.0 and flat.size > whole:
+            n = max(whole, int(flat.size * keep))
+            flat = flat[np.sort(rs.choice(flat.size, n, replace=False))]
+            a = flat
+        np.save(os.path.join(path, name + ".npy"), a)
+        out[name] = [list(host[name].shape), int(flat.size)]
+    return out
+
+
 def dry_launch(args):
     """Launcher check without GPUs (tests/test_data_parallel.py): the ranks rendezvous over gloo,
     all-reduce a gradient arena and rank 0 prints the JSON line with n_gpus = world."""
@@ -960,6 +989,9 @@ def main():
     ap.add_argument("--no-kernel-records", action="store_true",
                     help="the train-step line only (no roofline / loss_path / cpu_baseline records)")
     ap.add_argument("--no-pmc", action="store_true", help="do not run the rocprofv3 PMC passes")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (the loss it returned, the "
+                         "gradients it applied, the weights it left) as DIR/<name>.npy; see dump_outputs")
     ap.add_argument("--probe-graph", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dry-launch", action="store_true", help=argparse.SUPPRESS)
     argv = sys.argv[1:]
@@ -1085,6 +1117,8 @@ def main():
     # gradient maxima every step, clamp once 1000 steps have been seen
     trainer = train.Trainer(net, arena, clip_num_mads=0)
     if args.chunk_len_range and not args.probe_graph:
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs writes the fixed-shape timed steps; not with --chunk-len-range")
         print(json.dumps(variable_length_bench(args, cfg, trainer, dev, rank, use_graph, args.chunk_len_range[0],
                                                args.chunk_len_range[1], args.steps, args.warmup)), flush=True)
         return
@@ -1146,17 +1180,19 @@ def main():
             return dict(indata=b.indata, seqs=b.seqs, seqlens=b.seqlens, ignore_empty=True)
     def timed_steps(k_warm, k_steps, first=0):
         """W untimed steps, then EXACTLY K steps bracketed by a barrier + synchronize on both sides; returns this
-        rank's seconds."""
+        rank's seconds.  What the last timed step returned is kept in `last_step["loss"]`."""
         for i in range(k_warm):
             stepper.step(next_batch(first + i))
         comm.barrier() if comm.active else (dist.barrier() if dist.is_initialized() else None)
         torch.cuda.synchronize()
         t_start = time.perf_counter()
         for i in range(k_steps):
-            stepper.step(next_batch(first + i))
+            last_step["loss"] = stepper.step(next_batch(first + i))
         comm.barrier() if comm.active else (dist.barrier() if dist.is_initialized() else None)
         torch.cuda.synchronize()
         return time.perf_counter() - t_start
+
+    last_step = {}
 
     def event_time_us(fn, reps, warm=5):
         for _ in range(warm):
@@ -1175,6 +1211,13 @@ def main():
 
     elapsed = timed_steps(args.warmup, args.steps)
     _lib.raise_if_nonfinite()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # (before anything else steps this network: the legs below run more steps on it)
+        dumped = dump_outputs(args.dump_outputs, dict(
+            loss=last_step["loss"].detach().reshape(1),
+            grads=arena.flat,
+            params=torch.cat([p.detach().reshape(-1) for p in net.parameters()])))
     rccl = None
     per_rank = None
     grouped = comm.active or dist.is_initialized()          # (a forced one-rank group counts: N = 1 overhead child)
@@ -1243,6 +1286,8 @@ def main():
                                parallelism="dp%d (reads sharded; %s)" % (
                                    world, "gradient all-reduce in %d slices from backward hooks" % args.overlap_buckets
                                    if args.overlap_buckets > 1 else "one flat RCCL gradient all-reduce after backward")))
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if rccl is not None:
             out["rccl"] = rccl
             out["per_rank_ms"] = per_rank

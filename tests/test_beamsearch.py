@@ -10,6 +10,7 @@ import pytest
 from oracle import beam
 from tests.conftest import load_golden
 from tests.golden import make_golden_beam as mk
+from tests.golden import make_golden_refc as refc
 
 
 def test_hash_chain_known_values():
@@ -69,26 +70,21 @@ def test_restatement_follows_the_reference_through_exact_ties():
 
 
 def test_restatement_matches_the_reference_library_on_random_cases():
-    if not beam.ref_available():
-        pytest.skip("oracle/_ref/libref_decodeutil.so not built (no /root/reference here)")
-    from taiyaki_amd import synth
-    rng = np.random.RandomState(4)
-    for k in range(10):
-        T = int(rng.randint(5, 160))
-        sc = (synth.scores(T, 1, 40, 900 + k)[:, 0, :] * np.float32(rng.uniform(0.3, 1.6))).astype(np.float32)
-        w, cut, g = int(rng.randint(1, 13)), float(rng.choice([0.0, 0.0, 0.01, 0.2])), bool(rng.randint(2))
-        rs, rsc, rbwd = beam.ref_beamsearch(sc, cut, w, g)
+    """Ten continuous and six tie-heavy cases (tests/golden/make_golden_refc.py): the restatement gives the
+    reference C's sequences, scores and backward matrices bit for bit -- as stored in refc_answers.npz, and
+    from the live library where oracle/_ref was built."""
+    gold = load_golden("refc_answers.npz")
+    for k, (sc, cut, w, g) in enumerate(refc.beam_random_cases()):
         ms, msc = beam.beamsearch(sc, cut, w, g)
-        assert np.array_equal(rs, ms), (T, w, cut, g)
-        assert np.float32(rsc) == np.float32(msc)
-        if g:
-            assert np.array_equal(beam.backward(sc)[0], rbwd)
-    for k in range(6):                                      # tie-heavy
-        w, cut, g = int(rng.choice([3, 5, 12])), float(rng.choice([0.0, 0.05])), bool(rng.randint(2))
-        sc = quantised_scores(int(rng.randint(20, 140)), 50 + k)
-        rs, rsc, _ = beam.ref_beamsearch(sc, cut, w, g)
-        ms, msc = beam.beamsearch(sc, cut, w, g)
-        assert np.array_equal(rs, ms) and np.float32(rsc) == np.float32(msc), (k, w, cut, g)
+        refs = [(gold["beam/%d/seq" % k], gold["beam/%d/score" % k], gold["beam/%d/bwd" % k] if g else None)]
+        if beam.ref_available():
+            rs, rsc, rbwd = beam.ref_beamsearch(sc, cut, w, g)
+            refs.append((rs, rsc, rbwd if g else None))
+        for rs, rsc, rbwd in refs:
+            assert np.array_equal(rs, ms), (k, len(sc), w, cut, g)
+            assert np.float32(rsc) == np.float32(msc), (k, w, cut, g)
+            if g and k < 10:
+                assert np.array_equal(beam.backward(sc)[0], rbwd)
 
 
 @pytest.mark.gpu
@@ -212,15 +208,16 @@ def check_reference_unit_test_properties(fwd_fn, bwd_fn):
 
 def test_lattice_restatement_against_reference_library_and_unit_test():
     check_reference_unit_test_properties(beam.forward, beam.backward)
-    if not beam.ref_available():
-        pytest.skip("oracle/_ref/libref_decodeutil.so not built (no /root/reference here)")
-    rng = np.random.RandomState(8)
-    for k in range(6):
-        sc = (rng.randn(int(rng.randint(1, 90)), 40) * 2).astype(np.float32)
-        init = None if k % 2 else (rng.randn(8) * 3).astype(np.float32)
+    gold = load_golden("refc_answers.npz")
+    for k, (sc, init) in enumerate(refc.lattice_cases()):
         for fwdp, fn in ((True, beam.forward), (False, beam.backward)):
-            mine, ref = fn(sc, init), beam.ref_lattice(sc, init, fwdp)
-            assert np.array_equal(mine[0], ref[0]) and np.float32(mine[1]) == np.float32(ref[1])
+            mine = fn(sc, init)
+            key = "lattice/%d/%s/" % (k, "fwd" if fwdp else "bwd")
+            refs = [(gold[key + "mat"], gold[key + "tot"])]
+            if beam.ref_available():
+                refs.append(beam.ref_lattice(sc, init, fwdp))
+            for ref in refs:
+                assert np.array_equal(mine[0], ref[0]) and np.float32(mine[1]) == np.float32(ref[1]), (k, fwdp)
 
 
 @pytest.mark.gpu

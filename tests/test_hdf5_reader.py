@@ -1,6 +1,6 @@
 """The built-in mapped-signal HDF5 reader (taiyaki_amd/hdf5_lite.py; h5py is not in this image)
-on data files the reference's own tests hold (test/data/mapped_signal_file/*.hdf5 and one raw
-fast5 of test/data/reads, copied as fixtures to tests/golden/mapped_signal/).
+on data files the reference's own tests hold (test/data/mapped_signal_file/*.hdf5, test/data/reads/*.fast5
+and test/data/multireads/*.fast5, copied as fixtures to tests/golden/mapped_signal/).
 
 The container is validated three ways: the documented structure and invariants of the format
 (docs/FILE_FORMATS.md:43-75); an INDEPENDENT file -- the raw fast5 MinKNOW wrote for the same read
@@ -244,25 +244,35 @@ def test_variable_length_string_elements_decode_through_the_global_heap():
     assert hdf5_lite.decode_vlen(FakeFile(), dt, raw) == ["read-one", "r2", ""]
 
 
-REFDATA = "/root/reference/test/data"
+# the reference's test/data containers, stored as fixtures beside the others: mapped_signal_file/*.hdf5
+# (mapped_reads_1.hdf5 gzipped), reads/*.fast5 and multireads/*.fast5
+REF_MAPPED = ["mapped_reads_0.hdf5", "mapped_reads_1.hdf5.gz", "mapped_remap_samref.hdf5"]
+REF_READS = ["0f776a08-1101-41d4-8097-89136494a46e.fast5", "1f1a0f33-e2ac-431a-8f48-c3c687a7a7dc.fast5",
+             "b7096acd-b528-474e-a863-51295d18d3de.fast5", "db6b45aa-5d21-45cf-a435-05fb8f12e839.fast5",
+             "de1508c4-755b-489e-9ffb-51af35c9a7e6.fast5"]
+REF_MULTIREAD = "FAK40126_2fd3b110ca0d020049836a61f0dfb2b9983808f9_0.fast5"
 
 
-@pytest.mark.skipif(not os.path.isdir(REFDATA), reason="the reference's test data is only in the build container")
-def test_every_hdf5_file_of_the_reference_test_data_parses():
+def test_every_hdf5_file_of_the_reference_test_data_parses(tmp_path):
     """All nine HDF5 containers under the reference's test/data (three mapped-signal files, five
     single-read fast5, one multi-read fast5): structure invariants, and the multi-read fast5 holds
     exactly the signals of the single-read files (two writers, two layouts of the same reads)."""
-    import glob
-    for path in sorted(glob.glob(os.path.join(REFDATA, "mapped_signal_file", "*.hdf5"))):
+    import gzip
+    for name in REF_MAPPED:
+        path = os.path.join(HERE, name)
+        if name.endswith(".gz"):
+            path = str(tmp_path / name[:-3])
+            with open(path, "wb") as fh:
+                fh.write(gzip.open(os.path.join(HERE, name)).read())
         info, reads = hdf5_lite.read_mapped_signal_file(path)
         assert info["version"] == 8 and len(reads) >= 2
         for r in reads:
             assert len(r["Ref_to_signal"]) == len(r["Reference"]) + 1 and np.all(np.diff(r["Ref_to_signal"]) >= 0)
             assert r["Ref_to_signal"][-1] <= len(r["Dacs"]) + 1
-    multi = hdf5_lite.File(glob.glob(os.path.join(REFDATA, "multireads", "*.fast5"))[0])
+    multi = hdf5_lite.File(os.path.join(HERE, REF_MULTIREAD))
     singles = {}
-    for path in glob.glob(os.path.join(REFDATA, "reads", "*.fast5")):
-        rg = hdf5_lite.File(path)["Raw/Reads"]
+    for fname in REF_READS:
+        rg = hdf5_lite.File(os.path.join(HERE, fname))["Raw/Reads"]
         (name,) = rg.keys()
         sig = rg[name]["Signal"].read()
         assert int(rg[name].attrs["duration"]) == len(sig)

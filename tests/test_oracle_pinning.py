@@ -13,6 +13,7 @@ import pytest
 
 from tests.conftest import load_golden
 from tests.golden import cases
+from tests.golden import make_golden_refc as refc
 
 
 def _check_grad(gold, prefix, grad, atol):
@@ -59,18 +60,40 @@ def test_c_harness_cat_mod(oracle_mod):
     np.testing.assert_allclose(-cost * lp.shape[0], ka["ccm/score"], rtol=2e-7)
 
 
-@pytest.mark.skipif(not os.path.exists(
-    os.path.join(os.path.dirname(__file__), "..", "oracle", "_ref", "crf_twostate_test")),
-    reason="oracle/_ref not built")
-def test_ref_harness_binaries_print_known_answers():
+def test_ref_harness_binaries_print_known_answers(oracle_mod):
+    """What the reference's harness binaries print (oracle/_ref where it was built, else their output as
+    tests/golden/make_golden_refc.py stored it), and the restatement reproduces the printed scores."""
     here = os.path.join(os.path.dirname(__file__), "..", "oracle", "_ref")
-    out = subprocess.run([os.path.join(here, "crf_twostate_test")],
-                         capture_output=True, text=True).stdout
-    assert "Forwards scores: -2.378088 -2.378088" in out
-    assert "Backwards scores: -2.378088 -2.378088" in out
-    out = subprocess.run([os.path.join(here, "cat_mod_test")],
-                         capture_output=True, text=True).stdout
-    assert "Forwards scores: -52.354622 -195.435257" in out
+    gold = load_golden("refc_answers.npz")
+    outs = {}
+    for name in ("crf_twostate_test", "cat_mod_test"):
+        stored = "\n".join(str(ln) for ln in gold["harness/" + name])
+        outs[name] = [stored]
+        if os.path.exists(os.path.join(here, name)):
+            out = subprocess.run([os.path.join(here, name)], capture_output=True, text=True).stdout
+            assert all(ln in out.splitlines() for ln in stored.splitlines()), name
+            outs[name].append(out)
+    for out in outs["crf_twostate_test"]:
+        assert "Forwards scores: -2.378088 -2.378088" in out
+        assert "Backwards scores: -2.378088 -2.378088" in out
+    for out in outs["cat_mod_test"]:
+        assert "Forwards scores: -52.354622 -195.435257" in out
+    # the printed forward scores, as the restatement computes them on the harnesses' inputs (tolerances of
+    # test_c_harness_crf_twostate / test_c_harness_cat_mod)
+    def printed(out):
+        line = [ln for ln in out.splitlines() if ln.startswith("Forwards scores:")][0]
+        return np.array([float(v) for v in line.split(":")[1].split()])
+    ka = load_golden("known_answers.npz")
+    lp = ka["ccrf/logprob"]
+    cost, _ = oracle_mod._seq_call(oracle_mod.lib(), "oracle_", lp, ka["ccrf/move"].astype(np.uintp),
+                                   ka["ccrf/stay"].astype(np.uintp), ka["ccrf/seqlen"])
+    for out in outs["crf_twostate_test"]:
+        np.testing.assert_allclose(-cost * lp.shape[0], printed(out), atol=2e-6)
+    lp = ka["ccm/logprob"]
+    cost, _ = oracle_mod._seq_call(oracle_mod.lib(), "oracle_", lp, ka["ccm/move"], ka["ccm/stay"], ka["ccm/seqlen"],
+                                   ka["ccm/modmoveidx"], ka["ccm/modmovefact"])
+    for out in outs["cat_mod_test"]:
+        np.testing.assert_allclose(-cost * lp.shape[0], printed(out), rtol=2e-7)
 
 
 def test_decodeutil_known_logpartition(oracle_mod):
@@ -190,26 +213,38 @@ def test_logz_viterbi_small_vs_reference_python(oracle_mod, name):
 # --------------------------------------------------------------------------
 # restatement == genuine reference C (oracle/_ref), same inputs
 # --------------------------------------------------------------------------
-@pytest.mark.parametrize("T,N,seed", [(60, 5, 3), (257, 9, 4)])
-def test_restatement_equals_reference_c(oracle_mod, T, N, seed):
+def _reference_answers(oracle_mod, key, live):
+    """The genuine reference C's (loss, grad): as stored in refc_answers.npz, and from the live library where
+    oracle/_ref was built (`live()`), which must still give what was stored."""
+    gold = load_golden("refc_answers.npz")
+    stored = (gold[key + "loss"], gold[key + "grad"])
     if not oracle_mod.ref_available():
-        pytest.skip("oracle/_ref not built")
-    from taiyaki_amd import synth
-    inp = synth.crf_case(T, N, seed)
-    a, ga = oracle_mod.crf_flipflop_loss(inp["scores"], inp["seqs"], inp["seqlens"], 1.3)
-    b, gb = oracle_mod.crf_flipflop_loss(inp["scores"], inp["seqs"], inp["seqlens"], 1.3,
-                                         use_ref=True)
-    np.testing.assert_allclose(a, b, rtol=1e-6)
-    np.testing.assert_allclose(ga, gb, atol=5e-6)
-    inp = synth.crf_case(T, N, seed, nmods_per_base=cases.NMODS)
+        return [stored]
+    b, gb = live()
+    np.testing.assert_array_equal(b, stored[0])
+    np.testing.assert_array_equal(gb, stored[1])
+    return [stored, (b, gb)]
+
+
+@pytest.mark.parametrize("T,N,seed", refc.RESTATEMENT_CASES)
+def test_restatement_equals_reference_c(oracle_mod, T, N, seed):
+    key = "restatement/%d_%d_%d/" % (T, N, seed)
+    sharp = refc.RESTATEMENT_SHARPEN
+    inp = refc.restatement_input(T, N, seed)
+    a, ga = oracle_mod.crf_flipflop_loss(inp["scores"], inp["seqs"], inp["seqlens"], sharp)
+    for b, gb in _reference_answers(oracle_mod, key + "crf_", lambda: oracle_mod.crf_flipflop_loss(
+            inp["scores"], inp["seqs"], inp["seqlens"], sharp, use_ref=True)):
+        np.testing.assert_allclose(a, b, rtol=1e-6)
+        np.testing.assert_allclose(ga, gb, atol=5e-6)
+    inp = refc.restatement_input(T, N, seed, cases.NMODS)
     a, ga = oracle_mod.cat_mod_flipflop_loss(
         inp["scores"], inp["seqs"], inp["seqlens"], inp["mod_cats"],
         inp["can_mods_offsets"], inp["mod_cat_weights"], 1.0)
-    b, gb = oracle_mod.cat_mod_flipflop_loss(
-        inp["scores"], inp["seqs"], inp["seqlens"], inp["mod_cats"],
-        inp["can_mods_offsets"], inp["mod_cat_weights"], 1.0, use_ref=True)
-    np.testing.assert_allclose(a, b, rtol=1e-6)
-    np.testing.assert_allclose(ga, gb, atol=2e-5)
+    for b, gb in _reference_answers(oracle_mod, key + "catmod_", lambda: oracle_mod.cat_mod_flipflop_loss(
+            inp["scores"], inp["seqs"], inp["seqlens"], inp["mod_cats"],
+            inp["can_mods_offsets"], inp["mod_cat_weights"], 1.0, use_ref=True)):
+        np.testing.assert_allclose(a, b, rtol=1e-6)
+        np.testing.assert_allclose(ga, gb, atol=2e-5)
 
 
 def test_float64_witness_agrees_with_the_fp32_restatement_and_the_reference(oracle_mod):
@@ -218,21 +253,22 @@ def test_float64_witness_agrees_with_the_fp32_restatement_and_the_reference(orac
     fp32 rounding of it -- plain and cat-mod, sharpened, an empty read --, and the distance grows
     with T as rounding noise does (which is why long-T parity is judged against the witness)."""
     from taiyaki_amd import synth
-    for T, seqlens, mods, sharp in ((7, [6, 2], None, 1.0), (50, [25, 40, 7, 12], None, 2.5),
-                                    (50, [30, 17, 0], None, 1.0), (60, [25, 40, 7], (1, 1, 0, 0), 1.0),
-                                    (60, [25, 40, 7], (1, 1, 0, 0), 2.5), (200, [90, 150, 30, 180], None, 1.0)):
-        inp = synth.crf_case(T, len(seqlens), 91 + T, seqlens=np.array(seqlens, dtype=np.int32), nmods_per_base=mods)
+    for i, (T, seqlens, mods, sharp) in enumerate(refc.WITNESS_CASES):
+        inp = refc.witness_input(T, seqlens, mods)
         margs = (inp["mod_cats"], inp["can_mods_offsets"], inp["mod_cat_weights"]) if mods else ()
         wl, wg = oracle_mod.crf_flipflop_loss_f64(inp["scores"], inp["seqs"], inp["seqlens"], sharp, *margs)
         assert wl.dtype == np.float64 and wg.dtype == np.float64
-        for use_ref in ([False, True] if oracle_mod.ref_available() else [False]):
+
+        def call(use_ref):
             if mods:
-                ol, og = oracle_mod.cat_mod_flipflop_loss(inp["scores"], inp["seqs"], inp["seqlens"], *margs, sharp,
-                                                          use_ref=use_ref)
-            else:
-                ol, og = oracle_mod.crf_flipflop_loss(inp["scores"], inp["seqs"], inp["seqlens"], sharp, use_ref=use_ref)
+                return oracle_mod.cat_mod_flipflop_loss(inp["scores"], inp["seqs"], inp["seqlens"], *margs, sharp,
+                                                        use_ref=use_ref)
+            return oracle_mod.crf_flipflop_loss(inp["scores"], inp["seqs"], inp["seqlens"], sharp, use_ref=use_ref)
+        results = [("restatement", call(False))]
+        results += [("reference", r) for r in _reference_answers(oracle_mod, "witness/%d/" % i, lambda: call(True))]
+        for who, (ol, og) in results:
             np.testing.assert_allclose(ol, wl, rtol=2e-6, atol=1e-7)
-            assert np.abs(og - wg).max() * T < (3e-4 if mods else 3e-5), (T, mods, sharp, use_ref)
+            assert np.abs(og - wg).max() * T < (3e-4 if mods else 3e-5), (T, mods, sharp, who)
     # the reference's own noise at a long T: larger than at T = 200, far below 1 % (a handful of reads)
     T = 2000
     inp = synth.crf_case(T, 3, 7, seqlens=np.array([900, 1500, 400], dtype=np.int32))
@@ -248,10 +284,7 @@ def test_empty_read_inside_a_batch_is_scored_apart(oracle_mod):
     genuine reference when it is built -- at least one later read differs from its value alone --, while the
     oracle's operator-level functions (what the HIP path is held to) give every read the value it has in a
     batch of its own, the empty read cost 0 and zero gradient rows.  Trailing empty reads take the plain route."""
-    from taiyaki_amd import synth
-    T = 40
-    seqlens = np.array([12, 0, 20, 9, 0], dtype=np.int32)
-    inp = synth.crf_case(T, len(seqlens), 5, seqlens=seqlens)
+    inp, seqlens = refc.empty_read_input()
     off = np.concatenate([[0], np.cumsum(seqlens)])
     solo = np.zeros(len(seqlens), dtype=np.float32)
     solo_g = np.zeros_like(inp["scores"])
@@ -259,18 +292,19 @@ def test_empty_read_inside_a_batch_is_scored_apart(oracle_mod):
         one, one_g = oracle_mod.crf_flipflop_loss(np.ascontiguousarray(inp["scores"][:, n:n + 1]), inp["seqs"][off[n]:off[n + 1]],
                                          seqlens[n:n + 1], 1.0)
         solo[n], solo_g[:, n] = one[0], one_g[:, 0]
-    for use_ref in ([False, True] if oracle_mod.ref_available() else [False]):
-        loss, grad = oracle_mod.crf_flipflop_loss(inp["scores"], inp["seqs"], seqlens, 1.0, use_ref=use_ref)
+    results = [oracle_mod.crf_flipflop_loss(inp["scores"], inp["seqs"], seqlens, 1.0)]
+    results += _reference_answers(oracle_mod, "empty/", lambda: oracle_mod.crf_flipflop_loss(
+        inp["scores"], inp["seqs"], seqlens, 1.0, use_ref=True))
+    for loss, grad in results:
         np.testing.assert_array_equal(loss, solo)
         np.testing.assert_allclose(grad, solo_g, rtol=1e-5, atol=1e-8)       # (vector-width remainders round differently)
     wl, _ = oracle_mod.crf_flipflop_loss_f64(inp["scores"], inp["seqs"], seqlens, 1.0)
     np.testing.assert_allclose(wl, solo, rtol=2e-6, atol=1e-7)
+    # the raw reference call on the same batch (stored; live where oracle/_ref was built): reads 2 and 3 are not
+    # what they are alone
+    raws = [load_golden("refc_answers.npz")["empty/raw_loss"]]
     if oracle_mod.ref_available():
-        # the raw reference call on the same batch: reads 2 and 3 are not what they are alone
-        from oracle import _seq_call, flipflop_indices, ref
-        nbase = 4
-        move = np.concatenate([flipflop_indices(inp["seqs"][off[n]:off[n + 1]], seqlens[n:n + 1], nbase)[0][:max(seqlens[n] - 1, 0)]
-                               for n in range(len(seqlens))] + [np.zeros(2, dtype=np.uintp)])
-        stay = flipflop_indices(inp["seqs"], seqlens, nbase)[1]
-        raw, _ = _seq_call(ref(), "", inp["scores"], move, stay, seqlens)
+        raws.append(refc.empty_read_raw_call(oracle_mod, inp, seqlens)[0])
+        np.testing.assert_array_equal(raws[1], raws[0])
+    for raw in raws:
         assert raw[0] == solo[0] and (raw[2] != solo[2] or raw[3] != solo[3])
