@@ -22,19 +22,6 @@ size_t viterbi_workspace_bytes(size_t T, size_t N, size_t nbase);
 int viterbi_dispatch(const float *scores, size_t T, size_t N, size_t nbase, float *fwd,
                      int64_t *tb, int64_t *path, void *workspace, size_t workspace_bytes,
                      hipStream_t stream);
-size_t crf_workspace_bytes(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen,
-                           int want_grad);
-size_t crf_workspace_bytes_sharp(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen,
-                                 int want_grad, float sharp);
-int crf_dispatch(const float *logprob, size_t ntrans, size_t nblk, size_t nbatch,
-                 const int32_t *stayidx, const int32_t *moveidx, const int32_t *modidx,
-                 const float *modfact, const int32_t *seqlen, const int64_t *seqoff,
-                 size_t max_seqlen, size_t ncan, float sharp_can, float sharp_mod,
-                 float out_scale, float grad_scale, const float *grad_scale_vec, float *cost, float *grad,
-                 void *workspace, size_t workspace_bytes, uint32_t *status, hipStream_t stream,
-                 const float *add_grad = nullptr, const float *add_cost = nullptr, int add_S = 0,
-                 float add_scale = 0.f, hipEvent_t add_ready = nullptr, const float *mod_col_weights = nullptr,
-                 const SeqLabels *labels = nullptr);
 bool logz_side_stream(hipStream_t *s, hipEvent_t *fork, hipEvent_t *join);
 #ifdef TK_LAB
 void crf_band_lab_phase(int phase);
@@ -193,7 +180,7 @@ int tk_flipflop_errprobs_dev(const float *trans, const int64_t *path, size_t nbl
 
 size_t tk_crf_flipflop_workspace_bytes(size_t ntrans, size_t nblk, size_t nbatch,
                                        size_t max_seqlen, int want_grad) {
-    return tk::crf_workspace_bytes(ntrans, nblk, nbatch, max_seqlen, want_grad);
+    return tk::crf_workspace_bytes_sharp(ntrans, nblk, nbatch, max_seqlen, want_grad, 1.0f);
 }
 
 size_t tk_crf_flipflop_workspace_bytes_sharp(size_t ntrans, size_t nblk, size_t nbatch,
@@ -201,8 +188,9 @@ size_t tk_crf_flipflop_workspace_bytes_sharp(size_t ntrans, size_t nblk, size_t 
     return tk::crf_workspace_bytes_sharp(ntrans, nblk, nbatch, max_seqlen, want_grad, sharpfact);
 }
 
-static bool labels_ok(const tk_seq_labels *labels, tk::SeqLabels *out) {
+static bool labels_ok(const tk_seq_labels *labels, const int32_t *modidx, tk::SeqLabels *out) {
     if (labels == nullptr || labels->nbase == 0 || (labels->seqs == nullptr && labels->total_len != 0)) return false;
+    if ((labels->mod_cats != nullptr) != (modidx != nullptr)) return false;
     *out = tk::SeqLabels{labels->seqs, labels->total_len, labels->nbase, labels->mod_cats, labels->can_mods_offsets,
                          labels->mod_cat_weights, labels->bulk_seqlen};
     return true;
@@ -218,11 +206,31 @@ static int crf_flipflop_impl(const float *logprob, size_t ntrans, size_t nblk, s
     if (!logprob || !stayidx || !moveidx || !seqlen || !seqoff || !cost || !workspace) return TK_ERR_BAD_ARG;
     if (ntrans == 0 || nblk == 0 || nbatch == 0) return TK_ERR_BAD_ARG;
     if ((modidx == nullptr) != (modfact == nullptr)) return TK_ERR_BAD_ARG;
-    return tk::crf_dispatch(logprob, ntrans, nblk, nbatch, stayidx, moveidx, modidx, modfact,
-                            seqlen, seqoff, max_seqlen, ncan, sharp_can, sharp_mod, out_scale, 1.0f, nullptr,
-                            cost, grad, workspace, workspace_bytes, status,
-                            static_cast<hipStream_t>(stream), nullptr, nullptr, 0, 0.f, nullptr,
-                            modidx != nullptr ? mod_col_weights : nullptr, labels);
+    tk::CrfCall c;
+    c.lp = logprob;
+    c.ntrans = ntrans;
+    c.nblk = nblk;
+    c.nbatch = nbatch;
+    c.max_seqlen = max_seqlen;
+    c.ncan = ncan;
+    c.stay = stayidx;
+    c.move = moveidx;
+    c.mod = modidx;
+    c.modfact = modfact;
+    c.seqlen = seqlen;
+    c.seqoff = seqoff;
+    c.labels = labels;
+    c.sharp_can = sharp_can;
+    c.sharp_mod = sharp_mod;
+    c.out_scale = out_scale;
+    c.cost = cost;
+    c.grad = grad;
+    c.workspace = workspace;
+    c.workspace_bytes = workspace_bytes;
+    c.status = status;
+    c.stream = static_cast<hipStream_t>(stream);
+    c.mod_col_weights = modidx != nullptr ? mod_col_weights : nullptr;
+    return tk::crf_dispatch(c);
 }
 
 int tk_crf_flipflop_dev(const float *logprob, size_t ntrans, size_t nblk, size_t nbatch,
@@ -243,8 +251,7 @@ int tk_crf_flipflop_labels_dev(const float *logprob, size_t ntrans, size_t nblk,
                                float out_scale, float *cost, float *grad, void *workspace,
                                size_t workspace_bytes, uint32_t *status, void *stream) {
     tk::SeqLabels lab;
-    if (!labels_ok(labels, &lab)) return TK_ERR_BAD_ARG;
-    if ((labels->mod_cats != nullptr) != (modidx != nullptr)) return TK_ERR_BAD_ARG;
+    if (!labels_ok(labels, modidx, &lab)) return TK_ERR_BAD_ARG;
     // (modfact is filled from mod_cat_weights by column: the per-column form of the cat-mod kernels applies)
     return crf_flipflop_impl(logprob, ntrans, nblk, nbatch, stayidx, moveidx, modidx, modfact, seqlen, seqoff, max_seqlen,
                              ncan, sharp_can, sharp_mod, out_scale, cost, grad, workspace, workspace_bytes, status, stream,
@@ -319,15 +326,39 @@ static int loss_fused_impl(const float *scores, size_t nblk, size_t nbatch, size
     if (!catmod && ntrans != ncan) return TK_ERR_BAD_ARG;
     if (catmod && (ntrans <= ncan || ntrans > 62)) return TK_ERR_BAD_ARG;
     if (catmod && (aux == nullptr || aux_bytes < 2 * one)) return TK_ERR_WORKSPACE;
+    // ctc.pyx:258-303: only the canonical columns are sharpened; cost / sharp
+    tk::CrfCall c;
+    c.lp = scores;
+    c.ntrans = ntrans;
+    c.nblk = nblk;
+    c.nbatch = nbatch;
+    c.max_seqlen = max_seqlen;
+    c.ncan = ncan;
+    c.stay = stayidx;
+    c.move = moveidx;
+    c.mod = modidx;
+    c.modfact = modfact;
+    c.seqlen = seqlen;
+    c.seqoff = seqoff;
+    c.labels = labels;
+    c.sharp_can = sharpfact;
+    c.sharp_mod = catmod ? 1.0f : sharpfact;
+    c.out_scale = 1.0f / sharpfact;
+    c.grad_scale = grad_scale;
+    c.grad_scale_vec = grad_scale_per_read;
+    c.cost = lossvector;
+    c.grad = grad;
+    c.workspace = crf_workspace;
+    c.workspace_bytes = crf_workspace_bytes;
+    c.status = status;
+    c.stream = st;
+    c.mod_col_weights = catmod ? mod_col_weights : nullptr;
 
     if (!catmod && (aux == nullptr || aux_bytes < one || !loss_overlap_enabled(st))) {
         // (A) first: per-read costs into `lossvector`, its gradient into `grad`; (B) then ADDS
         // logZ / nblk and (d logZ / d scores) / nblk in place -- in its posterior kernel, whose stores
         // are whole coalesced row sets
-        int rc = tk::crf_dispatch(scores, ntrans, nblk, nbatch, stayidx, moveidx, nullptr, nullptr, seqlen, seqoff,
-                                  max_seqlen, ntrans, sharpfact, sharpfact, 1.0f / sharpfact, grad_scale,
-                                  grad_scale_per_read, lossvector, grad, crf_workspace, crf_workspace_bytes, status, st,
-                                  nullptr, nullptr, 0, 0.f, nullptr, nullptr, labels);
+        int rc = tk::crf_dispatch(c);
         if (rc != 0) return rc;
         return tk::logz_dispatch(scores, nblk, nbatch, nbase, logz, grad, logz_workspace, logz_workspace_bytes, status,
                                  st, lossvector, 1.0f / (float)nblk, grad_scale, grad_scale_per_read);
@@ -361,11 +392,12 @@ static int loss_fused_impl(const float *scores, size_t nblk, size_t nbatch, size
         if (side) (void)hipStreamWaitEvent(st, join, 0);        // (never leave the side queue dangling in a capture)
         return rc;
     }
-    // ctc.pyx:258-303: only the canonical columns are sharpened; cost / sharp
-    rc = tk::crf_dispatch(scores, ntrans, nblk, nbatch, stayidx, moveidx, modidx, modfact, seqlen, seqoff, max_seqlen,
-                          ncan, sharpfact, catmod ? 1.0f : sharpfact, 1.0f / sharpfact, grad_scale, grad_scale_per_read,
-                          lossvector, grad, crf_workspace, crf_workspace_bytes, status, st, g40, logz, (int)ncan,
-                          1.0f / (float)nblk, side ? join : nullptr, catmod ? mod_col_weights : nullptr, labels);
+    c.add_grad = g40;
+    c.add_cost = logz;
+    c.add_S = (int)ncan;
+    c.add_scale = 1.0f / (float)nblk;
+    c.add_ready = side ? join : nullptr;
+    rc = tk::crf_dispatch(c);
     if (rc != 0 && side) (void)hipStreamWaitEvent(st, join, 0);
     return rc;
 }
@@ -393,8 +425,7 @@ int tk_flipflop_loss_fused_labels_dev(const float *scores, size_t nblk, size_t n
                                       void *logz_workspace, size_t logz_workspace_bytes, void *aux, size_t aux_bytes,
                                       uint32_t *status, void *stream) {
     tk::SeqLabels lab;
-    if (!labels_ok(labels, &lab)) return TK_ERR_BAD_ARG;
-    if ((labels->mod_cats != nullptr) != (modidx != nullptr)) return TK_ERR_BAD_ARG;
+    if (!labels_ok(labels, modidx, &lab)) return TK_ERR_BAD_ARG;
     return loss_fused_impl(scores, nblk, nbatch, labels->nbase, ntrans, stayidx, moveidx, modidx, modfact, seqlen, seqoff,
                            max_seqlen, sharpfact, grad_scale, grad_scale_per_read, lossvector, grad, logz, crf_workspace,
                            crf_workspace_bytes, logz_workspace, logz_workspace_bytes, aux, aux_bytes, status, stream,
@@ -530,7 +561,7 @@ bool host_seq_call(float const *logprob, size_t ntrans, size_t nblk, size_t nbat
         }
     }
     const size_t nelt = nblk * nbatch * ntrans;
-    const size_t wsb = tk::crf_workspace_bytes(ntrans, nblk, nbatch, (size_t)maxlen, grad != nullptr);
+    const size_t wsb = tk::crf_workspace_bytes_sharp(ntrans, nblk, nbatch, (size_t)maxlen, grad != nullptr, 1.0f);
     DevBuf d_lp, d_stay, d_move, d_mod, d_fact, d_len, d_off, d_cost, d_grad, d_ws;
     if (!d_lp.alloc(nelt * 4) || !d_stay.alloc(stay.size() * 4) || !d_move.alloc(move.size() * 4) ||
         !d_len.alloc(nbatch * 4) || !d_off.alloc((nbatch + 1) * 8) || !d_cost.alloc(nbatch * 4) ||
@@ -559,14 +590,24 @@ bool host_seq_call(float const *logprob, size_t ntrans, size_t nblk, size_t nbat
             for (size_t p = 0; p + 1 < (size_t)seqlen[b]; ++p)
                 if (modmoveidxs[mbase(b) + p] < ncan) ncan = modmoveidxs[mbase(b) + p];
     }
-    const int rc = tk::crf_dispatch(
-        static_cast<const float *>(d_lp.p), ntrans, nblk, nbatch,
-        static_cast<const int32_t *>(d_stay.p), static_cast<const int32_t *>(d_move.p),
-        modmoveidxs ? static_cast<const int32_t *>(d_mod.p) : nullptr,
-        modmoveidxs ? static_cast<const float *>(d_fact.p) : nullptr,
-        static_cast<const int32_t *>(d_len.p), static_cast<const int64_t *>(d_off.p),
-        (size_t)maxlen, ncan, 1.0f, 1.0f, 1.0f, 1.0f, nullptr, static_cast<float *>(d_cost.p),
-        grad ? static_cast<float *>(d_grad.p) : nullptr, d_ws.p, wsb, nullptr, nullptr);
+    tk::CrfCall c;
+    c.lp = static_cast<const float *>(d_lp.p);
+    c.ntrans = ntrans;
+    c.nblk = nblk;
+    c.nbatch = nbatch;
+    c.max_seqlen = (size_t)maxlen;
+    c.ncan = ncan;
+    c.stay = static_cast<const int32_t *>(d_stay.p);
+    c.move = static_cast<const int32_t *>(d_move.p);
+    c.mod = modmoveidxs ? static_cast<const int32_t *>(d_mod.p) : nullptr;
+    c.modfact = modmoveidxs ? static_cast<const float *>(d_fact.p) : nullptr;
+    c.seqlen = static_cast<const int32_t *>(d_len.p);
+    c.seqoff = static_cast<const int64_t *>(d_off.p);
+    c.cost = static_cast<float *>(d_cost.p);
+    c.grad = grad ? static_cast<float *>(d_grad.p) : nullptr;
+    c.workspace = d_ws.p;
+    c.workspace_bytes = wsb;
+    const int rc = tk::crf_dispatch(c);
     if (rc != 0 || hipDeviceSynchronize() != hipSuccess) return false;
     std::vector<float> cost(nbatch);
     if (hipMemcpy(cost.data(), d_cost.p, nbatch * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;

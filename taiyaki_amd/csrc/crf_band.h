@@ -122,4 +122,30 @@ int crf_band_retry_R(size_t max_seqlen);
 int crf_band_dispatch(const BandArgs &a, int R, bool mod, int bk, hipStream_t stream);
 // (the tail launch -- retry, then the log domain: crf_log.h: crf_band_tail_dispatch)
 
+// One call of kernel A (crf_kernels.hip: crf_dispatch).  A caller sets the fields it uses; the rest keep these defaults.
+struct CrfCall {
+    const float *lp = nullptr;          // (T, N, S) scores (unsharpened)
+    size_t ntrans = 0, nblk = 0, nbatch = 0, max_seqlen = 0;    // max_seqlen 0: nblk + 1
+    size_t ncan = 0;                    // canonical transition columns (== ntrans for the plain CRF)
+    const int32_t *stay = nullptr, *move = nullptr, *mod = nullptr;     // padded per-position ids; mod null: the plain CRF
+    const float *modfact = nullptr;
+    const int32_t *seqlen = nullptr;    // (N)
+    const int64_t *seqoff = nullptr;    // (N + 1)
+    const SeqLabels *labels = nullptr;  // non-null: stay / move / mod / modfact / seqoff are OUTPUTS, built from these
+    float sharp_can = 1.f, sharp_mod = 1.f, out_scale = 1.f, grad_scale = 1.f;
+    const float *grad_scale_vec = nullptr;
+    float *cost = nullptr, *grad = nullptr;     // (N); (T, N, S) or null (cost only)
+    void *workspace = nullptr;
+    size_t workspace_bytes = 0;
+    uint32_t *status = nullptr;
+    hipStream_t stream = nullptr;
+    const float *add_grad = nullptr, *add_cost = nullptr;   // the fused loss (BandArgs::add_grad) ...
+    int add_S = 0;
+    float add_scale = 0.f;
+    hipEvent_t add_ready = nullptr;     // ... what they hold is ready when this event is; null: now
+    const float *mod_col_weights = nullptr;     // cat-mod only (BandArgs::colw)
+};
+int crf_dispatch(const CrfCall &c);
+size_t crf_workspace_bytes_sharp(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, int want_grad, float sharp);
+
 }  // namespace tk

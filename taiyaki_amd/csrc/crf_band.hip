@@ -1410,34 +1410,28 @@ BandLayout crf_band_layout(size_t ntrans, size_t nblk, size_t nbatch, size_t max
     l.LP = (size_t)l.W * PW;
     const size_t KINDS = mod ? 3 : 2, NB = (nblk + BK - 1) / BK, Wp = l.LP / WAVE;
     size_t off = 0;
-    auto take = [&](size_t bytes) {
+    auto take = [&](size_t bytes, bool need) {
         const size_t r = off;
-        if (want_grad) off += (bytes + 255) / 256 * 256;        // (a cost-only call needs the gate alone)
+        if (need) off += (bytes + 255) / 256 * 256;
         return r;
     };
-    l.ckFm = take(nbatch * NB * l.LP * sizeof(float));
-    l.ckBm = take(nbatch * NB * l.LP * sizeof(float));
-    l.ckFf = take(nbatch * NB * l.LP * sizeof(int16_t));
-    l.ckBf = take(nbatch * NB * l.LP * sizeof(int16_t));
-    l.ckFb = take(nbatch * NB * l.W * sizeof(int));
-    l.ckBb = take(nbatch * NB * l.W * sizeof(int));
-    l.bndF = take(nbatch * NB * Wp * BK * sizeof(float));
-    l.bndB = take(nbatch * NB * Wp * BK * sizeof(float));
-    // (the two sweep scores also in a cost-only call: it runs both sweeps and is only believed where they agree)
-    l.scoreF = off;
-    off += (nbatch * sizeof(double) + 255) / 256 * 256;
-    l.scoreB = off;
-    off += (nbatch * sizeof(double) + 255) / 256 * 256;
-    l.rec = take(nbatch * Wp * KINDS * WAVE * sizeof(uint32_t));
-    l.segend = take(nbatch * Wp * WAVE * sizeof(int));
-    l.gate = off;
-    off += (nbatch * sizeof(int) + 255) / 256 * 256;
-    l.gate2 = off;              // the retry launch's verdicts, per read of the batch
-    off += (nbatch * sizeof(int) + 255) / 256 * 256;
-    l.anygate = off;
-    off += 256;
-    l.zeros = off;
-    off += 256;
+    // (a cost-only call needs the gate alone, and the two sweep scores: it runs both, and is only believed where they agree)
+    l.ckFm = take(nbatch * NB * l.LP * sizeof(float), want_grad);
+    l.ckBm = take(nbatch * NB * l.LP * sizeof(float), want_grad);
+    l.ckFf = take(nbatch * NB * l.LP * sizeof(int16_t), want_grad);
+    l.ckBf = take(nbatch * NB * l.LP * sizeof(int16_t), want_grad);
+    l.ckFb = take(nbatch * NB * l.W * sizeof(int), want_grad);
+    l.ckBb = take(nbatch * NB * l.W * sizeof(int), want_grad);
+    l.bndF = take(nbatch * NB * Wp * BK * sizeof(float), want_grad);
+    l.bndB = take(nbatch * NB * Wp * BK * sizeof(float), want_grad);
+    l.scoreF = take(nbatch * sizeof(double), true);
+    l.scoreB = take(nbatch * sizeof(double), true);
+    l.rec = take(nbatch * Wp * KINDS * WAVE * sizeof(uint32_t), want_grad);
+    l.segend = take(nbatch * Wp * WAVE * sizeof(int), want_grad);
+    l.gate = take(nbatch * sizeof(int), true);
+    l.gate2 = take(nbatch * sizeof(int), true);     // the retry launch's verdicts, per read of the batch
+    l.anygate = take(256, true);
+    l.zeros = take(256, true);
     l.total = off + 256;
     return l;
 }
@@ -1487,10 +1481,9 @@ static int band_launch(const BandArgs &a, hipStream_t stream) {
     const bool want_grad = a.grad != nullptr;
     if (g_band_lab_phase != 2) {
         int rc;
-        bool rows = false;
-        if constexpr (BK >= 8 && (!MOD || CW)) rows = band_use_rows(a, MOD, BK);
         if constexpr (BK >= 8 && (!MOD || CW)) {
-            rc = rows ? band_launch_sweep<R, MOD, CW, BK, true>(a, stream) : band_launch_sweep<R, MOD, CW, BK, false>(a, stream);
+            rc = band_use_rows(a, MOD, BK) ? band_launch_sweep<R, MOD, CW, BK, true>(a, stream)
+                                           : band_launch_sweep<R, MOD, CW, BK, false>(a, stream);
         } else {
             rc = band_launch_sweep<R, MOD, CW, BK, false>(a, stream);
         }
@@ -1515,6 +1508,17 @@ static int band_launch_bk(const BandArgs &a, int bk, hipStream_t stream) {
         if (bk == 12) return band_launch<R, MOD, CW, 12>(a, stream);
     }
     return 2;
+}
+
+// the instantiations of a band launch: cells per lane R (1, 2, 4), cat-mod, per-column factors (cat-mod only) -> go(R, MOD, CW)
+template <class F>
+static int band_variant(int R, bool mod, bool colw, F &&go) {
+    using N = std::false_type;
+    using Y = std::true_type;
+    auto with = [&](auto r) { return !mod ? go(r, N{}, N{}) : colw ? go(r, Y{}, Y{}) : go(r, Y{}, N{}); };
+    if (R == 1) return with(std::integral_constant<int, 1>{});
+    if (R == 2) return with(std::integral_constant<int, 2>{});
+    return R == 4 ? with(std::integral_constant<int, 4>{}) : 2;
 }
 
 int crf_band_dispatch(const BandArgs &a0, int R, bool mod, int bk, hipStream_t stream) {
@@ -1546,15 +1550,9 @@ int crf_band_dispatch(const BandArgs &a0, int R, bool mod, int bk, hipStream_t s
     } printer{a.dbg, stream};
 #endif
     if (a.W < 1 || a.W > BAND_MAXW) return 2;
-    switch (R * 2 + (mod ? 1 : 0)) {
-        case 2: return band_launch_bk<1, false, false>(a, bk, stream);
-        case 3: return a.colw ? band_launch_bk<1, true, true>(a, bk, stream) : band_launch_bk<1, true, false>(a, bk, stream);
-        case 4: return band_launch_bk<2, false, false>(a, bk, stream);
-        case 5: return a.colw ? band_launch_bk<2, true, true>(a, bk, stream) : band_launch_bk<2, true, false>(a, bk, stream);
-        case 8: return band_launch_bk<4, false, false>(a, bk, stream);
-        case 9: return a.colw ? band_launch_bk<4, true, true>(a, bk, stream) : band_launch_bk<4, true, false>(a, bk, stream);
-        default: return 2;
-    }
+    return band_variant(R, mod, a.colw != nullptr, [&](auto r, auto m, auto cw) {
+        return band_launch_bk<decltype(r)::value, decltype(m)::value, decltype(cw)::value>(a, bk, stream);
+    });
 }
 
 template <int R, bool MOD, bool CW>
@@ -1571,15 +1569,9 @@ static int band_tail_launch(const BandArgs &a, const BandRetry &r, const CrfArgs
 
 int crf_band_tail_dispatch(const BandArgs &a, const BandRetry &r, const CrfArgs &ca, int R, bool mod, size_t nslots, hipStream_t stream) {
     if (a.W < 1 || a.W > BAND_MAXW || nslots == 0) return 2;
-    switch (R * 2 + (mod ? 1 : 0)) {
-        case 2: return band_tail_launch<1, false, false>(a, r, ca, nslots, stream);
-        case 3: return a.colw ? band_tail_launch<1, true, true>(a, r, ca, nslots, stream) : band_tail_launch<1, true, false>(a, r, ca, nslots, stream);
-        case 4: return band_tail_launch<2, false, false>(a, r, ca, nslots, stream);
-        case 5: return a.colw ? band_tail_launch<2, true, true>(a, r, ca, nslots, stream) : band_tail_launch<2, true, false>(a, r, ca, nslots, stream);
-        case 8: return band_tail_launch<4, false, false>(a, r, ca, nslots, stream);
-        case 9: return a.colw ? band_tail_launch<4, true, true>(a, r, ca, nslots, stream) : band_tail_launch<4, true, false>(a, r, ca, nslots, stream);
-        default: return 2;
-    }
+    return band_variant(R, mod, a.colw != nullptr, [&](auto rc, auto m, auto cw) {
+        return band_tail_launch<decltype(rc)::value, decltype(m)::value, decltype(cw)::value>(a, r, ca, nslots, stream);
+    });
 }
 
 }  // namespace tk

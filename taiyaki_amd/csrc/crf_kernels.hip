@@ -193,16 +193,6 @@ static CrfShape crf_pick_shape(size_t max_seqlen) {
     return {R, W};
 }
 
-// (a cost-only call keeps no checkpoint column: crf_kernel stores them under want_grad only)
-static size_t crf_ckpt_bytes(size_t nblk, size_t nbatch, CrfShape sh, bool want_grad = true) {
-    if (!want_grad) return 256;
-    const int CK = crf_ck(sh.R, sh.W, 3);   // the cat-mod tile is the smaller one: upper bound
-    const size_t NK = (nblk + CK - 1) / CK;
-    const size_t ck = nbatch * NK * (size_t)sh.R * sh.W * WAVE * sizeof(float);
-    const size_t co = nbatch * NK * sizeof(double);
-    return (ck + 255) / 256 * 256 + (co + 255) / 256 * 256 + 256;
-}
-
 // Which form of kernel A runs (TK_CRF_MODE overrides: band | ckpt):
 //   band     crf_band.hip -- linear-domain banded skewed sweep + recomputing gradient pass, followed
 //            by ONE tail launch (crf_band.hip: crf_band_tail_kernel) that retries the reads the band path disowned alone
@@ -233,49 +223,61 @@ static size_t crf_lattice_cap_bytes() {
     }
     return cap[dev];
 }
-// `bk`: the block length the linear path would use for this call (crf_band_pick_block; 0 = it does not take it)
-// the band layout's size for workspace queries: the plain CRF and cat-mod may pick different cells per lane
-// (crf_band_pick_R), hence different padded read lengths -- the bound covers both
-static size_t crf_band_total_bound(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, bool want_grad, int bk) {
-    const size_t a = crf_band_layout(ntrans, nblk, nbatch, max_seqlen, true, want_grad, bk).total;
-    const size_t b = crf_band_layout(ntrans, nblk, nbatch, max_seqlen, false, want_grad, bk).total;
-    return a > b ? a : b;
-}
+// `bk`: the block length the linear path would use for this call (crf_band_pick_block; 0 = it does not take it).
+// The band layout is checked against the cap for both forms: the plain CRF and cat-mod may pick different cells per
+// lane (crf_band_pick_R), hence different padded read lengths -- the bound covers both.
 static CrfMode crf_pick_mode(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, bool want_grad, int bk) {
     const char *e = TK_LAB_ENV("TK_CRF_MODE");
-    const bool force_ckpt = e && e[0] == 'c';
-    if (!force_ckpt && bk > 0 && crf_band_fits(max_seqlen) &&
-        crf_band_total_bound(ntrans, nblk, nbatch, max_seqlen, want_grad, bk) <= crf_lattice_cap_bytes())
-        return CRF_BAND;
-    return CRF_CKPT;
+    if ((e && e[0] == 'c') || bk <= 0 || !crf_band_fits(max_seqlen)) return CRF_CKPT;
+    const size_t a = crf_band_layout(ntrans, nblk, nbatch, max_seqlen, true, want_grad, bk).total;
+    const size_t b = crf_band_layout(ntrans, nblk, nbatch, max_seqlen, false, want_grad, bk).total;
+    return (a > b ? a : b) <= crf_lattice_cap_bytes() ? CRF_BAND : CRF_CKPT;
 }
 
-// the retry's workspace (round 6): the band layout of 4-step blocks for crf_band_retry_slots(nbatch) reads (gradient
-// form whatever the call: a cost-only retry runs the same sweeps)
-static size_t crf_retry_bytes(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen) {
-    const int R = crf_band_retry_R(max_seqlen);
-    const size_t a = crf_band_layout(ntrans, nblk, crf_band_retry_slots(nbatch), max_seqlen, true, true, 4, R).total;
-    const size_t b = crf_band_layout(ntrans, nblk, crf_band_retry_slots(nbatch), max_seqlen, false, true, 4, R).total;
-    return a > b ? a : b;
-}
-// the log-domain form's checkpoint columns behind the band path: one set per workgroup of the TAIL launch (crf_band.hip:
-// crf_band_tail_kernel -- 16 waves, cells per lane by the band launch's)
-static CrfShape crf_tail_shape(int band_R) { return {crf_tail_log_R(band_R), 16}; }
-static size_t crf_tail_ckpt_bound(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, bool want_grad) {
-    (void)ntrans;
-    return crf_ckpt_bytes(nblk, crf_band_retry_slots(nbatch), crf_tail_shape(crf_band_retry_R(max_seqlen)), want_grad);
+// THE WORKSPACE PLAN of one call: [band layout | the retry's band layout | checkpoint columns + offsets of the log-domain form].
+// Band mode (`bk` > 0): the batch launch's layout; the retry's (`rbk` > 0, round 6: the band layout of 4-step blocks for
+// crf_band_retry_slots(nbatch) reads, gradient form whatever the call -- a cost-only retry runs the same sweeps); and one set
+// of checkpoint columns per workgroup of the TAIL launch (crf_band.hip: crf_band_tail_kernel -- 16 waves, cells per lane by
+// the retry's): a sixteenth of the batch, at least 4 -- it redoes only what the linear path disowned twice, none on the inputs
+// a network produces (round 3 sized them for the whole batch: 8.4 of 12.2 GB at T = 4000 / N = 256).  Checkpoint mode
+// (`bk` = 0): crf_kernel's columns, one set per read.
+struct CrfPlan {
+    BandLayout band, retry;     // at 0 and at band.total (total 0: not in this plan)
+    CrfShape sh;                // the log-domain form: its shape and workgroups
+    size_t nslots;
+    size_t ck, ckcols, total;   // its region: at ck, ckcols bytes of columns (the call's kinds), then the offsets, up to total
+};
+static CrfPlan crf_plan(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, bool mod, bool want_grad, int bk, int rbk) {
+    CrfPlan p{};
+    p.sh = crf_pick_shape(max_seqlen);
+    p.nslots = nbatch;
+    if (bk > 0) {
+        p.band = crf_band_layout(ntrans, nblk, nbatch, max_seqlen, mod, want_grad, bk);
+        p.nslots = crf_band_retry_slots(nbatch);
+        if (rbk > 0) p.retry = crf_band_layout(ntrans, nblk, p.nslots, max_seqlen, mod, true, rbk, crf_band_retry_R(max_seqlen));
+        p.sh = {crf_tail_log_R(crf_band_retry_R(max_seqlen)), 16};
+    }
+    // one column of R W 64 cells every CK steps, NK per workgroup; then one offset per column
+    auto NK = [&](int kinds) {
+        const size_t CK = (size_t)crf_ck(p.sh.R, p.sh.W, kinds);
+        return (nblk + CK - 1) / CK;
+    };
+    auto aligned = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t cells = p.nslots * (size_t)p.sh.R * p.sh.W * WAVE;
+    // (a cost-only call keeps no checkpoint column: crf_kernel stores them under want_grad only)
+    p.ck = p.band.total + p.retry.total;
+    // (the region is sized for three kinds: the cat-mod tile is the smaller one, an upper bound for both)
+    p.ckcols = want_grad ? aligned(cells * NK(mod ? 3 : 2) * sizeof(float)) : 0;
+    p.total = p.ck + (want_grad ? aligned(cells * NK(3) * sizeof(float)) + aligned(p.nslots * NK(3) * sizeof(double)) + 256 : 256);
+    return p;
 }
 
-// workspace = [band layout (band mode only)] [the retry's band layout] [checkpoint columns + offsets of the log-domain form:
-// behind the band path one set per workgroup of the tail launch -- a sixteenth of the batch, at least 4: it redoes only what
-// the linear path disowned twice, none on the inputs a network produces (round 3 sized them for the whole batch: 8.4 of
-// 12.2 GB at T = 4000 / N = 256) --, else one per read]
 // `sharp`: the call's sharpening factor -- it picks the linear path's block length, and short blocks keep
 // more checkpoint columns.  The block lengths of the plain CRF and of cat-mod differ; the bound covers both.
 size_t crf_workspace_bytes_sharp(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen,
                                  int want_grad, float sharp) {
     if (max_seqlen == 0) max_seqlen = nblk + 1;
-    const CrfShape sh = crf_pick_shape(max_seqlen);
+    const bool g = want_grad != 0;
     // (every block length either form may take for this shape: with and without per-column factors; a batch with narrow
     // bands takes 8 steps where wider ones take 12)
     // (... and whatever the batch's bulk is: between "unknown" and "every read as long as the longest")
@@ -284,20 +286,17 @@ size_t crf_workspace_bytes_sharp(size_t ntrans, size_t nblk, size_t nbatch, size
     for (int bulk = 0; bulk < 2; ++bulk)
         for (int form = 0; form < 3; ++form)
             bk = shortest(bk, crf_band_pick_block(sharp, form > 0, max_seqlen, form == 2, nblk, bulk ? max_seqlen : 0).bk);
-    // (the cat-mod layout is the larger one: an upper bound for both)
     // (a call whose own block choice differs from the one assumed here -- another sharpening factor than the
     // query's -- needs what ITS factor's query returns; with less, crf_dispatch falls back to the log-domain
     // kernel on every read if the workspace holds that kernel's whole-batch columns, and returns 3 otherwise:
     // sizing every workspace for that case would be 8.0 instead of 4.7 GB at T = 4000 / N = 256)
-    if (crf_pick_mode(ntrans, nblk, nbatch, max_seqlen, want_grad != 0, bk) == CRF_BAND)
-        return crf_tail_ckpt_bound(ntrans, nblk, nbatch, max_seqlen, want_grad != 0) +
-               crf_band_total_bound(ntrans, nblk, nbatch, max_seqlen, want_grad != 0, bk) + crf_retry_bytes(ntrans, nblk, nbatch, max_seqlen);
-    return crf_ckpt_bytes(nblk, nbatch, sh, want_grad != 0);
-}
-
-size_t crf_workspace_bytes(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen,
-                           int want_grad) {
-    return crf_workspace_bytes_sharp(ntrans, nblk, nbatch, max_seqlen, want_grad, 1.0f);
+    if (crf_pick_mode(ntrans, nblk, nbatch, max_seqlen, g, bk) != CRF_BAND)
+        return crf_plan(ntrans, nblk, nbatch, max_seqlen, false, g, 0, 0).total;
+    // (each band region the larger of the plain CRF's and cat-mod's: see crf_pick_mode)
+    const CrfPlan p = crf_plan(ntrans, nblk, nbatch, max_seqlen, false, g, bk, 4);
+    const CrfPlan q = crf_plan(ntrans, nblk, nbatch, max_seqlen, true, g, bk, 4);
+    auto larger = [](size_t x, size_t y) { return x > y ? x : y; };
+    return larger(p.band.total, q.band.total) + larger(p.retry.total, q.retry.total) + (p.total - p.ck);
 }
 
 template <int R, int W, bool MOD>
@@ -328,245 +327,186 @@ static int crf_launch_mod(CrfShape sh, const CrfArgs &a, hipStream_t stream, siz
 #undef TK_CRF_CASE
 }
 
-int crf_dispatch(const float *logprob, size_t ntrans, size_t nblk, size_t nbatch,
-                 const int32_t *stayidx, const int32_t *moveidx, const int32_t *modidx,
-                 const float *modfact, const int32_t *seqlen, const int64_t *seqoff,
-                 size_t max_seqlen, size_t ncan, float sharp_can, float sharp_mod,
-                 float out_scale, float grad_scale, const float *grad_scale_vec, float *cost, float *grad,
-                 void *workspace, size_t workspace_bytes, uint32_t *status, hipStream_t stream,
-                 const float *add_grad, const float *add_cost, int add_S, float add_scale,
-                 hipEvent_t add_ready, const float *mod_col_weights, const SeqLabels *labels) {
-    if (ntrans > 62 || ncan > ntrans || ncan == 0) return 2;
+// The fields CrfArgs and BandArgs share, from the call (the two structs keep their own layouts: the kernels read them).
+// `ids_from` non-null: this launch forms its ids from those labels and writes no index array (crf_band.h: BandArgs::codes).
+template <class Args>
+static void crf_fill_args(Args &x, const CrfCall &c, const SeqLabels *ids_from) {
+    x.lp = c.lp;
+    x.T = (int)c.nblk;
+    x.N = (int)c.nbatch;
+    x.S = (int)c.ntrans;
+    x.ncan = (int)c.ncan;
+    x.stay = c.stay;
+    x.move = c.move;
+    x.mod = c.mod;
+    x.modfact = c.modfact;
+    x.seqlen = c.seqlen;
+    x.seqoff = c.seqoff;
+    x.c_can = c.sharp_can * LOG2E;
+    x.c_mod = c.sharp_mod * LOG2E;
+    x.out_scale = c.out_scale;
+    x.grad_scale = c.grad_scale;
+    x.grad_scale_vec = c.grad_scale_vec;
+    x.add_grad = c.add_grad;
+    x.add_cost = c.add_cost;
+    x.add_S = c.add_S;
+    x.add_scale = c.add_scale;
+    x.cost = c.cost;
+    x.grad = c.grad;
+    x.status = c.status;
+    // (a batch of empty reads has no label array: any non-null pointer says "build here", nothing reads it)
+    x.codes = ids_from != nullptr ? (ids_from->seqs != nullptr ? ids_from->seqs : c.stay) : nullptr;
+    x.mod_cats = ids_from != nullptr ? ids_from->mod_cats : nullptr;
+    x.cmo = ids_from != nullptr ? ids_from->can_mods_offsets : nullptr;
+    x.mcw = ids_from != nullptr ? ids_from->mod_cat_weights : nullptr;
+    x.nbase = ids_from != nullptr ? (int)ids_from->nbase : 0;
+}
+
+// a band layout placed at `base` -> the sweep and gradient-pass arrays of a launch (a cost-only launch has only the scores)
+static void crf_bind_layout(BandArgs &b, const BandLayout &l, char *base, bool g) {
+    b.W = l.W;
+    b.LP = (int)l.LP;
+    b.Wp = (int)(l.LP / WAVE);
+    b.ckFm = g ? reinterpret_cast<float *>(base + l.ckFm) : nullptr;
+    b.ckBm = g ? reinterpret_cast<float *>(base + l.ckBm) : nullptr;
+    b.ckFf = g ? reinterpret_cast<int16_t *>(base + l.ckFf) : nullptr;
+    b.ckBf = g ? reinterpret_cast<int16_t *>(base + l.ckBf) : nullptr;
+    b.ckFb = g ? reinterpret_cast<int *>(base + l.ckFb) : nullptr;
+    b.ckBb = g ? reinterpret_cast<int *>(base + l.ckBb) : nullptr;
+    b.bndF = g ? reinterpret_cast<float *>(base + l.bndF) : nullptr;
+    b.bndB = g ? reinterpret_cast<float *>(base + l.bndB) : nullptr;
+    b.scoreF = reinterpret_cast<double *>(base + l.scoreF);
+    b.scoreB = reinterpret_cast<double *>(base + l.scoreB);
+    b.rec = g ? reinterpret_cast<uint32_t *>(base + l.rec) : nullptr;
+    b.segend = g ? reinterpret_cast<int *>(base + l.segend) : nullptr;
+}
+
+// lab (TK_CRF_GATE_DUMP; tests/helpers/gate_dump.py reads it): the reads the batch's launch disowned; with `rblk`, the tail's verdicts
+static void crf_gate_dump(const BandArgs &b, const BandBlock *rblk, size_t nbatch, hipStream_t stream) {
+    if (!TK_LAB_ENV("TK_CRF_GATE_DUMP")) return;
+    (void)hipStreamSynchronize(stream);
+    static int h1[1 << 16], h2[1 << 16];
+    const size_t ng = nbatch < (1u << 16) ? nbatch : (1u << 16);
+    (void)hipMemcpy(h1, b.gate, ng * sizeof(int), hipMemcpyDeviceToHost);
+    if (rblk != nullptr) (void)hipMemcpy(h2, b.gate2, ng * sizeof(int), hipMemcpyDeviceToHost);
+    size_t cnt = 0, why[8] = {0}, tried = 0, kept = 0;
+    for (size_t i = 0; i < ng; ++i) {
+        cnt += h1[i] != 0;
+        ++why[h1[i] & 7];
+        tried += h2[i] != -1;
+        kept += h2[i] == 0;
+    }
+    if (rblk == nullptr)
+        fprintf(stderr, "crf band: %zu of %zu reads gated (non-finite score %zu, sweeps disagree %zu, row lost mass %zu)\n",
+                cnt, ng, why[1], why[4], why[2]);
+    else
+        fprintf(stderr, "crf band tail (retry: bk %d, bias %.1f, slope %d): %zu reads taken, %zu kept on the linear path\n",
+                rblk->bk, rblk->wbias, rblk->klip, tried, kept);
+    for (size_t i = 0, shown = 0; i < ng && shown < 16; ++i) {
+        if (rblk == nullptr && h1[i]) fprintf(stderr, "crf band:   read %zu (reason %d)\n", i, h1[i]), ++shown;
+        if (rblk != nullptr && h2[i] > 0) fprintf(stderr, "crf band tail:   read %zu first %d retry %d\n", i, h1[i], h2[i]), ++shown;
+    }
+}
+
+int crf_dispatch(const CrfCall &c) {
+    const SeqLabels *labels = c.labels;
+    if (c.ntrans > 62 || c.ncan > c.ntrans || c.ncan == 0) return 2;
     if (labels != nullptr && ((labels->seqs == nullptr && labels->total_len != 0) || labels->nbase == 0 ||
-                              2 * labels->nbase * (labels->nbase + 1) != ncan ||
-                              ((modidx != nullptr) != (labels->mod_cats != nullptr)) ||
+                              2 * labels->nbase * (labels->nbase + 1) != c.ncan ||
+                              ((c.mod != nullptr) != (labels->mod_cats != nullptr)) ||
                               (labels->mod_cats != nullptr && (labels->can_mods_offsets == nullptr || labels->mod_cat_weights == nullptr))))
         return 1;
-    if (max_seqlen == 0) max_seqlen = nblk + 1;
+    const size_t max_seqlen = c.max_seqlen != 0 ? c.max_seqlen : c.nblk + 1;
     const CrfShape sh = crf_pick_shape(max_seqlen);
     if ((size_t)sh.R * sh.W * WAVE < max_seqlen || sh.R > 4) return 2;
-    const bool mod = modidx != nullptr;
+    const bool mod = c.mod != nullptr, g = c.grad != nullptr;
     // the linear path's block length for this sharpening factor; when the workspace the caller brought is
     // too small for it (sized without the factor: tk_crf_flipflop_workspace_bytes) but large enough for the
     // log-domain kernel on every read, that kernel does the call
-    BandBlock blk = crf_band_pick_block(sharp_can, mod, max_seqlen, mod && mod_col_weights != nullptr, nblk,
-                                        labels != nullptr ? labels->bulk_seqlen : 0);
-    bool band = crf_pick_mode(ntrans, nblk, nbatch, max_seqlen, grad != nullptr, blk.bk) == CRF_BAND;
+    const BandBlock blk = crf_band_pick_block(c.sharp_can, mod, max_seqlen, mod && c.mod_col_weights != nullptr, c.nblk,
+                                              labels != nullptr ? labels->bulk_seqlen : 0);
+    bool band = crf_pick_mode(c.ntrans, c.nblk, c.nbatch, max_seqlen, g, blk.bk) == CRF_BAND;
     // the second chance for what the batch's launch disowns (round 6); left out when the workspace the caller brought has no
     // room for it (sized by an older query): such reads go straight to the log-domain kernel, as in round 5
-    BandBlock rblk = band ? crf_band_pick_retry(sharp_can, blk) : BandBlock{0, 0.f, 0};
-    const size_t retry_slots = crf_band_retry_slots(nbatch);
-    const BandLayout bl = crf_band_layout(ntrans, nblk, nbatch, max_seqlen, mod, grad != nullptr, blk.bk > 0 ? blk.bk : 8);
-    const size_t band_bytes = band ? bl.total : 0;
-    // (the tail launch has its own cells per lane: the retry's sweeps run side by side when 2 W waves fit its 16)
-    const int tailR = crf_band_retry_R(max_seqlen);
-    const CrfShape tsh = crf_tail_shape(tailR);
-    const size_t tail_ckpt = crf_ckpt_bytes(nblk, retry_slots, tsh, grad != nullptr);
-    size_t retry_bytes = (band && rblk.bk > 0) ? crf_band_layout(ntrans, nblk, retry_slots, max_seqlen, mod, true, rblk.bk, tailR).total : 0;
-    if (band && tail_ckpt + band_bytes + retry_bytes > workspace_bytes) {
+    BandBlock rblk = band ? crf_band_pick_retry(c.sharp_can, blk) : BandBlock{0, 0.f, 0};
+    auto plan = [&](int bk, int rbk) { return crf_plan(c.ntrans, c.nblk, c.nbatch, max_seqlen, mod, g, bk, rbk); };
+    CrfPlan p = plan(band ? blk.bk : 0, rblk.bk);
+    if (band && p.total > c.workspace_bytes) {
         rblk.bk = 0;
-        retry_bytes = 0;
+        p = plan(blk.bk, 0);
     }
-    if (band && tail_ckpt + band_bytes > workspace_bytes)
+    if (band && p.total > c.workspace_bytes) {
         band = false;
-    if (!band && crf_ckpt_bytes(nblk, nbatch, sh, grad != nullptr) > workspace_bytes) return 3;
+        p = plan(0, 0);
+    }
+    if (!band && p.total > c.workspace_bytes) return 3;
     if (labels != nullptr && !band) {
         // the index arrays are OUTPUTS of this call; the band launch builds them itself, this path takes the
         // stand-alone kernel (tk_flipflop_build_indices_dev's)
-        const int rc = build_indices_dispatch(labels->seqs, seqlen, nbatch, labels->nbase, labels->mod_cats,
-                                              labels->can_mods_offsets, labels->mod_cat_weights, const_cast<int64_t *>(seqoff),
-                                              const_cast<int32_t *>(stayidx), const_cast<int32_t *>(moveidx),
-                                              const_cast<int32_t *>(modidx), const_cast<float *>(modfact), labels->total_len,
-                                              status, stream);
+        const int rc = build_indices_dispatch(labels->seqs, c.seqlen, c.nbatch, labels->nbase, labels->mod_cats,
+                                              labels->can_mods_offsets, labels->mod_cat_weights, const_cast<int64_t *>(c.seqoff),
+                                              const_cast<int32_t *>(c.stay), const_cast<int32_t *>(c.move),
+                                              const_cast<int32_t *>(c.mod), const_cast<float *>(c.modfact), labels->total_len,
+                                              c.status, c.stream);
         if (rc != 0) return rc;
     }
+    char *wb = static_cast<char *>(c.workspace);
+    // (ids from the labels wherever the band launch took them: it wrote no index array)
     CrfArgs a;
-    a.lp = logprob;
-    a.T = (int)nblk;
-    a.N = (int)nbatch;
-    a.S = (int)ntrans;
-    a.ncan = (int)ncan;
-    a.stay = stayidx;
-    a.move = moveidx;
-    a.mod = modidx;
-    a.modfact = modfact;
-    a.seqlen = seqlen;
-    a.seqoff = seqoff;
-    a.c_can = sharp_can * LOG2E;
-    a.c_mod = sharp_mod * LOG2E;
-    a.out_scale = out_scale;
-    a.grad_scale = grad_scale;
-    a.grad_scale_vec = grad_scale_vec;
-    a.add_grad = add_grad;
-    a.add_cost = add_cost;
-    a.add_S = add_S;
-    a.add_scale = add_scale;
-    a.cost = cost;
-    a.grad = grad;
-    a.codes = a.mod_cats = a.cmo = nullptr;
-    a.mcw = nullptr;
-    a.nbase = 0;
-    a.status = status;
-    char *wb = static_cast<char *>(workspace);
+    crf_fill_args(a, c, band ? labels : nullptr);
+    a.ckpt = reinterpret_cast<float *>(wb + p.ck);
+    a.ckoff = reinterpret_cast<double *>(wb + p.ck + p.ckcols);
     // (what add_grad / add_cost hold may come from another stream: the band path waits between its sweeps
     // and its gradient pass, the single-launch form before it starts)
-    if (add_ready != nullptr && !(band && grad != nullptr) && hipStreamWaitEvent(stream, add_ready, 0) != hipSuccess) return 4;
-    if (band) {
-        const bool g = grad != nullptr;
-        const BandLayout l = bl;
-        BandArgs b;
-        b.lp = logprob;
-        b.T = (int)nblk;
-        b.N = (int)nbatch;
-        b.S = (int)ntrans;
-        b.ncan = (int)ncan;
-        b.stay = stayidx;
-        b.move = moveidx;
-        b.mod = modidx;
-        b.modfact = modfact;
-        b.seqlen = seqlen;
-        b.seqoff = seqoff;
-        b.c_can = sharp_can * LOG2E;
-        b.c_mod = sharp_mod * LOG2E;
-        b.out_scale = out_scale;
-        b.grad_scale = grad_scale;
-        b.grad_scale_vec = grad_scale_vec;
-        b.add_grad = add_grad;
-        b.add_cost = add_cost;
-        b.add_S = add_S;
-        b.add_scale = add_scale;
-        b.cost = cost;
-        b.grad = grad;
-        b.status = status;
-        b.W = l.W;
-        b.LP = (int)l.LP;
-        b.Wp = (int)(l.LP / WAVE);
-        b.ckFm = g ? reinterpret_cast<float *>(wb + l.ckFm) : nullptr;
-        b.ckBm = g ? reinterpret_cast<float *>(wb + l.ckBm) : nullptr;
-        b.ckFf = g ? reinterpret_cast<int16_t *>(wb + l.ckFf) : nullptr;
-        b.ckBf = g ? reinterpret_cast<int16_t *>(wb + l.ckBf) : nullptr;
-        b.ckFb = g ? reinterpret_cast<int *>(wb + l.ckFb) : nullptr;
-        b.ckBb = g ? reinterpret_cast<int *>(wb + l.ckBb) : nullptr;
-        b.bndF = g ? reinterpret_cast<float *>(wb + l.bndF) : nullptr;
-        b.bndB = g ? reinterpret_cast<float *>(wb + l.bndB) : nullptr;
-        b.scoreF = reinterpret_cast<double *>(wb + l.scoreF);
-        b.scoreB = reinterpret_cast<double *>(wb + l.scoreB);
-        b.rec = g ? reinterpret_cast<uint32_t *>(wb + l.rec) : nullptr;
-        b.segend = g ? reinterpret_cast<int *>(wb + l.segend) : nullptr;
-        b.gate = reinterpret_cast<int *>(wb + l.gate);
-        b.gate2 = reinterpret_cast<int *>(wb + l.gate2);
-        b.anygate = g ? reinterpret_cast<int *>(wb + l.anygate) : nullptr;
-        b.zeros = reinterpret_cast<const float *>(wb + l.zeros);
-        b.dbg = nullptr;
-        b.before_gradient = add_ready;
-        b.colw = mod ? mod_col_weights : nullptr;
-        b.wbias = blk.wbias;
-        b.klip = blk.klip;
-        // (a batch of empty reads has no label array: any non-null pointer says "build here", nothing reads it)
-        b.codes = labels != nullptr ? (labels->seqs != nullptr ? labels->seqs : stayidx) : nullptr;
-        b.mod_cats = labels != nullptr ? labels->mod_cats : nullptr;
-        b.cmo = labels != nullptr ? labels->can_mods_offsets : nullptr;
-        b.mcw = labels != nullptr ? labels->mod_cat_weights : nullptr;
-        b.total_len = labels != nullptr ? (long long)labels->total_len : 0;
-        b.nbase = labels != nullptr ? (int)labels->nbase : 0;
-        const int rc = crf_band_dispatch(b, l.R, mod, blk.bk, stream);
-        if (rc != 0) return rc;
-        if (TK_LAB_ENV("TK_CRF_GATE_DUMP")) {                       // lab: how many reads did the band path disown?
-            (void)hipStreamSynchronize(stream);
-            static int hostg[1 << 16];
-            const size_t ng = nbatch < (1u << 16) ? nbatch : (1u << 16);
-            (void)hipMemcpy(hostg, b.gate, ng * sizeof(int), hipMemcpyDeviceToHost);
-            size_t cnt = 0, why[8] = {0};
-            for (size_t i = 0; i < ng; ++i) {
-                cnt += hostg[i] != 0;
-                ++why[hostg[i] & 7];
-            }
-            fprintf(stderr, "crf band: %zu of %zu reads gated (non-finite score %zu, sweeps disagree %zu, row lost mass %zu)\n",
-                    cnt, ng, why[1], why[4], why[2]);
-            for (size_t i = 0, shown = 0; i < ng && shown < 16; ++i)
-                if (hostg[i]) fprintf(stderr, "crf band:   read %zu (reason %d)\n", i, hostg[i]), ++shown;
-        }
-        // THE TAIL LAUNCH (round 6; crf_band.hip: crf_band_tail_kernel): the reads the batch's launch disowned, once more on
-        // the linear path -- alone, 4-step blocks, steep frames -- and what that disowns too, redone in the log domain by the
-        // same workgroup.  One launch; it finds nothing to do on the inputs a network produces.
-        BandArgs c = b;
-        c.gate = nullptr;
-        c.gate2 = nullptr;
-        c.anygate = nullptr;
-        if (rblk.bk > 0) {
-            const BandLayout q = crf_band_layout(ntrans, nblk, retry_slots, max_seqlen, mod, true, rblk.bk, tailR);
-            char *wr = wb + l.total;
-            c.W = q.W;
-            c.LP = (int)q.LP;
-            c.Wp = (int)(q.LP / WAVE);
-            c.ckFm = reinterpret_cast<float *>(wr + q.ckFm);
-            c.ckBm = reinterpret_cast<float *>(wr + q.ckBm);
-            c.ckFf = reinterpret_cast<int16_t *>(wr + q.ckFf);
-            c.ckBf = reinterpret_cast<int16_t *>(wr + q.ckBf);
-            c.ckFb = reinterpret_cast<int *>(wr + q.ckFb);
-            c.ckBb = reinterpret_cast<int *>(wr + q.ckBb);
-            c.bndF = reinterpret_cast<float *>(wr + q.bndF);
-            c.bndB = reinterpret_cast<float *>(wr + q.bndB);
-            c.scoreF = reinterpret_cast<double *>(wr + q.scoreF);
-            c.scoreB = reinterpret_cast<double *>(wr + q.scoreB);
-            c.rec = reinterpret_cast<uint32_t *>(wr + q.rec);
-            c.segend = reinterpret_cast<int *>(wr + q.segend);
-            c.wbias = rblk.wbias;
-            c.klip = rblk.klip;
-        }
-        // (the offsets and -- a call that brought index arrays -- the ids are the batch launch's; a launch that built its
-        // ids from the labels left seqoff behind, and the tail forms its ids from the codes as well)
-        BandRetry r;
-        r.gate = b.gate;
-        r.gate2 = b.gate2;
-        r.firstF = g ? nullptr : b.scoreF;
-        r.firstB = g ? nullptr : b.scoreB;
-        r.first_wbias = blk.wbias;
-        r.anygate = b.anygate;
-        r.retry = rblk.bk > 0 ? 1 : 0;
-        r.log_domain = 1;
-        if (const char *e = TK_LAB_ENV("TK_CRF_NO_FALLBACK"))       // lab: time / test the linear path alone
-            if (e[0] == '1') r.log_domain = 0;
-        a.codes = b.codes;      // (ids from the labels wherever the band launch took them: it wrote no index array)
-        a.mod_cats = b.mod_cats;
-        a.cmo = b.cmo;
-        a.mcw = b.mcw;
-        a.nbase = b.nbase;
-        wb += l.total + retry_bytes;
-        {
-            const int CK = crf_ck(tsh.R, tsh.W, mod ? 3 : 2);
-            const size_t NK = (nblk + CK - 1) / CK;
-            const size_t ckb = (retry_slots * NK * (size_t)tsh.R * tsh.W * WAVE * sizeof(float) + 255) / 256 * 256;
-            a.ckpt = reinterpret_cast<float *>(wb);
-            a.ckoff = reinterpret_cast<double *>(wb + (grad ? ckb : 0));
-        }
-        const int rr = crf_band_tail_dispatch(c, r, a, tailR, mod, retry_slots, stream);
-        if (rr != 0) return rr;
-        if (TK_LAB_ENV("TK_CRF_GATE_DUMP")) {
-            (void)hipStreamSynchronize(stream);
-            static int h1[1 << 16], h2[1 << 16];
-            const size_t ng = nbatch < (1u << 16) ? nbatch : (1u << 16);
-            (void)hipMemcpy(h1, b.gate, ng * sizeof(int), hipMemcpyDeviceToHost);
-            (void)hipMemcpy(h2, b.gate2, ng * sizeof(int), hipMemcpyDeviceToHost);
-            size_t tried = 0, kept = 0;
-            for (size_t i = 0; i < ng; ++i) {
-                tried += h2[i] != -1;
-                kept += h2[i] == 0;
-            }
-            fprintf(stderr, "crf band tail (retry: bk %d, bias %.1f, slope %d): %zu reads taken, %zu kept on the linear path\n", rblk.bk, rblk.wbias, rblk.klip, tried, kept);
-            for (size_t i = 0, shown = 0; i < ng && shown < 16; ++i)
-                if (h2[i] > 0) fprintf(stderr, "crf band tail:   read %zu first %d retry %d\n", i, h1[i], h2[i]), ++shown;
-        }
-        return 0;
+    if (c.add_ready != nullptr && !(band && g) && hipStreamWaitEvent(c.stream, c.add_ready, 0) != hipSuccess) return 4;
+    if (!band) return mod ? crf_launch_mod<true>(p.sh, a, c.stream, c.nbatch) : crf_launch_mod<false>(p.sh, a, c.stream, c.nbatch);
+
+    BandArgs b;
+    crf_fill_args(b, c, labels);
+    b.total_len = labels != nullptr ? (long long)labels->total_len : 0;
+    crf_bind_layout(b, p.band, wb, g);
+    b.gate = reinterpret_cast<int *>(wb + p.band.gate);
+    b.gate2 = reinterpret_cast<int *>(wb + p.band.gate2);
+    b.anygate = g ? reinterpret_cast<int *>(wb + p.band.anygate) : nullptr;
+    b.zeros = reinterpret_cast<const float *>(wb + p.band.zeros);
+    b.dbg = nullptr;
+    b.before_gradient = c.add_ready;
+    b.colw = mod ? c.mod_col_weights : nullptr;
+    b.wbias = blk.wbias;
+    b.klip = blk.klip;
+    const int rc = crf_band_dispatch(b, p.band.R, mod, blk.bk, c.stream);
+    if (rc != 0) return rc;
+    crf_gate_dump(b, nullptr, c.nbatch, c.stream);
+    // THE TAIL LAUNCH (round 6; crf_band.hip: crf_band_tail_kernel): the reads the batch's launch disowned, once more on
+    // the linear path -- alone, 4-step blocks, steep frames -- and what that disowns too, redone in the log domain by the
+    // same workgroup.  One launch; it finds nothing to do on the inputs a network produces.
+    BandArgs t = b;
+    t.gate = nullptr;
+    t.gate2 = nullptr;
+    t.anygate = nullptr;
+    if (rblk.bk > 0) {
+        crf_bind_layout(t, p.retry, wb + p.band.total, true);
+        t.wbias = rblk.wbias;
+        t.klip = rblk.klip;
     }
-    {
-        const int CK = crf_ck(sh.R, sh.W, mod ? 3 : 2);
-        const size_t NK = (nblk + CK - 1) / CK;
-        const size_t ckb = (nbatch * NK * (size_t)sh.R * sh.W * WAVE * sizeof(float) + 255) / 256 * 256;
-        a.ckpt = reinterpret_cast<float *>(wb);
-        a.ckoff = reinterpret_cast<double *>(wb + (grad ? ckb : 0));
-    }
-    return mod ? crf_launch_mod<true>(sh, a, stream, nbatch) : crf_launch_mod<false>(sh, a, stream, nbatch);
+    // (the offsets and -- a call that brought index arrays -- the ids are the batch launch's; a launch that built its
+    // ids from the labels left seqoff behind, and the tail forms its ids from the codes as well)
+    BandRetry r;
+    r.gate = b.gate;
+    r.gate2 = b.gate2;
+    r.firstF = g ? nullptr : b.scoreF;
+    r.firstB = g ? nullptr : b.scoreB;
+    r.first_wbias = blk.wbias;
+    r.anygate = b.anygate;
+    r.retry = rblk.bk > 0 ? 1 : 0;
+    r.log_domain = 1;
+    if (const char *e = TK_LAB_ENV("TK_CRF_NO_FALLBACK"))       // lab: time / test the linear path alone
+        if (e[0] == '1') r.log_domain = 0;
+    // (the tail launch has its own cells per lane: the retry's sweeps run side by side when 2 W waves fit its 16)
+    const int rr = crf_band_tail_dispatch(t, r, a, crf_band_retry_R(max_seqlen), mod, p.nslots, c.stream);
+    if (rr != 0) return rr;
+    crf_gate_dump(b, &rblk, c.nbatch, c.stream);
+    return 0;
 }
 
 }  // namespace tk

@@ -10,7 +10,6 @@ averaged over the launches.
 The JSON (with the kernel-source hash) is what bench.py's `roofline_crf.*.issue_floor_us` is computed from."""
 import argparse
 import collections
-import hashlib
 import json
 import os
 import shutil
@@ -27,13 +26,10 @@ KEYS = {"cfg2r": "crf:800:128:4000", "rowK": "crf:4000:256:0", "cfg5r": "crf:160
 
 
 def kernel_hash():
-    h = hashlib.sha256()
-    d = os.path.join(ROOT, "taiyaki_amd", "csrc")
-    for name in sorted(os.listdir(d)):
-        if name.endswith((".hip", ".h")):
-            with open(os.path.join(d, name), "rb") as fh:
-                h.update(fh.read())
-    return h.hexdigest()[:16]
+    # bench.py's own hash (it covers crf_band_posterior.inc as well): the one its issue floor is compared against
+    sys.path.insert(0, ROOT)
+    import bench
+    return bench.kernel_hash()
 
 
 def read(db):
