@@ -61,6 +61,8 @@ extern "C" {
 #define TK_STATUS_NONFINITE_GRAD 2u
 #define TK_STATUS_SEQS_OVERFLOW 4u      /* tk_chunks_gather_dev: seqs buffer too small */
 #define TK_STATUS_SEQ_TOO_LONG 16u      /* CRF: a sequence longer than the max_seqlen the launch was sized for */
+#define TK_STATUS_LSTM_TIMEOUT 32u      /* LSTM recurrence: a workgroup waited past its clock budget for its group
+                                           (the launch's outputs are not valid) */
 #define TK_STATUS_BAD_LABEL 8u          /* tk_flipflop_build_indices_dev: a flip-flop code outside
                                            [0, 2 nbase), a mod category outside its base's range, or
                                            sum(seqlen) > total_len (the reference asserts that move /
@@ -277,6 +279,28 @@ size_t tk_flipflop_logz_workspace_bytes(size_t nblk, size_t nbatch, size_t nbase
 
 int tk_flipflop_logz_dev(const float *scores, size_t nblk, size_t nbatch,
                          size_t nbase, float *logz, float *grad, void *workspace,
+                         size_t workspace_bytes, uint32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * LSTM recurrence of one nn.LSTM layer (layers.Lstm; gate order i, f, g, o;
+ * h0 = c0 = 0), one persistent launch per call (csrc/lstm_kernels.hip).
+ *   gx (T, N, 4H) = x W_ih^T + b_ih + b_hh; w_hh (4H, H); reverse != 0 runs the
+ *   recurrence from t = T-1 down to 0 (layers.Reverse) with every tensor in time order.
+ *   forward: y (T, N, H) = h, gates (T, N, 4H) = the activations i, f, g, o, cell (T, N, H) = c.
+ *   backward: dy (T, N, H) = dL/dy -> dgates (T, N, 4H) = dL/d(gate pre-activation).
+ * tk_lstm_workspace_bytes: the workspace either call needs at (nbatch, size) on a device with
+ * cu_count CUs, 0 where the kernels do not run (the caller falls back to nn.LSTM);
+ * the same cu_count goes to both calls.  TK_STATUS_LSTM_TIMEOUT in *status if a
+ * workgroup's wait for its group ran out of time.
+ * ------------------------------------------------------------------------- */
+size_t tk_lstm_workspace_bytes(size_t nbatch, size_t size, int cu_count);
+
+int tk_lstm_forward_dev(const float *gx, const float *w_hh, size_t nblk, size_t nbatch, size_t size, int reverse,
+                        int cu_count, float *y, float *gates, float *cell, void *workspace, size_t workspace_bytes,
+                        uint32_t *status, void *stream);
+
+int tk_lstm_backward_dev(const float *w_hh, const float *gates, const float *cell, const float *dy, size_t nblk,
+                         size_t nbatch, size_t size, int reverse, int cu_count, float *dgates, void *workspace,
                          size_t workspace_bytes, uint32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------- *

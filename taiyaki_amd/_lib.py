@@ -51,6 +51,9 @@ SIGNATURES = {
     "tk_flipflop_viterbi_dev": (_i, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tk_flipflop_errprobs_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "tk_devcopy_f32_dev": (_i, [_vp, _vp, _sz, _vp]),
+    "tk_lstm_workspace_bytes": (_sz, [_sz, _sz, _i]),
+    "tk_lstm_forward_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "tk_lstm_backward_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _sz, _vp, _vp]),
     "tk_grad_maxabs_clip_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "tk_flipflop_remap_dev": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     "tk_remap_path_to_ref_to_signal_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp]),
@@ -91,7 +94,7 @@ ERRORS = {1: "bad argument (NULL / shape / 16-byte alignment)",
           2: "unsupported nbase / ntrans / sequence length for this build",
           3: "workspace too small", 4: "HIP launch failure"}
 
-LAB_SIGNATURES = {"tk_lab_crf_band_phase": (None, [_i])}
+LAB_SIGNATURES = {"tk_lab_crf_band_phase": (None, [_i]), "tk_lab_lstm_cols": (None, [_i])}
 
 _lib = None
 _handles = {}
@@ -315,6 +318,9 @@ def _raise(bits):
         raise AssertionError("Error: sequence labels out of range for the flip-flop model (flip-flop code "
                              "outside [0, 2 nbase), modification category outside its base's range, or "
                              "sum(seqlen) larger than the label array)")
+    if bits & 32:
+        raise RuntimeError("LSTM recurrence: a workgroup waited past its time budget for the rest of its group "
+                           "(the layer's outputs are not valid)")
     if bits & 16:
         raise RuntimeError("a sequence is longer than the max_seqlen the CRF kernel was launched for")
     if bits & 4:

@@ -67,6 +67,16 @@ struct RemapArgs {
     const int64_t *tb_off;
 };
 int remap_dispatch(const RemapArgs &a, size_t nread, size_t max_M, hipStream_t stream);
+size_t lstm_workspace_bytes(size_t N, size_t H, int cu_count);
+int lstm_forward_dispatch(const float *gx, const float *whh, size_t T, size_t N, size_t H, int reverse,
+                          int cu_count, float *y, float *gates, float *cell, void *ws, size_t wsb,
+                          uint32_t *status, hipStream_t stream);
+int lstm_backward_dispatch(const float *whh, const float *gates, const float *cell, const float *dy, size_t T,
+                           size_t N, size_t H, int reverse, int cu_count, float *dgates, void *ws, size_t wsb,
+                           uint32_t *status, hipStream_t stream);
+#ifdef TK_LAB
+void lstm_lab_cols(int cols);
+#endif
 int path_to_reftosignal_dispatch(const int64_t *path, const int64_t *path_off, const int64_t *ref_off,
                                  const int64_t *signalstart, const int64_t *siglen, int stride, size_t nread,
                                  int32_t *rts, hipStream_t stream);
@@ -458,7 +468,27 @@ int tk_devcopy_f32_dev(float *dst, const float *src, size_t n, void *stream) {
 #ifdef TK_LAB
 // lab hook (lab build only; declared in tools/lab_api.h, not in the public header): see crf_band.hip
 extern "C" void tk_lab_crf_band_phase(int phase) { tk::crf_band_lab_phase(phase); }
+// the LSTM recurrence's batch columns per workgroup, 8 or 16 (0: the launcher's rule; lstm_kernels.hip)
+extern "C" void tk_lab_lstm_cols(int cols) { tk::lstm_lab_cols(cols); }
 #endif
+
+size_t tk_lstm_workspace_bytes(size_t nbatch, size_t size, int cu_count) {
+    return tk::lstm_workspace_bytes(nbatch, size, cu_count);
+}
+
+int tk_lstm_forward_dev(const float *gx, const float *w_hh, size_t nblk, size_t nbatch, size_t size, int reverse,
+                        int cu_count, float *y, float *gates, float *cell, void *workspace, size_t workspace_bytes,
+                        uint32_t *status, void *stream) {
+    return tk::lstm_forward_dispatch(gx, w_hh, nblk, nbatch, size, reverse, cu_count, y, gates, cell, workspace,
+                                     workspace_bytes, status, static_cast<hipStream_t>(stream));
+}
+
+int tk_lstm_backward_dev(const float *w_hh, const float *gates, const float *cell, const float *dy, size_t nblk,
+                         size_t nbatch, size_t size, int reverse, int cu_count, float *dgates, void *workspace,
+                         size_t workspace_bytes, uint32_t *status, void *stream) {
+    return tk::lstm_backward_dispatch(w_hh, gates, cell, dy, nblk, nbatch, size, reverse, cu_count, dgates,
+                                      workspace, workspace_bytes, status, static_cast<hipStream_t>(stream));
+}
 
 int tk_flipflop_lattice_dev(const float *scores, size_t nblk, size_t nbatch, size_t nbase, int forward,
                             const float *init, float *out, float *total, void *stream) {

@@ -5,8 +5,10 @@ that feeds them.
   kernels (csrc/logz_kernels.hip) instead of cupy / the T-step torch loop.
 * ``Convolution``, ``Lstm``, ``GruMod``, ``Reverse``, ``Serial``, ``GlobalNormFlipFlop``
   and ``GlobalNormFlipFlopCatMod`` restate the reference layers minimally on
-  PyTorch-ROCm (MIOpen LSTM/GRU, Conv1d): by scope they STAY PyTorch
+  PyTorch-ROCm (MIOpen GRU, Conv1d): by scope they STAY PyTorch modules
   (BASELINE.json north_star) and only produce the (T, N, S) score tensor.
+  ``Lstm`` keeps its nn.LSTM parameters, but on the GPU its recurrence runs as the
+  persistent HIP kernels of csrc/lstm_kernels.hip (`LstmRecurrence`).
 """
 import numpy as np
 import torch
@@ -150,11 +152,105 @@ class _Rnn(nn.Module):
         return self.rnn(x)[0]
 
 
+# False: every Lstm runs nn.LSTM (MIOpen on the GPU), for comparisons against the HIP recurrence
+USE_HIP_LSTM = True
+_CU_COUNT = {}
+
+
+def _cu_count(dev):
+    n = _CU_COUNT.get(dev.index)
+    if n is None:
+        n = _CU_COUNT[dev.index] = torch.cuda.get_device_properties(dev).multi_processor_count
+    return n
+
+
+def hip_lstm_workspace_bytes(rnn, x):
+    """Workspace of the HIP recurrence for this layer and input, 0 where it does not run (CPU tensors, other
+    dtypes, nn.LSTM options the kernels do not implement, sizes the launch geometry does not cover)."""
+    if not (USE_HIP_LSTM and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
+            and rnn.weight_hh_l0.is_cuda and rnn.weight_hh_l0.dtype == torch.float32):
+        return 0
+    if rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or rnn.batch_first or rnn.proj_size:
+        return 0
+    return _lib.lib().tk_lstm_workspace_bytes(x.shape[1], rnn.hidden_size, _cu_count(x.device))
+
+
+class LstmRecurrence(torch.autograd.Function):
+    """One nn.LSTM layer (h0 = c0 = 0) with its recurrence on the HIP kernels.  Forward: G_x = x W_ih^T + b_ih +
+    b_hh as one GEMM, then tk_lstm_forward_dev.  Backward: tk_lstm_backward_dev gives dG (the gates'
+    pre-activation gradient, T x N x 4H), the parameter and input gradients are GEMMs / a sum over it.
+    `reverse` runs the recurrence from the last time step (layers.Reverse) on tensors in time order."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, wsb):
+        T, N, _ = x.shape
+        H = w_hh.shape[1]
+        dev = x.device
+        L = _lib.lib()
+        x = x.contiguous()
+        w_hh = w_hh.contiguous()
+        gx = torch.addmm(b_ih + b_hh, x.view(T * N, -1), w_ih.t())
+        y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
+        gates = torch.empty(T, N, 4 * H, dtype=torch.float32, device=dev)
+        cell = torch.empty(T, N, H, dtype=torch.float32, device=dev)
+        ws = _lib.workspace(wsb, dev, "lstm")
+        status = _lib.status_word(dev)
+        rc = L.tk_lstm_forward_dev(_lib.ptr(gx), _lib.ptr(w_hh), T, N, H, int(reverse), _cu_count(dev),
+                                   _lib.ptr(y), _lib.ptr(gates), _lib.ptr(cell), _lib.ptr(ws), wsb,
+                                   _lib.ptr(status), _lib.stream_ptr())
+        _lib.check(rc, "tk_lstm_forward_dev")
+        _lib.finish(status)
+        ctx.save_for_backward(x, w_ih, w_hh, y, gates, cell)
+        ctx.reverse, ctx.wsb = reverse, wsb
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w_ih, w_hh, y, gates, cell = ctx.saved_tensors
+        T, N, I = x.shape
+        H = w_hh.shape[1]
+        dev = x.device
+        dy = dy.contiguous()
+        dg = torch.empty_like(gates)
+        ws = _lib.workspace(ctx.wsb, dev, "lstm")
+        status = _lib.status_word(dev)
+        rc = _lib.lib().tk_lstm_backward_dev(_lib.ptr(w_hh), _lib.ptr(gates), _lib.ptr(cell), _lib.ptr(dy), T, N,
+                                             H, int(ctx.reverse), _cu_count(dev), _lib.ptr(dg), _lib.ptr(ws),
+                                             ctx.wsb, _lib.ptr(status), _lib.stream_ptr())
+        _lib.check(rc, "tk_lstm_backward_dev")
+        _lib.finish(status)
+        dg2 = dg.view(T * N, 4 * H)
+        need = ctx.needs_input_grad
+        dx = (dg2 @ w_ih).view(T, N, I) if need[0] else None
+        dw_ih = dg2.t() @ x.view(T * N, I) if need[1] else None
+        dw_hh = None
+        if need[2]:
+            # dW_hh = sum over steps of dG_t^T h_prev, h_prev = the output of the recurrence's previous step
+            if T > 1:
+                dgs, hp = (dg[:-1], y[1:]) if ctx.reverse else (dg[1:], y[:-1])
+                dw_hh = dgs.reshape(-1, 4 * H).t() @ hp.reshape(-1, H)
+            else:
+                dw_hh = torch.zeros_like(w_hh)
+        db = dg2.sum(0) if (need[3] or need[4]) else None
+        return dx, dw_ih, dw_hh, db if need[3] else None, db if need[4] else None, None, None
+
+
 class Lstm(_Rnn):
-    """layers.py:491-606 (wraps nn.LSTM, bias_hh frozen)"""
+    """layers.py:491-606 (wraps nn.LSTM, bias_hh frozen).  On the GPU the recurrence runs on the HIP kernels
+    (`LstmRecurrence`); nn.LSTM evaluates CPU tensors, sizes the kernels do not cover, and USE_HIP_LSTM = False."""
 
     def __init__(self, insize, size):
         super().__init__(nn.LSTM(insize, size))
+
+    def forward(self, x, reverse=False):
+        rnn = self.rnn
+        wsb = hip_lstm_workspace_bytes(rnn, x)
+        if wsb:
+            return LstmRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
+                                        bool(reverse), wsb)
+        if reverse:
+            return torch.flip(rnn(torch.flip(x, (0,)))[0], (0,))
+        return rnn(x)[0]
 
 
 class GruMod(_Rnn):
@@ -172,6 +268,8 @@ class Reverse(nn.Module):
         self.layer = layer
 
     def forward(self, x):
+        if isinstance(self.layer, Lstm):
+            return self.layer(x, reverse=True)      # (the HIP recurrence runs backwards in time itself)
         return torch.flip(self.layer(torch.flip(x, (0,))), (0,))
 
 
