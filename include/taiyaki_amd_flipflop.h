@@ -21,6 +21,8 @@
  *   batch stacking, flip-flop coding)                       tk_chunks_{locate,select,gather}_dev
  *   taiyaki/flipflop_remap.py:6-88 map_to_crf_viterbi       tk_flipflop_remap_dev
  *   taiyaki/signal_mapping.py:202-316 from_remapping_path   tk_remap_path_to_ref_to_signal_dev
+ *   taiyaki/squiggle_match/c_squiggle_match.c:457-694       tk_squiggle_match_{cost,grad,path}_dev
+ *      (squiggle_match.pyx:27-97)
  *
  * Conventions
  *  - plain C: pointers and sizes only, no torch / HIP types in the signatures
@@ -63,6 +65,8 @@ extern "C" {
 #define TK_STATUS_SEQ_TOO_LONG 16u      /* CRF: a sequence longer than the max_seqlen the launch was sized for */
 #define TK_STATUS_LSTM_TIMEOUT 32u      /* LSTM recurrence: a workgroup waited past its clock budget for its group
                                            (the launch's outputs are not valid) */
+#define TK_STATUS_BAD_SIGLEN 64u        /* squiggle match: a siglen <= 0, or reads that run past the end of
+                                           the signal vector (the reference asserts or reads out of bounds) */
 #define TK_STATUS_BAD_LABEL 8u          /* tk_flipflop_build_indices_dev: a flip-flop code outside
                                            [0, 2 nbase), a mod category outside its base's range, or
                                            sum(seqlen) > total_len (the reference asserts that move /
@@ -430,6 +434,48 @@ int tk_remap_path_to_ref_to_signal_dev(const int64_t *path, const int64_t *path_
                                        const int64_t *ref_off, const int64_t *signalstart,
                                        const int64_t *siglen, size_t stride, size_t nread,
                                        int32_t *ref_to_signal, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * Squiggle match (taiyaki/squiggle_match: c_squiggle_match.c, squiggle_match.pyx:27-97), one wave
+ * per read (csrc/squiggle_kernels.hip).
+ *   params   (npos, nbatch, 3) float32, C-contiguous: level, log-scale, move logit of position p
+ *            of read b at params[(p * nbatch + b) * 3 + k]
+ *   signal   nsignal float32: every read's samples back to back
+ *   siglen   (nbatch) int32;  sig_off (nbatch + 1) int64, its exclusive prefix sum (sig_off[0] = 0):
+ *            read b owns signal[sig_off[b] .. sig_off[b] + siglen[b])
+ *   back_prob  probability of entering a back state
+ * A read with siglen <= 0 or one that runs past nsignal sets TK_STATUS_BAD_SIGLEN in *status
+ * (nullable) and gets NaN outputs.  1 <= npos <= 1024 (TK_ERR_UNSUPPORTED beyond).
+ *
+ * tk_squiggle_match_workspace_bytes: op 0 cost, 1 grad (the forward lattice: (nsignal + nbatch)
+ *   columns of 2 * 64 ceil-bucketed positions), 2 path (a byte per sample and position plus an
+ *   int32 per sample).  0 for npos outside the build's range.
+ * tk_squiggle_match_cost_dev: cost (nbatch) = -forward score (squiggle_match.pyx:47).  With a
+ *   workspace (>= op 1 bytes) it also leaves the forward lattice there, for a grad call with
+ *   have_forward = 1 on the same inputs; workspace may be NULL otherwise.
+ * tk_squiggle_match_grad_dev: grad (npos, nbatch, 3) = -gradient of c_squiggle_match.c:591-694 as
+ *   written there (squiggle_match.pyx:73); cost (nullable) as above.  have_forward = 0 runs the
+ *   forward sweep itself.
+ * tk_squiggle_match_path_dev: Viterbi of c_squiggle_match.c:270-454; cost (nbatch) = -score,
+ *   path (nsignal) int32: read b's at sig_off[b], -1 in the start / end states, else the position
+ *   (a back state reports its position).  localpen / minscore: the reference's, already resolved
+ *   (None = 50000). */
+size_t tk_squiggle_match_workspace_bytes(int op, size_t npos, size_t nbatch, size_t nsignal);
+
+int tk_squiggle_match_cost_dev(const float *params, const float *signal, const int32_t *siglen,
+                               const int64_t *sig_off, size_t npos, size_t nbatch, size_t nsignal,
+                               float back_prob, float *cost, void *workspace, size_t workspace_bytes,
+                               uint32_t *status, void *stream);
+
+int tk_squiggle_match_grad_dev(const float *params, const float *signal, const int32_t *siglen,
+                               const int64_t *sig_off, size_t npos, size_t nbatch, size_t nsignal,
+                               float back_prob, int have_forward, float *cost, float *grad, void *workspace,
+                               size_t workspace_bytes, uint32_t *status, void *stream);
+
+int tk_squiggle_match_path_dev(const float *params, const float *signal, const int32_t *siglen,
+                               const int64_t *sig_off, size_t npos, size_t nbatch, size_t nsignal,
+                               float back_prob, float localpen, float minscore, float *cost, int32_t *path,
+                               void *workspace, size_t workspace_bytes, uint32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Exact reference prototypes (HOST pointers; taiyaki/ctc/c_crf_flipflop.h:3-11,

@@ -54,6 +54,11 @@ SIGNATURES = {
     "tk_lstm_workspace_bytes": (_sz, [_sz, _sz, _i]),
     "tk_lstm_forward_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "tk_lstm_backward_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _sz, _vp, _vp]),
+    "tk_squiggle_match_workspace_bytes": (_sz, [_i, _sz, _sz, _sz]),
+    "tk_squiggle_match_cost_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _f, _vp, _vp, _sz, _vp, _vp]),
+    "tk_squiggle_match_grad_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _f, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "tk_squiggle_match_path_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _f, _f, _f, _vp, _vp, _vp, _sz, _vp,
+                                       _vp]),
     "tk_grad_maxabs_clip_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "tk_flipflop_remap_dev": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     "tk_remap_path_to_ref_to_signal_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp]),
@@ -313,6 +318,9 @@ def retried_total():
 
 def _raise(bits):
     bits = _u32(bits) & 0xff
+    if bits & 64:
+        # the reference asserts nsample > 0 (c_squiggle_match.c:112) and reads past the signal otherwise
+        raise ValueError("squiggle match: a siglen is <= 0, or sum(siglen) exceeds len(signal)")
     if bits & 8:
         # the reference: `assert np.all(stayidxs >= 0) and ...` style index checks in ctc.pyx
         raise AssertionError("Error: sequence labels out of range for the flip-flop model (flip-flop code "

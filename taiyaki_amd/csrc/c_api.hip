@@ -11,6 +11,7 @@
 
 #include "../../include/taiyaki_amd_flipflop.h"
 #include "crf_band.h"
+#include "squiggle_match.h"
 
 namespace tk {
 size_t logz_workspace_bytes(size_t T, size_t N, size_t nbase);
@@ -133,6 +134,84 @@ int tk_remap_path_to_ref_to_signal_dev(const int64_t *path, const int64_t *path_
     if (nread > (size_t)INT32_MAX || stride > (size_t)INT32_MAX) return TK_ERR_UNSUPPORTED;
     return tk::path_to_reftosignal_dispatch(path, path_off, ref_off, signalstart, siglen, (int)stride, nread,
                                             ref_to_signal, static_cast<hipStream_t>(stream));
+}
+
+// squiggle match: the checks every entry shares (lengths themselves are checked on the device)
+static int sq_args(tk::SqArgs &a, const float *params, const float *signal, const int32_t *siglen,
+                   const int64_t *sig_off, size_t npos, size_t nbatch, size_t nsignal, float back_prob,
+                   uint32_t *status) {
+    if (!params || !signal || !siglen || !sig_off || npos == 0 || nbatch == 0) return TK_ERR_BAD_ARG;
+    if (tk::sq_positions_per_lane(npos) == 0 || nbatch > (size_t)INT32_MAX || nsignal > (size_t)INT64_MAX / 2)
+        return TK_ERR_UNSUPPORTED;
+    a = tk::SqArgs{};
+    a.params = params;
+    a.signal = signal;
+    a.siglen = siglen;
+    a.sig_off = sig_off;
+    a.nbatch = (int)nbatch;
+    a.npos = (int)npos;
+    a.nsignal = (int64_t)nsignal;
+    a.prob_back = back_prob;
+    a.status = status;
+    return TK_OK;
+}
+
+size_t tk_squiggle_match_workspace_bytes(int op, size_t npos, size_t nbatch, size_t nsignal) {
+    if (op == 1) return tk::sq_lattice_bytes(npos, nbatch, nsignal);
+    if (op == 2) return tk::sq_path_bytes(npos, nsignal);
+    return 0;
+}
+
+int tk_squiggle_match_cost_dev(const float *params, const float *signal, const int32_t *siglen,
+                               const int64_t *sig_off, size_t npos, size_t nbatch, size_t nsignal,
+                               float back_prob, float *cost, void *workspace, size_t workspace_bytes,
+                               uint32_t *status, void *stream) {
+    tk::SqArgs a;
+    int rc = sq_args(a, params, signal, siglen, sig_off, npos, nbatch, nsignal, back_prob, status);
+    if (rc != TK_OK) return rc;
+    if (!cost) return TK_ERR_BAD_ARG;
+    a.cost = cost;
+    if (workspace) {
+        if (workspace_bytes < tk::sq_lattice_bytes(npos, nbatch, nsignal)) return TK_ERR_WORKSPACE;
+        a.lattice = static_cast<float *>(workspace);
+    }
+    return tk::squiggle_dispatch(workspace ? 1 : 0, a, static_cast<hipStream_t>(stream));
+}
+
+int tk_squiggle_match_grad_dev(const float *params, const float *signal, const int32_t *siglen,
+                               const int64_t *sig_off, size_t npos, size_t nbatch, size_t nsignal,
+                               float back_prob, int have_forward, float *cost, float *grad, void *workspace,
+                               size_t workspace_bytes, uint32_t *status, void *stream) {
+    tk::SqArgs a;
+    int rc = sq_args(a, params, signal, siglen, sig_off, npos, nbatch, nsignal, back_prob, status);
+    if (rc != TK_OK) return rc;
+    if (!grad || !workspace) return TK_ERR_BAD_ARG;
+    if (workspace_bytes < tk::sq_lattice_bytes(npos, nbatch, nsignal)) return TK_ERR_WORKSPACE;
+    a.cost = cost;
+    a.grad = grad;
+    a.lattice = static_cast<float *>(workspace);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!have_forward && (rc = tk::squiggle_dispatch(1, a, s)) != TK_OK) return rc;
+    return tk::squiggle_dispatch(2, a, s);
+}
+
+int tk_squiggle_match_path_dev(const float *params, const float *signal, const int32_t *siglen,
+                               const int64_t *sig_off, size_t npos, size_t nbatch, size_t nsignal,
+                               float back_prob, float localpen, float minscore, float *cost, int32_t *path,
+                               void *workspace, size_t workspace_bytes, uint32_t *status, void *stream) {
+    tk::SqArgs a;
+    int rc = sq_args(a, params, signal, siglen, sig_off, npos, nbatch, nsignal, back_prob, status);
+    if (rc != TK_OK) return rc;
+    if (!cost || !path || !workspace) return TK_ERR_BAD_ARG;
+    if (workspace_bytes < tk::sq_path_bytes(npos, nsignal)) return TK_ERR_WORKSPACE;
+    a.localpen = localpen;
+    a.minscore = minscore;
+    a.cost = cost;
+    a.path = path;
+    a.tb = static_cast<uint8_t *>(workspace);
+    a.endtb = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(workspace) +
+                                          nsignal * 64 * (size_t)tk::sq_positions_per_lane(npos));
+    return tk::squiggle_dispatch(3, a, static_cast<hipStream_t>(stream));
 }
 
 static bool store_ok(const tk_mapped_store *s) {

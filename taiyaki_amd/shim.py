@@ -11,13 +11,14 @@
   `taiyaki_amd.ctc`, `taiyaki.layers.flipflop_logpartition` / `log_partition_flipflop` (layers.py:1875-1890, 1277-1299),
   `taiyaki.decode.flipflop_viterbi` / `flipflop_make_trans` (decode.py:15-72),
   `taiyaki.qscores.errprobs_from_trans` (qscores.py:88-142),
-  `taiyaki.flipflop_remap.flipflop_remap` (flipflop_remap.py:6-88) and
-  `taiyaki.decodeutil.beamsearch` / `forward` / `backward` (decodeutil/decodeutil.pyx:9-108) by their
+  `taiyaki.flipflop_remap.flipflop_remap` (flipflop_remap.py:6-88),
+  `taiyaki.decodeutil.beamsearch` / `forward` / `backward` (decodeutil/decodeutil.pyx:9-108) and
+  `taiyaki.squiggle_match.squiggle_match_loss` / `embed_sequence` (squiggle_match.pyx:114-192) by their
   HIP counterparts;
 * it is not (this repository on its own): a package `taiyaki` is registered whose submodules
   ARE the taiyaki_amd ones, so `bin/train_flipflop.py`-shaped callers resolve every name of
   the hot path (`ctc`, `layers`, `decode`, `flipflopfings`, `flipflop_remap`, `qscores`,
-  `decodeutil`, `basecall_helpers`, `maths.RollingMAD`).
+  `decodeutil`, `basecall_helpers`, `squiggle_match`, `maths.RollingMAD`).
 
 `uninstall()` restores what was there.  Nothing here computes: it is name plumbing, and the
 operators it installs still refuse CPU tensors (no fallback).
@@ -39,6 +40,7 @@ _SUBMODULES = {
     "qscores": "taiyaki_amd.qscores",
     "decodeutil": "taiyaki_amd.decodeutil",
     "basecall_helpers": "taiyaki_amd.basecall_helpers",
+    "squiggle_match": "taiyaki_amd.squiggle_match",
 }
 _FUNCTIONS = [
     ("layers", "flipflop_logpartition", "taiyaki_amd.layers"),
@@ -51,6 +53,8 @@ _FUNCTIONS = [
     ("decodeutil", "beamsearch", "taiyaki_amd.decodeutil"),
     ("decodeutil", "forward", "taiyaki_amd.decodeutil"),
     ("decodeutil", "backward", "taiyaki_amd.decodeutil"),
+    ("squiggle_match", "squiggle_match_loss", "taiyaki_amd.squiggle_match"),
+    ("squiggle_match", "embed_sequence", "taiyaki_amd.squiggle_match"),
 ]
 
 

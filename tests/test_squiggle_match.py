@@ -1,0 +1,245 @@
+"""Squiggle match (taiyaki_amd.squiggle_match, csrc/squiggle_kernels.hip) against the reference's own answers
+(tests/golden/squiggle_small.npz, written by make_golden_squiggle.py from the reference C) and against the
+float64 restatement tests/helpers/squiggle_model.py.
+
+Tolerances come from the reference's own error: its fp32 C differs from the float64 restatement by at most
+1.8e-6 relative in the cost and 1.2e-4 of a column's largest magnitude in the gradient on these cases
+and 5.4e-6 relative in the Viterbi score (test_restatement_matches_the_reference_fixture holds that); the HIP
+results may differ from the fixture or the restatement by a few times that.
+"""
+import numpy as np
+import pytest
+import torch
+
+from tests.conftest import load_golden
+from tests.golden import squiggle_cases as C
+from tests.helpers import squiggle_model as M
+
+COST_RTOL = 1e-5                # HIP / fixture (the reference's own error: 1.8e-6)
+GRAD_COL_TOL = 5e-4             # x the column's largest |gradient| (the reference's own error: 1.2e-4)
+REF_COST_RTOL = 5e-6            # the restatement / fixture
+REF_GRAD_COL_TOL = 2.5e-4
+VITERBI_F64_RTOL = 2e-5         # fp32 Viterbi score / float64 (the reference's own error: 5.4e-6)
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return load_golden("squiggle_small.npz")
+
+
+def _grad_err(got, want):
+    """Largest |difference| per parameter column over its largest |want|."""
+    scale = np.maximum(np.abs(want).max(axis=(0, 1)), 1e-30)
+    return np.abs(got - want).max(axis=(0, 1)) / scale
+
+
+def _reachable(case):
+    return case["siglen"] >= case["params"].shape[0] - 1
+
+
+# ----------------------------------------------------------------------------------------------------------
+# CPU
+# ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", C.NAMES)
+def test_restatement_matches_the_reference_fixture(gold, name):
+    case = C.from_fixture(gold, name)
+    cost = np.array(M.batch(M.cost, case))
+    np.testing.assert_allclose(cost, gold[name + "/cost"], rtol=REF_COST_RTOL)
+    ok = _reachable(case)
+    grad = np.stack(M.batch(M.grad, case), axis=1)
+    assert np.all(_grad_err(grad[:, ok], gold[name + "/grad"][:, ok]) < REF_GRAD_COL_TOL)
+    vit = M.batch(M.viterbi, case, case["localpen"], case["minscore"])
+    np.testing.assert_allclose([v[0] for v in vit], gold[name + "/vcost"], rtol=1e-5)
+    n = int(case["siglen"].sum())
+    assert np.array_equal(np.concatenate([v[1] for v in vit]), gold[name + "/path"][:n])
+
+
+def test_embed_sequence_matches_the_fixture(gold):
+    from taiyaki_amd.squiggle_match import embed_sequence
+    seq = str(gold["embed/sequence"])
+    want = gold["embed/expected"]
+    assert np.array_equal(embed_sequence(seq), want)
+    assert np.array_equal(embed_sequence(seq.encode()), want)
+    idx = np.array(["ACGT".index(b) for b in seq])
+    assert np.array_equal(embed_sequence(idx, alphabet=None), want)
+    with pytest.raises(Exception):
+        embed_sequence(seq, alphabet="ACGU")
+
+
+def test_workspace_query_without_a_gpu():
+    from taiyaki_amd import _lib
+    lib = _lib.lib()
+    assert lib.tk_squiggle_match_workspace_bytes(0, 300, 100, 300000) == 0
+    # lattice: (nsignal + nbatch) columns of 2 x 64 x 5 floats (300 positions -> 5 per lane)
+    assert lib.tk_squiggle_match_workspace_bytes(1, 300, 100, 300000) == (300000 + 100) * 2 * 64 * 5 * 4
+    assert lib.tk_squiggle_match_workspace_bytes(1, 1024, 2, 100) == 102 * 2 * 64 * 16 * 4
+    assert lib.tk_squiggle_match_workspace_bytes(2, 37, 3, 1000) >= 1000 * (37 + 4)
+    assert lib.tk_squiggle_match_workspace_bytes(1, 1025, 1, 10) == 0
+
+
+def _small():
+    params = np.zeros((5, 2, 3), dtype=np.float32)
+    return params, np.zeros(20, dtype=np.float32), np.array([10, 10], dtype=np.int32)
+
+
+@pytest.mark.parametrize("fn", ["squiggle_match_cost", "squiggle_match_grad", "squiggle_match_path"])
+def test_argument_errors_raise_before_any_launch(fn):
+    from taiyaki_amd import squiggle_match as sm
+    call = getattr(sm, fn)
+    extra = (None, None) if fn == "squiggle_match_path" else ()
+    params, signal, siglen = _small()
+    with pytest.raises(ValueError, match="siglen"):
+        call(params, signal, np.array([10, 0], dtype=np.int32), 0.1, *extra)
+    with pytest.raises(ValueError, match="exceeds"):
+        call(params, signal[:19], siglen, 0.1, *extra)
+    with pytest.raises(ValueError):
+        call(params[:, :1], signal, siglen, 0.1, *extra)
+    with pytest.raises(ValueError):
+        call(params[..., :2], signal, siglen, 0.1, *extra)
+    with pytest.raises(ValueError, match="npos = 0"):
+        call(params[:0], signal, siglen, 0.1, *extra)
+    with pytest.raises(ValueError, match="1024"):
+        call(np.zeros((1025, 2, 3), dtype=np.float32), signal, siglen, 0.1, *extra)
+
+
+def test_cpu_tensors_have_no_fallback():
+    from taiyaki_amd import squiggle_match as sm
+    params, signal, siglen = _small()
+    p = torch.from_numpy(params).requires_grad_()
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        sm.squiggle_match_loss(p, torch.from_numpy(signal), torch.from_numpy(siglen), 0.1)
+    if not torch.cuda.is_available():
+        with pytest.raises(RuntimeError, match="no CPU fallback"):
+            sm.squiggle_match_cost(params, signal, siglen, 0.1)
+
+
+def test_standalone_shim_resolves_the_squiggle_match_names():
+    from taiyaki_amd import shim
+    import taiyaki_amd.squiggle_match as sm
+    assert shim.install(force_standalone=True) == "standalone"
+    try:
+        from taiyaki.squiggle_match import squiggle_match_loss, embed_sequence
+        assert squiggle_match_loss is sm.squiggle_match_loss
+        assert embed_sequence is sm.embed_sequence
+    finally:
+        shim.uninstall()
+
+
+# ----------------------------------------------------------------------------------------------------------
+# GPU
+# ----------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", C.NAMES)
+def test_hip_matches_the_reference_fixture(gold, gpu_device, name):
+    from taiyaki_amd import squiggle_match as sm
+    case = C.from_fixture(gold, name)
+    args = (case["params"], case["signal"], case["siglen"], case["back_prob"])
+    cost = sm.squiggle_match_cost(*args)
+    np.testing.assert_allclose(cost, gold[name + "/cost"], rtol=COST_RTOL)
+    grad = sm.squiggle_match_grad(*args)
+    assert np.all(np.isfinite(grad))
+    ok = _reachable(case)
+    err = _grad_err(grad[:, ok], gold[name + "/grad"][:, ok])
+    assert np.all(err < GRAD_COL_TOL), err
+    vcost, path = sm.squiggle_match_path(*args, case["localpen"], case["minscore"])
+    np.testing.assert_allclose(vcost, gold[name + "/vcost"], rtol=1e-6)
+    assert np.array_equal(path, gold[name + "/path"]), np.flatnonzero(path != gold[name + "/path"])[:10]
+
+
+@pytest.mark.gpu
+def test_unreachable_read_cost_matches_and_gradient_is_finite(gold, gpu_device):
+    from taiyaki_amd import squiggle_match as sm
+    case = C.from_fixture(gold, "unreachable")
+    assert not _reachable(case).all()
+    args = (case["params"], case["signal"], case["siglen"], case["back_prob"])
+    cost = sm.squiggle_match_cost(*args)
+    assert cost[1] > 1e29
+    np.testing.assert_allclose(cost, gold["unreachable/cost"], rtol=1e-6)
+    assert np.all(np.isfinite(sm.squiggle_match_grad(*args)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("npos,nbatch,seed,back_prob", [(5, 6, 1, 1e-15), (64, 3, 2, 0.3), (65, 3, 3, 1e-15),
+                                                        (130, 2, 4, 0.3), (1024, 1, 5, 1e-15)])
+def test_hip_matches_the_float64_restatement(gpu_device, npos, nbatch, seed, back_prob):
+    from taiyaki_amd import squiggle_match as sm
+    case = C.random_batch(npos, nbatch, seed, back_prob)
+    args = (case["params"], case["signal"], case["siglen"], case["back_prob"])
+    np.testing.assert_allclose(sm.squiggle_match_cost(*args), M.batch(M.cost, case), rtol=COST_RTOL)
+    if npos <= 130:
+        err = _grad_err(sm.squiggle_match_grad(*args), np.stack(M.batch(M.grad, case), axis=1))
+        assert np.all(err < GRAD_COL_TOL), err
+    vcost, path = sm.squiggle_match_path(*args, None, None)
+    best = np.array([v[0] for v in M.batch(M.viterbi, case)])
+    np.testing.assert_allclose(vcost, best, rtol=VITERBI_F64_RTOL)
+    off = np.concatenate([[0], np.cumsum(case["siglen"])])
+    for b in range(nbatch):
+        # the path's own best score (states restricted to what it folds onto) is the best score
+        rescored, _ = M.viterbi(case["params"][:, b], case["signal"][off[b]:off[b + 1]], back_prob,
+                                allowed=path[off[b]:off[b + 1]])
+        np.testing.assert_allclose(rescored, best[b], rtol=VITERBI_F64_RTOL)
+
+
+@pytest.mark.gpu
+def test_device_lengths_report_through_the_status_word(gpu_device):
+    from taiyaki_amd import squiggle_match as sm
+    params, signal, _ = _small()
+    p, s = torch.from_numpy(params).to(gpu_device), torch.from_numpy(signal).to(gpu_device)
+    with pytest.raises(ValueError, match="siglen"):
+        sm.cost_dev(p, s, torch.tensor([10, 0], device=gpu_device), 0.1)
+    with pytest.raises(ValueError, match="siglen"):
+        sm.cost_dev(p, s, torch.tensor([10, 11], device=gpu_device), 0.1)
+    cost = sm.cost_dev(p, s, torch.tensor([10, 10], device=gpu_device), 0.1)
+    assert torch.isfinite(cost).all()
+
+
+@pytest.mark.gpu
+def test_loss_through_a_conv_net_with_weighted_upstream_gradient(gold, gpu_device):
+    """train_squiggle.py:216-223: loss = squiggle_match_loss(net(embedding), signal, siglen, back_prob), the
+    sum over siglen.sum() backpropagated -- here with a non-uniform weight per read as well."""
+    from taiyaki_amd import squiggle_match as sm
+    case = C.from_fixture(gold, "npos37_back03")
+    npos, nbatch = case["params"].shape[:2]
+    torch.manual_seed(0)
+    net = torch.nn.Conv1d(3, 3, 5, padding=2).to(gpu_device)
+    rng = np.random.RandomState(3)
+    emb = torch.from_numpy(np.stack([sm.embed_sequence(rng.randint(0, 4, npos), alphabet=None)
+                                     for _ in range(nbatch)], axis=1)).to(gpu_device)
+    signal = torch.from_numpy(case["signal"]).to(gpu_device)
+    siglen = torch.from_numpy(case["siglen"].astype(np.int64)).to(gpu_device)
+    weights = torch.linspace(0.5, 2.0, nbatch, device=gpu_device)
+
+    def predict():
+        return net(emb.permute(1, 2, 0)).permute(2, 0, 1)           # (npos, nbatch, 3)
+
+    params = predict()
+    loss = sm.squiggle_match_loss(params, signal, siglen, case["back_prob"])
+    assert loss.is_cuda and loss.shape == (nbatch,)
+    fval = (loss * weights).sum() / float(siglen.sum())
+    fval.backward()
+    got = [t.grad.detach().cpu().numpy().copy() for t in net.parameters()]
+
+    # the same chain with the operator's own gradient applied by hand
+    net.zero_grad()
+    params = predict()
+    p = params.detach().cpu().numpy()
+    np.testing.assert_allclose(loss.detach().cpu().numpy(),
+                               sm.squiggle_match_cost(p, case["signal"], case["siglen"], case["back_prob"]), rtol=1e-6)
+    g = sm.squiggle_match_grad(p, case["signal"], case["siglen"], case["back_prob"])
+    upstream = torch.from_numpy(g).to(gpu_device) * (weights / float(siglen.sum())).unsqueeze(1)
+    params.backward(upstream)
+    for a, b in zip(got, [t.grad.detach().cpu().numpy() for t in net.parameters()]):
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-7)
+
+
+@pytest.mark.gpu
+def test_repeated_calls_are_bit_identical(gold, gpu_device):
+    from taiyaki_amd import squiggle_match as sm
+    case = C.from_fixture(gold, "npos300_back03_local")
+    args = (case["params"], case["signal"], case["siglen"], case["back_prob"])
+    for fn, extra in ((sm.squiggle_match_cost, ()), (sm.squiggle_match_grad, ()),
+                      (sm.squiggle_match_path, (case["localpen"], case["minscore"]))):
+        a, b = fn(*args, *extra), fn(*args, *extra)
+        for x, y in zip(a if isinstance(a, tuple) else (a,), b if isinstance(b, tuple) else (b,)):
+            assert np.array_equal(x.view(np.uint32) if x.dtype == np.float32 else x,
+                                  y.view(np.uint32) if y.dtype == np.float32 else y)
