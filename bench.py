@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- flip-flop train-step throughput + loss-kernel rooflines on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,5}]
+    python bench.py --gpus N --steps K --warmup W [--config {1,2,3,4,5}] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -24,7 +24,10 @@ Forward + loss and AdamW are replayed from hipGraphs, the MIOpen RNN backward (n
 launched eagerly.  Synthetic chunks (resident in HBM before the timed region), random-init weights.
 Weak scaling: per-GPU batch is fixed, value = all ranks' chunks / max-over-ranks time.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs if asked and prints the contract fields; N > 1 adds "per_rank_ms" (every rank's
+own ms/step: min / max / all) and "cores_per_rank" (the host cores each rank is pinned to).
+Everything else the bench measures runs only with --full, after the timed steps, and adds
   "roofline"        the logZ forward-backward op on the tensor BASELINE.json's north_star names
                     for the roofline target (T=4000 blocks, N=256 reads): HIP events on the
                     launching stream; achieved = 3*T*N*S*4 bytes / mean duration (SURVEY 8d);
@@ -36,10 +39,15 @@ Rank 0 prints ONE JSON line with the contract fields plus
   "loss_path"       the whole loss path (A + B) in chunks/s on the GPU, on the host cores, and
                     on the host cores including the D->H / H->D copies of the score and gradient
                     tensors the reference design incurs (ctc.pyx:119, 139-141)
+  "roofline_viterbi" the Viterbi path kernel at the step's shape and at the north_star shape
   "rccl"            (N > 1) ranks, bytes and event-timed duration of the gradient all-reduce, whole and
-                    slice by slice (`bucket_us`); "per_rank_ms": every rank's own ms/step (min / max /
-                    all); "cores_per_rank": the host cores each rank is pinned to
-  "cpu_baseline"    the reference C (oracle/_ref) or the oracle port on host cores.
+                    slice by slice (`bucket_us`), and the same steps re-timed with the C-ABI
+                    collective (`direct`); (N = 1) the step re-run in a child with a forced
+                    one-rank RCCL process group (`overhead_ms`)
+  "cpu_baseline"    the reference C (oracle/_ref) or the oracle port on host cores
+  "varlen"          (N = 1) ten steps with the reference's per-iteration chunk length draw.
+--no-forced-group, --no-varlen, --no-kernel-records, --no-cpu-baseline, --no-rowk and --no-pmc
+drop parts of a --full run.
 """
 import argparse
 import hashlib
@@ -597,7 +605,7 @@ def _gather_per_rank(ms, dev, world):
 
 def variable_length_bench(args, cfg, trainer, dev, rank, use_graph, lo, hi, steps, warmup):
     """The reference's per-iteration chunk length draw (bin/train_flipflop.py:554-563) on graph replay: `--chunk-len-range
-    MIN MAX` prints the record as its own line; the default N = 1 run carries a short leg of it as `varlen`."""
+    MIN MAX` prints the record as its own line; a --full N = 1 run carries a short leg of it as `varlen`."""
     from taiyaki_amd import _lib, train
     stride, cat_mod = cfg["stride"], cfg["model"] == "mLstm_cat_mod_flipflop"
     lens = sorted({train.bucket_chunk_len(x, stride, args.len_bucket) for x in range(lo, hi + 1, stride)})
@@ -860,7 +868,7 @@ def rccl_debug_summary(limit=14):
 
 
 def direct_leg(args, arena, comm, rank, world, dev, timed_steps, event_time_us, nbatch, on_timeout=None, budget_s=150.0):
-    """`rccl.direct` of the default N > 1 line: the C-ABI collective (own rendezvous) on the same steps.  A
+    """`rccl.direct` of a --full N > 1 line: the C-ABI collective (own rendezvous) on the same steps.  A
     watchdog thread lets the line go out without this leg if it hangs: every rank then leaves through
     os._exit after rank 0 has printed what it has."""
     import threading
@@ -969,10 +977,14 @@ def main():
                          "3-4 ms each (profiles/r4_forced_group_bisect.txt), the one flat call nothing")
     ap.add_argument("--collective", choices=["pg", "direct"], default="pg",
                     help="N > 1: what reduces the gradients.  pg (default): torch.distributed's ProcessGroupNCCL (= RCCL); "
-                         "the line then also carries `rccl.direct`, the same steps re-timed with this repo's C-ABI "
+                         "a --full line then also carries `rccl.direct`, the same steps re-timed with this repo's C-ABI "
                          "collective.  direct: libtaiyaki_amd_rccl.so (tk_allreduce_f32_dev) with its OWN socket "
                          "rendezvous -- no torch.distributed process group exists in the ranks at all (barriers and "
                          "the max over ranks go through the same all-reduce)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything besides the headline figure: the kernel "
+                         "records (rooflines, loss path, CPU baseline), the variable-length leg and the RCCL records "
+                         "(N = 1: the forced-group child; N > 1: all-reduce timings and the C-ABI collective leg)")
     ap.add_argument("--no-varlen", action="store_true",
                     help="N = 1: skip the short leg with the reference's per-iteration chunk length draw (`varlen`)")
     ap.add_argument("--no-forced-group", action="store_true",
@@ -987,7 +999,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-rowk", action="store_true")
     ap.add_argument("--no-kernel-records", action="store_true",
-                    help="the train-step line only (no roofline / loss_path / cpu_baseline records)")
+                    help="with --full: no roofline / loss_path / cpu_baseline / varlen records")
     ap.add_argument("--no-pmc", action="store_true", help="do not run the rocprofv3 PMC passes")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last of them computed (the loss it returned, the "
@@ -1226,6 +1238,7 @@ def main():
         vals = [round(v, 3) for v in comm.gather(mine_ms)] if comm.active else [round(mine_ms, 3)]
         per_rank = dict(min=min(vals), max=max(vals), all=vals)
         elapsed = max(comm.gather(elapsed)) if comm.active else elapsed
+    if grouped and args.full:
         # the gradient all-reduce on its own, event-timed on the launching stream (waiting on the work object
         # makes the current stream wait for RCCL's), whole and slice by slice as the step issues it
         reduce_flat = lambda t=arena.flat: arena._all_reduce(t).wait()       # noqa: E731
@@ -1290,11 +1303,12 @@ def main():
             out["dump_outputs"] = dumped
         if rccl is not None:
             out["rccl"] = rccl
+        elif args.full and world == 1 and not args.no_forced_group and not dist.is_initialized():
+            out["rccl"] = forced_group_overhead(args, argv, elapsed / args.steps * 1e3)
+        if per_rank is not None:
             out["per_rank_ms"] = per_rank
             out["cores_per_rank"] = len(cores)
-        elif world == 1 and not args.no_forced_group and not dist.is_initialized():
-            out["rccl"] = forced_group_overhead(args, argv, elapsed / args.steps * 1e3)
-        if not args.no_kernel_records:
+        if args.full and not args.no_kernel_records:
             kernel_records(out, args, cfg, dev, world, T, nbatch, chunk_len, cat_mod, S)
             if world == 1 and not args.no_varlen and not grouped:
                 # the schedule the reference actually trains with (chunk_len drawn per iteration, defaults 3000 .. 8000):
@@ -1319,7 +1333,7 @@ def main():
         print(json.dumps(line), flush=True)
 
     comm.barrier()
-    if (comm.active and world > 1 and arena.collective is None and dev.type == "cuda"
+    if (args.full and comm.active and world > 1 and arena.collective is None and dev.type == "cuda"
             and not os.environ.get("TK_BENCH_SHARE_GPU") and not os.environ.get("TK_BENCH_NO_DIRECT_LEG")):
         # Both transports in one go: the SAME steps again with the C-ABI collective behind its own socket
         # rendezvous (a second communicator next to the process group's).  Guarded: this leg has never seen

@@ -1223,7 +1223,7 @@ def test_bench_contract_with_live_rccl_group(gpu_device):
                WORLD_SIZE="1", TK_FORCE_PROCESS_GROUP="1")
     pr = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--chunk-len", "400",
                          "--batch", "8", "--size", "32", "--steps", "2", "--warmup", "1",
-                         "--no-cpu-baseline", "--no-rowk"],
+                         "--full", "--no-cpu-baseline", "--no-rowk"],
                         env=env, capture_output=True, text=True, timeout=900)
     assert pr.returncode == 0, pr.stderr[-800:]
     line = pr.stdout.strip().splitlines()[-1]
@@ -1250,7 +1250,7 @@ def test_bench_two_ranks_self_launched_on_one_gpu(gpu_device):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["TK_BENCH_SHARE_GPU"] = "1"
     pr = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--chunk-len", "400",
-                         "--batch", "8", "--size", "32", "--steps", "3", "--warmup", "1", "--no-rowk"],
+                         "--batch", "8", "--size", "32", "--steps", "3", "--warmup", "1", "--full", "--no-rowk"],
                         env=env, capture_output=True, text=True, timeout=1200)
     assert pr.returncode == 0, (pr.stdout[-400:], pr.stderr[-1200:])
     lines = [ln for ln in pr.stdout.strip().splitlines() if ln.startswith("{")]

@@ -7,13 +7,13 @@ cd "$(dirname "$0")/.."; TAG=${TAG:-r6}; O=gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
 H=$(python -c "import bench; print(bench.kernel_hash())" 2>/dev/null | tail -1); echo "kernel hash $H" | tee $O/hash.txt
 timeout 900 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; grep -E "passed|failed" $O/pytest_gpu.log | tail -1
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; python tools/show_bench.py $O/bench_default.json
-for c in 4 5; do timeout 600 python bench.py --config $c --no-forced-group --no-varlen > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err; done
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; python tools/show_bench.py $O/bench_default.json
+for c in 4 5; do timeout 600 python bench.py --config $c --full --no-forced-group --no-varlen > $O/bench_cfg$c.json 2> $O/bench_cfg$c.err; done
 # fuzz sweeps beside the profiler passes (CPU-heavy -- the float64 witness -- so NOT beside the bench lines above: the
 # train step is bound by its host thread, two fuzz processes next to it halve its rate)
 for s in ${FUZZ_SEEDS:-21 22}; do timeout 2000 python -m tests.helpers.fuzz_shapes --cases ${FUZZ_CASES:-100} --seed $s > $O/fuzz_shapes_$s.log 2>&1 & done
 # kernel summary of the bench command under rocprofv3 (kernel trace only)
-rm -rf /tmp/tk_prof; (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/tk_prof -o bench -- python $OLDPWD/bench.py --steps 10 --warmup 3 --no-forced-group --no-cpu-baseline --no-pmc --no-varlen > /dev/null 2> $OLDPWD/$O/rocprof_bench.err)
+rm -rf /tmp/tk_prof; (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/tk_prof -o bench -- python $OLDPWD/bench.py --steps 10 --warmup 3 --full --no-forced-group --no-cpu-baseline --no-pmc --no-varlen > /dev/null 2> $OLDPWD/$O/rocprof_bench.err)
 DB=$(find /tmp/tk_prof -name "*.db" | head -1)
 if [ -n "$DB" ]; then python tools/rocpd_stats.py $DB 30 > $O/bench_kernel_stats.txt; python tools/prof_by_shape.py $DB "%tk%" > $O/bench_loss_kernels_by_shape.txt; fi
 find /tmp/tk_prof -name "*kernel_stats.csv" | head -1 | xargs -r -I{} cp {} $O/bench_rocprofv3_kernel_stats.csv

@@ -39,7 +39,7 @@ def main():
             e.update(BASE)
             e["MASTER_PORT"] = str(port + k)
         e.update(env)
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline",
                "--no-pmc", "--no-rowk", "--no-kernel-records"] + extra
         pr = subprocess.run(cmd, env=e, capture_output=True, text=True)
         line = [ln for ln in pr.stdout.splitlines() if ln.startswith("{")]
