@@ -99,7 +99,9 @@ ERRORS = {1: "bad argument (NULL / shape / 16-byte alignment)",
           2: "unsupported nbase / ntrans / sequence length for this build",
           3: "workspace too small", 4: "HIP launch failure"}
 
-LAB_SIGNATURES = {"tk_lab_crf_band_phase": (None, [_i]), "tk_lab_lstm_cols": (None, [_i])}
+LAB_SIGNATURES = {"tk_lab_crf_band_phase": (None, [_i]), "tk_lab_lstm_cols": (None, [_i]),
+                  "tk_lab_lstm_units": (None, [_i]),
+                  "tk_lab_lstm_geometry": (_i, [_sz, _sz, _i, ctypes.POINTER(_sz)])}
 
 _lib = None
 _handles = {}

@@ -77,6 +77,8 @@ int lstm_backward_dispatch(const float *whh, const float *gates, const float *ce
                            uint32_t *status, hipStream_t stream);
 #ifdef TK_LAB
 void lstm_lab_cols(int cols);
+void lstm_lab_units(int units);
+bool lstm_lab_geometry(size_t N, size_t H, int cu_count, size_t *out);
 #endif
 int path_to_reftosignal_dispatch(const int64_t *path, const int64_t *path_off, const int64_t *ref_off,
                                  const int64_t *signalstart, const int64_t *siglen, int stride, size_t nread,
@@ -549,6 +551,13 @@ int tk_devcopy_f32_dev(float *dst, const float *src, size_t n, void *stream) {
 extern "C" void tk_lab_crf_band_phase(int phase) { tk::crf_band_lab_phase(phase); }
 // the LSTM recurrence's batch columns per workgroup, 8 or 16 (0: the launcher's rule; lstm_kernels.hip)
 extern "C" void tk_lab_lstm_cols(int cols) { tk::lstm_lab_cols(cols); }
+// the LSTM recurrence's hidden units per workgroup, 16, 32 or 64 (0: the launcher's rule)
+extern "C" void tk_lab_lstm_units(int units) { tk::lstm_lab_units(units); }
+// the LSTM recurrence's launch plan at (nbatch, size, cu_count): out[8] = admitted C and groups, U, C, groups,
+// grid, forward and backward granule bytes; 0 where the kernels do not run
+extern "C" int tk_lab_lstm_geometry(size_t nbatch, size_t size, int cu_count, size_t *out) {
+    return tk::lstm_lab_geometry(nbatch, size, cu_count, out) ? 1 : 0;
+}
 #endif
 
 size_t tk_lstm_workspace_bytes(size_t nbatch, size_t size, int cu_count) {

@@ -1,9 +1,11 @@
 // lstm_kernels.hip -- the recurrence of layers.Lstm (one nn.LSTM layer, gate order i, f, g, o; h0 = c0 = 0)
 // as one persistent, weight-stationary launch per layer and direction of the pass.
 //
-// Geometry.  A workgroup owns kUnits = 16 hidden units (their 64 gate rows of W_hh, held in VGPRs for the whole
-// launch: H / 4 floats per lane) and C batch columns.  The G = H / 16 workgroups that share C columns form a
-// group; a group needs nothing from another group.  Grid = ceil(N / C) * G <= the CU count, one workgroup per CU.
+// Geometry.  A workgroup owns U hidden units (their 4 U gate rows of W_hh, held in VGPRs for the whole launch) and
+// C batch columns.  The G = H / U workgroups that share C columns form a group; a group needs nothing from another
+// group.  The admission rule and the workspace size are those of U = 16 with 8 or 16 columns (lstm_geometry); a
+// launch at U = 32 or 64 takes C * 16 / U columns per workgroup, so its grid and its granule buffers are never
+// larger than the admitted ones (lstm_plan).
 //
 // Hand-off.  Inside a group every step is an all-to-all: forward, each member needs the whole h_{t-1} of its
 // columns; backward, each member needs the sum over members of W_hh[rows(m), J]^T dG_{t+1}[rows(m)] for its units J
@@ -13,6 +15,12 @@
 // before every member has read step s.  The granule buffers are zeroed by a kernel in front of every launch.
 // Every spin is bounded by a clock budget; on expiry TK_STATUS_LSTM_TIMEOUT is OR-ed into *status and the whole
 // grid leaves (the other spins see the bit).
+//
+// Step schedule.  vmcnt is one in-order counter per wave for loads and stores, so every wait of a poll also waits
+// for whatever the wave issued before it.  Nothing bound for HBM is issued ahead of a poll in the same step: the
+// inputs of step s + 1 (forward: gx; backward: dy, c_{t-1}, the gates) are loaded right after step s's poll, and
+// the bulk outputs of step s (forward: y, c, gates; backward: dG) are held in registers and stored right after
+// step s + 1's poll.  Both drain under the matvec; the granule publish is the last memory operation of a step.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -23,10 +31,11 @@
 namespace tk {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kUnits = 16;                      // hidden units per workgroup
-constexpr int kRows = 4 * kUnits;               // their gate rows
 constexpr uint64_t kSpinTicks = 200000000ull;   // 2 s of s_memrealtime (100 MHz) per wait
+
+// threads per workgroup at U units: 4 U H / threads W_hh floats per lane, <= 128 at H = 256
+template <int U>
+constexpr int threads_for() { return U <= 32 ? 256 : 512; }
 
 typedef unsigned long long u64;
 typedef __attribute__((address_space(1))) u64 gu64;
@@ -37,21 +46,22 @@ __device__ __forceinline__ void store_granule(u64 *g, unsigned tag, float v) {
                        __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// This lane's NG granules g[q * stride] (q < nvalid) until every lane of the wave sees `tag` in all of its own;
-// false when the clock budget runs out or another workgroup has already given up.
+// This lane's NG granules g[e0 + q * stride] that lie below `end` until every lane of the wave sees `tag` in all
+// of its own; false when the clock budget runs out or another workgroup has already given up.  Every pass issues
+// all NG loads before it waits (a granule at or past `end` is read at g[0] and ignored: no branch per load).
 template <int NG>
-__device__ __forceinline__ bool sweep(const u64 *g, int stride, int nvalid, unsigned tag, float (&v)[NG],
+__device__ __forceinline__ bool sweep(const u64 *g, int e0, int stride, int end, unsigned tag, float (&v)[NG],
                                       uint32_t *status) {
     const uint64_t start = __builtin_amdgcn_s_memrealtime();
     for (unsigned spins = 0;; ++spins) {
         bool ok = true;
 #pragma unroll
         for (int q = 0; q < NG; ++q) {
-            if (q < nvalid) {
-                const u64 x = __hip_atomic_load((gu64 *)(g + q * stride), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                v[q] = __uint_as_float((unsigned)x);
-                ok &= (unsigned)(x >> 32) == tag;
-            }
+            const int e = e0 + q * stride;
+            const bool in = e < end;
+            const u64 x = __hip_atomic_load((gu64 *)(g + (in ? e : 0)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            v[q] = __uint_as_float((unsigned)x);
+            ok &= !in || (unsigned)(x >> 32) == tag;
         }
         if (__all(ok)) return true;
         if ((spins & 31) == 31) {
@@ -76,7 +86,42 @@ __device__ __forceinline__ void place(int G, int &group, int &member) {
     member = L % G;
 }
 
+// Values loaded from HBM, pinned as ready here: the compiler waits for their loads at this point, not at their first
+// use after a later prefetch (vmcnt is in order, so that wait would also wait for the prefetch).
+template <int M>
+__device__ __forceinline__ void settle(float (&v)[M]) {
+#pragma unroll
+    for (int i = 0; i < M; ++i) asm volatile("" : "+v"(v[i]));
+}
+template <int M, int K>
+__device__ __forceinline__ void settle(float (&v)[M][K]) {
+#pragma unroll
+    for (int i = 0; i < M; ++i) settle(v[i]);
+}
+
 __device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
+
+// C consecutive floats of LDS (16-byte aligned where C is a multiple of 4)
+template <int C>
+__device__ __forceinline__ void lds_row(const float *p, float (&v)[C]) {
+    if constexpr (C % 4 == 0) {
+#pragma unroll
+        for (int c4 = 0; c4 < C / 4; ++c4) {
+            const float4 q = reinterpret_cast<const float4 *>(p)[c4];
+            v[4 * c4 + 0] = q.x;
+            v[4 * c4 + 1] = q.y;
+            v[4 * c4 + 2] = q.z;
+            v[4 * c4 + 3] = q.w;
+        }
+    } else if constexpr (C == 2) {
+        const float2 q = *reinterpret_cast<const float2 *>(p);
+        v[0] = q.x;
+        v[1] = q.y;
+    } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) v[c] = p[c];
+    }
+}
 
 __global__ void zero_u64x2_kernel(uint4 *p, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
@@ -85,141 +130,176 @@ __global__ void zero_u64x2_kernel(uint4 *p, size_t n) {
 
 // Forward.  gx (T, N, 4H) = x W_ih^T + b_ih + b_hh.  Writes y = h (T, N, H), the gate activations (T, N, 4H) and
 // c (T, N, H).  Recurrence step s runs time t = s (reverse: T - 1 - s).  hbuf: [2][ngroups][C][H] granules.
-template <int H, int C>
-constexpr int fwd_lds_bytes() { return (kRows * H + H * C + kRows * C) * 4 + 16; }
-
-template <int H, int C>
-__global__ __launch_bounds__(kThreads, 1) void lstm_fwd_kernel(const float *__restrict__ gx,
-                                                               const float *__restrict__ whh, int T, int N,
-                                                               int reverse, int ngroups, float *__restrict__ y,
-                                                               float *__restrict__ gates, float *__restrict__ cell,
-                                                               u64 *hbuf, uint32_t *status) {
-    constexpr int G = H / kUnits;
-    constexpr int NG = (H * C + kThreads - 1) / kThreads;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float4 *wl = reinterpret_cast<float4 *>(smem);                 // this lane's W_hh: [H / 16][lane] float4
-    float *hs = reinterpret_cast<float *>(smem) + kRows * H;       // h_{t-1} as [k][c]
-    float *pre = hs + H * C;                                       // W_hh h_{t-1} as [row][c]
-    int *give_up = reinterpret_cast<int *>(pre + kRows * C);
+//
+// Lane (u, kp), kp < KP = threads / U: the 4 gate rows of unit u over the columns k = i KP + kp (i < KS = H / KP)
+// in VGPRs, so each h value read from LDS feeds 4 rows (KS C-wide LDS reads per lane per step).  The KP partial
+// sums are combined by xor shuffles: the first log2(C) rounds halve the columns a lane keeps, the rest add the 4
+// gates of its one column; lane kp < C then holds the 4 pre-activations of column col(kp) and runs its cell update.
+template <int H, int C, int U>
+__global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const float *__restrict__ gx,
+                                                                       const float *__restrict__ whh, int T, int N,
+                                                                       int reverse, int ngroups,
+                                                                       float *__restrict__ y,
+                                                                       float *__restrict__ gates,
+                                                                       float *__restrict__ cell, u64 *hbuf,
+                                                                       uint32_t *status) {
+    constexpr int NT = threads_for<U>();
+    constexpr int G = H / U;
+    constexpr int KP = NT / U;
+    constexpr int KS = H / KP;
+    constexpr int NG = (H * C + NT - 1) / NT;
+    static_assert(KS >= 1 && KP <= 64 && C <= KP, "lane (u, kp) inside one wave; one cell lane per (u, column)");
+    __shared__ __attribute__((aligned(16))) float hs[2][H * C];      // h_{t-1} as [k][c], by step parity
+    __shared__ int give_up;
 
     int group, member;
     place(G, group, member);
     const int tid = threadIdx.x;
-    const int j0 = member * kUnits, n0 = group * C;
+    const int j0 = member * U, n0 = group * C;
+    const int u = tid / KP, kp = tid % KP;
 
-    // lane (r, kc): local gate row r = gate * 16 + unit, columns k = 16 i + 4 kc + (0..3).  Its W_hh values sit in
-    // LDS in lane order (each lane reads back only what it wrote: one conflict-free ds_read_b128 per 4 columns)
-    const int r = tid >> 2, kc = tid & 3;
-    const int grow = (r / kUnits) * H + j0 + (r % kUnits);
-    for (int i = 0; i < H / 16; ++i) {
-        const float *p = whh + (size_t)grow * H + 16 * i + 4 * kc;
-        wl[i * kThreads + tid] = make_float4(p[0], p[1], p[2], p[3]);
-    }
+    float w[4][KS];
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int i = 0; i < KS; ++i) w[g][i] = whh[((size_t)g * H + j0 + u) * H + i * KP + kp];
+    settle(w);
 
-    // cell lane (c, u)
-    const bool cell_lane = tid < kUnits * C;
-    const int cc = tid / kUnits, u = tid % kUnits;
-    const int n = n0 + cc;
+    int col = 0;                                       // the column this lane keeps through the reduction
+#pragma unroll
+    for (int m = 1, width = C; width > 1; m <<= 1, width >>= 1)
+        if (kp & m) col += width / 2;
+    const bool cell_lane = kp < C;
+    const int n = n0 + col;
     const bool valid = cell_lane && n < N;
     float cst = 0.f;
 
-    for (int i = tid; i < H * C; i += kThreads) hs[i] = 0.f;
-    if (tid == 0) *give_up = 0;
-    __syncthreads();
+    for (int i = tid; i < H * C; i += NT) hs[0][i] = 0.f;
+    if (tid == 0) give_up = 0;
 
     const size_t H4 = 4 * (size_t)H;
+    float gq[4] = {0.f, 0.f, 0.f, 0.f};              // gx of this step (loaded one step ahead)
+    if (valid) {
+        const float *p = gx + ((size_t)(reverse ? T - 1 : 0) * N + n) * H4 + j0 + u;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) gq[g] = p[(size_t)g * H];
+    }
+    float held[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // h, c, i, f, g, o of the previous step, stored one step late
+    __syncthreads();
+
     for (int s = 0; s < T; ++s) {
         const int t = reverse ? T - 1 - s : s;
-        float gxv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (valid) {
-            const float *p = gx + ((size_t)t * N + n) * H4 + j0 + u;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) gxv[g] = p[(size_t)g * H];
-        }
+        float *hb = hs[s & 1];
+        settle(gq);
         if (s > 0) {
             const u64 *src = hbuf + ((size_t)((s - 1) & 1) * ngroups + group) * (H * C);
             float v[NG];
-            const int nvalid = tid < H * C ? (H * C - tid + kThreads - 1) / kThreads : 0;
-            if (!sweep<NG>(src + tid, kThreads, nvalid, (unsigned)s, v, status)) *give_up = 1;
+            if (!sweep<NG>(src, tid, NT, H * C, (unsigned)s, v, status)) give_up = 1;
 #pragma unroll
             for (int q = 0; q < NG; ++q) {
-                const int e = tid + q * kThreads;        // granule e = c * H + k
-                if (q < nvalid) hs[(e % H) * C + e / H] = v[q];
+                const int e = tid + q * NT;              // granule e = c * H + k
+                if (e < H * C) hb[(e % H) * C + e / H] = v[q];
             }
             __syncthreads();
-            if (*give_up) return;
+            if (give_up) return;
+            if (valid) {
+                const int tl = reverse ? t + 1 : t - 1;
+                const size_t o = ((size_t)tl * N + n) * H + j0 + u;
+                y[o] = held[0];
+                cell[o] = held[1];
+                float *gp = gates + ((size_t)tl * N + n) * H4 + j0 + u;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) gp[(size_t)g * H] = held[2 + g];
+            }
         }
+        float gn[4] = {0.f, 0.f, 0.f, 0.f};
+        if (valid && s + 1 < T) {
+            const float *p = gx + ((size_t)(reverse ? t - 1 : t + 1) * N + n) * H4 + j0 + u;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) gn[g] = p[(size_t)g * H];
+        }
+        asm volatile("" ::: "memory");                   // the deferred stores and the prefetch stay here
 
-        float acc[C];
+        float acc[4][C];
 #pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = 0.f;
-#pragma unroll 2
-        for (int i = 0; i < H / 16; ++i) {
-            const float4 w4 = wl[i * kThreads + tid];
-            const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
+        for (int g = 0; g < 4; ++g)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float4 *hp = reinterpret_cast<const float4 *>(hs + (16 * i + 4 * kc + j) * C);
+            for (int c = 0; c < C; ++c) acc[g][c] = 0.f;
 #pragma unroll
-                for (int c4 = 0; c4 < C / 4; ++c4) {
-                    const float4 h4 = hp[c4];
-                    acc[4 * c4 + 0] = fmaf(wv[j], h4.x, acc[4 * c4 + 0]);
-                    acc[4 * c4 + 1] = fmaf(wv[j], h4.y, acc[4 * c4 + 1]);
-                    acc[4 * c4 + 2] = fmaf(wv[j], h4.z, acc[4 * c4 + 2]);
-                    acc[4 * c4 + 3] = fmaf(wv[j], h4.w, acc[4 * c4 + 3]);
+        for (int i = 0; i < KS; ++i) {
+            float hv[C];
+            lds_row<C>(hb + (i * KP + kp) * C, hv);
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int c = 0; c < C; ++c) acc[g][c] = fmaf(w[g][i], hv[c], acc[g][c]);
+        }
+#pragma unroll
+        for (int m = 1; m < KP; m <<= 1) {
+            const int half = C / (2 * m);                // 0 once a lane keeps one column
+            const bool up = (kp & m) != 0;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if (half == 0) acc[g][0] += __shfl_xor(acc[g][0], m);
+#pragma unroll
+                for (int c = 0; c < C / 2; ++c) {        // (constant trip count: unrolled before the rounds are)
+                    if (c < half) {
+                        const float send = up ? acc[g][c] : acc[g][c + half];
+                        const float keep = up ? acc[g][c + half] : acc[g][c];
+                        acc[g][c] = keep + __shfl_xor(send, m);
+                    }
                 }
             }
         }
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            acc[c] += __shfl_xor(acc[c], 1);
-            acc[c] += __shfl_xor(acc[c], 2);
-            if ((c & 3) == kc) pre[r * C + c] = acc[c];
-        }
-        __syncthreads();
 
         if (cell_lane) {
-            const float zi = pre[(0 * kUnits + u) * C + cc] + gxv[0];
-            const float zf = pre[(1 * kUnits + u) * C + cc] + gxv[1];
-            const float zg = pre[(2 * kUnits + u) * C + cc] + gxv[2];
-            const float zo = pre[(3 * kUnits + u) * C + cc] + gxv[3];
-            const float ig = sigmoidf(zi), fg = sigmoidf(zf), gg = tanhf(zg), og = sigmoidf(zo);
+            const float ig = sigmoidf(acc[0][0] + gq[0]), fg = sigmoidf(acc[1][0] + gq[1]);
+            const float gg = tanhf(acc[2][0] + gq[2]), og = sigmoidf(acc[3][0] + gq[3]);
             cst = fg * cst + ig * gg;
             const float h = og * tanhf(cst);
-            if (valid) {
-                const size_t o = ((size_t)t * N + n) * H + j0 + u;
-                y[o] = h;
-                cell[o] = cst;
-                float *gp = gates + ((size_t)t * N + n) * H4 + j0 + u;
-                gp[0] = ig;
-                gp[(size_t)H] = fg;
-                gp[2 * (size_t)H] = gg;
-                gp[3 * (size_t)H] = og;
-            }
             if (s + 1 < T)
-                store_granule(hbuf + ((size_t)(s & 1) * ngroups + group) * (H * C) + cc * H + j0 + u,
+                store_granule(hbuf + ((size_t)(s & 1) * ngroups + group) * (H * C) + col * H + j0 + u,
                               (unsigned)(s + 1), h);
+            held[0] = h;
+            held[1] = cst;
+            held[2] = ig;
+            held[3] = fg;
+            held[4] = gg;
+            held[5] = og;
         }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) gq[g] = gn[g];
+    }
+    if (valid && T > 0) {
+        const int tl = reverse ? 0 : T - 1;
+        const size_t o = ((size_t)tl * N + n) * H + j0 + u;
+        y[o] = held[0];
+        cell[o] = held[1];
+        float *gp = gates + ((size_t)tl * N + n) * H4 + j0 + u;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) gp[(size_t)g * H] = held[2 + g];
     }
 }
 
 // Backward.  From the saved gate activations and c, and dy = dL/dy (T, N, H), writes dgates = dL/d(pre-activation)
 // (T, N, 4H) walking the recurrence from its last step.  pbuf: [2][ngroups][G producers][C][H] granules.
-template <int H, int C>
-__global__ __launch_bounds__(kThreads, 1) void lstm_bwd_kernel(const float *__restrict__ whh,
-                                                               const float *__restrict__ gates,
-                                                               const float *__restrict__ cell,
-                                                               const float *__restrict__ dy, int T, int N,
-                                                               int reverse, int ngroups, float *__restrict__ dgates,
-                                                               u64 *pbuf, uint32_t *status) {
-    constexpr int G = H / kUnits;
-    constexpr int RP = kThreads / H;                  // row partitions: lane (k, rp) holds W_hh[rows of rp, k]
-    constexpr int R = kRows / RP;                     // = H / 4 floats per lane
-    constexpr int PAIRS = kUnits * C;                 // (c, u) pairs of the cell update
-    constexpr int PL = kThreads / PAIRS >= 1 ? kThreads / PAIRS : 1;   // producer planes of the gather
+template <int H, int C, int U>
+__global__ __launch_bounds__(threads_for<U>(), 1) void lstm_bwd_kernel(const float *__restrict__ whh,
+                                                                       const float *__restrict__ gates,
+                                                                       const float *__restrict__ cell,
+                                                                       const float *__restrict__ dy, int T, int N,
+                                                                       int reverse, int ngroups,
+                                                                       float *__restrict__ dgates, u64 *pbuf,
+                                                                       uint32_t *status) {
+    constexpr int NT = threads_for<U>();
+    constexpr int G = H / U;
+    constexpr int RP = NT / H;                        // row partitions: lane (k, rp) holds W_hh[rows of rp, k]
+    constexpr int R = 4 * U / RP;                     // floats per lane
+    constexpr int PAIRS = U * C;                      // (c, u) pairs of the cell update
+    constexpr int PL = NT / PAIRS;                    // producer planes of the gather
     constexpr int NP = (G + PL - 1) / PL;
-    static_assert(PAIRS <= kThreads, "one cell lane per (column, unit)");
-    __shared__ __attribute__((aligned(16))) float dgs[kRows * C];      // dG_t of the owned rows as [row][c]
+    static_assert(RP >= 1 && R >= 1 && PL >= 1 && PL * PAIRS == NT, "every lane polls; one cell lane per pair");
+    __shared__ __attribute__((aligned(16))) float dgs[4 * U * C];      // dG_t of the owned rows as [row][c]
     __shared__ float gath[PL * PAIRS];
     __shared__ __attribute__((aligned(16))) float red[RP > 1 ? RP * C * H : 1];
     __shared__ int give_up;
@@ -227,66 +307,88 @@ __global__ __launch_bounds__(kThreads, 1) void lstm_bwd_kernel(const float *__re
     int group, member;
     place(G, group, member);
     const int tid = threadIdx.x;
-    const int j0 = member * kUnits, n0 = group * C;
+    const int j0 = member * U, n0 = group * C;
 
     const int k = tid % H, rp = tid / H;
     float w[R];
 #pragma unroll
     for (int i = 0; i < R; ++i) {
         const int r = rp * R + i;
-        w[i] = whh[((size_t)(r / kUnits) * H + j0 + (r % kUnits)) * H + k];
+        w[i] = whh[((size_t)(r / U) * H + j0 + (r % U)) * H + k];
     }
+    settle(w);
 
     const bool cell_lane = tid < PAIRS;
     const int pair = tid % PAIRS, plane = tid / PAIRS;
-    const int cc = pair / kUnits, u = pair % kUnits;
+    const int cc = pair / U, u = pair % U;
     const int n = n0 + cc;
     const bool valid = cell_lane && n < N;
     float dc_next = 0.f, f_next = 0.f;
     if (tid == 0) give_up = 0;
+
+    // this step's inputs, loaded one step ahead: dy, c_t, c_{t-1}, the four gates (c_t of a step is the c_{t-1}
+    // of the step before)
+    const size_t H4 = 4 * (size_t)H;
+    float in[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (valid) {
+        const int t = reverse ? 0 : T - 1;
+        const size_t o = ((size_t)t * N + n) * H + j0 + u;
+        in[0] = dy[o];
+        in[1] = cell[o];
+        if (T > 1) in[2] = cell[((size_t)(reverse ? t + 1 : t - 1) * N + n) * H + j0 + u];
+        const float *gp = gates + ((size_t)t * N + n) * H4 + j0 + u;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) in[3 + g] = gp[(size_t)g * H];
+    }
+    float held[4] = {0.f, 0.f, 0.f, 0.f};             // dG of the previous step, stored one step late
     __syncthreads();
 
-    const size_t H4 = 4 * (size_t)H;
     const u64 *mine = pbuf + (size_t)group * G * C * H + cc * H + j0 + u;
     for (int s = 0; s < T; ++s) {
         const int tt = T - 1 - s;                         // recurrence position
         const int t = reverse ? T - 1 - tt : tt;          // time index
         const int tp = reverse ? t + 1 : t - 1;           // time index of the recurrence's previous step
-        float dyv = 0.f, ig = 0.f, fg = 0.f, gg = 0.f, og = 0.f, ct = 0.f, cp = 0.f;
-        if (valid) {
-            const size_t o = ((size_t)t * N + n) * H + j0 + u;
-            dyv = dy[o];
-            ct = cell[o];
-            if (tt > 0) cp = cell[((size_t)tp * N + n) * H + j0 + u];
-            const float *gp = gates + ((size_t)t * N + n) * H4 + j0 + u;
-            ig = gp[0];
-            fg = gp[(size_t)H];
-            gg = gp[2 * (size_t)H];
-            og = gp[3 * (size_t)H];
-        }
+        settle(in);
         float dhr = 0.f;
         if (s > 0) {
-            if (plane < PL) {
-                float v[NP];
-                const int nvalid = plane < G ? (G - plane + PL - 1) / PL : 0;
-                const u64 *src = mine + (size_t)((s - 1) & 1) * ngroups * G * C * H + (size_t)plane * C * H;
-                if (!sweep<NP>(src, PL * C * H, nvalid, (unsigned)s, v, status)) give_up = 1;
-                float sum = 0.f;
+            float v[NP];
+            const int nvalid = plane < G ? (G - plane + PL - 1) / PL : 0;
+            const u64 *src = mine + (size_t)((s - 1) & 1) * ngroups * G * C * H;
+            if (!sweep<NP>(src, plane * C * H, PL * C * H, G * C * H, (unsigned)s, v, status)) give_up = 1;
+            float sum = 0.f;
 #pragma unroll
-                for (int q = 0; q < NP; ++q)
-                    if (q < nvalid) sum += v[q];
-                gath[plane * PAIRS + pair] = sum;
-            }
+            for (int q = 0; q < NP; ++q)
+                if (q < nvalid) sum += v[q];
+            gath[plane * PAIRS + pair] = sum;
             __syncthreads();
             if (give_up) return;
             if (cell_lane) {
 #pragma unroll
                 for (int p = 0; p < PL; ++p) dhr += gath[p * PAIRS + pair];
             }
+            if (valid) {
+                const int tl = reverse ? t - 1 : t + 1;
+                float *dp = dgates + ((size_t)tl * N + n) * H4 + j0 + u;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) dp[(size_t)g * H] = held[g];
+            }
         }
+        float nx[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (valid && tt > 0) {
+            const size_t o = ((size_t)tp * N + n) * H + j0 + u;
+            nx[0] = dy[o];
+            nx[1] = in[2];
+            if (tt > 1) nx[2] = cell[((size_t)(reverse ? tp + 1 : tp - 1) * N + n) * H + j0 + u];
+            const float *gp = gates + ((size_t)tp * N + n) * H4 + j0 + u;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) nx[3 + g] = gp[(size_t)g * H];
+        }
+        asm volatile("" ::: "memory");                   // the deferred stores and the prefetch stay here
 
         if (cell_lane) {
-            const float dh = dyv + dhr;
+            const float ct = in[1], cp = in[2];
+            const float ig = in[3], fg = in[4], gg = in[5], og = in[6];
+            const float dh = in[0] + dhr;
             const float tc = tanhf(ct);
             const float dc = dh * og * (1.f - tc * tc) + dc_next * f_next;
             const float di = dc * gg * ig * (1.f - ig);
@@ -295,18 +397,17 @@ __global__ __launch_bounds__(kThreads, 1) void lstm_bwd_kernel(const float *__re
             const float dout = dh * tc * og * (1.f - og);
             dc_next = dc;
             f_next = fg;
-            if (valid) {
-                float *dp = dgates + ((size_t)t * N + n) * H4 + j0 + u;
-                dp[0] = di;
-                dp[(size_t)H] = df;
-                dp[2 * (size_t)H] = dg;
-                dp[3 * (size_t)H] = dout;
-            }
-            dgs[(0 * kUnits + u) * C + cc] = valid ? di : 0.f;
-            dgs[(1 * kUnits + u) * C + cc] = valid ? df : 0.f;
-            dgs[(2 * kUnits + u) * C + cc] = valid ? dg : 0.f;
-            dgs[(3 * kUnits + u) * C + cc] = valid ? dout : 0.f;
+            held[0] = di;
+            held[1] = df;
+            held[2] = dg;
+            held[3] = dout;
+            dgs[(0 * U + u) * C + cc] = valid ? di : 0.f;
+            dgs[(1 * U + u) * C + cc] = valid ? df : 0.f;
+            dgs[(2 * U + u) * C + cc] = valid ? dg : 0.f;
+            dgs[(3 * U + u) * C + cc] = valid ? dout : 0.f;
         }
+#pragma unroll
+        for (int q = 0; q < 7; ++q) in[q] = nx[q];
         __syncthreads();
         if (s + 1 == T) break;                            // the first step has no predecessor to feed
 
@@ -315,15 +416,10 @@ __global__ __launch_bounds__(kThreads, 1) void lstm_bwd_kernel(const float *__re
         for (int c = 0; c < C; ++c) acc[c] = 0.f;
 #pragma unroll
         for (int i = 0; i < R; ++i) {
-            const float4 *dp = reinterpret_cast<const float4 *>(dgs + (rp * R + i) * C);
+            float d[C];
+            lds_row<C>(dgs + (rp * R + i) * C, d);
 #pragma unroll
-            for (int c4 = 0; c4 < C / 4; ++c4) {
-                const float4 d4 = dp[c4];
-                acc[4 * c4 + 0] = fmaf(w[i], d4.x, acc[4 * c4 + 0]);
-                acc[4 * c4 + 1] = fmaf(w[i], d4.y, acc[4 * c4 + 1]);
-                acc[4 * c4 + 2] = fmaf(w[i], d4.z, acc[4 * c4 + 2]);
-                acc[4 * c4 + 3] = fmaf(w[i], d4.w, acc[4 * c4 + 3]);
-            }
+            for (int c = 0; c < C; ++c) acc[c] = fmaf(w[i], d[c], acc[c]);
         }
         u64 *dst = pbuf + (((size_t)(s & 1) * ngroups + group) * G + member) * C * H;
         if constexpr (RP == 1) {
@@ -333,7 +429,7 @@ __global__ __launch_bounds__(kThreads, 1) void lstm_bwd_kernel(const float *__re
 #pragma unroll
             for (int c = 0; c < C; ++c) red[(rp * C + c) * H + k] = acc[c];
             __syncthreads();
-            for (int e = tid; e < C * H; e += kThreads) {
+            for (int e = tid; e < C * H; e += NT) {
                 float v = 0.f;
 #pragma unroll
                 for (int q = 0; q < RP; ++q) v += red[q * C * H + e];
@@ -341,14 +437,22 @@ __global__ __launch_bounds__(kThreads, 1) void lstm_bwd_kernel(const float *__re
             }
         }
     }
+    if (valid && T > 0) {
+        const int tl = reverse ? T - 1 : 0;
+        float *dp = dgates + ((size_t)tl * N + n) * H4 + j0 + u;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) dp[(size_t)g * H] = held[g];
+    }
 }
 
-int g_lab_cols = 0;     // lab build: force the batch columns per workgroup (0 = the rule below)
+int g_lab_cols = 0;     // lab build: force the admitted batch columns, 8 or 16 (0 = the rule below)
+int g_lab_units = 0;    // lab build: force the hidden units per workgroup, 16, 32 or 64 (0 = the rule in lstm_plan)
 
-// The launch geometry: batch columns per workgroup C and groups; false where the kernels do not run.
+// The admission geometry: batch columns C per group of H / 16 workgroups and the number of groups; false where the
+// kernels do not run.  It fixes the workspace (tk_lstm_workspace_bytes) and bounds every launch plan.
 bool lstm_geometry(size_t N, size_t H, int cu_count, int *C_out, int *groups_out) {
     if (!(H == 16 || H == 32 || H == 64 || H == 128 || H == 256) || N == 0 || cu_count <= 0) return false;
-    const size_t G = H / kUnits;
+    const size_t G = H / 16;
     for (int C : {8, 16}) {
         if (g_lab_cols != 0 && C != g_lab_cols) continue;
         const size_t groups = (N + C - 1) / C;
@@ -361,9 +465,30 @@ bool lstm_geometry(size_t N, size_t H, int cu_count, int *C_out, int *groups_out
     return false;
 }
 
-size_t ws_bytes(size_t H, int C, int groups, bool backward) {
-    const size_t G = H / kUnits;
-    return 2 * (size_t)groups * (backward ? G : 1) * C * H * sizeof(u64);
+size_t ws_bytes(size_t H, int C, int groups, int U, bool backward) {
+    return 2 * (size_t)groups * (backward ? H / U : 1) * C * H * sizeof(u64);
+}
+
+// A launch: U units and C = C_admitted * 16 / U columns per workgroup, groups of H / U workgroups.  Release rule:
+// U = 64, or H where H < 64 (config 2's layer: 2.85 / 2.54 us per forward / backward step at U = 64, 2.84 / 3.58 at
+// U = 32, 3.44 / 4.02 at U = 16; tools/lstmbench.py).  C divides the admitted column count, so the grid and both granule buffers are never
+// larger than those of the admission geometry.
+struct Plan {
+    int U, C, groups;
+    unsigned grid;
+};
+
+bool lstm_plan(size_t N, size_t H, int cu_count, Plan *p) {
+    int C16 = 0, groups16 = 0;
+    if (!lstm_geometry(N, H, cu_count, &C16, &groups16)) return false;
+    int U = g_lab_units != 0 ? g_lab_units : 64;
+    if ((size_t)U > H) U = (int)H;
+    if (U != 16 && U != 32 && U != 64) return false;
+    p->U = U;
+    p->C = C16 * 16 / U;
+    p->groups = (int)((N + p->C - 1) / p->C);
+    p->grid = (unsigned)(p->groups * (H / U));
+    return true;
 }
 
 int zero_ws(void *ws, size_t bytes, hipStream_t stream) {
@@ -374,38 +499,42 @@ int zero_ws(void *ws, size_t bytes, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
 
-template <int C>
-int launch_fwd(size_t H, dim3 grid, hipStream_t st, const float *gx, const float *whh, int T, int N, int rev,
-               int groups, float *y, float *gates, float *cell, u64 *ws, uint32_t *status) {
-#define TK_LSTM_FWD(HH)                                                                                       \
-    case HH:                                                                                                  \
-        if (raise_dynamic_lds((const void *)lstm_fwd_kernel<HH, C>, fwd_lds_bytes<HH, C>())) return TK_ERR_LAUNCH; \
-        hipLaunchKernelGGL((lstm_fwd_kernel<HH, C>), grid, dim3(kThreads), (fwd_lds_bytes<HH, C>()), st, gx, whh, T, N, \
-                           rev, groups, y, gates, cell, ws, status);                                          \
-        break;
-    switch (H) {
-        TK_LSTM_FWD(16) TK_LSTM_FWD(32) TK_LSTM_FWD(64) TK_LSTM_FWD(128) TK_LSTM_FWD(256)
-        default: return TK_ERR_UNSUPPORTED;
+// (H, U, C) -> one instantiation: U = 16 takes 8 or 16 columns, U = 32 4 or 8, U = 64 2 or 4; U <= H
+#define TK_LSTM_SWITCH(LAUNCH)                                                                                    \
+    switch ((int)H * 100000 + p.U * 1000 + p.C) {                                                                 \
+        LAUNCH(16, 16, 8) LAUNCH(16, 16, 16) LAUNCH(32, 16, 8) LAUNCH(32, 16, 16) LAUNCH(64, 16, 8)                \
+        LAUNCH(64, 16, 16) LAUNCH(128, 16, 8) LAUNCH(128, 16, 16) LAUNCH(256, 16, 8) LAUNCH(256, 16, 16)          \
+        LAUNCH(32, 32, 4) LAUNCH(32, 32, 8) LAUNCH(64, 32, 4) LAUNCH(64, 32, 8) LAUNCH(128, 32, 4)                 \
+        LAUNCH(128, 32, 8) LAUNCH(256, 32, 4) LAUNCH(256, 32, 8)                                                  \
+        LAUNCH(64, 64, 2) LAUNCH(64, 64, 4) LAUNCH(128, 64, 2) LAUNCH(128, 64, 4) LAUNCH(256, 64, 2)               \
+        LAUNCH(256, 64, 4)                                                                                        \
+        default: return TK_ERR_UNSUPPORTED;                                                                       \
     }
+
+int launch_fwd(const Plan &p, size_t H, hipStream_t st, const float *gx, const float *whh, int T, int N, int rev,
+               float *y, float *gates, float *cell, u64 *ws, uint32_t *status) {
+#define TK_LSTM_FWD(HH, UU, CC)                                                                                  \
+    case HH * 100000 + UU * 1000 + CC:                                                                           \
+        hipLaunchKernelGGL((lstm_fwd_kernel<HH, CC, UU>), dim3(p.grid), dim3(threads_for<UU>()), 0, st, gx, whh, \
+                           T, N, rev, p.groups, y, gates, cell, ws, status);                                     \
+        break;
+    TK_LSTM_SWITCH(TK_LSTM_FWD)
 #undef TK_LSTM_FWD
     return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
 
-template <int C>
-int launch_bwd(size_t H, dim3 grid, hipStream_t st, const float *whh, const float *gates, const float *cell,
-               const float *dy, int T, int N, int rev, int groups, float *dg, u64 *ws, uint32_t *status) {
-#define TK_LSTM_BWD(HH)                                                                                        \
-    case HH:                                                                                                   \
-        hipLaunchKernelGGL((lstm_bwd_kernel<HH, C>), grid, dim3(kThreads), 0, st, whh, gates, cell, dy, T, N, \
-                           rev, groups, dg, ws, status);                                                       \
+int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const float *gates, const float *cell,
+               const float *dy, int T, int N, int rev, float *dg, u64 *ws, uint32_t *status) {
+#define TK_LSTM_BWD(HH, UU, CC)                                                                                   \
+    case HH * 100000 + UU * 1000 + CC:                                                                            \
+        hipLaunchKernelGGL((lstm_bwd_kernel<HH, CC, UU>), dim3(p.grid), dim3(threads_for<UU>()), 0, st, whh,      \
+                           gates, cell, dy, T, N, rev, p.groups, dg, ws, status);                                 \
         break;
-    switch (H) {
-        TK_LSTM_BWD(16) TK_LSTM_BWD(32) TK_LSTM_BWD(64) TK_LSTM_BWD(128) TK_LSTM_BWD(256)
-        default: return TK_ERR_UNSUPPORTED;
-    }
+    TK_LSTM_SWITCH(TK_LSTM_BWD)
 #undef TK_LSTM_BWD
     return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
+#undef TK_LSTM_SWITCH
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -414,7 +543,7 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 size_t lstm_workspace_bytes(size_t N, size_t H, int cu_count) {
     int C = 0, groups = 0;
     if (!lstm_geometry(N, H, cu_count, &C, &groups)) return 0;
-    return ws_bytes(H, C, groups, true);        // the backward's is the larger
+    return ws_bytes(H, C, groups, 16, true);    // the backward's at U = 16 bounds every plan's
 }
 
 int lstm_forward_dispatch(const float *gx, const float *whh, size_t T, size_t N, size_t H, int reverse,
@@ -423,18 +552,15 @@ int lstm_forward_dispatch(const float *gx, const float *whh, size_t T, size_t N,
     if (!gx || !whh || !y || !gates || !cell || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX ||
         N > (size_t)INT32_MAX)
         return TK_ERR_BAD_ARG;
-    int C = 0, groups = 0;
-    if (!lstm_geometry(N, H, cu_count, &C, &groups)) return TK_ERR_UNSUPPORTED;
-    const size_t need = ws_bytes(H, C, groups, false);
+    Plan p;
+    if (!lstm_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+    const size_t need = ws_bytes(H, p.C, p.groups, p.U, false);
     if (wsb < need) return TK_ERR_WORKSPACE;
     if (T == 0) return TK_OK;
     int rc = zero_ws(ws, need, stream);
     if (rc != TK_OK) return rc;
-    const dim3 grid((unsigned)(groups * (H / kUnits)));
-    u64 *hb = static_cast<u64 *>(ws);
-    return C == 8 ? launch_fwd<8>(H, grid, stream, gx, whh, (int)T, (int)N, reverse, groups, y, gates, cell, hb, status)
-                  : launch_fwd<16>(H, grid, stream, gx, whh, (int)T, (int)N, reverse, groups, y, gates, cell, hb,
-                                   status);
+    return launch_fwd(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, gates, cell, static_cast<u64 *>(ws),
+                      status);
 }
 
 int lstm_backward_dispatch(const float *whh, const float *gates, const float *cell, const float *dy, size_t T,
@@ -443,23 +569,32 @@ int lstm_backward_dispatch(const float *whh, const float *gates, const float *ce
     if (!whh || !gates || !cell || !dy || !dgates || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX ||
         N > (size_t)INT32_MAX)
         return TK_ERR_BAD_ARG;
-    int C = 0, groups = 0;
-    if (!lstm_geometry(N, H, cu_count, &C, &groups)) return TK_ERR_UNSUPPORTED;
-    const size_t need = ws_bytes(H, C, groups, true);
+    Plan p;
+    if (!lstm_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+    const size_t need = ws_bytes(H, p.C, p.groups, p.U, true);
     if (wsb < need) return TK_ERR_WORKSPACE;
     if (T == 0) return TK_OK;
     int rc = zero_ws(ws, need, stream);
     if (rc != TK_OK) return rc;
-    const dim3 grid((unsigned)(groups * (H / kUnits)));
-    u64 *pb = static_cast<u64 *>(ws);
-    return C == 8 ? launch_bwd<8>(H, grid, stream, whh, gates, cell, dy, (int)T, (int)N, reverse, groups, dgates, pb,
-                                  status)
-                  : launch_bwd<16>(H, grid, stream, whh, gates, cell, dy, (int)T, (int)N, reverse, groups, dgates,
-                                   pb, status);
+    return launch_bwd(p, H, stream, whh, gates, cell, dy, (int)T, (int)N, reverse, dgates, static_cast<u64 *>(ws),
+                      status);
 }
 
 #ifdef TK_LAB
 void lstm_lab_cols(int cols) { g_lab_cols = cols; }
+void lstm_lab_units(int units) { g_lab_units = units; }
+
+// out[0..7] = the admitted C and groups, then the launch plan's U, C, groups, grid and its forward and backward
+// granule bytes; false where the kernels do not run
+bool lstm_lab_geometry(size_t N, size_t H, int cu_count, size_t *out) {
+    int C16 = 0, groups16 = 0;
+    Plan p;
+    if (!lstm_geometry(N, H, cu_count, &C16, &groups16) || !lstm_plan(N, H, cu_count, &p)) return false;
+    const size_t v[8] = {(size_t)C16, (size_t)groups16, (size_t)p.U, (size_t)p.C, (size_t)p.groups, p.grid,
+                         ws_bytes(H, p.C, p.groups, p.U, false), ws_bytes(H, p.C, p.groups, p.U, true)};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return true;
+}
 #endif
 
 }  // namespace tk

@@ -1,0 +1,99 @@
+#!/usr/bin/env python
+"""Times one layer's LSTM recurrence (csrc/lstm_kernels.hip) on the GPU: tk_lstm_forward_dev and
+tk_lstm_backward_dev at (T, N, H), each timed with device events after warm-up; prints one JSON line per
+units setting (microseconds per timestep and direction, median and min over --steps).  The flagship layer
+(config 2) is the default shape.
+
+    python tools/lstmbench.py [--T 800] [--N 128] [--H 256] [--steps 20] [--warmup 3] [--units 0 16 32 64]
+
+--units (lab build) forces the hidden units per workgroup; 0 is the release rule.  Without --units the
+release library is timed.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from taiyaki_amd import _lib, layers  # noqa: E402
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return float(np.median(times)), float(np.min(times))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--T", type=int, default=800)
+    ap.add_argument("--N", type=int, default=128)
+    ap.add_argument("--H", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reverse", action="store_true")
+    ap.add_argument("--units", type=int, nargs="*", default=None, help="(lab) units per workgroup; 0 = release rule")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("lstmbench needs a GPU (the LSTM recurrence has no CPU fallback)")
+    dev = torch.device("cuda:0")
+    T, N, H = a.T, a.N, a.H
+    g = torch.Generator(device="cpu").manual_seed(11)
+    w_hh = (torch.rand(4 * H, H, generator=g) * 2 - 1).div_(H ** 0.5).to(dev)
+    gx = torch.randn(T, N, 4 * H, generator=g).to(dev)
+    dy = torch.randn(T, N, H, generator=g).div_((T * N) ** 0.5).to(dev)
+    y = torch.empty(T, N, H, device=dev)
+    gates = torch.empty(T, N, 4 * H, device=dev)
+    cell = torch.empty(T, N, H, device=dev)
+    dg = torch.empty(T, N, 4 * H, device=dev)
+    cus = layers._cu_count(dev)
+    _lib.set_strict(False)
+    for units in (a.units if a.units is not None else [None]):
+        L = _lib.use_lab(units is not None)
+        if units is not None:
+            L.tk_lab_lstm_units(units)
+        wsb = L.tk_lstm_workspace_bytes(N, H, cus)
+        if wsb == 0:
+            raise SystemExit("(N, H) = (%d, %d) is not admitted on %d CUs" % (N, H, cus))
+        ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
+        status = _lib.status_word(dev)
+        stream = _lib.stream_ptr()
+
+        def fwd():
+            _lib.check(L.tk_lstm_forward_dev(_lib.ptr(gx), _lib.ptr(w_hh), T, N, H, int(a.reverse), cus, _lib.ptr(y),
+                                             _lib.ptr(gates), _lib.ptr(cell), _lib.ptr(ws), wsb, _lib.ptr(status),
+                                             stream), "tk_lstm_forward_dev")
+
+        def bwd():
+            _lib.check(L.tk_lstm_backward_dev(_lib.ptr(w_hh), _lib.ptr(gates), _lib.ptr(cell), _lib.ptr(dy), T, N, H,
+                                              int(a.reverse), cus, _lib.ptr(dg), _lib.ptr(ws), wsb, _lib.ptr(status),
+                                              stream), "tk_lstm_backward_dev")
+
+        f_med, f_min = timed(fwd, a.steps, a.warmup)
+        b_med, b_min = timed(bwd, a.steps, a.warmup)
+        _lib.finish(status)
+        _lib.raise_if_nonfinite()
+        if units is not None:
+            L.tk_lab_lstm_units(0)
+        print(json.dumps({"T": T, "N": N, "H": H, "reverse": a.reverse, "units": units, "cus": cus,
+                          "fwd_ms": round(f_med, 3), "bwd_ms": round(b_med, 3),
+                          "fwd_us_per_step": round(1e3 * f_med / T, 3), "fwd_min_us_per_step": round(1e3 * f_min / T, 3),
+                          "bwd_us_per_step": round(1e3 * b_med / T, 3), "bwd_min_us_per_step": round(1e3 * b_min / T, 3),
+                          "device": torch.cuda.get_device_name(dev)}))
+    _lib.use_lab(False)
+
+
+if __name__ == "__main__":
+    main()
