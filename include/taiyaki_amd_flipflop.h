@@ -308,6 +308,32 @@ int tk_lstm_backward_dev(const float *w_hh, const float *gates, const float *cel
                          size_t workspace_bytes, uint32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * A narrow Convolution layer with swish (layers.Convolution, stride 1), fused (csrc/conv_kernels.hip):
+ *   x (T, N, insize), weight (size, insize, winlen) and bias (size) as nn.Conv1d holds them,
+ *   y (T, N, size) = swish(conv(x zero-padded by (winlen / 2, (winlen - 1) / 2)) + bias).
+ *   backward: from dy, x, weight, bias (the pre-activation is recomputed) -> dweight, dbias and,
+ *   where dx is not NULL, dx (T, N, insize).  x, y, dy, dx and the workspace are 16-byte aligned.
+ * tk_conv1d_small_supported: 1 for the shapes that are built, (insize, size, winlen, stride) =
+ *   (1, 4, 5, 1) and (4, 16, 5, 1); the calls return TK_ERR_UNSUPPORTED for any other.
+ * tk_conv1d_small_workspace_bytes: the backward's workspace (one partial dweight | dbias per
+ *   workgroup, in double, added in a fixed order: results are bit-identical run to run and do not depend on
+ *   what the workspace held), 0 where the kernels do not run.  The forward needs none.
+ * Nothing is allocated or synchronised inside; there is no status word (the kernels have nothing
+ * to report: non-finite values pass through as they do through nn.Conv1d).
+ * ------------------------------------------------------------------------- */
+int tk_conv1d_small_supported(size_t insize, size_t size, size_t winlen, size_t stride);
+
+size_t tk_conv1d_small_workspace_bytes(size_t nblk, size_t nbatch, size_t insize, size_t size, size_t winlen,
+                                       int cu_count);
+
+int tk_conv1d_small_forward_dev(const float *x, const float *weight, const float *bias, size_t nblk, size_t nbatch,
+                                size_t insize, size_t size, size_t winlen, int cu_count, float *y, void *stream);
+
+int tk_conv1d_small_backward_dev(const float *dy, const float *x, const float *weight, const float *bias, size_t nblk,
+                                 size_t nbatch, size_t insize, size_t size, size_t winlen, int cu_count, float *dx,
+                                 float *dweight, float *dbias, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Viterbi decode (decode.py:75-115: first-index tie rule, bit-exact fp32 adds)
  *   fwd (nblk+1, nbatch, 2nb) f32 ; traceback (nblk, nbatch, 2nb) int64 ;
  *   path (nblk+1, nbatch) int64.   fwd and traceback may BOTH be NULL (path only: what

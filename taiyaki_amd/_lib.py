@@ -54,6 +54,11 @@ SIGNATURES = {
     "tk_lstm_workspace_bytes": (_sz, [_sz, _sz, _i]),
     "tk_lstm_forward_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "tk_lstm_backward_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _sz, _vp, _vp]),
+    "tk_conv1d_small_supported": (_i, [_sz, _sz, _sz, _sz]),
+    "tk_conv1d_small_workspace_bytes": (_sz, [_sz, _sz, _sz, _sz, _sz, _i]),
+    "tk_conv1d_small_forward_dev": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _i, _vp, _vp]),
+    "tk_conv1d_small_backward_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _i, _vp, _vp, _vp, _vp, _sz,
+                                         _vp]),
     "tk_squiggle_match_workspace_bytes": (_sz, [_i, _sz, _sz, _sz]),
     "tk_squiggle_match_cost_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _f, _vp, _vp, _sz, _vp, _vp]),
     "tk_squiggle_match_grad_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _f, _i, _vp, _vp, _vp, _sz, _vp, _vp]),

@@ -80,6 +80,13 @@ void lstm_lab_cols(int cols);
 void lstm_lab_units(int units);
 bool lstm_lab_geometry(size_t N, size_t H, int cu_count, size_t *out);
 #endif
+bool conv_small_supported(size_t cin, size_t cout, size_t winlen, size_t stride);
+size_t conv_small_workspace_bytes(size_t T, size_t N, size_t cin, size_t cout, size_t winlen, int cu_count);
+int conv_small_forward_dispatch(const float *x, const float *w, const float *b, size_t T, size_t N, size_t cin,
+                                size_t cout, size_t winlen, int cu_count, float *y, hipStream_t stream);
+int conv_small_backward_dispatch(const float *dy, const float *x, const float *w, const float *b, size_t T, size_t N,
+                                 size_t cin, size_t cout, size_t winlen, int cu_count, float *dx, float *dw, float *db,
+                                 void *ws, size_t wsb, hipStream_t stream);
 int path_to_reftosignal_dispatch(const int64_t *path, const int64_t *path_off, const int64_t *ref_off,
                                  const int64_t *signalstart, const int64_t *siglen, int stride, size_t nread,
                                  int32_t *rts, hipStream_t stream);
@@ -576,6 +583,29 @@ int tk_lstm_backward_dev(const float *w_hh, const float *gates, const float *cel
                          size_t workspace_bytes, uint32_t *status, void *stream) {
     return tk::lstm_backward_dispatch(w_hh, gates, cell, dy, nblk, nbatch, size, reverse, cu_count, dgates,
                                       workspace, workspace_bytes, status, static_cast<hipStream_t>(stream));
+}
+
+int tk_conv1d_small_supported(size_t insize, size_t size, size_t winlen, size_t stride) {
+    return tk::conv_small_supported(insize, size, winlen, stride) ? 1 : 0;
+}
+
+size_t tk_conv1d_small_workspace_bytes(size_t nblk, size_t nbatch, size_t insize, size_t size, size_t winlen,
+                                       int cu_count) {
+    return tk::conv_small_workspace_bytes(nblk, nbatch, insize, size, winlen, cu_count);
+}
+
+int tk_conv1d_small_forward_dev(const float *x, const float *weight, const float *bias, size_t nblk, size_t nbatch,
+                                size_t insize, size_t size, size_t winlen, int cu_count, float *y, void *stream) {
+    return tk::conv_small_forward_dispatch(x, weight, bias, nblk, nbatch, insize, size, winlen, cu_count, y,
+                                           static_cast<hipStream_t>(stream));
+}
+
+int tk_conv1d_small_backward_dev(const float *dy, const float *x, const float *weight, const float *bias, size_t nblk,
+                                 size_t nbatch, size_t insize, size_t size, size_t winlen, int cu_count, float *dx,
+                                 float *dweight, float *dbias, void *workspace, size_t workspace_bytes, void *stream) {
+    return tk::conv_small_backward_dispatch(dy, x, weight, bias, nblk, nbatch, insize, size, winlen, cu_count, dx,
+                                            dweight, dbias, workspace, workspace_bytes,
+                                            static_cast<hipStream_t>(stream));
 }
 
 int tk_flipflop_lattice_dev(const float *scores, size_t nblk, size_t nbatch, size_t nbase, int forward,

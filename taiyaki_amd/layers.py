@@ -8,7 +8,9 @@ that feeds them.
   PyTorch-ROCm (MIOpen GRU, Conv1d): by scope they STAY PyTorch modules
   (BASELINE.json north_star) and only produce the (T, N, S) score tensor.
   ``Lstm`` keeps its nn.LSTM parameters, but on the GPU its recurrence runs as the
-  persistent HIP kernels of csrc/lstm_kernels.hip (`LstmRecurrence`).
+  persistent HIP kernels of csrc/lstm_kernels.hip (`LstmRecurrence`), and a narrow
+  ``Convolution`` with swish runs as the fused HIP kernels of csrc/conv_kernels.hip
+  (`SmallConvolution`).
 """
 import numpy as np
 import torch
@@ -99,6 +101,73 @@ def _truncated_normal_(param, sd):
         nn.init.trunc_normal_(param, std=sd, a=-2 * sd, b=2 * sd)
 
 
+# False: every Convolution with `use_gemm` runs unfold + GEMM, for comparisons against the HIP operator
+USE_HIP_CONV = True
+_CU_COUNT = {}
+
+
+def _cu_count(dev):
+    n = _CU_COUNT.get(dev.index)
+    if n is None:
+        n = _CU_COUNT[dev.index] = torch.cuda.get_device_properties(dev).multi_processor_count
+    return n
+
+
+def _aligned(t):
+    """Contiguous and 16-byte aligned (the kernels load and store float4)."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class SmallConvolution(torch.autograd.Function):
+    """swish(conv1d(x) + b) of a narrow `Convolution` (stride 1; the shapes tk_conv1d_small_supported names) on the
+    kernels of csrc/conv_kernels.hip: one forward launch writes y; the backward recomputes the pre-activation from x
+    and the weights and gives dx (when wanted), dW and db in one launch plus the fixed-order sum of its partial
+    slabs.  No GEMM, unfold copy or element-wise kernel."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        T, N, cin = x.shape
+        cout, _, winlen = weight.shape
+        dev = x.device
+        weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+        if ctx.needs_input_grad[0]:
+            x = _aligned(x.detach())
+        else:
+            # the network's input: a captured train step reloads that buffer in place before every replay, which
+            # autograd refuses for a saved tensor -- keep a copy (made inside the captured graph; 4 bytes a sample)
+            x = x.detach().clone(memory_format=torch.contiguous_format)
+        with torch.cuda.device(dev):
+            y = torch.empty(T, N, cout, dtype=torch.float32, device=dev)
+            rc = _lib.lib().tk_conv1d_small_forward_dev(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), T, N, cin, cout,
+                                                        winlen, _cu_count(dev), _lib.ptr(y), _lib.stream_ptr())
+        _lib.check(rc, "tk_conv1d_small_forward_dev")
+        ctx.save_for_backward(x, weight, bias)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight, bias = ctx.saved_tensors
+        T, N, cin = x.shape
+        cout, _, winlen = weight.shape
+        dev = x.device
+        L = _lib.lib()
+        dy = _aligned(dy)
+        with torch.cuda.device(dev):
+            dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+            dw, db = torch.empty_like(weight), torch.empty_like(bias)
+            if T * N == 0:
+                return dx, dw.zero_(), db.zero_()
+            wsb = L.tk_conv1d_small_workspace_bytes(T, N, cin, cout, winlen, _cu_count(dev))
+            ws = _lib.workspace(wsb, dev, "conv")
+            rc = L.tk_conv1d_small_backward_dev(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), T, N, cin,
+                                                cout, winlen, _cu_count(dev), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
+                                                _lib.ptr(ws), wsb, _lib.stream_ptr())
+        _lib.check(rc, "tk_conv1d_small_backward_dev")
+        return dx, dw, db
+
+
 class Convolution(nn.Module):
     """layers.py:744-850: TBF in/out, pad (winlen//2, (winlen-1)//2), then activation.
 
@@ -108,6 +177,12 @@ class Convolution(nn.Module):
     direct/weight-gradient kernels that cost more than the whole LSTM stack, while
     the same contraction as a rocBLAS GEMM is a few hundred microseconds.  Set
     `use_gemm=False` for the plain nn.Conv1d evaluation (identical result).
+
+    The GEMM library is in turn the wrong tool for the two narrow layers at the head of the
+    model (1 -> 4 and 4 -> 16 channels on raw samples): their weight gradients are 4 x 5 and
+    16 x 20 results over 512 000 rows, one macro tile on nine workgroups, 3 ms each.  With
+    `use_gemm` set, a float32 CUDA input, swish and a shape `tk_conv1d_small_supported` names,
+    the layer runs as the fused HIP operator `SmallConvolution` (USE_HIP_CONV = False: never).
     """
 
     def __init__(self, insize, size, winlen, stride=1, fun=torch.tanh, use_gemm=True):
@@ -121,10 +196,18 @@ class Convolution(nn.Module):
         _orthonormal_(self.conv.weight)
         _truncated_normal_(self.conv.bias, 0.5)
 
+    def _hip_small(self, x):
+        w = self.conv.weight
+        return (USE_HIP_CONV and self.activation is swish and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
+                and w.is_cuda and w.dtype == torch.float32
+                and bool(_lib.lib().tk_conv1d_small_supported(w.shape[1], w.shape[0], self.winlen, self.stride)))
+
     def forward(self, x):
         if not self.use_gemm:
             out = self.activation(self.conv(self.pad(x.permute(1, 2, 0))))
             return out.permute(2, 0, 1)
+        if self._hip_small(x):
+            return SmallConvolution.apply(x, self.conv.weight, self.conv.bias)
         # x: (T, N, C) -> pad time -> windows (Tout, N, C, winlen) -> GEMM with (C*winlen, size)
         xp = nn.functional.pad(x, (0, 0, 0, 0, self.winlen // 2, (self.winlen - 1) // 2))
         win = xp.unfold(0, self.winlen, self.stride)            # (Tout, N, C, winlen) view
@@ -154,14 +237,6 @@ class _Rnn(nn.Module):
 
 # False: every Lstm runs nn.LSTM (MIOpen on the GPU), for comparisons against the HIP recurrence
 USE_HIP_LSTM = True
-_CU_COUNT = {}
-
-
-def _cu_count(dev):
-    n = _CU_COUNT.get(dev.index)
-    if n is None:
-        n = _CU_COUNT[dev.index] = torch.cuda.get_device_properties(dev).multi_processor_count
-    return n
 
 
 def hip_lstm_workspace_bytes(rnn, x):
