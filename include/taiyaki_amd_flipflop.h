@@ -65,6 +65,7 @@ extern "C" {
 #define TK_STATUS_SEQ_TOO_LONG 16u      /* CRF: a sequence longer than the max_seqlen the launch was sized for */
 #define TK_STATUS_LSTM_TIMEOUT 32u      /* LSTM recurrence: a workgroup waited past its clock budget for its group
                                            (the launch's outputs are not valid) */
+#define TK_STATUS_RNN_TIMEOUT TK_STATUS_LSTM_TIMEOUT    /* the same bit for the GRU recurrence (one name for both) */
 #define TK_STATUS_BAD_SIGLEN 64u        /* squiggle match: a siglen <= 0, or reads that run past the end of
                                            the signal vector (the reference asserts or reads out of bounds) */
 #define TK_STATUS_BAD_LABEL 8u          /* tk_flipflop_build_indices_dev: a flip-flop code outside
@@ -306,6 +307,34 @@ int tk_lstm_forward_dev(const float *gx, const float *w_hh, size_t nblk, size_t 
 int tk_lstm_backward_dev(const float *w_hh, const float *gates, const float *cell, const float *dy, size_t nblk,
                          size_t nbatch, size_t size, int reverse, int cu_count, float *dgates, void *workspace,
                          size_t workspace_bytes, uint32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * GRU recurrence of one nn.GRU layer (layers.GruMod; gate order r, z, n; h0 = 0),
+ * one persistent launch per call (csrc/gru_kernels.hip).
+ *   gx (T, N, 3H) = x W_ih^T + b_ih; w_hh (3H, H); b_hh (3H) (its third slab sits inside
+ *   the reset gate's product and cannot be folded into gx); reverse != 0 runs the
+ *   recurrence from t = T-1 down to 0 (layers.Reverse) with every tensor in time order.
+ *   forward: with a = W_hh h_prev: r = sigmoid(gx_r + a_r + bhh_r), z = sigmoid(gx_z + a_z + bhh_z),
+ *     q = a_n + bhh_n, n = tanh(gx_n + r q), h = (1 - z) n + z h_prev.  Writes y (T, N, H) = h,
+ *     gates (T, N, 3H) = the activations r, z, n and q (T, N, H).  gates and q may both be NULL
+ *     (inference: nothing is saved for a backward call and those stores are not issued).
+ *   backward: dy (T, N, H) = dL/dy -> dgates (T, N, 3H) = dL/d(gx) = [dr_pre, dz_pre, dn_pre] and
+ *     dq (T, N, H) = dn_pre r: the hidden side's pre-activation gradient is [dr_pre, dz_pre, dq].
+ * tk_gru_workspace_bytes: the workspace either call needs at (nbatch, size) on a device with
+ * cu_count CUs, 0 where the kernels do not run (the caller falls back to nn.GRU); never 0
+ * where they do.  Sizes 32, 64, 96 and 128 run at any nbatch >= 1; size 256 where
+ * ceil(nbatch / 4) * 4 <= cu_count.  The same cu_count goes to both calls.
+ * TK_STATUS_RNN_TIMEOUT in *status if a workgroup's wait for its group ran out of time.
+ * ------------------------------------------------------------------------- */
+size_t tk_gru_workspace_bytes(size_t nbatch, size_t size, int cu_count);
+
+int tk_gru_forward_dev(const float *gx, const float *w_hh, const float *b_hh, size_t nblk, size_t nbatch, size_t size,
+                       int reverse, int cu_count, float *y, float *gates, float *q, void *workspace,
+                       size_t workspace_bytes, uint32_t *status, void *stream);
+
+int tk_gru_backward_dev(const float *w_hh, const float *y, const float *gates, const float *q, const float *dy,
+                        size_t nblk, size_t nbatch, size_t size, int reverse, int cu_count, float *dgates, float *dq,
+                        void *workspace, size_t workspace_bytes, uint32_t *status, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * A narrow Convolution layer with swish (layers.Convolution, stride 1), fused (csrc/conv_kernels.hip):

@@ -54,6 +54,9 @@ SIGNATURES = {
     "tk_lstm_workspace_bytes": (_sz, [_sz, _sz, _i]),
     "tk_lstm_forward_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "tk_lstm_backward_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _sz, _vp, _vp]),
+    "tk_gru_workspace_bytes": (_sz, [_sz, _sz, _i]),
+    "tk_gru_forward_dev": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "tk_gru_backward_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "tk_conv1d_small_supported": (_i, [_sz, _sz, _sz, _sz]),
     "tk_conv1d_small_workspace_bytes": (_sz, [_sz, _sz, _sz, _sz, _sz, _i]),
     "tk_conv1d_small_forward_dev": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _i, _vp, _vp]),
@@ -105,7 +108,7 @@ ERRORS = {1: "bad argument (NULL / shape / 16-byte alignment)",
           3: "workspace too small", 4: "HIP launch failure"}
 
 LAB_SIGNATURES = {"tk_lab_crf_band_phase": (None, [_i]), "tk_lab_lstm_cols": (None, [_i]),
-                  "tk_lab_lstm_units": (None, [_i]),
+                  "tk_lab_lstm_units": (None, [_i]), "tk_lab_gru_cols": (None, [_i]),
                   "tk_lab_lstm_geometry": (_i, [_sz, _sz, _i, ctypes.POINTER(_sz)])}
 
 _lib = None
@@ -334,7 +337,7 @@ def _raise(bits):
                              "outside [0, 2 nbase), modification category outside its base's range, or "
                              "sum(seqlen) larger than the label array)")
     if bits & 32:
-        raise RuntimeError("LSTM recurrence: a workgroup waited past its time budget for the rest of its group "
+        raise RuntimeError("LSTM / GRU recurrence: a workgroup waited past its time budget for the rest of its group "
                            "(the layer's outputs are not valid)")
     if bits & 16:
         raise RuntimeError("a sequence is longer than the max_seqlen the CRF kernel was launched for")

@@ -75,7 +75,15 @@ int lstm_forward_dispatch(const float *gx, const float *whh, size_t T, size_t N,
 int lstm_backward_dispatch(const float *whh, const float *gates, const float *cell, const float *dy, size_t T,
                            size_t N, size_t H, int reverse, int cu_count, float *dgates, void *ws, size_t wsb,
                            uint32_t *status, hipStream_t stream);
+size_t gru_workspace_bytes(size_t N, size_t H, int cu_count);
+int gru_forward_dispatch(const float *gx, const float *whh, const float *bhh, size_t T, size_t N, size_t H,
+                         int reverse, int cu_count, float *y, float *gates, float *q, void *ws, size_t wsb,
+                         uint32_t *status, hipStream_t stream);
+int gru_backward_dispatch(const float *whh, const float *y, const float *gates, const float *q, const float *dy,
+                          size_t T, size_t N, size_t H, int reverse, int cu_count, float *dgates, float *dq, void *ws,
+                          size_t wsb, uint32_t *status, hipStream_t stream);
 #ifdef TK_LAB
+void gru_lab_cols(int cols);
 void lstm_lab_cols(int cols);
 void lstm_lab_units(int units);
 bool lstm_lab_geometry(size_t N, size_t H, int cu_count, size_t *out);
@@ -558,6 +566,8 @@ int tk_devcopy_f32_dev(float *dst, const float *src, size_t n, void *stream) {
 extern "C" void tk_lab_crf_band_phase(int phase) { tk::crf_band_lab_phase(phase); }
 // the LSTM recurrence's batch columns per workgroup, 8 or 16 (0: the launcher's rule; lstm_kernels.hip)
 extern "C" void tk_lab_lstm_cols(int cols) { tk::lstm_lab_cols(cols); }
+// the GRU recurrence's batch columns per workgroup at sizes <= 128: 1 or 2 (0: the launcher's rule; gru_kernels.hip)
+extern "C" void tk_lab_gru_cols(int cols) { tk::gru_lab_cols(cols); }
 // the LSTM recurrence's hidden units per workgroup, 16, 32 or 64 (0: the launcher's rule)
 extern "C" void tk_lab_lstm_units(int units) { tk::lstm_lab_units(units); }
 // the LSTM recurrence's launch plan at (nbatch, size, cu_count): out[8] = admitted C and groups, U, C, groups,
@@ -583,6 +593,24 @@ int tk_lstm_backward_dev(const float *w_hh, const float *gates, const float *cel
                          size_t workspace_bytes, uint32_t *status, void *stream) {
     return tk::lstm_backward_dispatch(w_hh, gates, cell, dy, nblk, nbatch, size, reverse, cu_count, dgates,
                                       workspace, workspace_bytes, status, static_cast<hipStream_t>(stream));
+}
+
+size_t tk_gru_workspace_bytes(size_t nbatch, size_t size, int cu_count) {
+    return tk::gru_workspace_bytes(nbatch, size, cu_count);
+}
+
+int tk_gru_forward_dev(const float *gx, const float *w_hh, const float *b_hh, size_t nblk, size_t nbatch, size_t size,
+                       int reverse, int cu_count, float *y, float *gates, float *q, void *workspace,
+                       size_t workspace_bytes, uint32_t *status, void *stream) {
+    return tk::gru_forward_dispatch(gx, w_hh, b_hh, nblk, nbatch, size, reverse, cu_count, y, gates, q, workspace,
+                                    workspace_bytes, status, static_cast<hipStream_t>(stream));
+}
+
+int tk_gru_backward_dev(const float *w_hh, const float *y, const float *gates, const float *q, const float *dy,
+                        size_t nblk, size_t nbatch, size_t size, int reverse, int cu_count, float *dgates, float *dq,
+                        void *workspace, size_t workspace_bytes, uint32_t *status, void *stream) {
+    return tk::gru_backward_dispatch(w_hh, y, gates, q, dy, nblk, nbatch, size, reverse, cu_count, dgates, dq,
+                                     workspace, workspace_bytes, status, static_cast<hipStream_t>(stream));
 }
 
 int tk_conv1d_small_supported(size_t insize, size_t size, size_t winlen, size_t stride) {

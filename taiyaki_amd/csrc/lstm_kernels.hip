@@ -9,124 +9,23 @@
 //
 // Hand-off.  Inside a group every step is an all-to-all: forward, each member needs the whole h_{t-1} of its
 // columns; backward, each member needs the sum over members of W_hh[rows(m), J]^T dG_{t+1}[rows(m)] for its units J
-// (a reduce-scatter, summed in producer order: bit-reproducible).  Both go through 8-byte granules {value, tag}
-// written by ONE sc1 store and read by sc1 loads until every tag matches (cdna_hip_programming.md Guideline 16,
-// R2: the data is the flag, no fence).  Tag = step + 1, two slots by step parity: no member can publish step s + 2
-// before every member has read step s.  The granule buffers are zeroed by a kernel in front of every launch.
-// Every spin is bounded by a clock budget; on expiry TK_STATUS_LSTM_TIMEOUT is OR-ed into *status and the whole
-// grid leaves (the other spins see the bit).
+// (a reduce-scatter, summed in producer order: bit-reproducible).  Both go through the tagged granules of
+// rnn_common.h (its header has the protocol, the zeroing in front of every launch and the bounded spin).
 //
 // Step schedule.  vmcnt is one in-order counter per wave for loads and stores, so every wait of a poll also waits
 // for whatever the wave issued before it.  Nothing bound for HBM is issued ahead of a poll in the same step: the
 // inputs of step s + 1 (forward: gx; backward: dy, c_{t-1}, the gates) are loaded right after step s's poll, and
 // the bulk outputs of step s (forward: y, c, gates; backward: dG) are held in registers and stored right after
 // step s + 1's poll.  Both drain under the matvec; the granule publish is the last memory operation of a step.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/taiyaki_amd_flipflop.h"
 #include "ff_common.h"
+#include "rnn_common.h"
 
 namespace tk {
 namespace {
 
-constexpr uint64_t kSpinTicks = 200000000ull;   // 2 s of s_memrealtime (100 MHz) per wait
-
 // threads per workgroup at U units: 4 U H / threads W_hh floats per lane, <= 128 at H = 256
 template <int U>
 constexpr int threads_for() { return U <= 32 ? 256 : 512; }
-
-typedef unsigned long long u64;
-typedef __attribute__((address_space(1))) u64 gu64;
-typedef __attribute__((address_space(1))) uint32_t gu32;
-
-__device__ __forceinline__ void store_granule(u64 *g, unsigned tag, float v) {
-    __hip_atomic_store((gu64 *)g, ((u64)tag << 32) | __float_as_uint(v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// This lane's NG granules g[e0 + q * stride] that lie below `end` until every lane of the wave sees `tag` in all
-// of its own; false when the clock budget runs out or another workgroup has already given up.  Every pass issues
-// all NG loads before it waits (a granule at or past `end` is read at g[0] and ignored: no branch per load).
-template <int NG>
-__device__ __forceinline__ bool sweep(const u64 *g, int e0, int stride, int end, unsigned tag, float (&v)[NG],
-                                      uint32_t *status) {
-    const uint64_t start = __builtin_amdgcn_s_memrealtime();
-    for (unsigned spins = 0;; ++spins) {
-        bool ok = true;
-#pragma unroll
-        for (int q = 0; q < NG; ++q) {
-            const int e = e0 + q * stride;
-            const bool in = e < end;
-            const u64 x = __hip_atomic_load((gu64 *)(g + (in ? e : 0)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            v[q] = __uint_as_float((unsigned)x);
-            ok &= !in || (unsigned)(x >> 32) == tag;
-        }
-        if (__all(ok)) return true;
-        if ((spins & 31) == 31) {
-            const uint32_t st = __hip_atomic_load((gu32 *)status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((st & TK_STATUS_LSTM_TIMEOUT) || __builtin_amdgcn_s_memrealtime() - start > kSpinTicks) {
-                __hip_atomic_fetch_or((gu32 *)status, TK_STATUS_LSTM_TIMEOUT, __ATOMIC_RELAXED,
-                                      __HIP_MEMORY_SCOPE_AGENT);
-                return false;
-            }
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-}
-
-// Block -> (group, member).  Blocks b and b + 8 share an XCD under round-robin placement; members of a group are
-// taken from one residue of b mod 8 where the grid allows (speed only: the hand-off does not depend on placement).
-__device__ __forceinline__ void place(int G, int &group, int &member) {
-    const int b = blockIdx.x, nb = gridDim.x;
-    int L = b;
-    if (nb % 8 == 0 && (nb / 8) % G == 0) L = (b % 8) * (nb / 8) + b / 8;
-    group = L / G;
-    member = L % G;
-}
-
-// Values loaded from HBM, pinned as ready here: the compiler waits for their loads at this point, not at their first
-// use after a later prefetch (vmcnt is in order, so that wait would also wait for the prefetch).
-template <int M>
-__device__ __forceinline__ void settle(float (&v)[M]) {
-#pragma unroll
-    for (int i = 0; i < M; ++i) asm volatile("" : "+v"(v[i]));
-}
-template <int M, int K>
-__device__ __forceinline__ void settle(float (&v)[M][K]) {
-#pragma unroll
-    for (int i = 0; i < M; ++i) settle(v[i]);
-}
-
-__device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
-
-// C consecutive floats of LDS (16-byte aligned where C is a multiple of 4)
-template <int C>
-__device__ __forceinline__ void lds_row(const float *p, float (&v)[C]) {
-    if constexpr (C % 4 == 0) {
-#pragma unroll
-        for (int c4 = 0; c4 < C / 4; ++c4) {
-            const float4 q = reinterpret_cast<const float4 *>(p)[c4];
-            v[4 * c4 + 0] = q.x;
-            v[4 * c4 + 1] = q.y;
-            v[4 * c4 + 2] = q.z;
-            v[4 * c4 + 3] = q.w;
-        }
-    } else if constexpr (C == 2) {
-        const float2 q = *reinterpret_cast<const float2 *>(p);
-        v[0] = q.x;
-        v[1] = q.y;
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) v[c] = p[c];
-    }
-}
-
-__global__ void zero_u64x2_kernel(uint4 *p, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        p[i] = make_uint4(0u, 0u, 0u, 0u);
-}
 
 // Forward.  gx (T, N, 4H) = x W_ih^T + b_ih + b_hh.  Writes y = h (T, N, H), the gate activations (T, N, 4H) and
 // c (T, N, H).  Recurrence step s runs time t = s (reverse: T - 1 - s).  hbuf: [2][ngroups][C][H] granules.
@@ -491,14 +390,6 @@ bool lstm_plan(size_t N, size_t H, int cu_count, Plan *p) {
     return true;
 }
 
-int zero_ws(void *ws, size_t bytes, hipStream_t stream) {
-    // (a kernel, not hipMemsetAsync: see clip_kernels.hip on memset nodes replayed from a hipGraph)
-    const size_t n = bytes / 16;
-    const unsigned blocks = (unsigned)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
-    hipLaunchKernelGGL(zero_u64x2_kernel, dim3(blocks), dim3(256), 0, stream, static_cast<uint4 *>(ws), n);
-    return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
-}
-
 // (H, U, C) -> one instantiation: U = 16 takes 8 or 16 columns, U = 32 4 or 8, U = 64 2 or 4; U <= H
 #define TK_LSTM_SWITCH(LAUNCH)                                                                                    \
     switch ((int)H * 100000 + p.U * 1000 + p.C) {                                                                 \
@@ -535,8 +426,6 @@ int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const 
     return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
 #undef TK_LSTM_SWITCH
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 

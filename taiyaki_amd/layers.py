@@ -5,10 +5,11 @@ that feeds them.
   kernels (csrc/logz_kernels.hip) instead of cupy / the T-step torch loop.
 * ``Convolution``, ``Lstm``, ``GruMod``, ``Reverse``, ``Serial``, ``GlobalNormFlipFlop``
   and ``GlobalNormFlipFlopCatMod`` restate the reference layers minimally on
-  PyTorch-ROCm (MIOpen GRU, Conv1d): by scope they STAY PyTorch modules
+  PyTorch-ROCm (Conv1d): by scope they STAY PyTorch modules
   (BASELINE.json north_star) and only produce the (T, N, S) score tensor.
-  ``Lstm`` keeps its nn.LSTM parameters, but on the GPU its recurrence runs as the
-  persistent HIP kernels of csrc/lstm_kernels.hip (`LstmRecurrence`), and a narrow
+  ``Lstm`` and ``GruMod`` keep their nn.LSTM / nn.GRU parameters, but on the GPU their
+  recurrences run as the persistent HIP kernels of csrc/lstm_kernels.hip
+  (`LstmRecurrence`) and csrc/gru_kernels.hip (`GruRecurrence`), and a narrow
   ``Convolution`` with swish runs as the fused HIP kernels of csrc/conv_kernels.hip
   (`SmallConvolution`).
 """
@@ -328,11 +329,130 @@ class Lstm(_Rnn):
         return rnn(x)[0]
 
 
+# False: every GruMod runs nn.GRU (MIOpen on the GPU), for comparisons against the HIP recurrence
+USE_HIP_GRU = True
+
+
+def hip_gru_workspace_bytes(rnn, x):
+    """Workspace of the HIP recurrence for this layer and input, 0 where it does not run (CPU tensors, other
+    dtypes, nn.GRU options the kernels do not implement, sizes the launch geometry does not cover)."""
+    if not (USE_HIP_GRU and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
+            and rnn.weight_hh_l0.is_cuda and rnn.weight_hh_l0.dtype == torch.float32):
+        return 0
+    if rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or rnn.batch_first:
+        return 0
+    return _lib.lib().tk_gru_workspace_bytes(x.shape[1], rnn.hidden_size, _cu_count(x.device))
+
+
+def _time_sum_tn(a, b, rows=2048):
+    """sum over (t, n) of a[t, n, :, None] * b[t, n, None, :] for a (T, N, M) and b (T, N, P): a^T b over T N rows,
+    as a batched GEMM over runs of about `rows` rows whose partial results are then summed over the runs.  One GEMM
+    accumulates all T N products of an entry in float32 in a row (64 000 at bench.py --config 1's layer: 3.6e-6 of
+    the largest entry against float64, where MIOpen's weight gradient is at 6e-7)."""
+    T, N, M = a.shape
+    P = b.shape[2]
+    tc = max(1, rows // N)
+    B = T // tc
+    if B < 2:
+        return a.reshape(T * N, M).t() @ b.reshape(T * N, P)
+    main = B * tc
+    out = torch.bmm(a[:main].reshape(B, tc * N, M).transpose(1, 2), b[:main].reshape(B, tc * N, P)).sum(0)
+    if main < T:
+        out.addmm_(a[main:].reshape(-1, M).t(), b[main:].reshape(-1, P))
+    return out
+
+
+# forward launches of GruRecurrence by kind: "saved" wrote the activations for a backward pass, "inference" handed
+# the kernel NULL for them (what a test or a profile reads to see which path a call took)
+gru_forward_calls = {"saved": 0, "inference": 0}
+
+
+class GruRecurrence(torch.autograd.Function):
+    """One nn.GRU layer (h0 = 0) with its recurrence on the HIP kernels.  Forward: G_x = x W_ih^T + b_ih as one
+    GEMM, then tk_gru_forward_dev (b_hh goes to the kernel: its third slab sits inside the reset gate's product).
+    `save` False (GruMod.forward: grad mode off, or nothing that requires a gradient) hands NULL for the activations:
+    they are neither allocated nor written, and the call cannot be differentiated.  Backward: tk_gru_backward_dev gives
+    dG = dL/dG_x (T x N x 3H) and dq; the hidden side's pre-activation gradient is dG with dq as its third slab,
+    and the parameter and input gradients are GEMMs / sums over the two.  `reverse` runs the recurrence from the
+    last time step (layers.Reverse) on tensors in time order."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, wsb, save):
+        T, N, _ = x.shape
+        H = w_hh.shape[1]
+        dev = x.device
+        x = x.contiguous()
+        w_hh, b_hh = w_hh.contiguous(), b_hh.contiguous()
+        # (grad mode is off inside forward and ctx.needs_input_grad ignores it: the caller decides)
+        train = bool(save)
+        gru_forward_calls["saved" if train else "inference"] += 1
+        gx = torch.addmm(b_ih, x.view(T * N, -1), w_ih.t())
+        y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
+        gates = torch.empty(T, N, 3 * H, dtype=torch.float32, device=dev) if train else None
+        q = torch.empty(T, N, H, dtype=torch.float32, device=dev) if train else None
+        ws = _lib.workspace(wsb, dev, "gru")
+        status = _lib.status_word(dev)
+        rc = _lib.lib().tk_gru_forward_dev(_lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(b_hh), T, N, H, int(reverse),
+                                           _cu_count(dev), _lib.ptr(y), _lib.ptr(gates), _lib.ptr(q), _lib.ptr(ws),
+                                           wsb, _lib.ptr(status), _lib.stream_ptr())
+        _lib.check(rc, "tk_gru_forward_dev")
+        _lib.finish(status)
+        if train:
+            ctx.save_for_backward(x, w_ih, w_hh, y, gates, q)
+        ctx.reverse, ctx.wsb = reverse, wsb
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w_ih, w_hh, y, gates, q = ctx.saved_tensors
+        T, N, I = x.shape
+        H = w_hh.shape[1]
+        dev = x.device
+        dy = dy.contiguous()
+        dg = torch.empty_like(gates)
+        dq = torch.empty_like(q)
+        ws = _lib.workspace(ctx.wsb, dev, "gru")
+        status = _lib.status_word(dev)
+        rc = _lib.lib().tk_gru_backward_dev(_lib.ptr(w_hh), _lib.ptr(y), _lib.ptr(gates), _lib.ptr(q), _lib.ptr(dy),
+                                            T, N, H, int(ctx.reverse), _cu_count(dev), _lib.ptr(dg), _lib.ptr(dq),
+                                            _lib.ptr(ws), ctx.wsb, _lib.ptr(status), _lib.stream_ptr())
+        _lib.check(rc, "tk_gru_backward_dev")
+        _lib.finish(status)
+        dg2 = dg.view(T * N, 3 * H)
+        need = ctx.needs_input_grad
+        dx = (dg2 @ w_ih).view(T, N, I) if need[0] else None
+        dw_ih = _time_sum_tn(dg, x) if need[1] else None
+        dw_hh = None
+        if need[2]:
+            # dW_hh = sum over steps of [dr_pre, dz_pre, dq]_t^T h_prev, h_prev = the output of the recurrence's
+            # previous step (0 at its first)
+            if T > 1:
+                sl, hp = (slice(0, T - 1), y[1:]) if ctx.reverse else (slice(1, T), y[:-1])
+                dw_hh = torch.cat([_time_sum_tn(dg[sl][:, :, :2 * H], hp), _time_sum_tn(dq[sl], hp)])
+            else:
+                dw_hh = torch.zeros_like(w_hh)
+        db_ih = dg2.sum(0) if (need[3] or need[4]) else None
+        db_hh = torch.cat([db_ih[:2 * H], dq.view(T * N, H).sum(0)]) if need[4] else None
+        return dx, dw_ih, dw_hh, db_ih if need[3] else None, db_hh, None, None, None
+
+
 class GruMod(_Rnn):
-    """layers.py:609-725 (wraps nn.GRU, bias_hh frozen)"""
+    """layers.py:609-725 (wraps nn.GRU, bias_hh frozen).  On the GPU the recurrence runs on the HIP kernels
+    (`GruRecurrence`); nn.GRU evaluates CPU tensors, sizes the kernels do not cover, and USE_HIP_GRU = False."""
 
     def __init__(self, insize, size):
         super().__init__(nn.GRU(insize, size))
+
+    def forward(self, x, reverse=False):
+        rnn = self.rnn
+        wsb = hip_gru_workspace_bytes(rnn, x)
+        if wsb:
+            params = (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)
+            save = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+            return GruRecurrence.apply(x, *params, bool(reverse), wsb, save)
+        if reverse:
+            return torch.flip(rnn(torch.flip(x, (0,)))[0], (0,))
+        return rnn(x)[0]
 
 
 class Reverse(nn.Module):
@@ -343,8 +463,8 @@ class Reverse(nn.Module):
         self.layer = layer
 
     def forward(self, x):
-        if isinstance(self.layer, Lstm):
-            return self.layer(x, reverse=True)      # (the HIP recurrence runs backwards in time itself)
+        if isinstance(self.layer, (Lstm, GruMod)):
+            return self.layer(x, reverse=True)      # (the HIP recurrences run backwards in time themselves)
         return torch.flip(self.layer(torch.flip(x, (0,))), (0,))
 
 

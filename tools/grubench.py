@@ -1,0 +1,106 @@
+#!/usr/bin/env python
+"""Times one layer's GRU recurrence (csrc/gru_kernels.hip) on the GPU: tk_gru_forward_dev and tk_gru_backward_dev
+at (T, N, H), each timed with device events after warm-up; prints one JSON line (microseconds per timestep and
+direction, median and min over --steps).  bench.py --config 1's layer is the default shape; the other shape on
+record is --T 800 --N 128 --H 256.
+
+    python tools/grubench.py [--T 1000] [--N 64] [--H 96] [--steps 20] [--warmup 3] [--reverse] [--infer] [--cols C]
+
+--cols (lab build) forces the batch columns per workgroup at H <= 128; without it the release library is timed.
+
+--infer also times the forward with NULL for gates and q (what a torch.no_grad() call launches).
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from taiyaki_amd import _lib, layers  # noqa: E402
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return float(np.median(times)), float(np.min(times))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--T", type=int, default=1000)
+    ap.add_argument("--N", type=int, default=64)
+    ap.add_argument("--H", type=int, default=96)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reverse", action="store_true")
+    ap.add_argument("--infer", action="store_true", help="also time the forward that saves nothing (gates = q = NULL)")
+    ap.add_argument("--cols", type=int, default=None, help="(lab build) batch columns per workgroup at H <= 128")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("grubench needs a GPU (the GRU recurrence has no CPU fallback)")
+    dev = torch.device("cuda:0")
+    T, N, H = a.T, a.N, a.H
+    g = torch.Generator(device="cpu").manual_seed(11)
+    w_hh = (torch.rand(3 * H, H, generator=g) * 2 - 1).div_(H ** 0.5).to(dev)
+    b_hh = torch.zeros(3 * H, device=dev)
+    gx = torch.randn(T, N, 3 * H, generator=g).to(dev)
+    dy = torch.randn(T, N, H, generator=g).div_((T * N) ** 0.5).to(dev)
+    y = torch.empty(T, N, H, device=dev)
+    gates = torch.empty(T, N, 3 * H, device=dev)
+    q = torch.empty(T, N, H, device=dev)
+    dg = torch.empty(T, N, 3 * H, device=dev)
+    dq = torch.empty(T, N, H, device=dev)
+    cus = layers._cu_count(dev)
+    _lib.set_strict(False)
+    L = _lib.use_lab(a.cols is not None)
+    if a.cols is not None:
+        L.tk_lab_gru_cols(a.cols)
+    wsb = L.tk_gru_workspace_bytes(N, H, cus)
+    if wsb == 0:
+        raise SystemExit("(N, H) = (%d, %d) is not admitted on %d CUs" % (N, H, cus))
+    ws = torch.empty(max(wsb // 4, 4), dtype=torch.float32, device=dev)
+    status = _lib.status_word(dev)
+    stream = _lib.stream_ptr()
+
+    def fwd(save=True):
+        _lib.check(L.tk_gru_forward_dev(_lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(b_hh), T, N, H, int(a.reverse), cus,
+                                        _lib.ptr(y), _lib.ptr(gates if save else None), _lib.ptr(q if save else None),
+                                        _lib.ptr(ws), wsb, _lib.ptr(status), stream), "tk_gru_forward_dev")
+
+    def bwd():
+        _lib.check(L.tk_gru_backward_dev(_lib.ptr(w_hh), _lib.ptr(y), _lib.ptr(gates), _lib.ptr(q), _lib.ptr(dy), T, N,
+                                         H, int(a.reverse), cus, _lib.ptr(dg), _lib.ptr(dq), _lib.ptr(ws), wsb,
+                                         _lib.ptr(status), stream), "tk_gru_backward_dev")
+
+    out = {"T": T, "N": N, "H": H, "reverse": a.reverse, "cols": a.cols, "cus": cus}
+    if a.infer:
+        i_med, i_min = timed(lambda: fwd(False), a.steps, a.warmup)
+        out.update(infer_ms=round(i_med, 3), infer_us_per_step=round(1e3 * i_med / T, 3),
+                   infer_min_us_per_step=round(1e3 * i_min / T, 3))
+    f_med, f_min = timed(fwd, a.steps, a.warmup)
+    b_med, b_min = timed(bwd, a.steps, a.warmup)
+    _lib.finish(status)
+    _lib.raise_if_nonfinite()
+    out.update(fwd_ms=round(f_med, 3), bwd_ms=round(b_med, 3), fwd_us_per_step=round(1e3 * f_med / T, 3),
+               fwd_min_us_per_step=round(1e3 * f_min / T, 3), bwd_us_per_step=round(1e3 * b_med / T, 3),
+               bwd_min_us_per_step=round(1e3 * b_min / T, 3), device=torch.cuda.get_device_name(dev))
+    if a.cols is not None:
+        L.tk_lab_gru_cols(0)
+        _lib.use_lab(False)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
