@@ -6,6 +6,7 @@ shared library is missing or a tensor is not on an AMD GPU the operators raise.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 import torch
@@ -20,96 +21,73 @@ LIBPATH = os.environ.get("TAIYAKI_AMD_LIB") or os.path.join(CSRC, LIBNAME)   # (
 LAB_LIBNAME = "libtaiyaki_amd_flipflop_lab.so"
 LAB_LIBPATH = os.environ.get("TAIYAKI_AMD_LAB_LIB") or os.path.join(CSRC, LAB_LIBNAME)    # (override: A/B builds under tools/lab/)
 
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_flipflop.h")
+RCCL_LIBNAME = "libtaiyaki_amd_rccl.so"     # csrc/rccl_api.cpp: the header's multi-GPU section, a library of its own
+
 _vp = ctypes.c_void_p
-_sz = ctypes.c_size_t
-_f = ctypes.c_float
-_i = ctypes.c_int
+_SCALARS = {"size_t": ctypes.c_size_t, "int": ctypes.c_int, "float": ctypes.c_float}
 
-# symbol -> (restype, argtypes); mirrors include/taiyaki_amd_flipflop.h
-SIGNATURES = {
-    "tk_version": (ctypes.c_char_p, []),
-    "tk_flipflop_build_indices_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp,
-                                          _vp, _vp, _vp, _vp, _vp]),
-    "tk_crf_flipflop_workspace_bytes": (_sz, [_sz, _sz, _sz, _sz, _i]),
-    "tk_crf_flipflop_workspace_bytes_sharp": (_sz, [_sz, _sz, _sz, _sz, _i, _f]),
-    "tk_crf_flipflop_dev": (_i, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz,
-                                 _f, _f, _f, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
-    "tk_crf_flipflop_labels_dev": (_i, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz,
-                                        _f, _f, _f, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "tk_flipflop_loss_fused_labels_dev": (_i, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _vp, _vp,
-                                              _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
-    "tk_flipflop_loss_fused_aux_bytes": (_sz, [_sz, _sz, _sz, _sz]),
-    "tk_flipflop_loss_overlap": (ctypes.c_int, [ctypes.c_int]),
-    "tk_flipflop_loss_fused_dev": (_i, [_vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _vp, _vp,
-                                       _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
-    "tk_flipflop_lattice_dev": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _vp, _vp, _vp]),
-    "tk_flipflop_beamsearch_workspace_bytes": (_sz, [_sz, _sz, _sz]),
-    "tk_flipflop_beamsearch_dev": (_i, [_vp, _sz, _sz, _sz, _i, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "tk_flipflop_logz_workspace_bytes": (_sz, [_sz, _sz, _sz]),
-    "tk_flipflop_logz_dev": (_i, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "tk_flipflop_viterbi_workspace_bytes": (_sz, [_sz, _sz, _sz]),
-    "tk_flipflop_viterbi_dev": (_i, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "tk_flipflop_errprobs_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
-    "tk_devcopy_f32_dev": (_i, [_vp, _vp, _sz, _vp]),
-    "tk_lstm_workspace_bytes": (_sz, [_sz, _sz, _i]),
-    "tk_lstm_forward_dev": (_i, [_vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "tk_lstm_backward_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _sz, _vp, _vp]),
-    "tk_gru_workspace_bytes": (_sz, [_sz, _sz, _i]),
-    "tk_gru_forward_dev": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "tk_gru_backward_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _sz, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "tk_conv1d_small_supported": (_i, [_sz, _sz, _sz, _sz]),
-    "tk_conv1d_small_workspace_bytes": (_sz, [_sz, _sz, _sz, _sz, _sz, _i]),
-    "tk_conv1d_small_forward_dev": (_i, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _i, _vp, _vp]),
-    "tk_conv1d_small_backward_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _i, _vp, _vp, _vp, _vp, _sz,
-                                         _vp]),
-    "tk_squiggle_match_workspace_bytes": (_sz, [_i, _sz, _sz, _sz]),
-    "tk_squiggle_match_cost_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _f, _vp, _vp, _sz, _vp, _vp]),
-    "tk_squiggle_match_grad_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _f, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "tk_squiggle_match_path_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _sz, _f, _f, _f, _vp, _vp, _vp, _sz, _vp,
-                                       _vp]),
-    "tk_grad_maxabs_clip_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
-    "tk_flipflop_remap_dev": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "tk_remap_path_to_ref_to_signal_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp]),
-    "tk_chunks_locate_dev": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "tk_chunks_select_dev": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
-    "tk_chunks_gather_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _i, _i, _sz, _vp, _vp,
-                                  _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
-    # exact reference prototypes (host pointers)
-    "crf_flipflop_grad": (None, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
-    "crf_flipflop_cost": (None, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp]),
-    "cat_mod_flipflop_grad": (None, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "cat_mod_flipflop_cost": (None, [_vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-}
 
-# libtaiyaki_amd_rccl.so (csrc/rccl_api.cpp): the gradient all-reduce straight on RCCL, for hosts
-# that do not go through torch.distributed.  A library of its own; the Python trainers use
-# ProcessGroupNCCL (the same RCCL calls) and never load it.
-RCCL_LIBNAME = "libtaiyaki_amd_rccl.so"
-RCCL_SIGNATURES = {
-    "tk_rccl_unique_id_bytes": (_sz, []),
-    "tk_rccl_unique_id": (_i, [_vp, _sz]),
-    "tk_rccl_comm_init": (_i, [ctypes.POINTER(_vp), _i, _vp, _i]),
-    "tk_rendezvous_bytes": (_i, [ctypes.c_char_p, _i, _i, _i, _vp, _sz, _i]),
-    "tk_rccl_comm_init_rendezvous": (_i, [ctypes.POINTER(_vp), ctypes.c_char_p, _i, _i, _i, _i]),
-    "tk_allreduce_f32_dev": (_i, [_vp, _vp, _sz, _vp]),
-    "tk_broadcast_f32_dev": (_i, [_vp, _vp, _sz, _i, _vp]),
-    "tk_rccl_comm_destroy": (_i, [_vp]),
-}
+def _ctype(decl, where, named=True):
+    """The ctypes type of one C declarator (`const float *x`, `size_t n`), or of a result type (named=False).
+    Anything outside the map raises: the binding never guesses."""
+    words = decl.replace("*", " * ").split()
+    base, stars = [w for w in words if w not in ("*", "const")], words.count("*")
+    if len(base) == 1 + named:
+        if stars == 1:
+            return ctypes.c_char_p if base[0] == "char" and "const" in words else _vp
+        if stars == 2 and base[0] == "void":
+            return ctypes.POINTER(_vp)
+        if stars == 0 and base[0] in _SCALARS:
+            return _SCALARS[base[0]]
+        if stars == 0 and base[0] == "void" and not named:
+            return None
+    raise TypeError("%s: no ctypes type for `%s`" % (where, " ".join(words)))
+
+
+def _blank_comments(text):      # ... and preprocessor lines, with spaces: offsets into the text stay what they were
+    return re.sub(r"/\*.*?\*/|//[^\n]*|(?m:^[ \t]*#[^\n]*)", lambda m: " " * len(m.group()), text, flags=re.S)
+
+
+def parse_prototypes(text):
+    """C prototypes (comments blanked, one declarator per parameter) -> {name: (restype, argtypes, offset in text)}"""
+    out = {}
+    for m in re.finditer(r"(\w[\w\s*]*?)\b(\w+)\s*\(([^()]*)\)\s*;", text):
+        res, name, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        out[name] = (_ctype(res, name, named=False), [_ctype(p, name) for p in params], m.start(2))
+    return out
+
+
+def _read_header():
+    raw = open(HEADER).read()
+    text = _blank_comments(raw)
+    protos, multi_gpu = parse_prototypes(text), raw.index("Multi-GPU:")
+    sigs = {n: (r, a) for n, (r, a, at) in protos.items() if at < multi_gpu}
+    rccl = {n: (r, a) for n, (r, a, at) in protos.items() if at > multi_gpu}
+    fields = re.search(r"typedef struct tk_seq_labels \{(.*?)\}", text, re.S).group(1).split(";")[:-1]
+    fields = [(f.replace("*", " ").split()[-1], _ctype(f, "tk_seq_labels")) for f in fields]
+    defines = {k: int(v.rstrip("u"), 0) for k, v in re.findall(r"(?m)^#define (TK_\w+) (\w+)", raw) if v[0].isdigit()}
+    return sigs, rccl, fields, defines
+
+
+# symbol -> (restype, argtypes), read from include/taiyaki_amd_flipflop.h; RCCL_SIGNATURES: its multi-GPU section (the all-reduce
+# straight on RCCL for hosts without torch.distributed; the Python trainers use ProcessGroupNCCL and never load that library)
+SIGNATURES, RCCL_SIGNATURES, _seq_label_fields, DEFINES = _read_header()
+# the tk_lab_* hooks of the lab build: the extern "C" block that csrc/dispatch.h declares under TK_LAB
+LAB_SIGNATURES = {n: (r, a) for n, (r, a, _) in parse_prototypes(_blank_comments(re.search(
+    r'#ifdef TK_LAB\nextern "C" \{\n(.*?)\n\}\n#endif', open(os.path.join(CSRC, "dispatch.h")).read(), re.S).group(1))).items()}
+
 
 class SeqLabels(ctypes.Structure):
     """include/taiyaki_amd_flipflop.h: tk_seq_labels (what tk_flipflop_build_indices_dev takes, for the entry points
     that build their indices inside their first launch)."""
-    _fields_ = [("seqs", _vp), ("total_len", _sz), ("nbase", _sz), ("mod_cats", _vp), ("can_mods_offsets", _vp),
-                ("mod_cat_weights", _vp), ("bulk_seqlen", _sz)]
+    _fields_ = _seq_label_fields
 
 
-ERRORS = {1: "bad argument (NULL / shape / 16-byte alignment)",
-          2: "unsupported nbase / ntrans / sequence length for this build",
-          3: "workspace too small", 4: "HIP launch failure"}
-
-LAB_SIGNATURES = {"tk_lab_crf_band_phase": (None, [_i]), "tk_lab_lstm_cols": (None, [_i]),
-                  "tk_lab_lstm_units": (None, [_i]), "tk_lab_gru_cols": (None, [_i]),
-                  "tk_lab_lstm_geometry": (_i, [_sz, _sz, _i, ctypes.POINTER(_sz)])}
+ERRORS = {DEFINES["TK_ERR_" + name]: text for name, text in dict(
+    BAD_ARG="bad argument (NULL / shape / 16-byte alignment)", WORKSPACE="workspace too small", LAUNCH="HIP launch failure",
+    UNSUPPORTED="unsupported nbase / ntrans / sequence length for this build").items()}
 
 _lib = None
 _handles = {}
@@ -168,12 +146,7 @@ def rccl_lib():
     torch.distributed)."""
     global _rccl
     if _rccl is None:
-        handle = ctypes.CDLL(os.path.join(CSRC, RCCL_LIBNAME))
-        for name, (res, args) in RCCL_SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _rccl = handle
+        _rccl = _load(os.path.join(CSRC, RCCL_LIBNAME), RCCL_SIGNATURES)
     return _rccl
 
 
@@ -256,7 +229,7 @@ def status_word(device):
 
 
 _gated = {"last": 0, "total": 0, "last_retried": 0, "total_retried": 0}
-_COUNT_MASK, _GATED_SHIFT, _RETRIED_SHIFT = 0xfff, 8, 20       # include/taiyaki_amd_flipflop.h: TK_STATUS_*_SHIFT
+_COUNT_MASK, _GATED_SHIFT, _RETRIED_SHIFT = (DEFINES["TK_STATUS_" + k] for k in ("COUNT_MASK", "GATED_SHIFT", "RETRIED_SHIFT"))
 
 
 def last_gate_count():

@@ -26,6 +26,7 @@
 // (correctly rounded results, what glibc's float functions return in all but rare cases), so
 // scores agree with the reference to the last bit almost everywhere and the beam takes the
 // same decisions.
+#include "dispatch.h"
 #include "ff_common.h"
 
 namespace tk {

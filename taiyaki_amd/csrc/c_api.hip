@@ -11,96 +11,8 @@
 
 #include "../../include/taiyaki_amd_flipflop.h"
 #include "crf_band.h"
+#include "dispatch.h"
 #include "squiggle_match.h"
-
-namespace tk {
-size_t logz_workspace_bytes(size_t T, size_t N, size_t nbase);
-int logz_dispatch(const float *scores, size_t T, size_t N, size_t nbase, float *logz,
-                  float *grad, void *workspace, size_t workspace_bytes, uint32_t *status,
-                  hipStream_t stream, float *loss_acc = nullptr, float acc_scale = 0.f, float grad_scale = 1.f,
-                  const float *grad_scale_vec = nullptr);
-size_t viterbi_workspace_bytes(size_t T, size_t N, size_t nbase);
-int viterbi_dispatch(const float *scores, size_t T, size_t N, size_t nbase, float *fwd,
-                     int64_t *tb, int64_t *path, void *workspace, size_t workspace_bytes,
-                     hipStream_t stream);
-bool logz_side_stream(hipStream_t *s, hipEvent_t *fork, hipEvent_t *join);
-#ifdef TK_LAB
-void crf_band_lab_phase(int phase);
-#endif
-size_t beam_workspace_bytes(size_t T, size_t N, size_t nbase);
-int lattice_dispatch(const float *scores, size_t T, size_t N, size_t nbase, int forward, const float *init,
-                     float *out, float *total, hipStream_t stream);
-int beam_dispatch(const float *scores, size_t T, size_t N, size_t nbase, int width, float beam_cut, int guided,
-                  signed char *seq, int *seqlen, float *score, void *workspace, size_t workspace_bytes,
-                  hipStream_t stream);
-int grad_clip_dispatch(float *grads, const int64_t *seg_off, size_t nseg, size_t max_seg_len,
-                       const float *thresh, float *maxs, hipStream_t stream);
-int errprobs_dispatch(const float *trans, const int64_t *path, size_t T, size_t N, size_t nbase,
-                      float *out, hipStream_t stream);
-int build_indices_dispatch(const int32_t *seqs, const int32_t *seqlen, size_t nbatch,
-                           size_t nbase, const int32_t *mod_cats,
-                           const int32_t *can_mods_offsets, const float *mod_cat_weights,
-                           int64_t *seqoff, int32_t *stay, int32_t *move, int32_t *mod,
-                           float *fact, size_t total_len, uint32_t *status, hipStream_t stream);
-int chunks_locate_dispatch(const tk_mapped_store *st, const int32_t *cand_read, const int32_t *cand_start,
-                           const double *cand_frac, size_t ncand, size_t chunk_len,
-                           const tk_chunk_filter *fp, uint8_t *reason, int32_t *dacstart,
-                           int32_t *seqstart, int32_t *seqlen, int32_t *maxdwell, hipStream_t stream);
-int chunks_select_dispatch(const uint8_t *reason, const int32_t *seqlen, size_t ncand, size_t nwant,
-                           int32_t *sel, int64_t *seqoff, int32_t *counts, hipStream_t stream);
-int chunks_gather_dispatch(const tk_mapped_store *st, const int32_t *cand_read, const int32_t *dacstart,
-                           const int32_t *seqstart, const int32_t *seqlen, const int32_t *sel,
-                           const int64_t *seqoff, const int32_t *counts, size_t nwant, size_t chunk_len,
-                           int reverse, int standardize, size_t ncan, const int32_t *can_labels,
-                           const int32_t *mod_labels, float *indata, int32_t *seqs, size_t seqs_cap,
-                           int32_t *seqlens_out, int32_t *mod_cats, uint32_t *status, hipStream_t stream);
-struct RemapArgs {
-    const float *scores;
-    const int64_t *row_off;
-    const int32_t *stay_index;
-    const int32_t *step_index;
-    const int64_t *seq_off;
-    const double *localpen;
-    int K;
-    double *score;
-    int64_t *path;
-    uint64_t *tb;
-    const int64_t *tb_off;
-};
-int remap_dispatch(const RemapArgs &a, size_t nread, size_t max_M, hipStream_t stream);
-size_t lstm_workspace_bytes(size_t N, size_t H, int cu_count);
-int lstm_forward_dispatch(const float *gx, const float *whh, size_t T, size_t N, size_t H, int reverse,
-                          int cu_count, float *y, float *gates, float *cell, void *ws, size_t wsb,
-                          uint32_t *status, hipStream_t stream);
-int lstm_backward_dispatch(const float *whh, const float *gates, const float *cell, const float *dy, size_t T,
-                           size_t N, size_t H, int reverse, int cu_count, float *dgates, void *ws, size_t wsb,
-                           uint32_t *status, hipStream_t stream);
-size_t gru_workspace_bytes(size_t N, size_t H, int cu_count);
-int gru_forward_dispatch(const float *gx, const float *whh, const float *bhh, size_t T, size_t N, size_t H,
-                         int reverse, int cu_count, float *y, float *gates, float *q, void *ws, size_t wsb,
-                         uint32_t *status, hipStream_t stream);
-int gru_backward_dispatch(const float *whh, const float *y, const float *gates, const float *q, const float *dy,
-                          size_t T, size_t N, size_t H, int reverse, int cu_count, float *dgates, float *dq, void *ws,
-                          size_t wsb, uint32_t *status, hipStream_t stream);
-#ifdef TK_LAB
-void gru_lab_cols(int cols);
-void lstm_lab_cols(int cols);
-void lstm_lab_units(int units);
-bool lstm_lab_geometry(size_t N, size_t H, int cu_count, size_t *out);
-#endif
-bool conv_small_supported(size_t cin, size_t cout, size_t winlen, size_t stride);
-size_t conv_small_workspace_bytes(size_t T, size_t N, size_t cin, size_t cout, size_t winlen, int cu_count);
-int conv_small_forward_dispatch(const float *x, const float *w, const float *b, size_t T, size_t N, size_t cin,
-                                size_t cout, size_t winlen, int cu_count, float *y, hipStream_t stream);
-int conv_small_backward_dispatch(const float *dy, const float *x, const float *w, const float *b, size_t T, size_t N,
-                                 size_t cin, size_t cout, size_t winlen, int cu_count, float *dx, float *dw, float *db,
-                                 void *ws, size_t wsb, hipStream_t stream);
-int path_to_reftosignal_dispatch(const int64_t *path, const int64_t *path_off, const int64_t *ref_off,
-                                 const int64_t *signalstart, const int64_t *siglen, int stride, size_t nread,
-                                 int32_t *rts, hipStream_t stream);
-}  // namespace tk
-
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 extern "C" {
 
@@ -123,9 +35,7 @@ int tk_flipflop_build_indices_dev(const int32_t *seqs, const int32_t *seqlen, si
 int tk_grad_maxabs_clip_dev(float *grads, const int64_t *seg_off, size_t nseg, size_t max_seg_len,
                             const float *thresh, float *maxs, void *stream) {
     if (!grads || !seg_off || !maxs) return TK_ERR_BAD_ARG;
-    const int rc = tk::grad_clip_dispatch(grads, seg_off, nseg, max_seg_len, thresh, maxs,
-                                          static_cast<hipStream_t>(stream));
-    return rc == 0 ? TK_OK : TK_ERR_LAUNCH;
+    return tk::grad_clip_dispatch(grads, seg_off, nseg, max_seg_len, thresh, maxs, static_cast<hipStream_t>(stream));
 }
 
 int tk_flipflop_remap_dev(const float *scores, const int64_t *row_off, size_t ntrans,
@@ -278,10 +188,8 @@ int tk_chunks_gather_dev(const tk_mapped_store *store, const int32_t *cand_read,
 int tk_flipflop_errprobs_dev(const float *trans, const int64_t *path, size_t nblk, size_t nbatch,
                              size_t nbase, float *errprobs, void *stream) {
     if (!trans || !path || !errprobs || nblk == 0 || nbatch == 0) return TK_ERR_BAD_ARG;
-    if (!aligned16(trans)) return TK_ERR_BAD_ARG;
-    const int rc = tk::errprobs_dispatch(trans, path, nblk, nbatch, nbase, errprobs,
-                                         static_cast<hipStream_t>(stream));
-    return rc == 0 ? TK_OK : (rc == 2 ? TK_ERR_UNSUPPORTED : TK_ERR_LAUNCH);
+    if (!tk::aligned16(trans)) return TK_ERR_BAD_ARG;
+    return tk::errprobs_dispatch(trans, path, nblk, nbatch, nbase, errprobs, static_cast<hipStream_t>(stream));
 }
 
 size_t tk_crf_flipflop_workspace_bytes(size_t ntrans, size_t nblk, size_t nbatch,
@@ -423,7 +331,7 @@ static int loss_fused_impl(const float *scores, size_t nblk, size_t nbatch, size
     if (!scores || !stayidx || !moveidx || !seqlen || !seqoff || !lossvector || !grad || !logz || !crf_workspace ||
         !logz_workspace || nblk == 0 || nbatch == 0 || nbase == 0 || !(sharpfact > 0.f))
         return TK_ERR_BAD_ARG;
-    if (!aligned16(scores) || !aligned16(grad)) return TK_ERR_BAD_ARG;
+    if (!tk::aligned16(scores) || !tk::aligned16(grad)) return TK_ERR_BAD_ARG;
     if ((modidx == nullptr) != (modfact == nullptr)) return TK_ERR_BAD_ARG;
     const size_t ncan = 2 * nbase * (nbase + 1);
     const size_t one = (nblk * nbatch * ncan * sizeof(float) + 255) / 256 * 256;
@@ -553,7 +461,7 @@ __global__ __launch_bounds__(256) void devcopy_f4_kernel(const tk_f4 *__restrict
         if (base + (size_t)k * 256 < n4) __builtin_nontemporal_store(v[k], dst + base + (size_t)k * 256);
 }
 int tk_devcopy_f32_dev(float *dst, const float *src, size_t n, void *stream) {
-    if (dst == nullptr || src == nullptr || n % 4 != 0 || ((uintptr_t)dst | (uintptr_t)src) % 16 != 0) return TK_ERR_BAD_ARG;
+    if (dst == nullptr || src == nullptr || n % 4 != 0 || !tk::aligned16(dst) || !tk::aligned16(src)) return TK_ERR_BAD_ARG;
     if (n == 0) return TK_OK;
     const size_t n4 = n / 4;
     hipLaunchKernelGGL(devcopy_f4_kernel, dim3((unsigned)((n4 + 1023) / 1024)), dim3(256), 0, static_cast<hipStream_t>(stream),
@@ -562,19 +470,14 @@ int tk_devcopy_f32_dev(float *dst, const float *src, size_t n, void *stream) {
 }
 
 #ifdef TK_LAB
-// lab hook (lab build only; declared in tools/lab_api.h, not in the public header): see crf_band.hip
-extern "C" void tk_lab_crf_band_phase(int phase) { tk::crf_band_lab_phase(phase); }
-// the LSTM recurrence's batch columns per workgroup, 8 or 16 (0: the launcher's rule; lstm_kernels.hip)
-extern "C" void tk_lab_lstm_cols(int cols) { tk::lstm_lab_cols(cols); }
-// the GRU recurrence's batch columns per workgroup at sizes <= 128: 1 or 2 (0: the launcher's rule; gru_kernels.hip)
-extern "C" void tk_lab_gru_cols(int cols) { tk::gru_lab_cols(cols); }
-// the LSTM recurrence's hidden units per workgroup, 16, 32 or 64 (0: the launcher's rule)
-extern "C" void tk_lab_lstm_units(int units) { tk::lstm_lab_units(units); }
-// the LSTM recurrence's launch plan at (nbatch, size, cu_count): out[8] = admitted C and groups, U, C, groups,
-// grid, forward and backward granule bytes; 0 where the kernels do not run
-extern "C" int tk_lab_lstm_geometry(size_t nbatch, size_t size, int cu_count, size_t *out) {
+// the lab hooks (lab build only; declared in dispatch.h, not in the public header)
+void tk_lab_crf_band_phase(int phase) { tk::crf_band_lab_phase(phase); }
+void tk_lab_lstm_cols(int cols) { tk::lstm_lab_cols(cols); }
+void tk_lab_lstm_units(int units) { tk::lstm_lab_units(units); }
+int tk_lab_lstm_geometry(size_t nbatch, size_t size, int cu_count, size_t *out) {
     return tk::lstm_lab_geometry(nbatch, size, cu_count, out) ? 1 : 0;
 }
+void tk_lab_gru_cols(int cols) { tk::gru_lab_cols(cols); }
 #endif
 
 size_t tk_lstm_workspace_bytes(size_t nbatch, size_t size, int cu_count) {
@@ -638,7 +541,7 @@ int tk_conv1d_small_backward_dev(const float *dy, const float *x, const float *w
 
 int tk_flipflop_lattice_dev(const float *scores, size_t nblk, size_t nbatch, size_t nbase, int forward,
                             const float *init, float *out, float *total, void *stream) {
-    if (scores == nullptr || out == nullptr || total == nullptr) return 1;
+    if (scores == nullptr || out == nullptr || total == nullptr) return TK_ERR_BAD_ARG;
     return tk::lattice_dispatch(scores, nblk, nbatch, nbase, forward, init, out, total,
                                 static_cast<hipStream_t>(stream));
 }
@@ -664,7 +567,7 @@ int tk_flipflop_logz_dev(const float *scores, size_t nblk, size_t nbatch, size_t
                          float *logz, float *grad, void *workspace, size_t workspace_bytes,
                          uint32_t *status, void *stream) {
     if (!scores || !logz || !workspace || nblk == 0 || nbatch == 0) return TK_ERR_BAD_ARG;
-    if (!aligned16(scores) || (grad && !aligned16(grad))) return TK_ERR_BAD_ARG;
+    if (!tk::aligned16(scores) || (grad && !tk::aligned16(grad))) return TK_ERR_BAD_ARG;
     return tk::logz_dispatch(scores, nblk, nbatch, nbase, logz, grad, workspace,
                              workspace_bytes, status, static_cast<hipStream_t>(stream));
 }
@@ -677,7 +580,7 @@ int tk_flipflop_viterbi_dev(const float *scores, size_t nblk, size_t nbatch, siz
                             float *fwd, int64_t *traceback, int64_t *path, void *workspace,
                             size_t workspace_bytes, void *stream) {
     if (!scores || !path || !workspace || nbatch == 0) return TK_ERR_BAD_ARG;
-    if (!aligned16(scores)) return TK_ERR_BAD_ARG;
+    if (!tk::aligned16(scores)) return TK_ERR_BAD_ARG;
     if ((fwd == nullptr) != (traceback == nullptr)) return TK_ERR_BAD_ARG;      // both or neither
     return tk::viterbi_dispatch(scores, nblk, nbatch, nbase, fwd, traceback, path, workspace,
                                 workspace_bytes, static_cast<hipStream_t>(stream));

@@ -22,8 +22,8 @@
 //                     float32 like torch.tensor(..., dtype=float32).  Sequence: one block per
 //                     chunk, flip/flop by the parity of the run position.
 // HBM-bound and tiny: 6 B per sample (2 in, 4 out).
+#include "dispatch.h"
 #include "ff_common.h"
-#include "../../include/taiyaki_amd_flipflop.h"
 
 #pragma clang fp contract(off)
 

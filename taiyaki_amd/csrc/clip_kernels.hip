@@ -10,6 +10,7 @@
 // The maxima stay on the device and are copied to the host asynchronously for the rolling
 // MAD statistics of the NEXT step's thresholds.  HBM-bound: 4 B (pass 1) + 8 B (pass 2) per
 // gradient element.
+#include "dispatch.h"
 #include "ff_common.h"
 
 namespace tk {
@@ -76,7 +77,7 @@ __global__ void maxs_zero_kernel(float *__restrict__ maxs, int nseg) {
 
 int grad_clip_dispatch(float *grads, const int64_t *seg_off, size_t nseg, size_t max_seg_len,
                        const float *thresh, float *maxs, hipStream_t stream) {
-    if (nseg == 0) return 0;
+    if (nseg == 0) return TK_OK;
     const unsigned chunks = (unsigned)((max_seg_len + CLIP_THREADS * CLIP_PER_THREAD - 1) /
                                        (CLIP_THREADS * CLIP_PER_THREAD));
     // (a kernel, not hipMemsetAsync: replayed from a hipGraph on ROCm 7.2 the memset node of this
@@ -87,7 +88,7 @@ int grad_clip_dispatch(float *grads, const int64_t *seg_off, size_t nseg, size_t
     if (thresh != nullptr)
         hipLaunchKernelGGL(grad_clamp_kernel, dim3((unsigned)nseg, chunks ? chunks : 1), dim3(CLIP_THREADS), 0,
                            stream, grads, seg_off, thresh);
-    return hipGetLastError() == hipSuccess ? 0 : 4;
+    return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
 
 }  // namespace tk

@@ -27,7 +27,7 @@
 //             across the waves through LDS, and the workgroup writes ONE slab (dW | db, double).
 //             conv_slab_sum_kernel adds the slabs, one wave per element, in a fixed order, and rounds.
 // No atomics: grid and slab count depend on (T, N, CU count) only, so results are bit-identical run to run.
-#include "../../include/taiyaki_amd_flipflop.h"
+#include "dispatch.h"
 #include "ff_common.h"
 
 namespace tk {
@@ -309,8 +309,6 @@ int conv_backward(const float *dy, const float *x, const float *w, const float *
                        ws, (int)p.grid, slab, COUT * CIN * K, dw, db);
     return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // every element index of the kernels fits 32 bits
 bool conv_size_ok(size_t T, size_t N, size_t cout) {

@@ -62,6 +62,7 @@
 #include <type_traits>
 
 #include "crf_log.h"
+#include "dispatch.h"
 
 namespace tk {
 

@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include "crf_log.h"
+#include "dispatch.h"
 
 namespace tk {
 

@@ -19,6 +19,7 @@
 // inputs of step s + 1 are loaded right after step s's poll (G = 1: barrier), the bulk outputs of step s are held
 // in registers and stored right after step s + 1's.  Both drain under the matvec; the granule publish is the last
 // memory operation of a step.  Every sum runs in a fixed order: a launch is bit-reproducible.
+#include "dispatch.h"
 #include "ff_common.h"
 #include "rnn_common.h"
 

@@ -28,6 +28,7 @@
 //     transcendental sits on a serial dependency chain.
 #include <stdlib.h>
 
+#include "dispatch.h"
 #include "ff_common.h"
 
 namespace tk {

@@ -17,6 +17,7 @@
 // inputs of step s + 1 (forward: gx; backward: dy, c_{t-1}, the gates) are loaded right after step s's poll, and
 // the bulk outputs of step s (forward: y, c, gates; backward: dG) are held in registers and stored right after
 // step s + 1's poll.  Both drain under the matvec; the granule publish is the last memory operation of a step.
+#include "dispatch.h"
 #include "ff_common.h"
 #include "rnn_common.h"
 

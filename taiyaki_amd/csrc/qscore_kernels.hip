@@ -7,6 +7,7 @@
 // transpose, the same row-set mover as the logZ kernels), sums the transitions into each
 // base, normalises, picks the base of the Viterbi path and writes 4 bytes per (block,
 // read).  HBM-bound: T*N*S*4 bytes in, (T+1)*N*(8+4) bytes of path / output.
+#include "dispatch.h"
 #include "ff_common.h"
 
 namespace tk {
@@ -80,7 +81,7 @@ static int errprobs_launch(const float *trans, const int64_t *path, size_t T, si
     const size_t lds = (size_t)QS_WAVES * WAVE * FF<NB>::PIECES * sizeof(f4);
     hipLaunchKernelGGL(errprobs_kernel<NB>, dim3(ncols, (unsigned)((T + per_block - 1) / per_block)),
                        dim3(QS_WAVES * WAVE), lds, stream, trans, path, (int)T, (int)N, out);
-    return hipGetLastError() == hipSuccess ? 0 : 4;
+    return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
 
 int errprobs_dispatch(const float *trans, const int64_t *path, size_t T, size_t N, size_t nbase,
@@ -90,7 +91,7 @@ int errprobs_dispatch(const float *trans, const int64_t *path, size_t T, size_t 
         case 2: return errprobs_launch<2>(trans, path, T, N, out, stream);
         case 3: return errprobs_launch<3>(trans, path, T, N, out, stream);
         case 4: return errprobs_launch<4>(trans, path, T, N, out, stream);
-        default: return 2;
+        default: return TK_ERR_UNSUPPORTED;
     }
 }
 

@@ -25,8 +25,8 @@
 // HBM traffic is small (T K 4 bytes of scores, T M / 8 bytes of traceback each way); the
 // kernel is bound by the latency of the serial time loop, like the reference -- only per step
 // it costs ~0.1 us instead of ~60 us of numpy dispatch.
+#include "dispatch.h"
 #include "ff_common.h"
-#include "../../include/taiyaki_amd_flipflop.h"
 
 #pragma clang fp contract(off)
 
@@ -34,20 +34,6 @@ namespace tk {
 
 constexpr double REMAP_LARGE = 1e30;        // taiyaki/constants.py LARGE_VAL
 constexpr int RM_ROWS = 32;                 // score rows per LDS tile
-
-struct RemapArgs {
-    const float *scores;        // concatenated (sum T_i, K)
-    const int64_t *row_off;     // (nread + 1) row offsets
-    const int32_t *stay_index;  // concatenated, M_i per read
-    const int32_t *step_index;  // concatenated, M_i - 1 per read (read i starts at seq_off[i] - i)
-    const int64_t *seq_off;     // (nread + 1)
-    const double *localpen;     // per read
-    int K;
-    double *score;              // (nread)
-    int64_t *path;              // concatenated, T_i + 1 per read (read i starts at row_off[i] + i)
-    uint64_t *tb;               // traceback bits
-    const int64_t *tb_off;      // (nread) offsets into tb, in 64-bit words
-};
 
 __device__ __forceinline__ double wave_shift_up1_f64(double src, double fill) {
     const int lo = wave_shift_up1(__double2loint(src), __double2loint(fill));

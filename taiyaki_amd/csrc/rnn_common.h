@@ -119,7 +119,5 @@ int zero_ws(void *ws, size_t bytes, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 }  // namespace tk

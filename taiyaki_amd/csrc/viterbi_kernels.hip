@@ -28,6 +28,7 @@
 // states go out in one store.
 #include <type_traits>
 
+#include "dispatch.h"
 #include "ff_common.h"
 
 namespace tk {

@@ -500,7 +500,68 @@ def test_bulk_length_hint_host_logic():
     assert ctc._bulk_seqlen(torch.zeros(0, dtype=torch.int64)) == 0
     assert ctypes.sizeof(_lib.SeqLabels) == 7 * ctypes.sizeof(ctypes.c_void_p)
     hdr = open(os.path.join(ROOT, "include", "taiyaki_amd_flipflop.h")).read()
-    body = hdr[hdr.index("typedef struct tk_seq_labels {"):hdr.index("} tk_seq_labels;")]
-    assert [f for f in ("seqs;", "total_len;", "nbase;", "mod_cats;", "can_mods_offsets;", "mod_cat_weights;", "bulk_seqlen;")
-            if f not in body] == []
+    # names, order and types of the ctypes struct are the typedef's (read here apart from _lib's own parser)
+    body = re.sub(r"/\*.*?\*/", "", hdr[hdr.index("typedef struct tk_seq_labels {"):hdr.index("} tk_seq_labels;")], flags=re.S)
+    typedef = [(m.group(3), ctypes.c_void_p if m.group(2) else {"size_t": ctypes.c_size_t}[m.group(1)])
+               for m in re.finditer(r"(\w+) (\*?)(\w+);", body)]
+    assert [n for n, _ in typedef] == ["seqs", "total_len", "nbase", "mod_cats", "can_mods_offsets", "mod_cat_weights", "bulk_seqlen"]
+    assert [t for _, t in typedef] == [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_size_t]
+    assert list(_lib.SeqLabels._fields_) == typedef
     assert "TK_STATUS_RETRIED_SHIFT 20" in hdr and "TK_STATUS_GATED_SHIFT 8" in hdr and _lib._RETRIED_SHIFT == 20 and _lib._GATED_SHIFT == 8
+    assert "TK_STATUS_COUNT_MASK 0xfffu" in hdr and _lib._COUNT_MASK == 0xfff
+
+
+def _ctype_names(table):
+    import ctypes
+    names = {None: "None", ctypes.c_void_p: "c_void_p", ctypes.c_size_t: "c_size_t", ctypes.c_int: "c_int",
+             ctypes.c_float: "c_float", ctypes.c_char_p: "c_char_p", ctypes.POINTER(ctypes.c_void_p): "POINTER(c_void_p)"}
+    return {name: [names[res], [names[a] for a in args]] for name, (res, args) in table.items()}
+
+
+def test_binding_read_from_the_header_is_the_hand_typed_one():
+    """tests/golden/abi_signatures.json is the dump of the three tables `_lib.py` held, typed by hand, before it read
+    them from the headers: {name: [restype, [argtypes]]}.  The parsed tables equal it, keys and every code.  One entry
+    of the dump was corrected: the last parameter of tk_lab_lstm_geometry (`size_t *out`) was POINTER(c_size_t) there
+    and is c_void_p by the rule every other pointer follows (its callers pass a ctypes array, which both accept)."""
+    import json
+    from taiyaki_amd import _lib
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "abi_signatures.json")))
+    assert sorted(golden) == ["LAB_SIGNATURES", "RCCL_SIGNATURES", "SIGNATURES"]
+    for table, want in golden.items():
+        got = _ctype_names(getattr(_lib, table))
+        assert set(got) == set(want), table
+        assert [k for k in want if got[k] != want[k]] == [], table
+    assert len(golden["SIGNATURES"]) == 43 and len(golden["RCCL_SIGNATURES"]) == 8 and len(golden["LAB_SIGNATURES"]) == 5
+    assert _lib.ERRORS.keys() == {1, 2, 3, 4} and all(_lib.ERRORS.values())
+
+
+def test_header_parser_refuses_what_it_does_not_understand():
+    import ctypes
+    from taiyaki_amd import _lib
+    ok = _lib.parse_prototypes("const char *tk_a(void);\nint tk_b(void **h, const char *s,\n  size_t n, float x, const float *p);")
+    assert _ctype_names({k: v[:2] for k, v in ok.items()}) == {
+        "tk_a": ["c_char_p", []], "tk_b": ["c_int", ["POINTER(c_void_p)", "c_char_p", "c_size_t", "c_float", "c_void_p"]]}
+    for bad in ("int tk_x(double a);",                      # a type outside the map
+                "int tk_x(tk_seq_labels labels);",          # a struct by value
+                "int tk_x(struct tk_seq_labels labels);",
+                "int tk_x(unsigned int n);", "int tk_x(float **rows);", "int tk_x(void v);", "double tk_x(int n);",
+                "int tk_x(int);"):                          # no declarator: the header names every parameter
+        with pytest.raises(TypeError, match="tk_x"):
+            _lib.parse_prototypes(bad)
+
+
+def test_every_dispatcher_is_declared_once():
+    """One declaration per dispatcher (csrc/dispatch.h, crf_band.h, squiggle_match.h): c_api.hip declares no function
+    that it does not define itself, and `struct RemapArgs` has one definition."""
+    from taiyaki_amd import _lib
+    sources = {fn: open(os.path.join(_lib.CSRC, fn)).read() for fn in sorted(os.listdir(_lib.CSRC))
+               if fn.endswith((".hip", ".h", ".inc", ".cpp"))}
+    assert sum(len(re.findall(r"\bstruct\s+RemapArgs\b[^;]*\{", text)) for text in sources.values()) == 1
+    c_api = re.sub(r"/\*.*?\*/|//[^\n]*", "", sources["c_api.hip"], flags=re.S)
+    # a prototype: a line that starts a declaration at file or namespace level and ends in `);` without a body
+    proto = r"(?m)^(?!typedef\b)(?:[\w:<>]+[ \t*&]+)+(\w+)\s*\([^;{}]*\)\s*;"
+    assert re.findall(proto, "namespace tk {\nint f_dispatch(const float *x,\n              size_t n);\n}\n") == ["f_dispatch"]
+    for name in re.findall(proto, c_api):
+        assert re.search(r"\b%s\s*\([^;{}]*\)\s*\{" % name, c_api), "c_api.hip declares %s and does not define it" % name
+    assert "aligned16(const void" not in "".join(text for fn, text in sources.items() if fn != "dispatch.h")

@@ -6,7 +6,6 @@ sweep-only launches with HIP events.
 
     GPU_MAX_HW_QUEUES=4 python tools/overlap_probe.py    # (bench.py's import pins it to 1: one queue serialises the two streams)
 """
-import ctypes
 import os
 import sys
 import time
@@ -18,16 +17,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 from taiyaki_amd import _lib  # noqa: E402
 
-_lib.use_lab(True)              # tk_lab_crf_band_phase is a lab-build export
-
 
 def main():
     dev = torch.device("cuda:0")
     _lib.set_strict(False)
-    L = _lib.lib()
-    phase = L.tk_lab_crf_band_phase
-    phase.argtypes = [ctypes.c_int]
-    phase.restype = None
+    phase = _lib.use_lab(True).tk_lab_crf_band_phase       # a lab-build export, typed by _lib.LAB_SIGNATURES
     a = bench.LossOps(800, 128, dev, realistic_chunk_len=4000)
     b = bench.LossOps(800, 128, dev, realistic_chunk_len=4000)
     for ops in (a, b):
