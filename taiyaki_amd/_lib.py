@@ -23,6 +23,8 @@ LAB_LIBPATH = os.environ.get("TAIYAKI_AMD_LAB_LIB") or os.path.join(CSRC, LAB_LI
 
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_flipflop.h")
 RCCL_LIBNAME = "libtaiyaki_amd_rccl.so"     # csrc/rccl_api.cpp: the header's multi-GPU section, a library of its own
+BASECALL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_basecall.h")
+BASECALL_LIBNAME = "libtaiyaki_amd_basecall.so"     # csrc/basecall_kernels.hip: the basecaller's glue, header and library of its own
 
 _vp = ctypes.c_void_p
 _SCALARS = {"size_t": ctypes.c_size_t, "int": ctypes.c_int, "float": ctypes.c_float}
@@ -77,6 +79,16 @@ SIGNATURES, RCCL_SIGNATURES, _seq_label_fields, DEFINES = _read_header()
 # the tk_lab_* hooks of the lab build: the extern "C" block that csrc/dispatch.h declares under TK_LAB
 LAB_SIGNATURES = {n: (r, a) for n, (r, a, _) in parse_prototypes(_blank_comments(re.search(
     r'#ifdef TK_LAB\nextern "C" \{\n(.*?)\n\}\n#endif', open(os.path.join(CSRC, "dispatch.h")).read(), re.S).group(1))).items()}
+
+
+def _read_basecall_header():
+    raw = open(BASECALL_HEADER).read()
+    sigs = {n: (r, a) for n, (r, a, _) in parse_prototypes(_blank_comments(raw)).items()}
+    return sigs, {k: int(v.rstrip("u"), 0) for k, v in re.findall(r"(?m)^#define (TK_\w+) (\w+)", raw) if v[0].isdigit()}
+
+
+# the fourth table: include/taiyaki_amd_basecall.h (libtaiyaki_amd_basecall.so), and its status bits
+BASECALL_SIGNATURES, BASECALL_DEFINES = _read_basecall_header()
 
 
 class SeqLabels(ctypes.Structure):
@@ -148,6 +160,17 @@ def rccl_lib():
     if _rccl is None:
         _rccl = _load(os.path.join(CSRC, RCCL_LIBNAME), RCCL_SIGNATURES)
     return _rccl
+
+
+_basecall = None
+
+
+def basecall_lib():
+    """The basecaller's glue kernels (include/taiyaki_amd_basecall.h).  No fallback: a missing library raises."""
+    global _basecall
+    if _basecall is None:
+        _basecall = _load(os.path.join(CSRC, BASECALL_LIBNAME), BASECALL_SIGNATURES)
+    return _basecall
 
 
 def check(rc, what):

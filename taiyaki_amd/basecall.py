@@ -1,0 +1,240 @@
+"""Basecall batches of reads on the device: raw float32 signals in, sequences and quality strings out
+(``bin/basecall.py:151-242`` with ``beam=None``: the Viterbi path, `posterior` on or off).
+
+Between the upload of the signals and the download of the finished characters nothing runs on the host: median / MAD
+normalisation, chunking and the tail (stitch, collapse, quality characters) are the three kernels of
+include/taiyaki_amd_basecall.h; the network, `flipflop_make_trans`, the Viterbi and `errprobs_from_trans` are the
+operators this package already has.  There is no CPU fallback: a model that is not on an AMD GPU raises.
+"""
+import collections
+
+import numpy as np
+import torch
+
+from taiyaki_amd import _lib, basecall_helpers, decode, flipflopfings, qscores
+
+Slice = collections.namedtuple("Slice", "short first ncol reads")
+Slice.__doc__ = """One model invocation of the packing plan: `ncol` columns.  short=False: columns [first, first + ncol)
+of the batch's chunk tensor; short=True: the one chunk, of its own length, of read `first`.  `reads`: the read of
+every column."""
+
+
+def chunk_counts(lengths, chunk_size, overlap):
+    """Chunks per read in the batch's chunk tensor (samples): the closed form of basecall_helpers.chunk_read's count,
+    0 for a read shorter than `chunk_size` (it is called alone, as one chunk of its own length)."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    step = chunk_size - overlap
+    return np.where(lengths < chunk_size, 0, (lengths - chunk_size + step - 1) // step + 1)
+
+
+def packing_plan(lengths, chunk_size, overlap, max_concurrent_chunks, pack=True):
+    """The model invocations for reads of `lengths` samples, host arithmetic on lengths alone.  Every chunk appears
+    once, in read order; no slice is wider than `max_concurrent_chunks`.  pack=True fills every slice across read
+    boundaries; pack=False splits per read, as `torch.split` does in bin/basecall.py:208.  Reads shorter than
+    `chunk_size` follow as slices of one column each (reads without samples get none)."""
+    counts = chunk_counts(lengths, chunk_size, overlap)
+    owner = np.repeat(np.arange(len(counts)), counts)
+    plan = []
+    if pack:
+        bounds = [(0, len(owner))]
+    else:
+        off = np.concatenate([[0], np.cumsum(counts)])
+        bounds = [(int(off[r]), int(off[r + 1])) for r in range(len(counts)) if counts[r]]
+    for lo, hi in bounds:
+        for first in range(lo, hi, max_concurrent_chunks):
+            ncol = min(max_concurrent_chunks, hi - first)
+            plan.append(Slice(False, first, ncol, tuple(int(r) for r in owner[first:first + ncol])))
+    for r, n in enumerate(lengths):
+        if 0 < n < chunk_size:
+            plan.append(Slice(True, r, 1, (r,)))
+    return plan
+
+
+def stitched_rows(nchunks, siglen, chunk_size, overlap, stride, nrow):
+    """Rows that basecall_helpers.stitch_chunks keeps of a read's `nchunks` chunks of `nrow` rows each: the bound of
+    the read's call length."""
+    if nchunks <= 1:
+        return nrow * nchunks
+    starts, ends = basecall_helpers.chunk_bounds(siglen, chunk_size, overlap)
+    lo = np.concatenate([[starts[0] // stride], (ends[:-1] - starts[1:]) // (2 * stride)])
+    hi = np.concatenate([[(ends[0] + starts[1]) // (2 * stride)],
+                         (ends[1:-1] + starts[2:] - 2 * starts[1:-1]) // (2 * stride),
+                         [(ends[-1] - starts[-1]) // stride]])
+    return int(np.maximum(np.minimum(hi, nrow) - np.minimum(lo, nrow), 0).sum())
+
+
+def _align(n, to=16):
+    return (n + to - 1) // to * to
+
+
+class Basecaller:
+    """`call(signals)` -> [(sequence, quality string or None, nsamples)] for a batch of reads.
+
+    chunk_size / overlap are in blocks of the model's stride, as on the reference's command line; `stride` is guessed
+    from the model when not given (helpers.guess_model_stride).  `reverse`: the signals are reversed before calling
+    (the reference's model.metadata['reverse']).  `pack`: fill the model's batches across read boundaries; False
+    splits them per read, exactly as the reference's loop does."""
+
+    def __init__(self, model, stride=None, chunk_size=1000, overlap=100, max_concurrent_chunks=128, alphabet="ACGT",
+                 posterior=True, temperature=1.0, fastq=False, qscore_scale=1.0, qscore_offset=0.0, reverse=False,
+                 pack=True):
+        self.model = model
+        self.device = basecall_helpers.get_model_device(model)
+        if self.device.type != "cuda":
+            raise RuntimeError("Basecaller: the model is on %s; basecalling only runs as HIP kernels on an AMD GPU "
+                               "(no CPU fallback)" % self.device)
+        self.stride = int(stride) if stride is not None else basecall_helpers.guess_model_stride(model)
+        self.chunk_size, self.overlap = int(chunk_size) * self.stride, int(overlap) * self.stride
+        if not 0 <= self.overlap < self.chunk_size:
+            raise ValueError("overlap must be smaller than chunk_size")
+        self.max_concurrent_chunks = int(max_concurrent_chunks)
+        self.alphabet = alphabet.encode("ascii")
+        self.n_can_state = flipflopfings.nstate_flipflop(len(alphabet))
+        self.posterior, self.temperature, self.fastq = bool(posterior), float(temperature), bool(fastq)
+        self.qscore_scale, self.qscore_offset = float(qscore_scale), float(qscore_offset)
+        self.reverse, self.pack = bool(reverse), bool(pack)
+
+    def plan(self, lengths):
+        return packing_plan(lengths, self.chunk_size, self.overlap, self.max_concurrent_chunks, self.pack)
+
+    # -- steps 4-8 of a call: the network and the decode operators on one chunk tensor ---------------------------------
+    def _decode(self, outs):
+        trans = torch.cat(outs, 1) * self.temperature
+        if self.posterior:
+            trans = (decode.flipflop_make_trans(trans) + 1e-8).log()
+        path = decode.flipflop_viterbi_path(trans)
+        return path, (qscores.errprobs_from_trans(trans, path) if self.fastq else None)
+
+    def _run(self, chunks):
+        return self.model(chunks)[:, :, :self.n_can_state]
+
+    def call(self, signals, read_params=None):
+        L, dev, nread = _lib.basecall_lib(), self.device, len(signals)
+        if nread == 0:
+            return []
+        sigs = [np.asarray(s, dtype=np.float32).reshape(-1) for s in signals]
+        if self.reverse:
+            sigs = [s[::-1] for s in sigs]
+        lens = np.array([len(s) for s in sigs], dtype=np.int64)
+        params = list(read_params) if read_params is not None else [None] * nread
+        given = np.array([p is not None for p in params])
+        # 1. ONE upload: signals | offsets | the caller's shift and scale
+        nsig = int(lens.sum())
+        o_off = _align(4 * nsig)
+        o_shift = o_off + _align(8 * (nread + 1))
+        o_scale = o_shift + _align(4 * nread)
+        host = np.zeros(o_scale + _align(4 * nread), dtype=np.uint8)
+        host[:4 * nsig].view(np.float32)[:] = np.concatenate(sigs) if nsig else 0
+        host[o_off:o_off + 8 * (nread + 1)].view(np.int64)[:] = np.concatenate([[0], np.cumsum(lens)])
+        host[o_shift:o_shift + 4 * nread].view(np.float32)[:] = [p[0] if p is not None else 0 for p in params]
+        host[o_scale:o_scale + 4 * nread].view(np.float32)[:] = [p[1] if p is not None else 1 for p in params]
+        plan = self.plan(lens)
+        counts = chunk_counts(lens, self.chunk_size, self.overlap)
+        total = int(counts.sum())
+        with torch.cuda.device(dev), torch.no_grad():
+            stream = _lib.stream_ptr()
+            up = torch.from_numpy(host).to(dev)
+            signal, sig_off = up[:4 * max(nsig, 1)].view(torch.float32), up[o_off:o_off + 8 * (nread + 1)].view(torch.int64)
+            shift = up[o_shift:o_shift + 4 * nread].view(torch.float32)
+            scale = up[o_scale:o_scale + 4 * nread].view(torch.float32)
+            # the ONE download comes from here: seqlen | status | seq | qual (sized once the block counts are known)
+            head = torch.zeros(_align(4 * nread) + 16, dtype=torch.uint8, device=dev)
+            seqlen, status = head[:4 * nread].view(torch.int32), head[_align(4 * nread):]
+            # 2. median / MAD where no parameters were given
+            if not given.all():
+                medmad = torch.empty(2, nread, dtype=torch.float32, device=dev)
+                _lib.check(L.tk_signal_med_mad_dev(_lib.ptr(signal), _lib.ptr(sig_off), nread, _lib.ptr(medmad[0]),
+                                                   _lib.ptr(medmad[1]), _lib.ptr(status), stream), "tk_signal_med_mad_dev")
+                if given.any():
+                    mask = torch.from_numpy(given).to(dev)
+                    shift, scale = torch.where(mask, shift, medmad[0]), torch.where(mask, scale, medmad[1])
+                else:
+                    shift, scale = medmad[0], medmad[1]
+            # 3. normalise + chunk: the batch's chunk tensor, and each short read as one chunk of its own length
+            starts = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+            ends = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
+            read_chunk_off = torch.empty(nread + 1, dtype=torch.int64, device=dev)
+            chunks = torch.empty(self.chunk_size, total, 1, dtype=torch.float32, device=dev)
+            ws = torch.empty(max(L.tk_basecall_gather_workspace_bytes(total), 16), dtype=torch.uint8, device=dev)
+            _lib.check(L.tk_basecall_gather_chunks_dev(
+                _lib.ptr(signal), _lib.ptr(sig_off), nread, nsig, _lib.ptr(shift), _lib.ptr(scale), self.chunk_size,
+                self.overlap, total, _lib.ptr(chunks), _lib.ptr(starts), _lib.ptr(ends), _lib.ptr(read_chunk_off),
+                _lib.ptr(ws), ws.numel(), _lib.ptr(status), stream), "tk_basecall_gather_chunks_dev")
+            one = torch.tensor([0, 1], dtype=torch.int64, device=dev)      # read_chunk_off of a read called alone
+            outs, short = [], []
+            for sl in plan:
+                if not sl.short:
+                    # 4. the network on column slices of at most max_concurrent_chunks
+                    outs.append(self._run(chunks[:, sl.first:sl.first + sl.ncol].contiguous()))
+                    continue
+                r, n = sl.first, int(lens[sl.first])
+                own = torch.empty(n, 1, 1, dtype=torch.float32, device=dev)
+                geo = torch.empty(3, 2, dtype=torch.int64, device=dev)     # starts, ends, read_chunk_off
+                w1 = torch.empty(16, dtype=torch.uint8, device=dev)
+                _lib.check(L.tk_basecall_gather_chunks_dev(
+                    _lib.ptr(signal), _lib._vp(sig_off.data_ptr() + 8 * r), 1, nsig, _lib._vp(shift.data_ptr() + 4 * r),
+                    _lib._vp(scale.data_ptr() + 4 * r), n, 0, 1, _lib.ptr(own), _lib.ptr(geo[0]), _lib.ptr(geo[1]),
+                    _lib.ptr(geo[2]), _lib.ptr(w1), w1.numel(), _lib.ptr(status), stream), "tk_basecall_gather_chunks_dev")
+                path, err = self._decode([self._run(own)])
+                short.append((r, path, err, geo))
+            # 5.-8. temperature, posterior, Viterbi, error probabilities on all the batch's chunks at once
+            path = err = None
+            if total:
+                path, err = self._decode(outs)
+            # room per read: its stitched row count bounds its call length
+            rows = np.zeros(nread, dtype=np.int64)
+            for r in range(nread):
+                if counts[r]:
+                    rows[r] = stitched_rows(int(counts[r]), int(lens[r]), self.chunk_size, self.overlap, self.stride,
+                                            path.shape[0])
+            for r, spath, _, _ in short:
+                rows[r] = spath.shape[0]
+            out_off_host = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+            cap = max(int(out_off_host[-1]), 1)
+            out_off = torch.from_numpy(out_off_host).to(dev)
+            body = torch.empty(2 * _align(cap), dtype=torch.uint8, device=dev)
+            seq, qual = body[:cap], body[_align(cap):_align(cap) + cap]
+            qs, qo = self.qscore_scale, self.qscore_offset
+            # 9. the tail (reads without a chunk in `path` get seqlen 0 here; the short ones are written next)
+            if total:
+                _lib.check(L.tk_basecall_call_dev(
+                    _lib.ptr(path), _lib.ptr(err), path.shape[0] - 1, total, _lib.ptr(starts), _lib.ptr(ends),
+                    _lib.ptr(read_chunk_off), _lib.ptr(scale), nread, self.stride, len(self.alphabet), self.alphabet,
+                    qs, qo, _lib.ptr(out_off), _lib.ptr(seq), _lib.ptr(qual), _lib.ptr(seqlen), _lib.ptr(status),
+                    stream), "tk_basecall_call_dev")
+            for r, spath, serr, geo in short:
+                _lib.check(L.tk_basecall_call_dev(
+                    _lib.ptr(spath), _lib.ptr(serr), spath.shape[0] - 1, 1, _lib.ptr(geo[0]), _lib.ptr(geo[1]),
+                    _lib.ptr(one), _lib._vp(scale.data_ptr() + 4 * r), 1, self.stride, len(self.alphabet),
+                    self.alphabet, qs, qo, _lib._vp(out_off.data_ptr() + 8 * r), _lib.ptr(seq), _lib.ptr(qual),
+                    _lib._vp(seqlen.data_ptr() + 4 * r), _lib.ptr(status), stream), "tk_basecall_call_dev")
+            # 10. ONE download
+            got = torch.cat([head, body]).cpu().numpy()
+        nhead = head.numel()
+        bits = int(got[_align(4 * nread):nhead].view(np.uint32)[0])
+        if bits & _lib.BASECALL_DEFINES["TK_STATUS_CHUNK_PLAN"]:
+            raise RuntimeError("basecall: the device's chunk plan disagrees with the host's (status %#x)" % bits)
+        called, seq_h = got[:4 * nread].view(np.int32), got[nhead:nhead + cap]
+        qual_h = got[nhead + _align(cap):nhead + _align(cap) + cap]
+        results = []
+        for r in range(nread):
+            lo, hi = int(out_off_host[r]), int(out_off_host[r]) + int(called[r])
+            q = qual_h[lo:hi].tobytes().decode("ascii") if self.fastq else None
+            results.append((seq_h[lo:hi].tobytes().decode("ascii"), q, int(lens[r])))
+        return results
+
+
+def write_records(fh, ids, results, fastq, reverse=False):
+    """The output loop of bin/basecall.py:280-291: one FASTA / FASTQ record per read with a non-empty call
+    (`reverse`: sequence and qualities written back to front).  Returns (nbase, ncalled, nread, nsample)."""
+    nbase = ncalled = nread = nsample = 0
+    for read_id, (basecall, qstring, read_nsample) in zip(ids, results):
+        if basecall is not None and len(basecall) > 0:
+            fh.write("{}{}\n{}\n".format("@" if fastq else ">", read_id, basecall[::-1] if reverse else basecall))
+            nbase += len(basecall)
+            ncalled += 1
+            if fastq:
+                fh.write("+\n{}\n".format(qstring[::-1] if reverse else qstring))
+        nread += 1
+        nsample += read_nsample
+    return nbase, ncalled, nread, nsample

@@ -250,3 +250,18 @@ def mapped_reads(nreads, seed, nlabel=4, mean_reflen=400, mean_dwell=9, clip_pro
             digitisation=8192.0, shift_frompA=float(np.float32(60 + 60 * fl[2])),
             scale_frompA=float(np.float32(8 + 10 * fl[3]))))
     return reads
+
+
+def excite_network(net, gain=8.0, bias=0.2):
+    """Make a freshly initialised flip-flop network CALL BASES.  As initialised, the recurrent stack forgets its input
+    (the variation over time shrinks 30-fold through the layers) and the output layer's bias decides every block: one
+    state for ever and an empty basecall.  Input-to-hidden and output weights times `gain`, output bias times `bias`: the
+    Viterbi path then follows the signal (tens of moves per 100 blocks).  In place; returns `net`."""
+    import torch
+    with torch.no_grad():
+        for name, p in net.named_parameters():
+            if "weight_ih" in name:
+                p.mul_(gain)
+        net[-1].linear.weight.mul_(gain)
+        net[-1].linear.bias.mul_(bias)
+    return net

@@ -1,0 +1,138 @@
+#!/usr/bin/env python
+"""Times the basecaller's tail two ways on the same inputs, and a whole `Basecaller.call`.
+
+The tail, at --chunks 128 x --blocks 1000, stride 5, overlap 100 blocks (the reference's default
+max_concurrent_chunks and chunk_size), on Viterbi paths and error probabilities of `synth.confident_scores`:
+  device   tk_basecall_call_dev (stitch, collapse, quality characters) plus its ONE download of seq, qual, seqlen
+  host     the chain this repository had before: `.cpu()` of path and error probabilities, `stitch_chunks`,
+           `path_to_str`, `path_errprobs_to_qstring`, per read
+Both produce every read's sequence and quality string; they are compared before anything is timed.  Each side is
+warmed up, then timed --steps times with a host clock around work that ends in a synchronising copy, the two sides
+alternating; median and min are printed.
+
+The whole call: reads/s and samples/s of `Basecaller.call` (fastq, posterior) on a seeded mGru_flipflop and
+mLstm_flipflop for --reads reads of 20 000 - 100 000 samples.  Prints one JSON line.
+
+    python tools/basecallbench.py [--chunks 128] [--blocks 1000] [--reads-per-batch 8] [--steps 20] [--warmup 3]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from taiyaki_amd import _lib, basecall, basecall_helpers, decode, flipflopfings, models, qscores, synth  # noqa: E402
+
+STRIDE, OVERLAP_BLOCKS = 5, 100
+
+
+def stats(times):
+    return dict(median_us=round(1e6 * float(np.median(times)), 1), min_us=round(1e6 * float(np.min(times)), 1))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--chunks", type=int, default=128)
+    ap.add_argument("--blocks", type=int, default=1000)
+    ap.add_argument("--reads-per-batch", type=int, default=8, help="reads the tail's chunks are split into")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reads", type=int, default=32, help="reads of the whole-call measurement")
+    ap.add_argument("--size", type=int, default=256, help="layer size of the two models")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("basecallbench needs a GPU (the basecaller has no CPU fallback)")
+    dev = torch.device("cuda:0")
+    L = _lib.basecall_lib()
+    T, N = a.blocks, a.chunks
+    chunk, overlap = T * STRIDE, OVERLAP_BLOCKS * STRIDE
+
+    # ---- the tail's inputs: the chunks of `reads-per-batch` reads, paths and error probabilities from the decode kernels
+    per = np.full(a.reads_per_batch, N // a.reads_per_batch)
+    per[:N % a.reads_per_batch] += 1
+    lens = [chunk + (int(k) - 1) * (chunk - overlap) - 137 * (int(k) > 1) for k in per]
+    geo = [basecall_helpers.chunk_bounds(n, chunk, overlap) for n in lens]
+    assert [len(g[0]) for g in geo] == list(per)
+    rco = np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
+    starts_h, ends_h = (np.concatenate([g[i] for g in geo]).astype(np.int64) for i in (0, 1))
+    seqlens = (T * (0.35 + 0.2 * np.random.RandomState(5).uniform(size=N))).astype(np.int32)
+    scores = torch.from_numpy(synth.confident_scores(synth.crf_case(T, N, 5, seqlens=seqlens), 6, on=2.0, off=-1.0)["scores"]).to(dev)
+    trans = decode.flipflop_make_trans(scores)
+    path = decode.flipflop_viterbi_path(scores)
+    err = qscores.errprobs_from_trans(trans, path)
+    rows = [basecall.stitched_rows(int(k), n, chunk, overlap, STRIDE, T + 1) for k, n in zip(per, lens)]
+    out_off_h = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+    cap, nread = int(out_off_h[-1]), len(lens)
+    starts, ends, rco_d, out_off = (torch.from_numpy(x).to(dev) for x in (starts_h, ends_h, rco, out_off_h))
+    o_seq = basecall._align(4 * nread)
+    buf = torch.zeros(o_seq + 2 * basecall._align(cap), dtype=torch.uint8, device=dev)
+    seqlen, seq, qual = buf[:4 * nread].view(torch.int32), buf[o_seq:o_seq + cap], buf[o_seq + basecall._align(cap):]
+
+    def device_tail():
+        _lib.check(L.tk_basecall_call_dev(
+            _lib.ptr(path), _lib.ptr(err), T, N, _lib.ptr(starts), _lib.ptr(ends), _lib.ptr(rco_d), None, nread, STRIDE, 4,
+            b"ACGT", 1.0, 0.0, _lib.ptr(out_off), _lib.ptr(seq), _lib.ptr(qual), _lib.ptr(seqlen), None, _lib.stream_ptr()),
+            "tk_basecall_call_dev")
+        got = buf.cpu().numpy()                                 # the one download (synchronises)
+        n = got[:4 * nread].view(np.int32)
+        q0 = o_seq + basecall._align(cap)
+        return [(got[o_seq + out_off_h[r]:o_seq + out_off_h[r] + n[r]].tobytes().decode(),
+                 got[q0 + out_off_h[r]:q0 + out_off_h[r] + n[r]].tobytes().decode()) for r in range(nread)]
+
+    def host_tail():
+        p, e = path.cpu(), err.cpu()                            # (synchronises)
+        out = []
+        for r in range(nread):
+            c0, c1 = int(rco[r]), int(rco[r + 1])
+            sp = basecall_helpers.stitch_chunks(p[:, c0:c1], starts_h[c0:c1], ends_h[c0:c1], STRIDE).numpy()
+            se = basecall_helpers.stitch_chunks(e[:, c0:c1], starts_h[c0:c1], ends_h[c0:c1], STRIDE)
+            out.append((flipflopfings.path_to_str(sp, include_first_source=False),
+                        qscores.path_errprobs_to_qstring(se, sp, 1.0, 0.0)))
+        return out
+
+    dres, hres = device_tail(), host_tail()
+    assert [d[0] for d in dres] == [h[0] for h in hres], "device and host tails disagree on a sequence"
+    qdiff = sum(x != y for d, h in zip(dres, hres) for x, y in zip(d[1], h[1]))
+    for _ in range(a.warmup):
+        device_tail()
+        host_tail()
+    times = {"device": [], "host": []}
+    for _ in range(a.steps):                                    # alternating, same process, same inputs
+        for name, fn in (("device", device_tail), ("host", host_tail)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            times[name].append(time.perf_counter() - t0)
+    rec = dict(tail=dict(chunks=N, blocks=T, stride=STRIDE, overlap_blocks=OVERLAP_BLOCKS, reads=nread,
+                         bases=sum(len(d[0]) for d in dres), quality_characters_differing=qdiff,
+                         device_with_download=stats(times["device"]), host_chain=stats(times["host"]),
+                         host_over_device=round(float(np.median(times["host"]) / np.median(times["device"])), 2)))
+
+    # ---- the whole call
+    rs = np.random.RandomState(9)
+    sigs = [(90 + 12 * rs.standard_normal(int(n))).astype(np.float32) for n in rs.randint(20000, 100001, size=a.reads)]
+    for name, make in (("mGru_flipflop", models.mGru_flipflop), ("mLstm_flipflop", models.mLstm_flipflop)):
+        torch.manual_seed(17)
+        net = make(size=a.size).to(dev).eval()
+        caller = basecall.Basecaller(net, fastq=True)
+        caller.call(sigs[:2])
+        caller.call(sigs)                                       # warm-up at the timed shapes
+        torch.cuda.synchronize()
+        wall = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            res = caller.call(sigs)                             # ends in its download
+            wall.append(time.perf_counter() - t0)
+        t = float(np.median(wall))
+        rec[name] = dict(size=a.size, stride=caller.stride, reads=len(sigs), samples=int(sum(map(len, sigs))),
+                         bases=sum(len(r[0]) for r in res), seconds=round(t, 4), reads_per_s=round(len(sigs) / t, 1),
+                         samples_per_s=round(sum(map(len, sigs)) / t))
+    print(json.dumps(rec))
+
+
+if __name__ == "__main__":
+    main()
