@@ -11,6 +11,11 @@
  *   taiyaki/basecall_helpers.py:46-94 stitch_chunks +
  *      flipflopfings.py:81-97 path_to_str(include_first_source=False) +
  *      qscores.py:10-55,145-178 path_errprobs_to_qstring          tk_basecall_call_dev
+ *   taiyaki/basecall_helpers.py:46-94 stitch_chunks of the
+ *      transition scores (bin/basecall.py:216-218, --beam)        tk_basecall_stitch_scores_dev
+ *   taiyaki/decodeutil/decodeutil.pyx:9-51 beamsearch +
+ *      flipflopfings.py:81-97 path_to_str(include_first_source=False),
+ *      for every read of a batch                                  tk_basecall_beamsearch_dev
  *
  * Conventions (those of taiyaki_amd_flipflop.h)
  *  - plain C; every pointer is a DEVICE pointer unless its comment says "host"; `stream` is a hipStream_t passed as
@@ -37,9 +42,11 @@ extern "C" {
 /* bits of this library's device-side status word */
 #define TK_STATUS_BAD_SIGNAL 128u   /* tk_signal_med_mad_dev: a read with a non-finite sample, no samples, or MAD == 0 */
 #define TK_STATUS_CHUNK_PLAN 256u   /* tk_basecall_gather_chunks_dev: total_chunks is not what the lengths give;
-                                       tk_basecall_call_dev: a read's call did not fit between its out_off entries */
+                                       tk_basecall_call_dev: a read's call did not fit between its out_off entries;
+                                       tk_basecall_stitch_scores_dev: a read's rows did not fit between its row_off
+                                       entries; tk_basecall_beamsearch_dev: row_off does not fit total_rows */
 
-/* library / build identification, e.g. "taiyaki_amd basecall gfx950 r1" */
+/* library / build identification, e.g. "taiyaki_amd basecall gfx950 r2" */
 const char *tk_basecall_version(void);
 
 /* ------------------------------------------------------------------------- *
@@ -116,6 +123,51 @@ int tk_basecall_call_dev(const int64_t *path, const float *errprobs, size_t nblk
                          const float *read_scale, size_t nread, size_t stride, size_t nbase, const char *alphabet,
                          float qscore_scale, float qscore_offset, const int64_t *out_off, uint8_t *seq, uint8_t *qual,
                          int32_t *seqlen, uint32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * (d) the stitched transition scores of every read of a batch: stitch_chunks(trans, starts, ends, stride) with
+ *     path_stitching=False (basecall_helpers.py:46-94, as bin/basecall.py:216-218 calls it for --beam), all reads at once
+ *   trans     (nblk, nchunks, ntrans) f32: the network's scores or the log transition weights of every chunk
+ *   chunk_starts, chunk_ends, read_chunk_off, read_scale, stride   as in (c)
+ *   row_off   (nread + 1) int64: read r's rows go to [row_off[r], row_off[r + 1]) of `stitched`; the caller sizes the
+ *             room from the read's stitched row count (a closed form of its length, as for (c))
+ *   stitched  (total_rows, ntrans) f32, packed: row stride ntrans;  total_rows bounds every read
+ *   nrows     (nread) int32: the rows read r actually got
+ * The cuts are (c)'s -- the same device function.  A read of one chunk keeps all its rows; a read without chunks, or
+ * whose read_scale entry is NaN, gets no rows.  A pure copy: every output float is bit for bit an input float, rows of
+ * `stitched` past a read's count are not touched.  If a read has more rows than room, TK_STATUS_CHUNK_PLAN is set,
+ * the rows that fit are written and nrows[r] is the room.
+ * ------------------------------------------------------------------------- */
+int tk_basecall_stitch_scores_dev(const float *trans, size_t nblk, size_t nchunks, size_t ntrans,
+                                  const int64_t *chunk_starts, const int64_t *chunk_ends,
+                                  const int64_t *read_chunk_off, const float *read_scale, size_t nread, size_t stride,
+                                  const int64_t *row_off, size_t total_rows, float *stitched, int32_t *nrows,
+                                  uint32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * (e) the hash beam search (decodeutil.pyx:9-51, c_hashdecode.c:346-507) for reads of different lengths in ONE launch,
+ *     one wavefront per read -- the kernel body of tk_flipflop_beamsearch_dev, and its results to the last bit -- and
+ *     each read's call
+ *   scores    (total_rows, ntrans) f32 packed as (d) writes it, ntrans = 2 nbase (nbase + 1); row_off as in (d)
+ *   nrows     (nread) int32, DEVICE: the rows of read r (clamped to [0, row_off[r + 1] - row_off[r]])
+ *   max_rows  the longest room of the launch (host arithmetic on row_off): sizes the back-pointer window in LDS; reads
+ *             past 3584 rows walk their back-pointers in HBM
+ *   nbase 1..4; beam_width 1..12 with beam_width * (nbase + 1) <= 64 (else TK_ERR_UNSUPPORTED); beam_cut in [0, 1]
+ *             (else TK_ERR_BAD_ARG); guided: 0 / 1; alphabet: a HOST pointer to nbase bytes
+ *   states    int8, read r's flip-flop states from row_off[r]; nstate (nread) int32 their count; score (nread) f32
+ *   seq       uint8, from row_off[r]: alphabet[state % nbase] of every state after the first that differs from its
+ *             predecessor (path_to_str(states, include_first_source=False)); seqlen (nread) int32 its length
+ *   workspace tk_basecall_beamsearch_workspace_bytes(total_rows, nread, nbase) bytes: the guiding backward matrix and
+ *             the back-pointer table of every read, at the prefix offsets row_off gives
+ * A read of 0 rows gives nstate 0, seqlen 0, score 0.  Nothing is written past a read's counts.  The launch lasts as
+ * long as its longest read.  A row_off entry outside [0, total_rows] sets TK_STATUS_CHUNK_PLAN and its read gets 0 rows.
+ * ------------------------------------------------------------------------- */
+size_t tk_basecall_beamsearch_workspace_bytes(size_t total_rows, size_t nread, size_t nbase);
+int tk_basecall_beamsearch_dev(const float *scores, const int64_t *row_off, const int32_t *nrows, size_t nread,
+                               size_t total_rows, size_t max_rows, size_t nbase, const char *alphabet, int beam_width,
+                               float beam_cut, int guided, int8_t *states, int32_t *nstate, float *score, uint8_t *seq,
+                               int32_t *seqlen, void *workspace, size_t workspace_bytes, uint32_t *status,
+                               void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,18 +1,22 @@
 """Basecall batches of reads on the device: raw float32 signals in, sequences and quality strings out
-(``bin/basecall.py:151-242`` with ``beam=None``: the Viterbi path, `posterior` on or off).
+(``bin/basecall.py:151-242``: the Viterbi path, `posterior` on or off, or -- ``beam=(width, guided)`` -- the hash beam
+search on every read's stitched transition scores).
 
 Between the upload of the signals and the download of the finished characters nothing runs on the host: median / MAD
 normalisation, chunking and the tail (stitch, collapse, quality characters) are the three kernels of
 include/taiyaki_amd_basecall.h; the network, `flipflop_make_trans`, the Viterbi and `errprobs_from_trans` are the
-operators this package already has.  There is no CPU fallback: a model that is not on an AMD GPU raises.
+operators this package already has.  With a beam, the stitched scores of all the batch's reads
+(tk_basecall_stitch_scores_dev) go through ONE launch of the beam search (tk_basecall_beamsearch_dev), which writes the
+calls.  There is no CPU fallback: a model that is not on an AMD GPU raises.
 """
 import collections
 
 import numpy as np
 import torch
 
-from taiyaki_amd import _lib, basecall_helpers, decode, flipflopfings, qscores
+from taiyaki_amd import _lib, basecall_helpers, decode, decodeutil, flipflopfings, qscores
 
+Beam = collections.namedtuple("Beam", "width guided")       # bin/basecall.py's --beam
 Slice = collections.namedtuple("Slice", "short first ncol reads")
 Slice.__doc__ = """One model invocation of the packing plan: `ncol` columns.  short=False: columns [first, first + ncol)
 of the batch's chunk tensor; short=True: the one chunk, of its own length, of read `first`.  `reads`: the read of
@@ -63,6 +67,22 @@ def stitched_rows(nchunks, siglen, chunk_size, overlap, stride, nrow):
     return int(np.maximum(np.minimum(hi, nrow) - np.minimum(lo, nrow), 0).sum())
 
 
+def check_beam(beam, beam_cut, nbase, fastq):
+    """`Basecaller`'s beam arguments -> Beam(width, guided), or None.  ValueError for a beam together with fastq (the
+    reference has no quality string for a beam call), for a width outside the search's admission rule (1..12 with
+    width * (nbase + 1) <= 64; nbase 1..4) and for a beam_cut outside [0, 1]."""
+    if beam is None:
+        return None
+    if fastq:
+        raise ValueError("Basecaller: beam search gives no quality string (fastq=True needs beam=None)")
+    try:
+        width, guided = beam
+    except (TypeError, ValueError):
+        raise ValueError("Basecaller: beam is (width, guided), got %r" % (beam,)) from None
+    decodeutil.check_beam(nbase, width, beam_cut, "Basecaller")
+    return Beam(int(width), bool(guided))
+
+
 def _align(n, to=16):
     return (n + to - 1) // to * to
 
@@ -73,11 +93,14 @@ class Basecaller:
     chunk_size / overlap are in blocks of the model's stride, as on the reference's command line; `stride` is guessed
     from the model when not given (helpers.guess_model_stride).  `reverse`: the signals are reversed before calling
     (the reference's model.metadata['reverse']).  `pack`: fill the model's batches across read boundaries; False
-    splits them per read, exactly as the reference's loop does."""
+    splits them per read, exactly as the reference's loop does.  `beam`: (width, guided) decodes every read with the
+    hash beam search on its stitched scores instead of the Viterbi path (`beam_cut` as decodeutil.beamsearch's); no
+    quality strings then."""
 
     def __init__(self, model, stride=None, chunk_size=1000, overlap=100, max_concurrent_chunks=128, alphabet="ACGT",
                  posterior=True, temperature=1.0, fastq=False, qscore_scale=1.0, qscore_offset=0.0, reverse=False,
-                 pack=True):
+                 pack=True, beam=None, beam_cut=0.0):
+        self.beam, self.beam_cut = check_beam(beam, beam_cut, len(alphabet), fastq), float(beam_cut)
         self.model = model
         self.device = basecall_helpers.get_model_device(model)
         if self.device.type != "cuda":
@@ -98,10 +121,14 @@ class Basecaller:
         return packing_plan(lengths, self.chunk_size, self.overlap, self.max_concurrent_chunks, self.pack)
 
     # -- steps 4-8 of a call: the network and the decode operators on one chunk tensor ---------------------------------
-    def _decode(self, outs):
+    def _trans(self, outs):
         trans = torch.cat(outs, 1) * self.temperature
         if self.posterior:
             trans = (decode.flipflop_make_trans(trans) + 1e-8).log()
+        return trans
+
+    def _decode(self, outs):
+        trans = self._trans(outs)
         path = decode.flipflop_viterbi_path(trans)
         return path, (qscores.errprobs_from_trans(trans, path) if self.fastq else None)
 
@@ -175,8 +202,13 @@ class Basecaller:
                     _lib.ptr(signal), _lib._vp(sig_off.data_ptr() + 8 * r), 1, nsig, _lib._vp(shift.data_ptr() + 4 * r),
                     _lib._vp(scale.data_ptr() + 4 * r), n, 0, 1, _lib.ptr(own), _lib.ptr(geo[0]), _lib.ptr(geo[1]),
                     _lib.ptr(geo[2]), _lib.ptr(w1), w1.numel(), _lib.ptr(status), stream), "tk_basecall_gather_chunks_dev")
+                if self.beam:
+                    short.append((r, self._trans([self._run(own)]).contiguous(), None, geo))
+                    continue
                 path, err = self._decode([self._run(own)])
                 short.append((r, path, err, geo))
+            if self.beam:
+                return self._call_beam(outs, short, counts, lens, starts, ends, read_chunk_off, scale, head)
             # 5.-8. temperature, posterior, Viterbi, error probabilities on all the batch's chunks at once
             path = err = None
             if total:
@@ -222,6 +254,50 @@ class Basecaller:
             q = qual_h[lo:hi].tobytes().decode("ascii") if self.fastq else None
             results.append((seq_h[lo:hi].tobytes().decode("ascii"), q, int(lens[r])))
         return results
+
+    def _call_beam(self, outs, short, counts, lens, starts, ends, read_chunk_off, scale, head):
+        """The rest of a call with a beam, inside `call`'s device context (bin/basecall.py:216-221 for every read):
+        stitch the scores of the batch's chunk tensor and of each short read's own chunk into ONE packed buffer, ONE
+        launch of the beam search, which also writes the calls, ONE download of seqlen | status | seq."""
+        L, dev, nread, stream = _lib.basecall_lib(), self.device, len(lens), _lib.stream_ptr()
+        seqlen, status = head[:4 * nread].view(torch.int32), head[_align(4 * nread):]
+        total = int(counts.sum())
+        trans = self._trans(outs).contiguous() if total else None
+        # room per read: its stitched row count
+        rows = np.zeros(nread, dtype=np.int64)
+        for r in range(nread):
+            if counts[r]:
+                rows[r] = stitched_rows(int(counts[r]), int(lens[r]), self.chunk_size, self.overlap, self.stride,
+                                        trans.shape[0])
+        for r, strans, _, _ in short:
+            rows[r] = strans.shape[0]
+        row_off_host = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+        total_rows = int(row_off_host[-1])
+        row_off = torch.from_numpy(row_off_host).to(dev)
+        packed = torch.empty(total_rows, self.n_can_state, dtype=torch.float32, device=dev)
+        nrows = torch.zeros(nread, dtype=torch.int32, device=dev)
+        one = torch.tensor([0, 1], dtype=torch.int64, device=dev)
+        if total:       # (reads without a chunk in `trans` get 0 rows here; the short ones are written next)
+            _lib.check(L.tk_basecall_stitch_scores_dev(
+                _lib.ptr(trans), trans.shape[0], total, trans.shape[2], _lib.ptr(starts), _lib.ptr(ends),
+                _lib.ptr(read_chunk_off), _lib.ptr(scale), nread, self.stride, _lib.ptr(row_off), total_rows,
+                _lib.ptr(packed), _lib.ptr(nrows), _lib.ptr(status), stream), "tk_basecall_stitch_scores_dev")
+        for r, strans, _, geo in short:
+            _lib.check(L.tk_basecall_stitch_scores_dev(
+                _lib.ptr(strans), strans.shape[0], 1, strans.shape[2], _lib.ptr(geo[0]), _lib.ptr(geo[1]), _lib.ptr(one),
+                _lib._vp(scale.data_ptr() + 4 * r), 1, self.stride, _lib._vp(row_off.data_ptr() + 8 * r), total_rows,
+                _lib.ptr(packed), _lib._vp(nrows.data_ptr() + 4 * r), _lib.ptr(status), stream),
+                "tk_basecall_stitch_scores_dev")
+        _, _, _, seq, _ = decodeutil.beamsearch_packed(packed, row_off, nrows, int(rows.max()), self.alphabet,
+                                                       self.beam.width, self.beam_cut, self.beam.guided, status, seqlen)
+        got = torch.cat([head, seq[:max(total_rows, 1)]]).cpu().numpy()
+        nhead = head.numel()
+        bits = int(got[_align(4 * nread):nhead].view(np.uint32)[0])
+        if bits & _lib.BASECALL_DEFINES["TK_STATUS_CHUNK_PLAN"]:
+            raise RuntimeError("basecall: the device's chunk plan disagrees with the host's (status %#x)" % bits)
+        called, seq_h = got[:4 * nread].view(np.int32), got[nhead:]
+        return [(seq_h[int(row_off_host[r]):int(row_off_host[r]) + int(called[r])].tobytes().decode("ascii"), None,
+                 int(lens[r])) for r in range(nread)]
 
 
 def write_records(fh, ids, results, fastq, reverse=False):

@@ -1,6 +1,7 @@
 // basecall_kernels.hip -- the basecaller's device-side glue (gfx950) and its extern "C" boundary
 // (include/taiyaki_amd_basecall.h): per-read median / MAD by radix selection, normalise + chunk, and the tail
-// (stitch the Viterbi paths of overlapping chunks, collapse them into bases, quality characters).
+// (stitch the Viterbi paths of overlapping chunks, collapse them into bases, quality characters); for the beam search,
+// the stitched transition scores of every read, packed row after row (the search itself: basecall_beam.hip).
 //
 // Compiled with -ffp-contract=off: every float operation on a signal or an error probability is ONE IEEE float32
 // operation, which is what makes the normalised chunks bit-equal to numpy's.
@@ -225,6 +226,27 @@ __global__ __launch_bounds__(BC_THREADS) void chunk_gather_kernel(const float *_
 // ------------------------------------------------------------------------------------------------------------------
 // (c) the tail
 // ------------------------------------------------------------------------------------------------------------------
+// basecall_helpers.py:64-94, path_stitching=False: the rows [lo, hi) that stitching keeps of chunk `c`, the i-th of its
+// read's `nch` chunks of `nrow` rows -- the reference's integer floor divisions for the first, middle and last chunk;
+// a read of one chunk keeps all its rows.  (hi < lo where the cuts cross: no rows.)
+__device__ __forceinline__ void chunk_cut(const int64_t *__restrict__ starts, const int64_t *__restrict__ ends,
+                                          int64_t c, int64_t i, int64_t nch, int64_t stride, int64_t nrow,
+                                          int64_t *lo_out, int64_t *hi_out) {
+    int64_t lo = 0, hi = nrow;
+    if (nch > 1) {
+        const int64_t s = starts[c], e = ends[c];
+        if (i == 0) {
+            lo = s / stride;
+            hi = (e + starts[c + 1]) / (2 * stride);
+        } else {
+            lo = (ends[c - 1] - s) / (2 * stride);
+            hi = i == nch - 1 ? (e - s) / stride : (e + starts[c + 1] - 2 * s) / (2 * stride);
+        }
+    }
+    *lo_out = lo < 0 ? 0 : lo;
+    *hi_out = hi > nrow ? nrow : hi;
+}
+
 struct Alphabet {
     uint8_t ch[16];
 };
@@ -263,20 +285,8 @@ __global__ __launch_bounds__(BC_THREADS) void call_kernel(const int64_t *__restr
     bool overflow = false;
     for (int64_t i = 0; i < nch; ++i) {
         const int64_t c = cbeg + i;
-        // basecall_helpers.py:64-94, path_stitching=False
-        int64_t lo = 0, hi = nrow;
-        if (nch > 1) {
-            const int64_t s = starts[c], e = ends[c];
-            if (i == 0) {
-                lo = s / stride;
-                hi = (e + starts[c + 1]) / (2 * stride);
-            } else {
-                lo = (ends[c - 1] - s) / (2 * stride);
-                hi = i == nch - 1 ? (e - s) / stride : (e + starts[c + 1] - 2 * s) / (2 * stride);
-            }
-        }
-        lo = lo < 0 ? 0 : lo;
-        hi = hi > nrow ? nrow : hi;
+        int64_t lo, hi;
+        chunk_cut(starts, ends, c, i, nch, stride, nrow, &lo, &hi);
         for (int64_t base = lo; base < hi; base += BC_THREADS) {
             const int64_t row = base + tid;
             const bool live = row < hi;
@@ -315,6 +325,56 @@ __global__ __launch_bounds__(BC_THREADS) void call_kernel(const int64_t *__restr
     if (tid == 0) seqlen[r] = (int32_t)(count < room ? count : (room < 0 ? 0 : room));
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// (d) the stitched scores of every read, for the beam search
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int STITCH_SPLIT = 8;     // workgroups per read: workgroup y copies the chunks i = y, y + 8, ... of its read
+
+// stitched[row_off[r] + k][:] = the k-th row that stitching keeps of read r's chunks.  Every workgroup walks the cuts
+// of all its read's chunks (a few integer divisions per chunk) for the row each chunk starts at, and copies its own:
+// flat over (rows, S), so a row's S floats are read side by side and the writes are one contiguous run.
+__global__ __launch_bounds__(BC_THREADS) void stitch_scores_kernel(const uint32_t *__restrict__ trans, int64_t nrow,
+                                                                   int64_t nchunks, uint32_t S,
+                                                                   const int64_t *__restrict__ starts,
+                                                                   const int64_t *__restrict__ ends,
+                                                                   const int64_t *__restrict__ read_chunk_off,
+                                                                   const float *__restrict__ read_scale, int64_t stride,
+                                                                   const int64_t *__restrict__ row_off,
+                                                                   int64_t total_rows, uint32_t *__restrict__ stitched,
+                                                                   int32_t *__restrict__ nrows,
+                                                                   uint32_t *__restrict__ status) {
+    const int r = blockIdx.x, tid = threadIdx.x;
+    int64_t cbeg = read_chunk_off[r], cend = read_chunk_off[r + 1];
+    cbeg = cbeg < 0 ? 0 : cbeg;
+    cend = cend > nchunks ? nchunks : cend;
+    const bool refused = read_scale && read_scale[r] != read_scale[r];
+    const int64_t nch = refused ? 0 : cend - cbeg;
+    const int64_t obeg = row_off[r];
+    int64_t room = row_off[r + 1] - obeg;
+    if (obeg < 0 || room < 0 || obeg + room > total_rows) room = 0;     // (nothing is written out of range)
+    int64_t at = 0;             // stitched rows before chunk i
+    for (int64_t i = 0; i < nch; ++i) {
+        const int64_t c = cbeg + i;
+        int64_t lo, hi;
+        chunk_cut(starts, ends, c, i, nch, stride, nrow, &lo, &hi);
+        const int64_t keep = hi > lo ? hi - lo : 0;
+        if (i % STITCH_SPLIT == blockIdx.y) {
+            const int64_t fit = at + keep <= room ? keep : (room > at ? room - at : 0);
+            const uint32_t *src = trans + (lo * nchunks + c) * S;
+            uint32_t *dst = stitched + (obeg + at) * S;
+            for (int64_t e = tid; e < fit * S; e += BC_THREADS) {
+                const int64_t row = e / S;
+                dst[e] = src[row * nchunks * S + (e - row * S)];
+            }
+        }
+        at += keep;
+    }
+    if (blockIdx.y == 0 && tid == 0) {
+        nrows[r] = (int32_t)(at < room ? at : room);
+        if (at > room && status) atomicOr(status, TK_STATUS_CHUNK_PLAN);
+    }
+}
+
 }  // namespace tk
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -324,7 +384,7 @@ static int launched() { return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_
 
 extern "C" {
 
-const char *tk_basecall_version(void) { return "taiyaki_amd basecall gfx950 r1"; }
+const char *tk_basecall_version(void) { return "taiyaki_amd basecall gfx950 r2"; }
 
 int tk_signal_med_mad_dev(const float *signal, const int64_t *sig_off, size_t nread, float *med, float *mad,
                           uint32_t *status, void *stream) {
@@ -393,6 +453,27 @@ int tk_basecall_call_dev(const int64_t *path, const float *errprobs, size_t nblk
                        static_cast<hipStream_t>(stream), path, errprobs, (int64_t)nblk + 1, (int64_t)nchunks,
                        chunk_starts, chunk_ends, read_chunk_off, read_scale, (int64_t)stride, (uint32_t)nbase, alpha,
                        qscore_scale, qscore_offset, out_off, seq, qual, seqlen, status);
+    return launched();
+}
+
+int tk_basecall_stitch_scores_dev(const float *trans, size_t nblk, size_t nchunks, size_t ntrans,
+                                  const int64_t *chunk_starts, const int64_t *chunk_ends,
+                                  const int64_t *read_chunk_off, const float *read_scale, size_t nread, size_t stride,
+                                  const int64_t *row_off, size_t total_rows, float *stitched, int32_t *nrows,
+                                  uint32_t *status, void *stream) {
+    if (!trans || !chunk_starts || !chunk_ends || !read_chunk_off || !row_off || !nrows || stride == 0 ||
+        ntrans == 0 || nchunks == 0)
+        return TK_ERR_BAD_ARG;
+    if (total_rows > 0 && !stitched) return TK_ERR_BAD_ARG;
+    if (nread == 0) return TK_OK;
+    if (nread > (size_t)INT32_MAX || nblk >= (size_t)INT32_MAX || nchunks > (size_t)INT32_MAX ||
+        stride > (size_t)INT32_MAX || ntrans > 65535 || total_rows > (size_t)INT64_MAX / 65536)
+        return TK_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(tk::stitch_scores_kernel, dim3((unsigned)nread, tk::STITCH_SPLIT), dim3(tk::BC_THREADS), 0,
+                       static_cast<hipStream_t>(stream), reinterpret_cast<const uint32_t *>(trans), (int64_t)nblk,
+                       (int64_t)nchunks, (uint32_t)ntrans, chunk_starts, chunk_ends, read_chunk_off, read_scale,
+                       (int64_t)stride, row_off, (int64_t)total_rows, reinterpret_cast<uint32_t *>(stitched), nrows,
+                       status);
     return launched();
 }
 

@@ -13,7 +13,15 @@ alternating; median and min are printed.
 The whole call: reads/s and samples/s of `Basecaller.call` (fastq, posterior) on a seeded mGru_flipflop and
 mLstm_flipflop for --reads reads of 20 000 - 100 000 samples.  Prints one JSON line.
 
+--beam WIDTH adds a row per model: a whole `Basecaller.call` with beam=(WIDTH, guided) -- every read's stitched scores
+through ONE launch of the beam search -- at 1, 8 and 64 of those reads, beside the same reads through the per-read
+chain the operators allowed before (chunk_read, the network, `stitch_chunks` of the scores, one `decodeutil.beamsearch`
+launch and its downloads per read, `path_to_str`).  Both split the network's invocations per read (pack=False), so
+their calls are equal (compared first; a mismatch ends the run).  The two sides alternate --beam-steps times after one
+warm-up each.  Median, min and max per side: the spread is that of the alternated runs themselves.
+
     python tools/basecallbench.py [--chunks 128] [--blocks 1000] [--reads-per-batch 8] [--steps 20] [--warmup 3]
+                                  [--beam 5] [--beam-steps 5]
 """
 import argparse
 import json
@@ -25,13 +33,65 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from taiyaki_amd import _lib, basecall, basecall_helpers, decode, flipflopfings, models, qscores, synth  # noqa: E402
+from taiyaki_amd import _lib, basecall, basecall_helpers, clipping, decode, decodeutil, flipflopfings, models, qscores, synth  # noqa: E402
 
 STRIDE, OVERLAP_BLOCKS = 5, 100
 
 
 def stats(times):
     return dict(median_us=round(1e6 * float(np.median(times)), 1), min_us=round(1e6 * float(np.min(times)), 1))
+
+
+def chain_call(sigs, net, stride, width, guided, dev, chunk_blocks=1000, overlap_blocks=100, concurrent=128):
+    """bin/basecall.py:151-221 with a beam, read by read, on the operators this package had before the batched path."""
+    out = []
+    for x in sigs:
+        med, mad = clipping.med_mad(x)
+        if not mad > 0:                                                         # (Basecaller's answer for such a read)
+            out.append(("", None, len(x)))
+            continue
+        chunks, starts, ends = basecall_helpers.chunk_read(((x - med) / mad).astype("f4"), chunk_blocks * stride,
+                                                           overlap_blocks * stride)
+        with torch.no_grad():
+            chunks = torch.tensor(chunks, device=dev)
+            trans = torch.cat([net(c.contiguous())[:, :, :40] for c in torch.split(chunks, concurrent, 1)], 1)
+            trans = (decode.flipflop_make_trans(trans) + 1e-8).log()
+            stitched = basecall_helpers.stitch_chunks(trans, starts, ends, stride).contiguous()
+            best, _ = decodeutil.beamsearch(stitched, 0.0, width, guided)       # one launch, three downloads
+        out.append((flipflopfings.path_to_str(best, include_first_source=False), None, len(x)))
+    return out
+
+
+def beam_rows(net, sigs, width, steps, dev):
+    """{reads: timings} of the batched beam call and of the per-read chain on sigs[:reads], alternating."""
+    caller = basecall.Basecaller(net, beam=(width, True), pack=False)
+    rows = {}
+    for nread in (1, 8, 64):
+        batch = sigs[:nread]
+        sides = dict(batched=lambda: caller.call(batch),
+                     chain=lambda: chain_call(batch, net, caller.stride, width, True, dev))
+        first = {k: fn() for k, fn in sides.items()}                           # (the warm-up at the timed shapes)
+        same = sum(a == b for a, b in zip(first["batched"], first["chain"]))
+        if same != len(batch):
+            raise SystemExit("basecallbench --beam: %d of %d reads have the same call on both sides; nothing timed"
+                             % (same, len(batch)))
+        times = {k: [] for k in sides}
+        for _ in range(steps):
+            for k, fn in sides.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()                                                            # ends in a download
+                times[k].append(time.perf_counter() - t0)
+        blocks = [len(x) // caller.stride for x in batch]
+        row = dict(reads=len(batch), blocks_longest=max(blocks), blocks_total=sum(blocks),
+                   bases=sum(len(r[0]) for r in first["batched"]),
+                   reads_with_equal_calls=same)
+        for k, t in times.items():
+            row[k] = dict(median_ms=round(1e3 * float(np.median(t)), 2), min_ms=round(1e3 * float(np.min(t)), 2),
+                          max_ms=round(1e3 * float(np.max(t)), 2), reads_per_s=round(len(batch) / float(np.median(t)), 2))
+        row["chain_over_batched"] = round(float(np.median(times["chain"]) / np.median(times["batched"])), 2)
+        rows[str(nread)] = row
+    return rows
 
 
 def main():
@@ -43,6 +103,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reads", type=int, default=32, help="reads of the whole-call measurement")
     ap.add_argument("--size", type=int, default=256, help="layer size of the two models")
+    ap.add_argument("--beam", type=int, default=0, metavar="WIDTH",
+                    help="also time a whole call with beam=(WIDTH, guided) at 1, 8, 64 reads beside the per-read chain")
+    ap.add_argument("--beam-steps", type=int, default=5)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("basecallbench needs a GPU (the basecaller has no CPU fallback)")
@@ -114,7 +177,9 @@ def main():
 
     # ---- the whole call
     rs = np.random.RandomState(9)
-    sigs = [(90 + 12 * rs.standard_normal(int(n))).astype(np.float32) for n in rs.randint(20000, 100001, size=a.reads)]
+    sigs = [(90 + 12 * rs.standard_normal(int(n))).astype(np.float32)
+            for n in rs.randint(20000, 100001, size=max(a.reads, 64 if a.beam else 0))]
+    beam_sigs, sigs = sigs, sigs[:a.reads]
     for name, make in (("mGru_flipflop", models.mGru_flipflop), ("mLstm_flipflop", models.mLstm_flipflop)):
         torch.manual_seed(17)
         net = make(size=a.size).to(dev).eval()
@@ -131,6 +196,9 @@ def main():
         rec[name] = dict(size=a.size, stride=caller.stride, reads=len(sigs), samples=int(sum(map(len, sigs))),
                          bases=sum(len(r[0]) for r in res), seconds=round(t, 4), reads_per_s=round(len(sigs) / t, 1),
                          samples_per_s=round(sum(map(len, sigs)) / t))
+        if a.beam:
+            rec[name]["beam"] = dict(width=a.beam, guided=True, steps=a.beam_steps,
+                                     rows=beam_rows(net, beam_sigs, a.beam, a.beam_steps, dev))
     print(json.dumps(rec))
 
 
