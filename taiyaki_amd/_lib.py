@@ -26,6 +26,10 @@ RCCL_LIBNAME = "libtaiyaki_amd_rccl.so"     # csrc/rccl_api.cpp: the header's mu
 BASECALL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_basecall.h")
 BASECALL_LIBNAME = "libtaiyaki_amd_basecall.so"     # csrc/basecall_kernels.hip: the basecaller's glue, header and library of its own
 
+WGRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_lstm_wgrad.h")
+WGRAD_LIBNAME = "libtaiyaki_amd_lstm_wgrad.so"      # csrc/lstm_wgrad.hip: the LSTM's parameter gradients, header and library of its own
+WGRAD_LAB_LIBNAME = "libtaiyaki_amd_lstm_wgrad_lab.so"      # ... and its lab build (tk_lab_lstm_wgrad_*)
+
 _vp = ctypes.c_void_p
 _SCALARS = {"size_t": ctypes.c_size_t, "int": ctypes.c_int, "float": ctypes.c_float}
 
@@ -89,6 +93,16 @@ def _read_basecall_header():
 
 # the fourth table: include/taiyaki_amd_basecall.h (libtaiyaki_amd_basecall.so), and its status bits
 BASECALL_SIGNATURES, BASECALL_DEFINES = _read_basecall_header()
+
+
+def _read_wgrad_header():
+    sigs = {n: (r, a) for n, (r, a, _) in parse_prototypes(_blank_comments(open(WGRAD_HEADER).read())).items()}
+    return ({n: v for n, v in sigs.items() if not n.startswith("tk_lab_")},
+            {n: v for n, v in sigs.items() if n.startswith("tk_lab_")})
+
+
+# the fifth: include/taiyaki_amd_lstm_wgrad.h (libtaiyaki_amd_lstm_wgrad.so), and the hooks its lab build adds
+WGRAD_SIGNATURES, WGRAD_LAB_SIGNATURES = _read_wgrad_header()
 
 
 class SeqLabels(ctypes.Structure):
@@ -171,6 +185,14 @@ def basecall_lib():
     if _basecall is None:
         _basecall = _load(os.path.join(CSRC, BASECALL_LIBNAME), BASECALL_SIGNATURES)
     return _basecall
+
+
+def wgrad_lib():
+    """The LSTM's parameter gradients (include/taiyaki_amd_lstm_wgrad.h): the lab build of that library while the
+    process runs on the lab build (`use_lab`), the release one otherwise.  No fallback: a missing library raises."""
+    if is_lab():
+        return _load(os.path.join(CSRC, WGRAD_LAB_LIBNAME), dict(WGRAD_SIGNATURES, **WGRAD_LAB_SIGNATURES))
+    return _load(os.path.join(CSRC, WGRAD_LIBNAME), WGRAD_SIGNATURES)
 
 
 def check(rc, what):

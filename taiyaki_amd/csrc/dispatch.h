@@ -98,6 +98,12 @@ int conv_small_backward_dispatch(const float *dy, const float *x, const float *w
                                  size_t cin, size_t cout, size_t winlen, int cu_count, float *dx, float *dw, float *db,
                                  void *ws, size_t wsb, hipStream_t stream);
 
+// lstm_wgrad.hip (a library of its own, include/taiyaki_amd_lstm_wgrad.h: the file defines its C entries itself)
+size_t lstm_wgrad_workspace_bytes(size_t T, size_t N, size_t H, size_t I, int cu_count);
+int lstm_wgrad_dispatch(const float *dgates, const float *x, const float *y, size_t T, size_t N, size_t H, size_t I,
+                        int reverse, int cu_count, float *dw_ih, float *dw_hh, float *db, void *ws, size_t wsb,
+                        hipStream_t stream);
+
 #ifdef TK_LAB
 // what the lab hooks below set (crf_band.hip, lstm_kernels.hip, gru_kernels.hip)
 void crf_band_lab_phase(int phase);

@@ -1,0 +1,296 @@
+// lstm_wgrad.hip -- the parameter gradients of one LSTM layer, dG^T [x | y shifted | 1], as one split-K GEMM on the
+// float32 matrix cores and one reduction (include/taiyaki_amd_lstm_wgrad.h; libtaiyaki_amd_lstm_wgrad.so).
+//
+// dG (K = T N rows of M = 4H), x (K x I) and y (K x H) are row-major with the summed index as the row, so a block of
+// WG_KB rows of either is staged into LDS as it lies in memory, [k][m], and v_mfma_f32_32x32x2_f32 takes its operands
+// from there one float per lane: lane l reads [k + (l >> 5)][m0 + (l & 31)], 32 consecutive floats per half wave.
+// A workgroup of four waves owns a 128 x 128 output tile (each wave 64 x 64: 2 x 2 accumulators) over one run of
+// rows.  The output's columns are tiled per operand -- x's columns, then y's -- so a tile reads one of the two; a y
+// tile reads y at row k -/+ N (the previous step's h of the same batch element), rows outside [0, K) as zeros.  The
+// workgroups of the first column of tiles add up the columns of the dG block they stage anyway: db.
+// Rows per run are a multiple of WG_KB, so only the last block of all is ragged.  A run longer than WG_CHAIN rows is
+// cut again, inside its workgroup, into partial results of their own: no fmaf chain is longer than that.
+// blockIdx = column tile * rstride + (row tile * runs + run) with rstride a multiple of 8: the workgroups that
+// read the same rows of dG sit on one XCD and share its L2.
+#include "dispatch.h"
+
+#include "../../include/taiyaki_amd_lstm_wgrad.h"
+
+namespace tk {
+namespace {
+
+constexpr int WG_TILE = 128;        // output tile edge
+constexpr int WG_KB = 16;           // rows per staged block
+constexpr int WG_THREADS = 256;
+constexpr size_t WG_CHAIN = 8192;   // the longest fmaf chain, in rows
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct WgradPlan {
+    int tiles_m, tiles_x, tiles_y;  // output tiles down (4H) and across (I, then H)
+    int splits, nsub;               // runs of rows, partial results per run
+    int run_rows, sub_rows;         // rows per run and per partial result (multiples of WG_KB)
+    int rstride, grid;
+    size_t slab_floats, slabs;      // one partial result [4H][I + H] | [4H], and how many there are
+};
+
+int g_lab_splits = 0;   // lab build: force the number of runs (0 = the rule below)
+
+size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
+
+// The plan: a function of the shape and the CU count only.  tiles * runs <= cu_count where the tiles alone fit.
+bool wgrad_plan(size_t T, size_t N, size_t H, size_t I, int cu_count, WgradPlan *p) {
+    if (T == 0 || N == 0 || H == 0 || I == 0 || cu_count <= 0) return false;
+    if (H > (1u << 20) || I > (1u << 20) || N > (1u << 28) || T > (size_t(1) << 30) / N) return false;
+    const size_t K = T * N, M = 4 * H, W = I + H;
+    if (M * W + M >= (size_t(1) << 31)) return false;
+    const size_t tm = ceil_div(M, WG_TILE), tx = ceil_div(I, WG_TILE), ty = ceil_div(H, WG_TILE);
+    const size_t tiles = tm * (tx + ty);
+    size_t G = g_lab_splits > 0 ? (size_t)g_lab_splits : (size_t)cu_count / tiles;
+    if (G < 1) G = 1;
+    const size_t run = ceil_div(ceil_div(K, G), WG_KB) * WG_KB;
+    G = ceil_div(K, run);           // (no empty runs)
+    const size_t nsub = ceil_div(run, WG_CHAIN);
+    const size_t sub = ceil_div(ceil_div(run, nsub), WG_KB) * WG_KB;
+    const size_t rstride = ceil_div(tm * G, 8) * 8;
+    if (rstride * (tx + ty) >= (size_t(1) << 31)) return false;
+    p->tiles_m = (int)tm, p->tiles_x = (int)tx, p->tiles_y = (int)ty;
+    p->splits = (int)G, p->nsub = (int)nsub, p->run_rows = (int)run, p->sub_rows = (int)sub;
+    p->rstride = (int)rstride, p->grid = (int)(rstride * (tx + ty));
+    p->slab_floats = (M * W + M + 3) / 4 * 4;
+    p->slabs = G * nsub;
+    return true;
+}
+
+struct WgradArgs {
+    const float *dg, *x, *y;
+    float *ws;
+    int K, N, M, I, H, reverse;
+    int tiles_m, tiles_x, splits, nsub, run_rows, sub_rows, rstride;
+    size_t slab_floats;
+};
+
+// four floats of row `row` from column `col` on.  FAST (every tile lies inside its matrix and takes 16-byte loads) is
+// one unconditional load, of row 0 where the row is not there: the caller zeroes it when it stages the value, so
+// nothing branches or waits for memory before the block's MFMAs.  Otherwise zeros where the row is not there or the
+// column is past the edge.
+template <bool FAST>
+__device__ __forceinline__ float4 load4(const float *src, int ld, int row, bool row_ok, int col) {
+    if (FAST) return *reinterpret_cast<const float4 *>(src + (size_t)(row_ok ? row : 0) * (size_t)ld + col);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (row_ok) {
+        const float *p = src + (size_t)row * (size_t)ld + col;
+        if (col < ld) v.x = p[0];
+        if (col + 1 < ld) v.y = p[1];
+        if (col + 2 < ld) v.z = p[2];
+        if (col + 3 < ld) v.w = p[3];
+    }
+    return v;
+}
+
+template <bool FAST>
+__global__ __launch_bounds__(WG_THREADS) void lstm_wgrad_kernel(const WgradArgs a) {
+    __shared__ __attribute__((aligned(16))) float As[2][WG_KB][WG_TILE];
+    __shared__ __attribute__((aligned(16))) float Bs[2][WG_KB][WG_TILE];
+    __shared__ __attribute__((aligned(16))) float colsum[WG_THREADS / 32][WG_TILE];
+
+    const int tnx = blockIdx.x / a.rstride, q = blockIdx.x % a.rstride;
+    if (q >= a.tiles_m * a.splits) return;      // (the padding of rstride)
+    const int run = q % a.splits, tmx = q / a.splits;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l31 = lane & 31, lhalf = lane >> 5, wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+    const int c4 = (tid & 31) * 4, r0 = tid >> 5;       // staging: this thread's four columns and first row of a block
+
+    const bool is_x = tnx < a.tiles_x;
+    const float *bsrc = is_x ? a.x : a.y;
+    const int bld = is_x ? a.I : a.H;
+    const int bcol0 = (is_x ? tnx : tnx - a.tiles_x) * WG_TILE;
+    const int shift = is_x ? 0 : (a.reverse ? a.N : -a.N);
+    const int out_col0 = is_x ? bcol0 : a.I + bcol0;
+    const int W = a.I + a.H;
+    const bool sum_cols = tnx == 0;
+    const int acol = tmx * WG_TILE + c4, bcol = bcol0 + c4;
+
+    const int run_begin = run * a.run_rows;
+    const int run_end = min(run_begin + a.run_rows, a.K);
+
+    for (int sub = 0; sub < a.nsub; ++sub) {
+        const int k0 = run_begin + sub * a.sub_rows;
+        const int k1 = min(k0 + a.sub_rows, run_end);
+        const int nkb = k1 > k0 ? (k1 - k0 + WG_KB - 1) / WG_KB : 0;
+
+        f32x16 acc[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        float4 dbacc = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 ra[2], rb[2];
+        bool oka[2], okb[2];
+
+        auto fetch = [&](int kb) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int k = k0 + kb * WG_KB + r0 + 8 * j;
+                const int kk = k + shift;
+                oka[j] = k < k1, okb[j] = oka[j] && kk >= 0 && kk < a.K;
+                ra[j] = load4<FAST>(a.dg, a.M, k, oka[j], acol);
+                rb[j] = load4<FAST>(bsrc, bld, kk, okb[j], bcol);
+            }
+        };
+        auto stash = [&](int buf) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                if (!oka[j]) ra[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (!okb[j]) rb[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+                *reinterpret_cast<float4 *>(&As[buf][r0 + 8 * j][c4]) = ra[j];
+                *reinterpret_cast<float4 *>(&Bs[buf][r0 + 8 * j][c4]) = rb[j];
+                if (sum_cols) {
+                    dbacc.x += ra[j].x, dbacc.y += ra[j].y, dbacc.z += ra[j].z, dbacc.w += ra[j].w;
+                }
+            }
+        };
+
+        if (nkb > 0) {
+            fetch(0);
+            stash(0);
+        }
+        __syncthreads();
+        for (int kb = 0; kb < nkb; ++kb) {
+            const int cur = kb & 1;
+            const bool more = kb + 1 < nkb;
+            if (more) fetch(kb + 1);        // in flight under the block's MFMAs
+            // the operands of the next pair of rows are read from LDS under the four MFMAs of this one
+            float a0 = As[cur][lhalf][wm + l31], a1 = As[cur][lhalf][wm + 32 + l31];
+            float b0 = Bs[cur][lhalf][wn + l31], b1 = Bs[cur][lhalf][wn + 32 + l31];
+            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+#pragma unroll
+            for (int kk = 0; kk < WG_KB; kk += 2) {
+                const int kn = (kk + 2 < WG_KB ? kk + 2 : kk) + lhalf;
+                const float na0 = As[cur][kn][wm + l31], na1 = As[cur][kn][wm + 32 + l31];
+                const float nb0 = Bs[cur][kn][wn + l31], nb1 = Bs[cur][kn][wn + 32 + l31];
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);      // the next pair's two LDS reads, then the four MFMAs
+                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                a0 = na0, a1 = na1, b0 = nb0, b1 = nb1;
+            }
+            if (more) stash(cur ^ 1);       // (its last readers passed the barrier of block kb - 1)
+            __syncthreads();
+        }
+
+        // this partial result: C[m][n] of accumulator register r sits at row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31
+        float *slab = a.ws + (size_t)(run * a.nsub + sub) * a.slab_floats;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int n = wn + 32 * j + l31;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = tmx * WG_TILE + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
+                    if (m < a.M && bcol0 + n < bld) slab[(size_t)m * W + out_col0 + n] = acc[i][j][r];
+                }
+            }
+        if (sum_cols) {
+            *reinterpret_cast<float4 *>(&colsum[r0][c4]) = dbacc;
+            __syncthreads();
+            if (tid < WG_TILE) {
+                float v = colsum[0][tid];
+#pragma unroll
+                for (int r = 1; r < WG_THREADS / 32; ++r) v += colsum[r][tid];
+                const int m = tmx * WG_TILE + tid;
+                if (m < a.M) slab[(size_t)a.M * W + m] = v;
+            }
+        }
+    }
+}
+
+// dw_ih | dw_hh | db = the partial results added in their order
+__global__ __launch_bounds__(256) void lstm_wgrad_reduce_kernel(const float *ws, size_t slab_floats, int slabs, int M,
+                                                                int I, int H, int zero_hh, float *dw_ih, float *dw_hh,
+                                                                float *db) {
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t W = (size_t)I + H, MW = (size_t)M * W;
+    if (idx >= MW + M) return;
+    float v = ws[idx];
+#pragma unroll 4
+    for (int p = 1; p < slabs; ++p) v += ws[(size_t)p * slab_floats + idx];
+    if (idx >= MW) {
+        db[idx - MW] = v;
+        return;
+    }
+    const size_t m = idx / W, c = idx % W;
+    if (c < (size_t)I)
+        dw_ih[m * I + c] = v;
+    else
+        dw_hh[m * H + (c - I)] = zero_hh ? 0.f : v;
+}
+
+}  // namespace
+
+size_t lstm_wgrad_workspace_bytes(size_t T, size_t N, size_t H, size_t I, int cu_count) {
+    WgradPlan p;
+    if (!wgrad_plan(T, N, H, I, cu_count, &p)) return 0;
+    return p.slabs * p.slab_floats * sizeof(float);
+}
+
+int lstm_wgrad_dispatch(const float *dgates, const float *x, const float *y, size_t T, size_t N, size_t H, size_t I,
+                        int reverse, int cu_count, float *dw_ih, float *dw_hh, float *db, void *ws, size_t wsb,
+                        hipStream_t stream) {
+    if (!dgates || !x || !y || !dw_ih || !dw_hh || !db || !ws || !aligned16(ws)) return TK_ERR_BAD_ARG;
+    WgradPlan p;
+    if (!wgrad_plan(T, N, H, I, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+    if (wsb < p.slabs * p.slab_floats * sizeof(float)) return TK_ERR_WORKSPACE;
+    WgradArgs a;
+    a.dg = dgates, a.x = x, a.y = y, a.ws = static_cast<float *>(ws);
+    a.K = (int)(T * N), a.N = (int)N, a.M = (int)(4 * H), a.I = (int)I, a.H = (int)H, a.reverse = reverse != 0;
+    a.tiles_m = p.tiles_m, a.tiles_x = p.tiles_x, a.splits = p.splits, a.nsub = p.nsub;
+    a.run_rows = p.run_rows, a.sub_rows = p.sub_rows, a.rstride = p.rstride;
+    a.slab_floats = p.slab_floats;
+    // whole tiles and 16-byte loads everywhere, or the guarded loads
+    if (aligned16(dgates) && aligned16(x) && aligned16(y) && H % WG_TILE == 0 && I % WG_TILE == 0)
+        hipLaunchKernelGGL(lstm_wgrad_kernel<true>, dim3(p.grid), dim3(WG_THREADS), 0, stream, a);
+    else
+        hipLaunchKernelGGL(lstm_wgrad_kernel<false>, dim3(p.grid), dim3(WG_THREADS), 0, stream, a);
+    if (hipGetLastError() != hipSuccess) return TK_ERR_LAUNCH;
+    const size_t total = (size_t)a.M * (I + H) + a.M;
+    hipLaunchKernelGGL(lstm_wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
+                       static_cast<const float *>(ws), p.slab_floats, (int)p.slabs, a.M, a.I, a.H, T == 1 ? 1 : 0,
+                       dw_ih, dw_hh, db);
+    return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
+}
+
+}  // namespace tk
+
+extern "C" {
+
+size_t tk_lstm_weight_grad_workspace_bytes(size_t nblk, size_t nbatch, size_t size, size_t insize, int cu_count) {
+    return tk::lstm_wgrad_workspace_bytes(nblk, nbatch, size, insize, cu_count);
+}
+
+int tk_lstm_weight_grad_dev(const float *dgates, const float *x, const float *y, size_t nblk, size_t nbatch,
+                            size_t size, size_t insize, int reverse, int cu_count, float *dw_ih, float *dw_hh,
+                            float *db, void *workspace, size_t workspace_bytes, void *stream) {
+    return tk::lstm_wgrad_dispatch(dgates, x, y, nblk, nbatch, size, insize, reverse, cu_count, dw_ih, dw_hh, db,
+                                   workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+#ifdef TK_LAB
+void tk_lab_lstm_wgrad_splits(int splits) { tk::g_lab_splits = splits; }
+
+int tk_lab_lstm_wgrad_plan(size_t nblk, size_t nbatch, size_t size, size_t insize, int cu_count, size_t *out) {
+    tk::WgradPlan p;
+    if (!tk::wgrad_plan(nblk, nbatch, size, insize, cu_count, &p)) return 0;
+    const size_t v[8] = {(size_t)p.tiles_m, (size_t)(p.tiles_x + p.tiles_y), (size_t)p.splits, (size_t)p.nsub,
+                         (size_t)p.run_rows, (size_t)p.sub_rows, (size_t)p.grid, p.slabs};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return 1;
+}
+#endif
+
+}  // extern "C"

@@ -238,6 +238,9 @@ class _Rnn(nn.Module):
 
 # False: every Lstm runs nn.LSTM (MIOpen on the GPU), for comparisons against the HIP recurrence
 USE_HIP_LSTM = True
+# False: the parameter gradients of LstmRecurrence.backward are two GEMMs and a sum over dG (what they are wherever
+# tk_lstm_weight_grad_workspace_bytes is 0), for comparisons against the fused kernel
+USE_HIP_LSTM_WGRAD = True
 
 
 def hip_lstm_workspace_bytes(rnn, x):
@@ -298,6 +301,19 @@ class LstmRecurrence(torch.autograd.Function):
         dg2 = dg.view(T * N, 4 * H)
         need = ctx.needs_input_grad
         dx = (dg2 @ w_ih).view(T, N, I) if need[0] else None
+        if USE_HIP_LSTM_WGRAD and need[1] and need[2] and (need[3] or need[4]):
+            # the three parameter gradients in one pass over dG: dG^T [x | y shifted by a step | 1]
+            W = _lib.wgrad_lib()
+            wgb = W.tk_lstm_weight_grad_workspace_bytes(T, N, H, I, _cu_count(dev))
+            if wgb:
+                dw_ih, dw_hh = torch.empty_like(w_ih, memory_format=torch.contiguous_format), torch.empty_like(w_hh)
+                db = torch.empty(4 * H, dtype=torch.float32, device=dev)
+                wws = _lib.workspace(wgb, dev, "lstm_wgrad")
+                rc = W.tk_lstm_weight_grad_dev(_lib.ptr(dg), _lib.ptr(x), _lib.ptr(y), T, N, H, I, int(ctx.reverse),
+                                               _cu_count(dev), _lib.ptr(dw_ih), _lib.ptr(dw_hh), _lib.ptr(db),
+                                               _lib.ptr(wws), wgb, _lib.stream_ptr())
+                _lib.check(rc, "tk_lstm_weight_grad_dev")
+                return dx, dw_ih, dw_hh, db if need[3] else None, db if need[4] else None, None, None
         dw_ih = dg2.t() @ x.view(T * N, I) if need[1] else None
         dw_hh = None
         if need[2]:

@@ -2,7 +2,8 @@
 """Times one layer's LSTM recurrence (csrc/lstm_kernels.hip) on the GPU: tk_lstm_forward_dev and
 tk_lstm_backward_dev at (T, N, H), each timed with device events after warm-up; prints one JSON line per
 units setting (microseconds per timestep and direction, median and min over --steps).  The flagship layer
-(config 2) is the default shape.
+(config 2) is the default shape.  The weight-gradient leg follows: `wgrad_ms` is tk_lstm_weight_grad_dev
+(csrc/lstm_wgrad.hip) at (T, N, H, I = H), `wgrad_gemm_ms` the two GEMMs and the sum over dG that it replaces.
 
     python tools/lstmbench.py [--T 800] [--N 128] [--H 256] [--steps 20] [--warmup 3] [--units 0 16 32 64]
 
@@ -58,6 +59,7 @@ def main():
     gates = torch.empty(T, N, 4 * H, device=dev)
     cell = torch.empty(T, N, H, device=dev)
     dg = torch.empty(T, N, 4 * H, device=dev)
+    x_in = torch.randn(T, N, H, generator=g).to(dev)
     cus = layers._cu_count(dev)
     _lib.set_strict(False)
     for units in (a.units if a.units is not None else [None]):
@@ -83,6 +85,30 @@ def main():
 
         f_med, f_min = timed(fwd, a.steps, a.warmup)
         b_med, b_min = timed(bwd, a.steps, a.warmup)
+
+        # the parameter gradients from that dG, this y and an input of the layer's size
+        W = _lib.wgrad_lib()
+        wgb = W.tk_lstm_weight_grad_workspace_bytes(T, N, H, H, cus)
+        if wgb == 0:
+            raise SystemExit("(T, N, H, I) = (%d, %d, %d, %d) has no weight-gradient plan on %d CUs" % (T, N, H, H, cus))
+        wws = torch.empty(wgb // 4, dtype=torch.float32, device=dev)
+        dw_ih, dw_hh, db = torch.empty(4 * H, H, device=dev), torch.empty(4 * H, H, device=dev), torch.empty(4 * H, device=dev)
+
+        def wgrad():
+            _lib.check(W.tk_lstm_weight_grad_dev(_lib.ptr(dg), _lib.ptr(x_in), _lib.ptr(y), T, N, H, H, int(a.reverse),
+                                                 cus, _lib.ptr(dw_ih), _lib.ptr(dw_hh), _lib.ptr(db), _lib.ptr(wws), wgb,
+                                                 stream), "tk_lstm_weight_grad_dev")
+
+        def wgrad_gemm():
+            dg2 = dg.view(T * N, 4 * H)
+            dgs, hp = (dg[:-1], y[1:]) if a.reverse else (dg[1:], y[:-1])
+            return dg2.t() @ x_in.view(T * N, H), dgs.reshape(-1, 4 * H).t() @ hp.reshape(-1, H), dg2.sum(0)
+
+        w_med, w_min = timed(wgrad, a.steps, a.warmup)
+        g_med, g_min = timed(wgrad_gemm, a.steps, a.warmup)
+        ref = wgrad_gemm()
+        wgrad_diff = max(((p - q).abs().max() / q.abs().max()).item() for p, q in zip((dw_ih, dw_hh, db), ref))
+        gflop = 2.0 * T * N * 4 * H * (2 * H + 1) * 1e-9
         _lib.finish(status)
         _lib.raise_if_nonfinite()
         if units is not None:
@@ -91,6 +117,9 @@ def main():
                           "fwd_ms": round(f_med, 3), "bwd_ms": round(b_med, 3),
                           "fwd_us_per_step": round(1e3 * f_med / T, 3), "fwd_min_us_per_step": round(1e3 * f_min / T, 3),
                           "bwd_us_per_step": round(1e3 * b_med / T, 3), "bwd_min_us_per_step": round(1e3 * b_min / T, 3),
+                          "wgrad_ms": round(w_med, 4), "wgrad_min_ms": round(w_min, 4), "wgrad_gemm_ms": round(g_med, 4),
+                          "wgrad_gemm_min_ms": round(g_min, 4), "wgrad_tflops": round(gflop / w_med, 1),
+                          "wgrad_gemm_tflops": round(gflop / g_med, 1), "wgrad_vs_gemm_maxrel": wgrad_diff,
                           "device": torch.cuda.get_device_name(dev)}))
     _lib.use_lab(False)
 
