@@ -16,6 +16,9 @@
  *   taiyaki/decodeutil/decodeutil.pyx:9-51 beamsearch +
  *      flipflopfings.py:81-97 path_to_str(include_first_source=False),
  *      for every read of a batch                                  tk_basecall_beamsearch_dev
+ *   taiyaki/flipflopfings.py:100-143 extract_mod_weights on the
+ *      stitched path and the stitched categorical columns of a
+ *      cat-mod model, for every read of a batch                   tk_basecall_mod_weights_dev
  *
  * Conventions (those of taiyaki_amd_flipflop.h)
  *  - plain C; every pointer is a DEVICE pointer unless its comment says "host"; `stream` is a hipStream_t passed as
@@ -44,7 +47,11 @@ extern "C" {
 #define TK_STATUS_CHUNK_PLAN 256u   /* tk_basecall_gather_chunks_dev: total_chunks is not what the lengths give;
                                        tk_basecall_call_dev: a read's call did not fit between its out_off entries;
                                        tk_basecall_stitch_scores_dev: a read's rows did not fit between its row_off
-                                       entries; tk_basecall_beamsearch_dev: row_off does not fit total_rows */
+                                       entries; tk_basecall_beamsearch_dev: row_off does not fit total_rows;
+                                       tk_basecall_mod_weights_dev: a read's rows did not fit between its out_off entries */
+
+/* tk_basecall_mod_weights_dev: the most modifications an alphabet may have in all (sum of can_nmods) */
+#define TK_BASECALL_MAX_NMOD 32
 
 /* library / build identification, e.g. "taiyaki_amd basecall gfx950 r2" */
 const char *tk_basecall_version(void);
@@ -168,6 +175,41 @@ int tk_basecall_beamsearch_dev(const float *scores, const int64_t *row_off, cons
                                float beam_cut, int guided, int8_t *states, int32_t *nstate, float *score, uint8_t *seq,
                                int32_t *seqlen, void *workspace, size_t workspace_bytes, uint32_t *status,
                                void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * (f) the modified-base weights of every read's call: flipflopfings.py:100-143 extract_mod_weights(W, P, can_nmods)
+ *     without its first row, on P = stitch_chunks(path) and W = stitch_chunks(mod_weights) (path_stitching=False, the
+ *     cuts of (c): the same device function) -- all reads of a batch in one launch, one workgroup per read
+ *   path        (nblk + 1, nchunks) int64, as in (c)
+ *   mod_weights (nblk, nchunks, ncat) f32, contiguous: the columns of a GlobalNormFlipFlopCatMod output from
+ *               2 nbase (nbase + 1) on, ncat = nbase + nmod log-probabilities in the layer's grouped order
+ *               [base 0 unmodified, its modifications ..., base 1 unmodified, its modifications ..., ...]
+ *               (nblk == 0, a read too short for a block: may be NULL, nothing is read from it)
+ *   chunk_starts, chunk_ends, read_chunk_off, read_scale, nread, stride   as in (c)
+ *   can_nmods   a HOST pointer to nbase <= 16 ints >= 0: the modifications of each canonical base;
+ *               nmod = their sum, 1 .. TK_BASECALL_MAX_NMOD (0, a negative entry or NULL: TK_ERR_BAD_ARG; more:
+ *               TK_ERR_UNSUPPORTED)
+ *   out_off     (nread + 1) int64, in rows: the offsets (c) takes for `seq`
+ *   mods        f32, packed: read r's rows start at row out_off[r], row stride nmod
+ *   seqlen      (nread) int32: the rows of read r, which is what (c) writes there -- both kernels run the same walk
+ * Stitched row k >= 1 is a move when P[k] != P[k - 1] ((c)'s rule, also across a cut).  The i-th move, into base
+ * b = P[k] % nbase, writes row i: column j of the nmod columns, if it is the m-th modification of base b, gets
+ * W[k - 1][off_b + 1 + m] with off_b = sum over b' < b of (can_nmods[b'] + 1) -- the weight row of stitched row k - 1,
+ * from the chunk that holds it; every other column gets the quiet NaN 0x7fc00000.  Row i belongs to character i of (c)'s
+ * call (the reference's row 0, the never-entered first state, is the row path_to_str(include_first_source=False) drops).
+ * A read of one chunk keeps all its rows: P has nblk + 1 of them, W nblk.  With more chunks every kept row of a chunk
+ * lies below nblk for any chunk geometry (b) produces; should a cut keep a chunk's path row nblk, which has no weight
+ * row, a move out of it gets NaN in every column.
+ * A pure selection: every finite output float is bit for bit an input float; nothing is written past a read's seqlen
+ * rows; a read without chunks, or whose read_scale entry is NaN, gets seqlen 0 and no rows; results do not depend on
+ * the batch and repeat bit for bit.  A read with more moves than room sets TK_STATUS_CHUNK_PLAN, gets the rows that fit,
+ * and seqlen[r] is the room.
+ * ------------------------------------------------------------------------- */
+int tk_basecall_mod_weights_dev(const int64_t *path, const float *mod_weights, size_t nblk, size_t nchunks,
+                                const int64_t *chunk_starts, const int64_t *chunk_ends, const int64_t *read_chunk_off,
+                                const float *read_scale, size_t nread, size_t stride, size_t nbase,
+                                const int *can_nmods, const int64_t *out_off, float *mods, int32_t *seqlen,
+                                uint32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -5,16 +5,19 @@ search on every read's stitched transition scores).
 Between the upload of the signals and the download of the finished characters nothing runs on the host: median / MAD
 normalisation, chunking and the tail (stitch, collapse, quality characters) are the three kernels of
 include/taiyaki_amd_basecall.h; the network, `flipflop_make_trans`, the Viterbi and `errprobs_from_trans` are the
-operators this package already has.  With a beam, the stitched scores of all the batch's reads
+operators this package already has.  `call_mods` adds, for a cat-mod model, the modified-base scores of every called
+base (tk_basecall_mod_weights_dev on the Viterbi paths and the network's categorical columns), in the same download.
+With a beam, the stitched scores of all the batch's reads
 (tk_basecall_stitch_scores_dev) go through ONE launch of the beam search (tk_basecall_beamsearch_dev), which writes the
 calls.  There is no CPU fallback: a model that is not on an AMD GPU raises.
 """
 import collections
+import ctypes
 
 import numpy as np
 import torch
 
-from taiyaki_amd import _lib, basecall_helpers, decode, decodeutil, flipflopfings, qscores
+from taiyaki_amd import _lib, basecall_helpers, decode, decodeutil, flipflopfings, layers, qscores
 
 Beam = collections.namedtuple("Beam", "width guided")       # bin/basecall.py's --beam
 Slice = collections.namedtuple("Slice", "short first ncol reads")
@@ -83,24 +86,49 @@ def check_beam(beam, beam_cut, nbase, fastq):
     return Beam(int(width), bool(guided))
 
 
+def check_mods(model, mod_output, beam, nbase):
+    """`Basecaller`'s mod_output argument -> the model's can_nmods as a list, or None.  ValueError for mod_output
+    together with a beam (the search's states are not per chunk), on a model whose last layer is not
+    GlobalNormFlipFlopCatMod, and on one without a modification (or with more than the kernel's
+    TK_BASECALL_MAX_NMOD, or whose canonical alphabet is not `nbase` long)."""
+    if not mod_output:
+        return None
+    if beam is not None:
+        raise ValueError("Basecaller: mod_output needs the Viterbi path (beam=None); the beam search's states are not "
+                         "per chunk")
+    if not (isinstance(model, layers.Serial) and layers.is_cat_mod_model(model)):
+        raise ValueError("Basecaller: mod_output needs a model whose last layer is GlobalNormFlipFlopCatMod")
+    can_nmods = [int(n) for n in model[-1].can_nmods]
+    cap = _lib.BASECALL_DEFINES["TK_BASECALL_MAX_NMOD"]
+    if sum(can_nmods) == 0:
+        raise ValueError("Basecaller: mod_output on a model without a modification (can_nmods %r)" % (can_nmods,))
+    if len(can_nmods) != nbase or sum(can_nmods) > cap:
+        raise ValueError("Basecaller: can_nmods %r does not fit an alphabet of %d bases and at most %d modifications"
+                         % (can_nmods, nbase, cap))
+    return can_nmods
+
+
 def _align(n, to=16):
     return (n + to - 1) // to * to
 
 
 class Basecaller:
-    """`call(signals)` -> [(sequence, quality string or None, nsamples)] for a batch of reads.
+    """`call(signals)` -> [(sequence, quality string or None, nsamples)] for a batch of reads; with mod_output=True,
+    `call_mods(signals)` -> (the same list, [the modified-base scores of every read's call]).
 
     chunk_size / overlap are in blocks of the model's stride, as on the reference's command line; `stride` is guessed
     from the model when not given (helpers.guess_model_stride).  `reverse`: the signals are reversed before calling
     (the reference's model.metadata['reverse']).  `pack`: fill the model's batches across read boundaries; False
     splits them per read, exactly as the reference's loop does.  `beam`: (width, guided) decodes every read with the
     hash beam search on its stitched scores instead of the Viterbi path (`beam_cut` as decodeutil.beamsearch's); no
-    quality strings then."""
+    quality strings then.  `mod_output`: the model is a cat-mod model (its last layer GlobalNormFlipFlopCatMod) and
+    `call_mods` is wanted; `call` gives what it gives without it."""
 
     def __init__(self, model, stride=None, chunk_size=1000, overlap=100, max_concurrent_chunks=128, alphabet="ACGT",
                  posterior=True, temperature=1.0, fastq=False, qscore_scale=1.0, qscore_offset=0.0, reverse=False,
-                 pack=True, beam=None, beam_cut=0.0):
+                 pack=True, beam=None, beam_cut=0.0, mod_output=False):
         self.beam, self.beam_cut = check_beam(beam, beam_cut, len(alphabet), fastq), float(beam_cut)
+        self.can_nmods = check_mods(model, mod_output, beam, len(alphabet))
         self.model = model
         self.device = basecall_helpers.get_model_device(model)
         if self.device.type != "cuda":
@@ -122,6 +150,8 @@ class Basecaller:
 
     # -- steps 4-8 of a call: the network and the decode operators on one chunk tensor ---------------------------------
     def _trans(self, outs):
+        if self.can_nmods:      # (`_run` kept the categorical columns)
+            outs = [o[:, :, :self.n_can_state] for o in outs]
         trans = torch.cat(outs, 1) * self.temperature
         if self.posterior:
             trans = (decode.flipflop_make_trans(trans) + 1e-8).log()
@@ -133,12 +163,33 @@ class Basecaller:
         return path, (qscores.errprobs_from_trans(trans, path) if self.fastq else None)
 
     def _run(self, chunks):
-        return self.model(chunks)[:, :, :self.n_can_state]
+        """The network on one chunk tensor: its transition scores and, with mod_output, the categorical columns
+        behind them."""
+        out = self.model(chunks)
+        return out if self.can_nmods else out[:, :, :self.n_can_state]
+
+    def _mod_weights(self, outs):
+        return torch.cat([o[:, :, self.n_can_state:] for o in outs], 1).contiguous()
 
     def call(self, signals, read_params=None):
+        return self._call(signals, read_params, False)[0]
+
+    def call_mods(self, signals, read_params=None):
+        """-> (results, mods): `results` is exactly what `call` returns; mods[r] is a float32 array (len(sequence r),
+        nmod): row i holds, for character i of read r's call, the log-probabilities of the modifications of ITS
+        canonical base (the network's categorical columns at the block before the move, flipflopfings.py:100-143) and
+        NaN in the columns of the other bases' modifications; columns in can_nmods order.  With reverse=True the rows
+        are in the order of the unreversed call string in `results` -- the call of the reversed signal -- which
+        `write_records(reverse=True)` writes back to front.  The network runs once per slice, and the scores ride in
+        the call's one download, behind seq | qual."""
+        if not self.can_nmods:
+            raise RuntimeError("Basecaller.call_mods needs mod_output=True at construction")
+        return self._call(signals, read_params, True)
+
+    def _call(self, signals, read_params, want_mods):
         L, dev, nread = _lib.basecall_lib(), self.device, len(signals)
         if nread == 0:
-            return []
+            return [], []
         sigs = [np.asarray(s, dtype=np.float32).reshape(-1) for s in signals]
         if self.reverse:
             sigs = [s[::-1] for s in sigs]
@@ -188,7 +239,7 @@ class Basecaller:
                 self.overlap, total, _lib.ptr(chunks), _lib.ptr(starts), _lib.ptr(ends), _lib.ptr(read_chunk_off),
                 _lib.ptr(ws), ws.numel(), _lib.ptr(status), stream), "tk_basecall_gather_chunks_dev")
             one = torch.tensor([0, 1], dtype=torch.int64, device=dev)      # read_chunk_off of a read called alone
-            outs, short = [], []
+            outs, short, short_w = [], [], {}
             for sl in plan:
                 if not sl.short:
                     # 4. the network on column slices of at most max_concurrent_chunks
@@ -205,10 +256,13 @@ class Basecaller:
                 if self.beam:
                     short.append((r, self._trans([self._run(own)]).contiguous(), None, geo))
                     continue
-                path, err = self._decode([self._run(own)])
+                out = self._run(own)
+                path, err = self._decode([out])
                 short.append((r, path, err, geo))
+                if want_mods:
+                    short_w[r] = self._mod_weights([out])
             if self.beam:
-                return self._call_beam(outs, short, counts, lens, starts, ends, read_chunk_off, scale, head)
+                return self._call_beam(outs, short, counts, lens, starts, ends, read_chunk_off, scale, head), None
             # 5.-8. temperature, posterior, Viterbi, error probabilities on all the batch's chunks at once
             path = err = None
             if total:
@@ -224,8 +278,13 @@ class Basecaller:
             out_off_host = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
             cap = max(int(out_off_host[-1]), 1)
             out_off = torch.from_numpy(out_off_host).to(dev)
-            body = torch.empty(2 * _align(cap), dtype=torch.uint8, device=dev)
+            nmod = sum(self.can_nmods) if want_mods else 0
+            body = torch.empty(2 * _align(cap) + 4 * cap * nmod, dtype=torch.uint8, device=dev)
             seq, qual = body[:cap], body[_align(cap):_align(cap) + cap]
+            if want_mods:       # behind seq | qual: read r's rows from row out_off[r], as its characters
+                mods = body[2 * _align(cap):].view(torch.float32)
+                nbase, can_nmods = len(self.alphabet), (ctypes.c_int * len(self.alphabet))(*self.can_nmods)
+                weights = self._mod_weights(outs) if total else None
             qs, qo = self.qscore_scale, self.qscore_offset
             # 9. the tail (reads without a chunk in `path` get seqlen 0 here; the short ones are written next)
             if total:
@@ -240,6 +299,18 @@ class Basecaller:
                     _lib.ptr(one), _lib._vp(scale.data_ptr() + 4 * r), 1, self.stride, len(self.alphabet),
                     self.alphabet, qs, qo, _lib._vp(out_off.data_ptr() + 8 * r), _lib.ptr(seq), _lib.ptr(qual),
                     _lib._vp(seqlen.data_ptr() + 4 * r), _lib.ptr(status), stream), "tk_basecall_call_dev")
+            # 9b. the modified-base scores at the same moves: the same walk, the same offsets, the same seqlen
+            if want_mods and total:
+                _lib.check(L.tk_basecall_mod_weights_dev(
+                    _lib.ptr(path), _lib.ptr(weights), path.shape[0] - 1, total, _lib.ptr(starts), _lib.ptr(ends),
+                    _lib.ptr(read_chunk_off), _lib.ptr(scale), nread, self.stride, nbase, can_nmods, _lib.ptr(out_off),
+                    _lib.ptr(mods), _lib.ptr(seqlen), _lib.ptr(status), stream), "tk_basecall_mod_weights_dev")
+            for r, spath, _, geo in short if want_mods else ():
+                _lib.check(L.tk_basecall_mod_weights_dev(
+                    _lib.ptr(spath), _lib.ptr(short_w[r]), spath.shape[0] - 1, 1, _lib.ptr(geo[0]), _lib.ptr(geo[1]),
+                    _lib.ptr(one), _lib._vp(scale.data_ptr() + 4 * r), 1, self.stride, nbase, can_nmods,
+                    _lib._vp(out_off.data_ptr() + 8 * r), _lib.ptr(mods), _lib._vp(seqlen.data_ptr() + 4 * r),
+                    _lib.ptr(status), stream), "tk_basecall_mod_weights_dev")
             # 10. ONE download
             got = torch.cat([head, body]).cpu().numpy()
         nhead = head.numel()
@@ -253,7 +324,10 @@ class Basecaller:
             lo, hi = int(out_off_host[r]), int(out_off_host[r]) + int(called[r])
             q = qual_h[lo:hi].tobytes().decode("ascii") if self.fastq else None
             results.append((seq_h[lo:hi].tobytes().decode("ascii"), q, int(lens[r])))
-        return results
+        if not want_mods:
+            return results, None
+        mods_h = got[nhead + 2 * _align(cap):].view(np.float32).reshape(cap, nmod)
+        return results, [mods_h[int(out_off_host[r]):int(out_off_host[r]) + int(called[r])].copy() for r in range(nread)]
 
     def _call_beam(self, outs, short, counts, lens, starts, ends, read_chunk_off, scale, head):
         """The rest of a call with a beam, inside `call`'s device context (bin/basecall.py:216-221 for every read):

@@ -1,7 +1,8 @@
 // basecall_kernels.hip -- the basecaller's device-side glue (gfx950) and its extern "C" boundary
 // (include/taiyaki_amd_basecall.h): per-read median / MAD by radix selection, normalise + chunk, and the tail
 // (stitch the Viterbi paths of overlapping chunks, collapse them into bases, quality characters); for the beam search,
-// the stitched transition scores of every read, packed row after row (the search itself: basecall_beam.hip).
+// the stitched transition scores of every read, packed row after row (the search itself: basecall_beam.hip); the C entry
+// of the modified-base weights (the kernel: basecall_mods.hip).
 //
 // Compiled with -ffp-contract=off: every float operation on a signal or an error probability is ONE IEEE float32
 // operation, which is what makes the normalised chunks bit-equal to numpy's.
@@ -11,12 +12,10 @@
 #include <string.h>
 
 #include "../../include/taiyaki_amd_basecall.h"
+#include "basecall_walk.h"
+#include "dispatch.h"
 
 namespace tk {
-
-constexpr int BC_WAVE = 64;
-constexpr int BC_THREADS = 256;
-constexpr int BC_WAVES = BC_THREADS / BC_WAVE;
 
 // ------------------------------------------------------------------------------------------------------------------
 // (a) median and MAD: radix select
@@ -226,27 +225,7 @@ __global__ __launch_bounds__(BC_THREADS) void chunk_gather_kernel(const float *_
 // ------------------------------------------------------------------------------------------------------------------
 // (c) the tail
 // ------------------------------------------------------------------------------------------------------------------
-// basecall_helpers.py:64-94, path_stitching=False: the rows [lo, hi) that stitching keeps of chunk `c`, the i-th of its
-// read's `nch` chunks of `nrow` rows -- the reference's integer floor divisions for the first, middle and last chunk;
-// a read of one chunk keeps all its rows.  (hi < lo where the cuts cross: no rows.)
-__device__ __forceinline__ void chunk_cut(const int64_t *__restrict__ starts, const int64_t *__restrict__ ends,
-                                          int64_t c, int64_t i, int64_t nch, int64_t stride, int64_t nrow,
-                                          int64_t *lo_out, int64_t *hi_out) {
-    int64_t lo = 0, hi = nrow;
-    if (nch > 1) {
-        const int64_t s = starts[c], e = ends[c];
-        if (i == 0) {
-            lo = s / stride;
-            hi = (e + starts[c + 1]) / (2 * stride);
-        } else {
-            lo = (ends[c - 1] - s) / (2 * stride);
-            hi = i == nch - 1 ? (e - s) / stride : (e + starts[c + 1] - 2 * s) / (2 * stride);
-        }
-    }
-    *lo_out = lo < 0 ? 0 : lo;
-    *hi_out = hi > nrow ? nrow : hi;
-}
-
+// (the stitching cuts, `chunk_cut`, and the walk over a read's stitched rows, `walk_moves`: basecall_walk.h)
 struct Alphabet {
     uint8_t ch[16];
 };
@@ -271,58 +250,20 @@ __global__ __launch_bounds__(BC_THREADS) void call_kernel(const int64_t *__restr
                                                           uint8_t *__restrict__ seq, uint8_t *__restrict__ qual,
                                                           int32_t *__restrict__ seqlen,
                                                           uint32_t *__restrict__ status) {
-    __shared__ uint32_t wave_moves[BC_WAVES];
-    __shared__ int64_t last_state;          // state of the last stitched row so far
-    const int r = blockIdx.x, tid = threadIdx.x, wave = tid / BC_WAVE, lane = tid & (BC_WAVE - 1);
-    int64_t cbeg = read_chunk_off[r], cend = read_chunk_off[r + 1];
-    cbeg = cbeg < 0 ? 0 : cbeg;
-    cend = cend > nchunks ? nchunks : cend;
-    const bool refused = read_scale && read_scale[r] != read_scale[r];
+    __shared__ WalkShared ws;
+    const int r = blockIdx.x;
     const int64_t obeg = out_off[r], room = out_off[r + 1] - obeg;
-    const int64_t nch = refused ? 0 : cend - cbeg;
-    int64_t count = 0;          // moves so far (the same in every thread)
-    bool any_row = false;       // a stitched row exists already (uniform)
+    const WalkArgs walk = {path, nrow, nchunks, starts, ends, read_chunk_off, read_scale, stride};
     bool overflow = false;
-    for (int64_t i = 0; i < nch; ++i) {
-        const int64_t c = cbeg + i;
-        int64_t lo, hi;
-        chunk_cut(starts, ends, c, i, nch, stride, nrow, &lo, &hi);
-        for (int64_t base = lo; base < hi; base += BC_THREADS) {
-            const int64_t row = base + tid;
-            const bool live = row < hi;
-            int64_t st = 0, prev = 0;
-            bool move = false;
-            if (live) {
-                st = path[row * nchunks + c];
-                const bool has_prev = row > lo || any_row;
-                prev = row > lo ? path[(row - 1) * nchunks + c] : last_state;
-                move = has_prev && st != prev;
-            }
-            const uint64_t mask = __ballot(move);
-            if (lane == 0) wave_moves[wave] = (uint32_t)__popcll(mask);
-            __syncthreads();
-            int64_t at = count, total = 0;
-            for (int w = 0; w < BC_WAVES; ++w) {
-                if (w < wave) at += wave_moves[w];
-                total += wave_moves[w];
-            }
-            if (move) {
-                at += __popcll(mask & ((1ull << lane) - 1ull));
-                if (at < room) {
-                    seq[obeg + at] = alpha.ch[(uint32_t)((uint64_t)st % nbase)];
-                    if (errprobs) qual[obeg + at] = qchar(errprobs[row * nchunks + c], qscale, qoffset);
-                } else {
-                    overflow = true;
-                }
-            }
-            count += total;
-            if (live && row == hi - 1) last_state = st;
-            any_row = true;
-            __syncthreads();
-        }
-    }
+    const int64_t count = walk_moves(
+        walk, r, room, ws, &overflow,
+        [&](int64_t at, int64_t st, int64_t row, int64_t c, int64_t, int64_t) {
+            seq[obeg + at] = alpha.ch[(uint32_t)((uint64_t)st % nbase)];
+            if (errprobs) qual[obeg + at] = qchar(errprobs[row * nchunks + c], qscale, qoffset);
+        },
+        [](int64_t, int64_t) {});
     if (overflow && status) atomicOr(status, TK_STATUS_CHUNK_PLAN);
-    if (tid == 0) seqlen[r] = (int32_t)(count < room ? count : (room < 0 ? 0 : room));
+    if (threadIdx.x == 0) seqlen[r] = call_length(count, room);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -475,6 +416,38 @@ int tk_basecall_stitch_scores_dev(const float *trans, size_t nblk, size_t nchunk
                        (int64_t)stride, row_off, (int64_t)total_rows, reinterpret_cast<uint32_t *>(stitched), nrows,
                        status);
     return launched();
+}
+
+int tk_basecall_mod_weights_dev(const int64_t *path, const float *mod_weights, size_t nblk, size_t nchunks,
+                                const int64_t *chunk_starts, const int64_t *chunk_ends, const int64_t *read_chunk_off,
+                                const float *read_scale, size_t nread, size_t stride, size_t nbase,
+                                const int *can_nmods, const int64_t *out_off, float *mods, int32_t *seqlen,
+                                uint32_t *status, void *stream) {
+    if (!path || !chunk_starts || !chunk_ends || !read_chunk_off || !can_nmods || !out_off || !mods || !seqlen ||
+        stride == 0 || nbase == 0 || nchunks == 0)
+        return TK_ERR_BAD_ARG;
+    if (nblk > 0 && !mod_weights) return TK_ERR_BAD_ARG;    // (no block, no weight row: nothing is read from it)
+    if (nbase > sizeof(tk::Alphabet)) return TK_ERR_UNSUPPORTED;
+    tk::ModColumns cols;
+    memset(&cols, 0, sizeof(cols));
+    size_t nmod = 0, off = 0;       // off: where base b's {unmodified, its modifications} start in a weight row
+    for (size_t b = 0; b < nbase; ++b) {
+        if (can_nmods[b] < 0) return TK_ERR_BAD_ARG;
+        if ((size_t)can_nmods[b] > TK_BASECALL_MAX_NMOD - nmod) return TK_ERR_UNSUPPORTED;
+        for (int m = 0; m < can_nmods[b]; ++m, ++nmod) {
+            cols.base[nmod] = (uint8_t)b;
+            cols.src[nmod] = (uint8_t)(off + 1 + m);
+        }
+        off += 1 + can_nmods[b];
+    }
+    if (nmod == 0) return TK_ERR_BAD_ARG;
+    if (nread == 0) return TK_OK;
+    if (nread > (size_t)INT32_MAX || nblk >= (size_t)INT32_MAX || nchunks > (size_t)INT32_MAX ||
+        stride > (size_t)INT32_MAX)
+        return TK_ERR_UNSUPPORTED;
+    return tk::mod_weights_dispatch(path, mod_weights, nblk, nchunks, nbase + nmod, chunk_starts, chunk_ends,
+                                    read_chunk_off, read_scale, nread, stride, nbase, nmod, cols, out_off, mods, seqlen,
+                                    status, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/taiyaki_amd_basecall.h"
 #include "../../include/taiyaki_amd_flipflop.h"
 
 namespace tk {
@@ -103,6 +104,17 @@ size_t lstm_wgrad_workspace_bytes(size_t T, size_t N, size_t H, size_t I, int cu
 int lstm_wgrad_dispatch(const float *dgates, const float *x, const float *y, size_t T, size_t N, size_t H, size_t I,
                         int reverse, int cu_count, float *dw_ih, float *dw_hh, float *db, void *ws, size_t wsb,
                         hipStream_t stream);
+
+// basecall_mods.hip (libtaiyaki_amd_basecall.so; basecall_kernels.hip defines the C entry and fills the column map)
+struct ModColumns {
+    uint8_t base[TK_BASECALL_MAX_NMOD];     // the canonical base that output column j belongs to
+    uint8_t src[TK_BASECALL_MAX_NMOD];      // ... and its column in a weight row: off_b + 1 + m
+};
+int mod_weights_dispatch(const int64_t *path, const float *mod_weights, size_t nblk, size_t nchunks, size_t ncat,
+                         const int64_t *chunk_starts, const int64_t *chunk_ends, const int64_t *read_chunk_off,
+                         const float *read_scale, size_t nread, size_t stride, size_t nbase, size_t nmod,
+                         const ModColumns &cols, const int64_t *out_off, float *mods, int32_t *seqlen,
+                         uint32_t *status, hipStream_t stream);
 
 #ifdef TK_LAB
 // what the lab hooks below set (crf_band.hip, lstm_kernels.hip, gru_kernels.hip)

@@ -547,3 +547,9 @@ class GlobalNormFlipFlopCatMod(nn.Module):
         mods = [torch.log_softmax(cat.index_select(2, getattr(self, "can_index_%d" % k)), dim=2)
                 for k in range(self.ncan_base)]
         return torch.cat([trans] + mods, dim=2)
+
+
+def is_cat_mod_model(net):
+    """layers.py:1643-1656: is the final layer of the `Serial` network a categorical modified-base layer?"""
+    assert isinstance(net, Serial)
+    return isinstance(net[-1], GlobalNormFlipFlopCatMod)

@@ -20,8 +20,19 @@ launch and its downloads per read, `path_to_str`).  Both split the network's inv
 their calls are equal (compared first; a mismatch ends the run).  The two sides alternate --beam-steps times after one
 warm-up each.  Median, min and max per side: the spread is that of the alternated runs themselves.
 
+--mods times, instead of all the above, modified-base calling on a seeded size-256 mLstm_cat_mod_flipflop (excited so
+that it calls bases) at 1, 8 and 64 of those reads, three sides alternating --mods-steps times after one warm-up each,
+each ending in its downloads:
+  call_mods  `Basecaller(mod_output=True).call_mods`: calls and modified-base scores, one download
+  call       `Basecaller.call` on the same model: the calls alone
+  chain      what the operators allowed before: per read chunk_read, the network, posterior, the Viterbi, a download
+             of paths and categorical columns, then `stitch_chunks`, `path_to_str` and the numpy
+             extract_mod_weights on the host
+All at pack=False, so the three sides give equal calls and call_mods and chain equal scores (compared first, bit for
+bit; a mismatch ends the run).  Prints one JSON line.
+
     python tools/basecallbench.py [--chunks 128] [--blocks 1000] [--reads-per-batch 8] [--steps 20] [--warmup 3]
-                                  [--beam 5] [--beam-steps 5]
+                                  [--beam 5] [--beam-steps 5] [--mods] [--mods-steps 5]
 """
 import argparse
 import json
@@ -94,6 +105,89 @@ def beam_rows(net, sigs, width, steps, dev):
     return rows
 
 
+def host_extract_mod_weights(mod_weights, path, can_nmods):
+    """flipflopfings.py:100-143 in numpy, without its NaN row 0: what a user ran on the host, per read."""
+    move = np.flatnonzero(path[1:] != path[:-1]) + 1
+    base = path[move] % len(can_nmods)
+    out = np.full((len(move), int(sum(can_nmods))), np.nan, dtype=np.float32)
+    col = off = 0
+    for b, n in enumerate(can_nmods):
+        for m in range(n):
+            out[base == b, col] = mod_weights[move[base == b] - 1, off + 1 + m]
+            col += 1
+        off += 1 + n
+    return out
+
+
+def chain_mods(sigs, net, stride, can_nmods, dev, chunk_blocks=1000, overlap_blocks=100, concurrent=128):
+    """bin/basecall.py:151-242 read by read on the operators this package had before call_mods, plus the host's
+    extract_mod_weights on the downloaded paths and categorical columns."""
+    calls, mods = [], []
+    for x in sigs:
+        med, mad = clipping.med_mad(x)
+        chunks, starts, ends = basecall_helpers.chunk_read(((x - med) / mad).astype("f4"), chunk_blocks * stride,
+                                                           overlap_blocks * stride)
+        with torch.no_grad():
+            chunks = torch.tensor(chunks, device=dev)
+            out = torch.cat([net(c.contiguous()) for c in torch.split(chunks, concurrent, 1)], 1)
+            trans = (decode.flipflop_make_trans(out[:, :, :40].contiguous()) + 1e-8).log()
+            path = decode.flipflop_viterbi_path(trans)
+            err = qscores.errprobs_from_trans(trans, path)
+            p, e, w = path.cpu(), err.cpu(), out[:, :, 40:].cpu()              # the downloads (synchronise)
+        sp = basecall_helpers.stitch_chunks(p, starts, ends, stride).numpy()
+        se = basecall_helpers.stitch_chunks(e, starts, ends, stride)
+        sw = basecall_helpers.stitch_chunks(w, starts, ends, stride).numpy()
+        calls.append((flipflopfings.path_to_str(sp, include_first_source=False),
+                      qscores.path_errprobs_to_qstring(se, sp, 1.0, 0.0), len(x)))
+        mods.append(host_extract_mod_weights(sw, sp, can_nmods))
+    return calls, mods
+
+
+def same_bits(a, b):
+    nan = np.isnan(b)
+    return (a.shape == b.shape and np.array_equal(np.isnan(a), nan) and
+            np.array_equal(a.view(np.uint32)[~nan], b.view(np.uint32)[~nan]))
+
+
+def mods_rows(size, steps, dev):
+    can_nmods = (1, 1, 0, 0)
+    rs = np.random.RandomState(9)
+    sigs = [(90 + 12 * rs.standard_normal(int(n))).astype(np.float32) for n in rs.randint(20000, 100001, size=64)]
+    torch.manual_seed(17)
+    net = synth.excite_network(models.mLstm_cat_mod_flipflop(size=size, can_nmods=can_nmods)).to(dev).eval()
+    caller = basecall.Basecaller(net, fastq=True, pack=False, mod_output=True)
+    plain = basecall.Basecaller(net, fastq=True, pack=False)
+    rows = {}
+    for nread in (1, 8, 64):
+        batch = sigs[:nread]
+        sides = dict(call_mods=lambda: caller.call_mods(batch), call=lambda: (plain.call(batch), None),
+                     chain=lambda: chain_mods(batch, net, caller.stride, can_nmods, dev))
+        first = {k: fn() for k, fn in sides.items()}                           # (the warm-up at the timed shapes)
+        seqs = {k: [r[0] for r in v[0]] for k, v in first.items()}
+        if not seqs["call_mods"] == seqs["call"] == seqs["chain"]:
+            raise SystemExit("basecallbench --mods: the three sides disagree on a call; nothing timed")
+        if not all(same_bits(a, b) for a, b in zip(first["call_mods"][1], first["chain"][1])):
+            raise SystemExit("basecallbench --mods: call_mods and the host chain disagree on a score; nothing timed")
+        times = {k: [] for k in sides}
+        for _ in range(steps):
+            for k, fn in sides.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()                                                            # ends in its downloads
+                times[k].append(time.perf_counter() - t0)
+        bases = sum(len(s) for s in seqs["call"])
+        row = dict(reads=nread, samples=int(sum(map(len, batch))), bases=bases,
+                   mods_bytes_in_download=4 * bases * int(sum(can_nmods)))
+        for k, t in times.items():
+            row[k] = dict(median_ms=round(1e3 * float(np.median(t)), 2), min_ms=round(1e3 * float(np.min(t)), 2),
+                          max_ms=round(1e3 * float(np.max(t)), 2), reads_per_s=round(nread / float(np.median(t)), 2))
+        row["call_mods_minus_call_ms"] = round(1e3 * float(np.median(times["call_mods"]) - np.median(times["call"])), 2)
+        row["chain_over_call_mods"] = round(float(np.median(times["chain"]) / np.median(times["call_mods"])), 2)
+        rows[str(nread)] = row
+    return dict(model="mLstm_cat_mod_flipflop", size=size, stride=caller.stride, can_nmods=list(can_nmods), steps=steps,
+                pack=False, rows=rows)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chunks", type=int, default=128)
@@ -106,10 +200,16 @@ def main():
     ap.add_argument("--beam", type=int, default=0, metavar="WIDTH",
                     help="also time a whole call with beam=(WIDTH, guided) at 1, 8, 64 reads beside the per-read chain")
     ap.add_argument("--beam-steps", type=int, default=5)
+    ap.add_argument("--mods", action="store_true",
+                    help="time call_mods, call and the host chain on a cat-mod model at 1, 8, 64 reads (nothing else)")
+    ap.add_argument("--mods-steps", type=int, default=5)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("basecallbench needs a GPU (the basecaller has no CPU fallback)")
     dev = torch.device("cuda:0")
+    if a.mods:
+        print(json.dumps(dict(mods=mods_rows(a.size, a.mods_steps, dev))))
+        return
     L = _lib.basecall_lib()
     T, N = a.blocks, a.chunks
     chunk, overlap = T * STRIDE, OVERLAP_BLOCKS * STRIDE
