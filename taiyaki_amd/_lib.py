@@ -30,6 +30,9 @@ WGRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_lstm
 WGRAD_LIBNAME = "libtaiyaki_amd_lstm_wgrad.so"      # csrc/lstm_wgrad.hip: the LSTM's parameter gradients, header and library of its own
 WGRAD_LAB_LIBNAME = "libtaiyaki_amd_lstm_wgrad_lab.so"      # ... and its lab build (tk_lab_lstm_wgrad_*)
 
+VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
+VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
+
 _vp = ctypes.c_void_p
 _SCALARS = {"size_t": ctypes.c_size_t, "int": ctypes.c_int, "float": ctypes.c_float}
 
@@ -103,6 +106,16 @@ def _read_wgrad_header():
 
 # the fifth: include/taiyaki_amd_lstm_wgrad.h (libtaiyaki_amd_lstm_wgrad.so), and the hooks its lab build adds
 WGRAD_SIGNATURES, WGRAD_LAB_SIGNATURES = _read_wgrad_header()
+
+
+def _read_varlen_header():
+    raw = open(VARLEN_HEADER).read()
+    sigs = {n: (r, a) for n, (r, a, _) in parse_prototypes(_blank_comments(raw)).items()}
+    return sigs, {k: int(v, 0) for k, v in re.findall(r"(?m)^#define (TK_RNN_KIND_\w+) (\d+)", raw)}
+
+
+# the sixth: include/taiyaki_amd_rnn_varlen.h (libtaiyaki_amd_rnn_varlen.so), and its TK_RNN_KIND_* values
+VARLEN_SIGNATURES, VARLEN_DEFINES = _read_varlen_header()
 
 
 class SeqLabels(ctypes.Structure):
@@ -193,6 +206,12 @@ def wgrad_lib():
     if is_lab():
         return _load(os.path.join(CSRC, WGRAD_LAB_LIBNAME), dict(WGRAD_SIGNATURES, **WGRAD_LAB_SIGNATURES))
     return _load(os.path.join(CSRC, WGRAD_LIBNAME), WGRAD_SIGNATURES)
+
+
+def varlen_lib():
+    """The recurrences' forward with per-column lengths (include/taiyaki_amd_rnn_varlen.h).  No fallback: a missing
+    library raises."""
+    return _load(os.path.join(CSRC, VARLEN_LIBNAME), VARLEN_SIGNATURES)
 
 
 def check(rc, what):

@@ -19,6 +19,9 @@
 // inputs of step s + 1 are loaded right after step s's poll (G = 1: barrier), the bulk outputs of step s are held
 // in registers and stored right after step s + 1's.  Both drain under the matvec; the granule publish is the last
 // memory operation of a step.  Every sum runs in a fixed order: a launch is bit-reproducible.
+//
+// Two builds of this one source, as for lstm_kernels.hip: the flip-flop library takes the forward and the backward,
+// -DTK_RNN_VARLEN (libtaiyaki_amd_rnn_varlen.so) the forward alone in its VL form.
 #include "dispatch.h"
 #include "ff_common.h"
 #include "rnn_common.h"
@@ -40,11 +43,14 @@ constexpr int gru_threads() { return U == H ? 4 * U : 512; }
 // in VGPRs, so each h value read from LDS feeds 3 rows.  The KP partial sums are combined by xor shuffles: the first
 // log2(C) rounds halve the columns a lane keeps, the rest add the gates of its one column; lane kp < C then holds
 // the 3 hidden-side sums of column col(kp) and runs its cell update.
-template <int H, int U, int C>
+//
+// VL: column n has lengths[n] steps (NULL: T).  A step at t >= lengths[n] leaves h = 0, writes y = 0 and hands h = 0
+// on like any other step; gates and qout are not written (the pointers are not read).
+template <int H, int U, int C, bool VL = false>
 __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
     const float *__restrict__ gx, const float *__restrict__ whh, const float *__restrict__ bhh, int T, int N,
     int reverse, int ngroups, float *__restrict__ y, float *__restrict__ gates, float *__restrict__ qout, u64 *hbuf,
-    uint32_t *status) {
+    uint32_t *status, const int32_t *__restrict__ lengths) {
     constexpr int NT = gru_threads<H, U>();
     constexpr int G = H / U;
     constexpr int KP = NT / U;
@@ -80,6 +86,8 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
     const int n = n0 + col;
     const bool valid = cell_lane && n < N;
     float hprev = 0.f;
+    int len = 0;                                       // VL: the steps of this lane's column
+    if constexpr (VL) len = !valid ? 0 : lengths ? lengths[n] : T;
 
     for (int i = tid; i < H * C; i += NT) hs[0][i] = 0.f;
     if (tid == 0) give_up = 0;
@@ -116,12 +124,14 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
             if (valid) {
                 const size_t row = (size_t)(reverse ? t + 1 : t - 1) * N + n;
                 y[row * H + j0 + u] = held[0];
-                if (gates) {
-                    float *gp = gates + row * H3 + j0 + u;
+                if constexpr (!VL) {
+                    if (gates) {
+                        float *gp = gates + row * H3 + j0 + u;
 #pragma unroll
-                    for (int g = 0; g < 3; ++g) gp[(size_t)g * H] = held[1 + g];
+                        for (int g = 0; g < 3; ++g) gp[(size_t)g * H] = held[1 + g];
+                    }
+                    if (qout) qout[row * H + j0 + u] = held[4];
                 }
-                if (qout) qout[row * H + j0 + u] = held[4];
             }
         }
         float gn[3] = {0.f, 0.f, 0.f};
@@ -168,7 +178,10 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
             const float rg = sigmoidf(gq[0] + acc[0][0] + bh[0]), zg = sigmoidf(gq[1] + acc[1][0] + bh[1]);
             const float qv = acc[2][0] + bh[2];
             const float ng = tanhf(gq[2] + rg * qv);
-            const float h = (1.f - zg) * ng + zg * hprev;
+            float h = (1.f - zg) * ng + zg * hprev;
+            if constexpr (VL) {
+                if (t >= len) h = 0.f;
+            }
             hprev = h;
             if (s + 1 < T) {
                 if constexpr (G > 1)
@@ -189,15 +202,18 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
     if (valid && T > 0) {
         const size_t row = (size_t)(reverse ? 0 : T - 1) * N + n;
         y[row * H + j0 + u] = held[0];
-        if (gates) {
-            float *gp = gates + row * H3 + j0 + u;
+        if constexpr (!VL) {
+            if (gates) {
+                float *gp = gates + row * H3 + j0 + u;
 #pragma unroll
-            for (int g = 0; g < 3; ++g) gp[(size_t)g * H] = held[1 + g];
+                for (int g = 0; g < 3; ++g) gp[(size_t)g * H] = held[1 + g];
+            }
+            if (qout) qout[row * H + j0 + u] = held[4];
         }
-        if (qout) qout[row * H + j0 + u] = held[4];
     }
 }
 
+#ifndef TK_RNN_VARLEN
 // Backward.  From y, the saved activations r, z, n and q, and dy = dL/dy (T, N, H), writes dgates = dL/d(gx) =
 // [dr_pre, dz_pre, dn_pre] (T, N, 3H) and dq = dn_pre r (T, N, H), walking the recurrence from its last step:
 //   dh = dy + dh_rec;  dn_pre = dh (1 - z)(1 - n^2);  dz_pre = dh (h_prev - n) z (1 - z);  dr_pre = dn_pre q r (1 - r)
@@ -364,6 +380,8 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_bwd_kernel(
     }
 }
 
+#endif  // TK_RNN_VARLEN
+
 // A launch: U units and C columns per workgroup, groups of G = H / U workgroups; false where the kernels do not
 // run.  H <= 128 is one workgroup per group (any N); H = 256 hands h between the 4 members of a group, so its grid
 // must be co-resident: groups * 4 <= cu_count at one workgroup per CU.
@@ -409,18 +427,20 @@ size_t gru_ws_bytes(size_t H, const Plan &p, bool backward) {
         default: return TK_ERR_UNSUPPORTED;                                                                       \
     }
 
+template <bool VL>
 int launch_fwd(const Plan &p, size_t H, hipStream_t st, const float *gx, const float *whh, const float *bhh, int T,
-               int N, int rev, float *y, float *gates, float *q, u64 *ws, uint32_t *status) {
+               int N, int rev, float *y, float *gates, float *q, u64 *ws, uint32_t *status, const int32_t *lengths) {
 #define TK_GRU_FWD(HH, UU, CC)                                                                                    \
     case HH * 10 + CC:                                                                                            \
-        hipLaunchKernelGGL((gru_fwd_kernel<HH, UU, CC>), dim3(p.grid), dim3(gru_threads<HH, UU>()), 0, st, gx,    \
-                           whh, bhh, T, N, rev, p.groups, y, gates, q, ws, status);                               \
+        hipLaunchKernelGGL((gru_fwd_kernel<HH, UU, CC, VL>), dim3(p.grid), dim3(gru_threads<HH, UU>()), 0, st,    \
+                           gx, whh, bhh, T, N, rev, p.groups, y, gates, q, ws, status, lengths);                  \
         break;
     TK_GRU_SWITCH(TK_GRU_FWD)
 #undef TK_GRU_FWD
     return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
 
+#ifndef TK_RNN_VARLEN
 int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const float *y, const float *gates,
                const float *q, const float *dy, int T, int N, int rev, float *dg, float *dq, u64 *ws,
                uint32_t *status) {
@@ -433,10 +453,40 @@ int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const 
 #undef TK_GRU_BWD
     return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
+#endif  // TK_RNN_VARLEN
 #undef TK_GRU_SWITCH
 
 }  // namespace
 
+#ifdef TK_RNN_VARLEN
+// The forward-only launch with per-column lengths (include/taiyaki_amd_rnn_varlen.h): the plan, and so the grid and
+// the granule buffers, of gru_forward_dispatch at the same (N, H, cu_count).  Never 0 where the kernels run.
+size_t gru_varlen_workspace_bytes(size_t N, size_t H, int cu_count) {
+    Plan p;
+    if (!gru_plan(N, H, cu_count, &p)) return 0;
+    const size_t need = gru_ws_bytes(H, p, false);
+    return need ? need : 16;
+}
+
+int gru_forward_varlen_dispatch(const float *gx, const float *whh, const float *bhh, const int32_t *lengths, size_t T,
+                                size_t N, size_t H, int reverse, int cu_count, float *y, void *ws, size_t wsb,
+                                uint32_t *status, hipStream_t stream) {
+    if (!gx || !whh || !bhh || !y || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX ||
+        N > (size_t)INT32_MAX)
+        return TK_ERR_BAD_ARG;
+    Plan p;
+    if (!gru_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+    const size_t need = gru_ws_bytes(H, p, false);
+    if (wsb < (need ? need : 16)) return TK_ERR_WORKSPACE;
+    if (T == 0) return TK_OK;
+    if (need) {
+        int rc = zero_ws(ws, need, stream);
+        if (rc != TK_OK) return rc;
+    }
+    return launch_fwd<true>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, nullptr, nullptr,
+                            static_cast<u64 *>(ws), status, lengths);
+}
+#else
 // Never 0 where the kernels run (0 means "does not run here"): one granule pair at G = 1, which needs none.
 size_t gru_workspace_bytes(size_t N, size_t H, int cu_count) {
     Plan p;
@@ -460,8 +510,8 @@ int gru_forward_dispatch(const float *gx, const float *whh, const float *bhh, si
         int rc = zero_ws(ws, need, stream);
         if (rc != TK_OK) return rc;
     }
-    return launch_fwd(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, gates, q, static_cast<u64 *>(ws),
-                      status);
+    return launch_fwd<false>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, gates, q,
+                             static_cast<u64 *>(ws), status, nullptr);
 }
 
 int gru_backward_dispatch(const float *whh, const float *y, const float *gates, const float *q, const float *dy,
@@ -486,5 +536,6 @@ int gru_backward_dispatch(const float *whh, const float *y, const float *gates, 
 #ifdef TK_LAB
 void gru_lab_cols(int cols) { g_lab_cols = cols; }
 #endif
+#endif  // TK_RNN_VARLEN
 
 }  // namespace tk

@@ -17,6 +17,10 @@
 // inputs of step s + 1 (forward: gx; backward: dy, c_{t-1}, the gates) are loaded right after step s's poll, and
 // the bulk outputs of step s (forward: y, c, gates; backward: dG) are held in registers and stored right after
 // step s + 1's poll.  Both drain under the matvec; the granule publish is the last memory operation of a step.
+//
+// Two builds of this one source.  The flip-flop library takes the training pair: the forward that saves the gates
+// and c, and the backward.  -DTK_RNN_VARLEN (libtaiyaki_amd_rnn_varlen.so) takes the forward alone in its VL form:
+// per-column lengths, y the only output (DESIGN.md "Variable-length recurrences").
 #include "dispatch.h"
 #include "ff_common.h"
 #include "rnn_common.h"
@@ -35,14 +39,19 @@ constexpr int threads_for() { return U <= 32 ? 256 : 512; }
 // in VGPRs, so each h value read from LDS feeds 4 rows (KS C-wide LDS reads per lane per step).  The KP partial
 // sums are combined by xor shuffles: the first log2(C) rounds halve the columns a lane keeps, the rest add the 4
 // gates of its one column; lane kp < C then holds the 4 pre-activations of column col(kp) and runs its cell update.
-template <int H, int C, int U>
+//
+// VL: column n has lengths[n] steps (NULL: T).  A step at t >= lengths[n] leaves h = c = 0, writes y = 0 and
+// publishes h = 0 like any other step: every workgroup runs all T steps, so the hand-off is that of a full batch.
+// gates and cell are not written (the pointers are not read).
+template <int H, int C, int U, bool VL = false>
 __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const float *__restrict__ gx,
                                                                        const float *__restrict__ whh, int T, int N,
                                                                        int reverse, int ngroups,
                                                                        float *__restrict__ y,
                                                                        float *__restrict__ gates,
                                                                        float *__restrict__ cell, u64 *hbuf,
-                                                                       uint32_t *status) {
+                                                                       uint32_t *status,
+                                                                       const int32_t *__restrict__ lengths) {
     constexpr int NT = threads_for<U>();
     constexpr int G = H / U;
     constexpr int KP = NT / U;
@@ -73,6 +82,8 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
     const int n = n0 + col;
     const bool valid = cell_lane && n < N;
     float cst = 0.f;
+    int len = 0;                                       // VL: the steps of this lane's column
+    if constexpr (VL) len = !valid ? 0 : lengths ? lengths[n] : T;
 
     for (int i = tid; i < H * C; i += NT) hs[0][i] = 0.f;
     if (tid == 0) give_up = 0;
@@ -106,10 +117,12 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
                 const int tl = reverse ? t + 1 : t - 1;
                 const size_t o = ((size_t)tl * N + n) * H + j0 + u;
                 y[o] = held[0];
-                cell[o] = held[1];
-                float *gp = gates + ((size_t)tl * N + n) * H4 + j0 + u;
+                if constexpr (!VL) {
+                    cell[o] = held[1];
+                    float *gp = gates + ((size_t)tl * N + n) * H4 + j0 + u;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) gp[(size_t)g * H] = held[2 + g];
+                    for (int g = 0; g < 4; ++g) gp[(size_t)g * H] = held[2 + g];
+                }
             }
         }
         float gn[4] = {0.f, 0.f, 0.f, 0.f};
@@ -155,8 +168,14 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
         if (cell_lane) {
             const float ig = sigmoidf(acc[0][0] + gq[0]), fg = sigmoidf(acc[1][0] + gq[1]);
             const float gg = tanhf(acc[2][0] + gq[2]), og = sigmoidf(acc[3][0] + gq[3]);
-            cst = fg * cst + ig * gg;
-            const float h = og * tanhf(cst);
+            // (VL: the contraction the compiler gives the saving form, written out -- left to it, the mask's select
+            // moves the fma to the other product and a column's rows differ from the saving launch's in the last bit)
+            if constexpr (VL) cst = fmaf(ig, gg, fg * cst);
+            else cst = fg * cst + ig * gg;
+            float h = og * tanhf(cst);
+            if constexpr (VL) {
+                if (t >= len) cst = h = 0.f;
+            }
             if (s + 1 < T)
                 store_granule(hbuf + ((size_t)(s & 1) * ngroups + group) * (H * C) + col * H + j0 + u,
                               (unsigned)(s + 1), h);
@@ -174,13 +193,16 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
         const int tl = reverse ? 0 : T - 1;
         const size_t o = ((size_t)tl * N + n) * H + j0 + u;
         y[o] = held[0];
-        cell[o] = held[1];
-        float *gp = gates + ((size_t)tl * N + n) * H4 + j0 + u;
+        if constexpr (!VL) {
+            cell[o] = held[1];
+            float *gp = gates + ((size_t)tl * N + n) * H4 + j0 + u;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) gp[(size_t)g * H] = held[2 + g];
+            for (int g = 0; g < 4; ++g) gp[(size_t)g * H] = held[2 + g];
+        }
     }
 }
 
+#ifndef TK_RNN_VARLEN
 // Backward.  From the saved gate activations and c, and dy = dL/dy (T, N, H), writes dgates = dL/d(pre-activation)
 // (T, N, 4H) walking the recurrence from its last step.  pbuf: [2][ngroups][G producers][C][H] granules.
 template <int H, int C, int U>
@@ -345,6 +367,8 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_bwd_kernel(const flo
     }
 }
 
+#endif  // TK_RNN_VARLEN
+
 int g_lab_cols = 0;     // lab build: force the admitted batch columns, 8 or 16 (0 = the rule below)
 int g_lab_units = 0;    // lab build: force the hidden units per workgroup, 16, 32 or 64 (0 = the rule in lstm_plan)
 
@@ -403,18 +427,20 @@ bool lstm_plan(size_t N, size_t H, int cu_count, Plan *p) {
         default: return TK_ERR_UNSUPPORTED;                                                                       \
     }
 
+template <bool VL>
 int launch_fwd(const Plan &p, size_t H, hipStream_t st, const float *gx, const float *whh, int T, int N, int rev,
-               float *y, float *gates, float *cell, u64 *ws, uint32_t *status) {
+               float *y, float *gates, float *cell, u64 *ws, uint32_t *status, const int32_t *lengths) {
 #define TK_LSTM_FWD(HH, UU, CC)                                                                                  \
     case HH * 100000 + UU * 1000 + CC:                                                                           \
-        hipLaunchKernelGGL((lstm_fwd_kernel<HH, CC, UU>), dim3(p.grid), dim3(threads_for<UU>()), 0, st, gx, whh, \
-                           T, N, rev, p.groups, y, gates, cell, ws, status);                                     \
+        hipLaunchKernelGGL((lstm_fwd_kernel<HH, CC, UU, VL>), dim3(p.grid), dim3(threads_for<UU>()), 0, st, gx,  \
+                           whh, T, N, rev, p.groups, y, gates, cell, ws, status, lengths);                       \
         break;
     TK_LSTM_SWITCH(TK_LSTM_FWD)
 #undef TK_LSTM_FWD
     return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
 
+#ifndef TK_RNN_VARLEN
 int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const float *gates, const float *cell,
                const float *dy, int T, int N, int rev, float *dg, u64 *ws, uint32_t *status) {
 #define TK_LSTM_BWD(HH, UU, CC)                                                                                   \
@@ -426,10 +452,36 @@ int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const 
 #undef TK_LSTM_BWD
     return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
+#endif  // TK_RNN_VARLEN
 #undef TK_LSTM_SWITCH
 
 }  // namespace
 
+#ifdef TK_RNN_VARLEN
+// The forward-only launch with per-column lengths (include/taiyaki_amd_rnn_varlen.h): the plan, and so the grid and
+// the granule buffers, of lstm_forward_dispatch at the same (N, H, cu_count).
+size_t lstm_varlen_workspace_bytes(size_t N, size_t H, int cu_count) {
+    Plan p;
+    if (!lstm_plan(N, H, cu_count, &p)) return 0;
+    return ws_bytes(H, p.C, p.groups, p.U, false);
+}
+
+int lstm_forward_varlen_dispatch(const float *gx, const float *whh, const int32_t *lengths, size_t T, size_t N,
+                                 size_t H, int reverse, int cu_count, float *y, void *ws, size_t wsb,
+                                 uint32_t *status, hipStream_t stream) {
+    if (!gx || !whh || !y || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX || N > (size_t)INT32_MAX)
+        return TK_ERR_BAD_ARG;
+    Plan p;
+    if (!lstm_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+    const size_t need = ws_bytes(H, p.C, p.groups, p.U, false);
+    if (wsb < need) return TK_ERR_WORKSPACE;
+    if (T == 0) return TK_OK;
+    int rc = zero_ws(ws, need, stream);
+    if (rc != TK_OK) return rc;
+    return launch_fwd<true>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, nullptr, nullptr,
+                            static_cast<u64 *>(ws), status, lengths);
+}
+#else
 size_t lstm_workspace_bytes(size_t N, size_t H, int cu_count) {
     int C = 0, groups = 0;
     if (!lstm_geometry(N, H, cu_count, &C, &groups)) return 0;
@@ -449,8 +501,8 @@ int lstm_forward_dispatch(const float *gx, const float *whh, size_t T, size_t N,
     if (T == 0) return TK_OK;
     int rc = zero_ws(ws, need, stream);
     if (rc != TK_OK) return rc;
-    return launch_fwd(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, gates, cell, static_cast<u64 *>(ws),
-                      status);
+    return launch_fwd<false>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, gates, cell, static_cast<u64 *>(ws),
+                             status, nullptr);
 }
 
 int lstm_backward_dispatch(const float *whh, const float *gates, const float *cell, const float *dy, size_t T,
@@ -486,5 +538,6 @@ bool lstm_lab_geometry(size_t N, size_t H, int cu_count, size_t *out) {
     return true;
 }
 #endif
+#endif  // TK_RNN_VARLEN
 
 }  // namespace tk

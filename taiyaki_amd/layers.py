@@ -12,6 +12,9 @@ that feeds them.
   (`LstmRecurrence`) and csrc/gru_kernels.hip (`GruRecurrence`), and a narrow
   ``Convolution`` with swish runs as the fused HIP kernels of csrc/conv_kernels.hip
   (`SmallConvolution`).
+* ``forward_varlen`` runs a ``Serial`` on a batch whose columns have different lengths: every column's rows are what
+  the column gives run alone (``Lstm`` / ``GruMod`` ``forward(x, reverse, lengths)`` on the forward-only launches of
+  include/taiyaki_amd_rnn_varlen.h).
 """
 import numpy as np
 import torch
@@ -246,12 +249,16 @@ USE_HIP_LSTM_WGRAD = True
 def hip_lstm_workspace_bytes(rnn, x):
     """Workspace of the HIP recurrence for this layer and input, 0 where it does not run (CPU tensors, other
     dtypes, nn.LSTM options the kernels do not implement, sizes the launch geometry does not cover)."""
-    if not (USE_HIP_LSTM and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
-            and rnn.weight_hh_l0.is_cuda and rnn.weight_hh_l0.dtype == torch.float32):
-        return 0
-    if rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or rnn.batch_first or rnn.proj_size:
+    if not _hip_lstm_takes(rnn, x):
         return 0
     return _lib.lib().tk_lstm_workspace_bytes(x.shape[1], rnn.hidden_size, _cu_count(x.device))
+
+
+def _hip_lstm_takes(rnn, x):
+    if not (USE_HIP_LSTM and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
+            and rnn.weight_hh_l0.is_cuda and rnn.weight_hh_l0.dtype == torch.float32):
+        return False
+    return not (rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or rnn.batch_first or rnn.proj_size)
 
 
 class LstmRecurrence(torch.autograd.Function):
@@ -334,7 +341,9 @@ class Lstm(_Rnn):
     def __init__(self, insize, size):
         super().__init__(nn.LSTM(insize, size))
 
-    def forward(self, x, reverse=False):
+    def forward(self, x, reverse=False, lengths=None):
+        if lengths is not None:
+            return _rnn_forward_varlen(self, x, reverse, lengths)
         rnn = self.rnn
         wsb = hip_lstm_workspace_bytes(rnn, x)
         if wsb:
@@ -352,12 +361,16 @@ USE_HIP_GRU = True
 def hip_gru_workspace_bytes(rnn, x):
     """Workspace of the HIP recurrence for this layer and input, 0 where it does not run (CPU tensors, other
     dtypes, nn.GRU options the kernels do not implement, sizes the launch geometry does not cover)."""
-    if not (USE_HIP_GRU and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
-            and rnn.weight_hh_l0.is_cuda and rnn.weight_hh_l0.dtype == torch.float32):
-        return 0
-    if rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or rnn.batch_first:
+    if not _hip_gru_takes(rnn, x):
         return 0
     return _lib.lib().tk_gru_workspace_bytes(x.shape[1], rnn.hidden_size, _cu_count(x.device))
+
+
+def _hip_gru_takes(rnn, x):
+    if not (USE_HIP_GRU and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
+            and rnn.weight_hh_l0.is_cuda and rnn.weight_hh_l0.dtype == torch.float32):
+        return False
+    return not (rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or rnn.batch_first)
 
 
 def _time_sum_tn(a, b, rows=2048):
@@ -459,7 +472,9 @@ class GruMod(_Rnn):
     def __init__(self, insize, size):
         super().__init__(nn.GRU(insize, size))
 
-    def forward(self, x, reverse=False):
+    def forward(self, x, reverse=False, lengths=None):
+        if lengths is not None:
+            return _rnn_forward_varlen(self, x, reverse, lengths)
         rnn = self.rnn
         wsb = hip_gru_workspace_bytes(rnn, x)
         if wsb:
@@ -471,6 +486,64 @@ class GruMod(_Rnn):
         return rnn(x)[0]
 
 
+def hip_rnn_varlen_workspace_bytes(rnn, x):
+    """Workspace of the forward-only launch with per-column lengths (include/taiyaki_amd_rnn_varlen.h) for this nn.LSTM
+    or nn.GRU and input, 0 where it does not run: what `hip_lstm_workspace_bytes` / `hip_gru_workspace_bytes` rule
+    out, under the same switches."""
+    lstm = isinstance(rnn, nn.LSTM)
+    if not (_hip_lstm_takes(rnn, x) if lstm else _hip_gru_takes(rnn, x)):
+        return 0
+    kind = _lib.VARLEN_DEFINES["TK_RNN_KIND_LSTM" if lstm else "TK_RNN_KIND_GRU"]
+    return _lib.varlen_lib().tk_rnn_varlen_workspace_bytes(kind, x.shape[1], rnn.hidden_size, _cu_count(x.device))
+
+
+def _needs_grad(x, module):
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
+
+
+def _rnn_forward_varlen(layer, x, reverse, lengths):
+    """`Lstm` / `GruMod` forward on a batch whose column n has lengths[n] steps: rows [0, lengths[n]) of column n are
+    what `layer(x[:lengths[n], n:n + 1], reverse)` gives, the rows beyond are 0.  One launch of
+    tk_lstm_forward_varlen_dev / tk_gru_forward_varlen_dev where `hip_rnn_varlen_workspace_bytes` admits the tensors
+    (nothing is saved: inference only); every column alone at its own length otherwise."""
+    if _needs_grad(x, layer):
+        raise RuntimeError("%s.forward with lengths is inference only: call it under torch.no_grad() (training "
+                           "through variable-length batches is not implemented)" % type(layer).__name__)
+    rnn = layer.rnn
+    T, N, _ = x.shape
+    H = rnn.hidden_size
+    wsb = hip_rnn_varlen_workspace_bytes(rnn, x) if T and N else 0
+    if not wsb:
+        host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
+        assert len(host) == N and (N == 0 or (host.min() >= 0 and host.max() <= T)), "lengths: one per column, 0..T"
+        y = x.new_zeros(T, N, H)
+        for n, ln in enumerate(host):
+            if ln:
+                y[:ln, n:n + 1] = layer(x[:ln, n:n + 1], reverse=reverse)
+        return y
+    dev = x.device
+    lstm = isinstance(rnn, nn.LSTM)
+    with torch.no_grad(), torch.cuda.device(dev):
+        lens = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).reshape(-1).clamp(0, T).contiguous()
+        assert lens.numel() == N, "lengths: one per column"
+        x = x.contiguous()
+        w_hh, b_hh = rnn.weight_hh_l0.contiguous(), rnn.bias_hh_l0.contiguous()
+        gx = torch.addmm(rnn.bias_ih_l0 + b_hh if lstm else rnn.bias_ih_l0, x.view(T * N, -1), rnn.weight_ih_l0.t())
+        y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
+        ws = _lib.workspace(wsb, dev, "rnn_varlen")
+        status = _lib.status_word(dev)
+        tail = (T, N, H, int(bool(reverse)), _cu_count(dev), _lib.ptr(y), _lib.ptr(ws), wsb, _lib.ptr(status),
+                _lib.stream_ptr())
+        if lstm:
+            rc = _lib.varlen_lib().tk_lstm_forward_varlen_dev(_lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(lens), *tail)
+        else:
+            rc = _lib.varlen_lib().tk_gru_forward_varlen_dev(_lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(b_hh),
+                                                             _lib.ptr(lens), *tail)
+        _lib.check(rc, "tk_lstm_forward_varlen_dev" if lstm else "tk_gru_forward_varlen_dev")
+        _lib.finish(status)
+    return y
+
+
 class Reverse(nn.Module):
     """layers.py:117-153"""
 
@@ -478,7 +551,11 @@ class Reverse(nn.Module):
         super().__init__()
         self.layer = layer
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
+        if lengths is not None:
+            if not isinstance(self.layer, (Lstm, GruMod)):
+                raise TypeError("Reverse(%s) takes no lengths" % type(self.layer).__name__)
+            return self.layer(x, reverse=True, lengths=lengths)
         if isinstance(self.layer, (Lstm, GruMod)):
             return self.layer(x, reverse=True)      # (the HIP recurrences run backwards in time themselves)
         return torch.flip(self.layer(torch.flip(x, (0,))), (0,))
@@ -553,3 +630,88 @@ def is_cat_mod_model(net):
     """layers.py:1643-1656: is the final layer of the `Serial` network a categorical modified-base layer?"""
     assert isinstance(net, Serial)
     return isinstance(net[-1], GlobalNormFlipFlopCatMod)
+
+
+# ---------------------------------------------------------------------------
+# a network pass on columns of different lengths
+# ---------------------------------------------------------------------------
+def conv_out_lengths(lengths, stride):
+    """Rows a `Convolution` of this stride returns for a column of `lengths` samples run alone: ceil(length / stride),
+    whatever the window (the layer pads winlen // 2 in front and (winlen - 1) // 2 behind); 0 stays 0.  Integers,
+    arrays and tensors alike."""
+    return (lengths + (stride - 1)) // stride
+
+
+def _zero_beyond(y, lens_dev):
+    """Rows t >= lens[n] of column n of y (T, N, C) set to 0, in place."""
+    keep = torch.arange(y.shape[0], device=y.device)[:, None] < lens_dev[None, :]
+    return y.masked_fill_(~keep[:, :, None], 0)
+
+
+def _varlen_layers(model):
+    """(layer, recurrent layer or None, reverse) for every layer of the Serial; TypeError for a type the pass does
+    not know."""
+    plan = []
+    for layer in model:
+        inner, rev = (layer.layer, True) if isinstance(layer, Reverse) else (layer, False)
+        if isinstance(inner, (Lstm, GruMod)):
+            plan.append((layer, inner, rev))
+        elif not rev and isinstance(layer, (Convolution, GlobalNormFlipFlop, GlobalNormFlipFlopCatMod)):
+            plan.append((layer, None, False))
+        else:
+            raise TypeError("forward_varlen: no rule for a layer of type %s" % (
+                "Reverse(%s)" % type(inner).__name__ if rev else type(layer).__name__))
+    return plan
+
+
+def _varlen_batched(plan, x, lens):
+    """The whole batch through every layer once; None where a recurrent layer has no HIP launch for its input."""
+    h, lens_dev = x, torch.from_numpy(lens).to(x.device)
+    for layer, rnn_layer, rev in plan:
+        if rnn_layer is not None:
+            if not hip_rnn_varlen_workspace_bytes(rnn_layer.rnn, h):
+                return None
+            h = rnn_layer(h, reverse=rev, lengths=lens_dev)
+            continue
+        h = layer(h)
+        if isinstance(layer, Convolution):
+            lens = conv_out_lengths(lens, layer.stride)
+            lens_dev = torch.from_numpy(lens).to(x.device)
+        h = _zero_beyond(h, lens_dev)
+    return h
+
+
+def forward_varlen(model, x, lengths):
+    """`model` (a `Serial` of this module's layers) on x (T, N, C) whose column n has lengths[n] rows (zero beyond):
+    -> (out, out_lengths), where out[:out_lengths[n], n] is what `model(x[:lengths[n], n:n + 1])` gives and every row
+    beyond is 0.  out_lengths is a host int64 array (`conv_out_lengths` through every Convolution).  Inference only.
+
+    On the GPU the batch goes through every layer once: a Convolution's rows beyond the column's output length are
+    zeroed (the next window then sees the zeros its own padding would have supplied), the recurrences take the
+    lengths (`Lstm` / `GruMod` `forward(x, reverse, lengths)`), the output layers are pointwise per row.  Where a
+    recurrent layer has no HIP launch for the tensors (CPU tensors, a size the kernels do not admit, USE_HIP_LSTM or
+    USE_HIP_GRU off) every column is evaluated alone at its own length instead."""
+    if not isinstance(model, Serial):
+        raise TypeError("forward_varlen: the model must be a layers.Serial, not %s" % type(model).__name__)
+    plan = _varlen_layers(model)
+    if _needs_grad(x, model):
+        raise RuntimeError("forward_varlen is inference only: call it under torch.no_grad()")
+    T, N, _ = x.shape
+    lens = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
+    if len(lens) != N or (N and (lens.min() < 0 or lens.max() > T)):
+        raise ValueError("forward_varlen: lengths must hold one value in 0..%d for each of the %d columns" % (T, N))
+    out_lens, t_out = lens, T
+    for layer, _, _ in plan:
+        if isinstance(layer, Convolution):
+            out_lens, t_out = conv_out_lengths(out_lens, layer.stride), conv_out_lengths(t_out, layer.stride)
+    last = plan[-1][1] or plan[-1][0]
+    nout = last.rnn.hidden_size if isinstance(last, _Rnn) else last.conv.out_channels if isinstance(last, Convolution) \
+        else getattr(last, "nout", last.size)
+    with torch.no_grad():
+        out = _varlen_batched(plan, x, lens) if T and N else None
+        if out is None:
+            out = x.new_zeros(t_out, N, nout)
+            for n in range(N):
+                if lens[n]:
+                    out[:out_lens[n], n:n + 1] = model(x[:lens[n], n:n + 1])
+    return out, out_lens

@@ -4,11 +4,15 @@ at (T, N, H), each timed with device events after warm-up; prints one JSON line 
 direction, median and min over --steps).  bench.py --config 1's layer is the default shape; the other shape on
 record is --T 800 --N 128 --H 256.
 
-    python tools/grubench.py [--T 1000] [--N 64] [--H 96] [--steps 20] [--warmup 3] [--reverse] [--infer] [--cols C]
+    python tools/grubench.py [--T 1000] [--N 64] [--H 96] [--steps 20] [--warmup 3] [--reverse] [--infer] [--varlen] [--cols C]
 
 --cols (lab build) forces the batch columns per workgroup at H <= 128; without it the release library is timed.
 
 --infer also times the forward with NULL for gates and q (what a torch.no_grad() call launches).
+
+--varlen also times tk_gru_forward_varlen_dev (include/taiyaki_amd_rnn_varlen.h, the release rule) with every length
+equal to T, in turns with the forward above, five turns each: the mask's cost per step against the same run's forward
+and the spread of that forward between its turns.
 """
 import argparse
 import json
@@ -46,6 +50,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reverse", action="store_true")
     ap.add_argument("--infer", action="store_true", help="also time the forward that saves nothing (gates = q = NULL)")
+    ap.add_argument("--varlen", action="store_true", help="also time the forward with per-column lengths, all = T")
     ap.add_argument("--cols", type=int, default=None, help="(lab build) batch columns per workgroup at H <= 128")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -89,6 +94,19 @@ def main():
         i_med, i_min = timed(lambda: fwd(False), a.steps, a.warmup)
         out.update(infer_ms=round(i_med, 3), infer_us_per_step=round(1e3 * i_med / T, 3),
                    infer_min_us_per_step=round(1e3 * i_min / T, 3))
+    if a.varlen:
+        V = _lib.varlen_lib()
+        vwsb = V.tk_rnn_varlen_workspace_bytes(_lib.VARLEN_DEFINES["TK_RNN_KIND_GRU"], N, H, cus)
+        vws = torch.empty(max(vwsb // 4, 4), dtype=torch.float32, device=dev)
+        lens = torch.full((N,), T, dtype=torch.int32, device=dev)
+
+        def vfwd():
+            _lib.check(V.tk_gru_forward_varlen_dev(_lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(b_hh), _lib.ptr(lens), T, N, H,
+                                                   int(a.reverse), cus, _lib.ptr(y), _lib.ptr(vws), vwsb,
+                                                   _lib.ptr(status), stream), "tk_gru_forward_varlen_dev")
+        turns = [(timed(fwd, a.steps, a.warmup)[0], timed(vfwd, a.steps, a.warmup)[0]) for _ in range(5)]
+        out.update(fwd_turns_us_per_step=[round(1e3 * f / T, 3) for f, _ in turns],
+                   varlen_turns_us_per_step=[round(1e3 * v / T, 3) for _, v in turns])
     f_med, f_min = timed(fwd, a.steps, a.warmup)
     b_med, b_min = timed(bwd, a.steps, a.warmup)
     _lib.finish(status)

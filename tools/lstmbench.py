@@ -5,7 +5,7 @@ units setting (microseconds per timestep and direction, median and min over --st
 (config 2) is the default shape.  The weight-gradient leg follows: `wgrad_ms` is tk_lstm_weight_grad_dev
 (csrc/lstm_wgrad.hip) at (T, N, H, I = H), `wgrad_gemm_ms` the two GEMMs and the sum over dG that it replaces.
 
-    python tools/lstmbench.py [--T 800] [--N 128] [--H 256] [--steps 20] [--warmup 3] [--units 0 16 32 64]
+    python tools/lstmbench.py [--T 800] [--N 128] [--H 256] [--steps 20] [--warmup 3] [--units 0 16 32 64] [--varlen]
 
 --units (lab build) forces the hidden units per workgroup; 0 is the release rule.  Without --units the
 release library is timed.
@@ -45,6 +45,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reverse", action="store_true")
+    ap.add_argument("--varlen", action="store_true",
+                    help="also time tk_lstm_forward_varlen_dev (release rule) with every length = T, in turns with the forward")
     ap.add_argument("--units", type=int, nargs="*", default=None, help="(lab) units per workgroup; 0 = release rule")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -83,6 +85,21 @@ def main():
                                               int(a.reverse), cus, _lib.ptr(dg), _lib.ptr(ws), wsb, _lib.ptr(status),
                                               stream), "tk_lstm_backward_dev")
 
+        varlen = {}
+        if a.varlen and units is None:
+            # include/taiyaki_amd_rnn_varlen.h: five turns each, the forward above and the launch with lengths
+            V = _lib.varlen_lib()
+            vwsb = V.tk_rnn_varlen_workspace_bytes(_lib.VARLEN_DEFINES["TK_RNN_KIND_LSTM"], N, H, cus)
+            vws = torch.empty(vwsb // 4, dtype=torch.float32, device=dev)
+            lens = torch.full((N,), T, dtype=torch.int32, device=dev)
+
+            def vfwd():
+                _lib.check(V.tk_lstm_forward_varlen_dev(_lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(lens), T, N, H,
+                                                        int(a.reverse), cus, _lib.ptr(y), _lib.ptr(vws), vwsb,
+                                                        _lib.ptr(status), stream), "tk_lstm_forward_varlen_dev")
+            turns = [(timed(fwd, a.steps, a.warmup)[0], timed(vfwd, a.steps, a.warmup)[0]) for _ in range(5)]
+            varlen = {"fwd_turns_us_per_step": [round(1e3 * f / T, 3) for f, _ in turns],
+                      "varlen_turns_us_per_step": [round(1e3 * v / T, 3) for _, v in turns]}
         f_med, f_min = timed(fwd, a.steps, a.warmup)
         b_med, b_min = timed(bwd, a.steps, a.warmup)
 
@@ -113,7 +130,7 @@ def main():
         _lib.raise_if_nonfinite()
         if units is not None:
             L.tk_lab_lstm_units(0)
-        print(json.dumps({"T": T, "N": N, "H": H, "reverse": a.reverse, "units": units, "cus": cus,
+        print(json.dumps({"T": T, "N": N, "H": H, "reverse": a.reverse, "units": units, "cus": cus, **varlen,
                           "fwd_ms": round(f_med, 3), "bwd_ms": round(b_med, 3),
                           "fwd_us_per_step": round(1e3 * f_med / T, 3), "fwd_min_us_per_step": round(1e3 * f_min / T, 3),
                           "bwd_us_per_step": round(1e3 * b_med / T, 3), "bwd_min_us_per_step": round(1e3 * b_min / T, 3),
