@@ -15,8 +15,12 @@
 // Step schedule.  vmcnt is one in-order counter per wave for loads and stores, so every wait of a poll also waits
 // for whatever the wave issued before it.  Nothing bound for HBM is issued ahead of a poll in the same step: the
 // inputs of step s + 1 (forward: gx; backward: dy, c_{t-1}, the gates) are loaded right after step s's poll, and
-// the bulk outputs of step s (forward: y, c, gates; backward: dG) are held in registers and stored right after
-// step s + 1's poll.  Both drain under the matvec; the granule publish is the last memory operation of a step.
+// the bulk outputs of step s (forward: y, c, gates; backward: dG) are held back and stored right after step s + 1's
+// poll.  Both drain under the matvec; the granule publish is the last memory operation of a step.  The backward
+// holds them in registers (its cell lanes are (column, unit), unit contiguous: whole rows as they are).  The
+// forward's cell lanes are kp < C of every KP lanes, 32-byte pieces of a row per store, so they stage the six values
+// in LDS and the workgroup stores the block as whole rows, 16 bytes per lane (rows_to_global, rnn_common.h): 3 store
+// instructions per workgroup and step at H 256, U 64, C 2 where the cell lanes issued 48.
 //
 // Two builds of this one source.  The flip-flop library takes the training pair: the forward that saves the gates
 // and c, and the backward.  -DTK_RNN_VARLEN (libtaiyaki_amd_rnn_varlen.so) takes the forward alone in its VL form:
@@ -39,10 +43,13 @@ constexpr int threads_for() { return U <= 32 ? 256 : 512; }
 // in VGPRs, so each h value read from LDS feeds 4 rows (KS C-wide LDS reads per lane per step).  The KP partial
 // sums are combined by xor shuffles: the first log2(C) rounds halve the columns a lane keeps, the rest add the 4
 // gates of its one column; lane kp < C then holds the 4 pre-activations of column col(kp) and runs its cell update.
+// It leaves h, c and the activations in the staging block of the step's parity; behind the next step's barrier (after
+// the loop: one barrier of its own) lane tid stores the 16-byte chunks tid + i NT of that block.  No second barrier
+// per step: a block is written again two steps on, behind the barrier that every wave reaches after its stores.
 //
 // VL: column n has lengths[n] steps (NULL: T).  A step at t >= lengths[n] leaves h = c = 0, writes y = 0 and
 // publishes h = 0 like any other step: every workgroup runs all T steps, so the hand-off is that of a full batch.
-// gates and cell are not written (the pointers are not read).
+// gates and cell are not written (the pointers are not read); y goes out from the cell lane's register, one step late.
 template <int H, int C, int U, bool VL = false>
 __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const float *__restrict__ gx,
                                                                        const float *__restrict__ whh, int T, int N,
@@ -58,7 +65,13 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
     constexpr int KS = H / KP;
     constexpr int NG = (H * C + NT - 1) / NT;
     static_assert(KS >= 1 && KP <= 64 && C <= KP, "lane (u, kp) inside one wave; one cell lane per (u, column)");
+    constexpr int U4 = U / 4;
+    constexpr int NQ = VL ? 1 : (6 * C * U4 + NT - 1) / NT;        // 16-byte chunks of a staging block per lane
+    static_assert(U % 4 == 0, "a row of the staging block is whole 16-byte chunks");
     __shared__ __attribute__((aligned(16))) float hs[2][H * C];      // h_{t-1} as [k][c], by step parity
+    // a step's h, c, i, f, g, o as [value][column][unit], by step parity: written by the cell lanes at the end of step
+    // s, read behind step s + 1's barrier, written again behind step s + 2's
+    __shared__ __attribute__((aligned(16))) float stg[VL ? 1 : 2][VL ? 4 : 6 * C * U];
     __shared__ int give_up;
 
     int group, member;
@@ -89,13 +102,26 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
     if (tid == 0) give_up = 0;
 
     const size_t H4 = 4 * (size_t)H;
+    // the chunks of the staging block this lane stores: rows (value, column) of y, cell and the gates' four slabs
+    float *rp[NQ];
+    size_t rpitch[NQ];
+    if constexpr (!VL) {
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            const int q = tid + i * NT, row = q / U4, v = row / C, nn = n0 + row % C;
+            const size_t w = v < 2 ? (size_t)H : H4;
+            float *base = v == 0 ? y : v == 1 ? cell : gates + (size_t)(v - 2) * H;
+            rpitch[i] = (size_t)N * w;
+            rp[i] = q < 6 * C * U4 && nn < N ? base + (size_t)nn * w + j0 + 4 * (q % U4) : nullptr;
+        }
+    }
     float gq[4] = {0.f, 0.f, 0.f, 0.f};              // gx of this step (loaded one step ahead)
     if (valid) {
         const float *p = gx + ((size_t)(reverse ? T - 1 : 0) * N + n) * H4 + j0 + u;
 #pragma unroll
         for (int g = 0; g < 4; ++g) gq[g] = p[(size_t)g * H];
     }
-    float held[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // h, c, i, f, g, o of the previous step, stored one step late
+    float held = 0.f;                                  // VL: h of the previous step, stored one step late
     __syncthreads();
 
     for (int s = 0; s < T; ++s) {
@@ -113,16 +139,11 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
             }
             __syncthreads();
             if (give_up) return;
-            if (valid) {
-                const int tl = reverse ? t + 1 : t - 1;
-                const size_t o = ((size_t)tl * N + n) * H + j0 + u;
-                y[o] = held[0];
-                if constexpr (!VL) {
-                    cell[o] = held[1];
-                    float *gp = gates + ((size_t)tl * N + n) * H4 + j0 + u;
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) gp[(size_t)g * H] = held[2 + g];
-                }
+            const int tl = reverse ? t + 1 : t - 1;
+            if constexpr (VL) {
+                if (valid) y[((size_t)tl * N + n) * H + j0 + u] = held;
+            } else {
+                rows_to_global<NQ>(stg[(s - 1) & 1], tid, NT, rp, rpitch, (size_t)tl);
             }
         }
         float gn[4] = {0.f, 0.f, 0.f, 0.f};
@@ -168,10 +189,10 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
         if (cell_lane) {
             const float ig = sigmoidf(acc[0][0] + gq[0]), fg = sigmoidf(acc[1][0] + gq[1]);
             const float gg = tanhf(acc[2][0] + gq[2]), og = sigmoidf(acc[3][0] + gq[3]);
-            // (VL: the contraction the compiler gives the saving form, written out -- left to it, the mask's select
-            // moves the fma to the other product and a column's rows differ from the saving launch's in the last bit)
-            if constexpr (VL) cst = fmaf(ig, gg, fg * cst);
-            else cst = fg * cst + ig * gg;
+            // (the contraction written out: left to the compiler, which product the fma takes depends on the code around
+            // it -- the VL mask's select, the staging stores -- and a column's rows then differ in the last bit between
+            // the builds)
+            cst = fmaf(ig, gg, fg * cst);
             float h = og * tanhf(cst);
             if constexpr (VL) {
                 if (t >= len) cst = h = 0.f;
@@ -179,25 +200,28 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
             if (s + 1 < T)
                 store_granule(hbuf + ((size_t)(s & 1) * ngroups + group) * (H * C) + col * H + j0 + u,
                               (unsigned)(s + 1), h);
-            held[0] = h;
-            held[1] = cst;
-            held[2] = ig;
-            held[3] = fg;
-            held[4] = gg;
-            held[5] = og;
+            if constexpr (VL) {
+                held = h;
+            } else {
+                float *sp = stg[s & 1] + col * U + u;
+                sp[0 * C * U] = h;
+                sp[1 * C * U] = cst;
+                sp[2 * C * U] = ig;
+                sp[3 * C * U] = fg;
+                sp[4 * C * U] = gg;
+                sp[5 * C * U] = og;
+            }
         }
 #pragma unroll
         for (int g = 0; g < 4; ++g) gq[g] = gn[g];
     }
-    if (valid && T > 0) {
+    if (T > 0) {
         const int tl = reverse ? 0 : T - 1;
-        const size_t o = ((size_t)tl * N + n) * H + j0 + u;
-        y[o] = held[0];
-        if constexpr (!VL) {
-            cell[o] = held[1];
-            float *gp = gates + ((size_t)tl * N + n) * H4 + j0 + u;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) gp[(size_t)g * H] = held[2 + g];
+        if constexpr (VL) {
+            if (valid) y[((size_t)tl * N + n) * H + j0 + u] = held;
+        } else {
+            __syncthreads();                             // the last step's block: no poll, so no barrier, is behind it
+            rows_to_global<NQ>(stg[(T - 1) & 1], tid, NT, rp, rpitch, (size_t)tl);
         }
     }
 }
@@ -394,7 +418,7 @@ size_t ws_bytes(size_t H, int C, int groups, int U, bool backward) {
 }
 
 // A launch: U units and C = C_admitted * 16 / U columns per workgroup, groups of H / U workgroups.  Release rule:
-// U = 64, or H where H < 64 (config 2's layer: 2.85 / 2.54 us per forward / backward step at U = 64, 2.84 / 3.58 at
+// U = 64, or H where H < 64 (config 2's layer when the rule was set: 2.85 / 2.54 us per forward / backward step at U = 64, 2.84 / 3.58 at
 // U = 32, 3.44 / 4.02 at U = 16; tools/lstmbench.py).  C divides the admitted column count, so the grid and both granule buffers are never
 // larger than those of the admission geometry.
 struct Plan {

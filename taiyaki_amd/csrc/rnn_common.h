@@ -105,6 +105,25 @@ __device__ __forceinline__ void lds_row(const float *p, float (&v)[C]) {
     }
 }
 
+// Row staging.  The cell lanes of a forward step are a few lanes of every wave, so a store of theirs reaches global
+// memory as 32-byte pieces.  They write a step's bulk outputs into an LDS block of rows of U floats instead (U a
+// multiple of 4, the block 16-byte aligned), and behind the next barrier the block leaves as whole rows: lane tid of nt
+// moves the 16-byte chunks tid + i * nt, i < NQ, chunk q being floats [4 (q % (U / 4)), + 4) of row q / (U / 4).
+// dst[i] is where chunk i goes at time 0 (NULL: a chunk past the block or of a column past N, not stored), pitch[i]
+// its tensor's floats per time step.  One dwordx4 per chunk; the tensors need no more than a float's alignment.
+typedef float row_chunk __attribute__((ext_vector_type(4), aligned(4)));
+
+template <int NQ>
+__device__ __forceinline__ void rows_to_global(const float *blk, int tid, int nt, float *const (&dst)[NQ],
+                                               const size_t (&pitch)[NQ], size_t t) {
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+        if (!dst[i]) continue;
+        const float4 v = reinterpret_cast<const float4 *>(blk)[tid + i * nt];
+        *reinterpret_cast<row_chunk *>(dst[i] + t * pitch[i]) = row_chunk{v.x, v.y, v.z, v.w};
+    }
+}
+
 __global__ void zero_u64x2_kernel(uint4 *p, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         p[i] = make_uint4(0u, 0u, 0u, 0u);
