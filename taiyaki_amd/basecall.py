@@ -7,12 +7,13 @@ normalisation, chunking and the tail (stitch, collapse, quality characters) are 
 include/taiyaki_amd_basecall.h; the network, `flipflop_make_trans`, the Viterbi and `errprobs_from_trans` are the
 operators this package already has.  `call_mods` adds, for a cat-mod model, the modified-base scores of every called
 base (tk_basecall_mod_weights_dev on the Viterbi paths and the network's categorical columns), in the same download.
-With a beam, the stitched scores of all the batch's reads
-(tk_basecall_stitch_scores_dev) go through ONE launch of the beam search (tk_basecall_beamsearch_dev), which writes the
-calls.  There is no CPU fallback: a model that is not on an AMD GPU raises.
+With a beam, the stitched scores of all the batch's reads (tk_basecall_stitch_scores_dev) go through ONE launch of the
+beam search (tk_basecall_beamsearch_dev), which writes the calls.  There is no CPU fallback: a model that is not on an
+AMD GPU raises.
 """
 import collections
 import ctypes
+import types
 
 import numpy as np
 import torch
@@ -112,6 +113,45 @@ def _align(n, to=16):
     return (n + to - 1) // to * to
 
 
+class _Layout:
+    """The byte layout of one transfer: `fields` is an ordered list of (name, dtype, count).  Every field starts on a
+    16-byte boundary; `nbytes` ends with the last field.  `view(buf, name)` is that field, typed, of a uint8 numpy
+    array or torch tensor that starts with the block (`count`: another number of elements than the field's)."""
+
+    def __init__(self, fields):
+        self.fields, self.nbytes = {}, 0
+        for name, dtype, count in fields:
+            self.fields[name] = (_align(self.nbytes), np.dtype(dtype), count)
+            self.nbytes = _align(self.nbytes) + np.dtype(dtype).itemsize * count
+
+    def view(self, buf, name, count=None):
+        off, dtype, n = self.fields[name]
+        piece = buf[off:off + dtype.itemsize * (n if count is None else count)]
+        return piece.view(dtype if isinstance(buf, np.ndarray) else getattr(torch, dtype.name))
+
+
+def room_offsets(counts, lens, nrow, short, chunk_size, overlap, stride):
+    """Where every read's output starts, int64 (nread + 1).  A read's room is its stitched row count, which bounds
+    its call length: of `counts[r]` chunks of `nrow` rows each in the batch's chunk tensor, or -- `short`: (read,
+    rows) pairs -- the rows of its own chunk; none for a read without samples."""
+    rows = np.zeros(len(counts), dtype=np.int64)
+    for r in np.flatnonzero(counts):
+        rows[r] = stitched_rows(int(counts[r]), int(lens[r]), chunk_size, overlap, stride, nrow)
+    for r, n in short:
+        rows[r] = n
+    return np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+
+
+Segment = collections.namedtuple("Segment", "r0 nread ncol starts ends read_chunk_off nrow path err trans weights")
+Segment.__doc__ = """A decoded chunk tensor of `ncol` columns and `nrow` rows, and the reads [r0, r0 + nread) it belongs
+to: the batch's chunk tensor (r0 = 0, all reads) or a short read's own chunk (nread = 1).  `path`, `err` (fastq),
+`weights` (call_mods) on the Viterbi path, `trans` with a beam; `starts`, `ends`, `read_chunk_off` from the gather."""
+
+
+def _at(t, r0):     # &t[r0] of a per-read device array: where a segment's reads start in it
+    return _lib._vp(t.data_ptr() + r0 * t.element_size())
+
+
 class Basecaller:
     """`call(signals)` -> [(sequence, quality string or None, nsamples)] for a batch of reads; with mod_output=True,
     `call_mods(signals)` -> (the same list, [the modified-base scores of every read's call]).
@@ -148,29 +188,6 @@ class Basecaller:
     def plan(self, lengths):
         return packing_plan(lengths, self.chunk_size, self.overlap, self.max_concurrent_chunks, self.pack)
 
-    # -- steps 4-8 of a call: the network and the decode operators on one chunk tensor ---------------------------------
-    def _trans(self, outs):
-        if self.can_nmods:      # (`_run` kept the categorical columns)
-            outs = [o[:, :, :self.n_can_state] for o in outs]
-        trans = torch.cat(outs, 1) * self.temperature
-        if self.posterior:
-            trans = (decode.flipflop_make_trans(trans) + 1e-8).log()
-        return trans
-
-    def _decode(self, outs):
-        trans = self._trans(outs)
-        path = decode.flipflop_viterbi_path(trans)
-        return path, (qscores.errprobs_from_trans(trans, path) if self.fastq else None)
-
-    def _run(self, chunks):
-        """The network on one chunk tensor: its transition scores and, with mod_output, the categorical columns
-        behind them."""
-        out = self.model(chunks)
-        return out if self.can_nmods else out[:, :, :self.n_can_state]
-
-    def _mod_weights(self, outs):
-        return torch.cat([o[:, :, self.n_can_state:] for o in outs], 1).contiguous()
-
     def call(self, signals, read_params=None):
         return self._call(signals, read_params, False)[0]
 
@@ -187,192 +204,172 @@ class Basecaller:
         return self._call(signals, read_params, True)
 
     def _call(self, signals, read_params, want_mods):
-        L, dev, nread = _lib.basecall_lib(), self.device, len(signals)
-        if nread == 0:
+        """-> (results, every read's modified-base scores or None); nothing waits on the host before the download."""
+        if len(signals) == 0:
             return [], []
         sigs = [np.asarray(s, dtype=np.float32).reshape(-1) for s in signals]
         if self.reverse:
             sigs = [s[::-1] for s in sigs]
-        lens = np.array([len(s) for s in sigs], dtype=np.int64)
-        params = list(read_params) if read_params is not None else [None] * nread
-        given = np.array([p is not None for p in params])
-        # 1. ONE upload: signals | offsets | the caller's shift and scale
+        params = list(read_params) if read_params is not None else [None] * len(sigs)
+        with torch.cuda.device(self.device), torch.no_grad():
+            c = self._upload(sigs, params)                                              # 1.
+            self._normalisation(c, np.array([p is not None for p in params]))           # 2.
+            counts = chunk_counts(c.lens, self.chunk_size, self.overlap)
+            chunks, geo = self._chunk(c, int(counts.sum()))                             # 3.
+            batch, short = self._network(c, self.plan(c.lens), chunks, geo, want_mods)  # 4.-8.
+            off = room_offsets(counts, c.lens, batch.nrow if batch else 0, [(s.r0, s.nrow) for s in short],
+                               self.chunk_size, self.overlap, self.stride)
+            # Order is behaviour: the batch's launch comes first and writes a length of 0 for every read without a
+            # chunk in it; the short reads follow in plan order, each over its own slot.
+            segs = ([batch] if batch else []) + short
+            layout, body = (self._decode_beam(c, segs, off) if self.beam                # 9.
+                            else self._decode_viterbi(c, segs, off, want_mods))
+            return self._download(c, layout, body, off, want_mods)                      # 10.
+
+    def _upload(self, sigs, params):
+        """Step 1, the ONE upload: signals | offsets | the caller's shift and scale -> the call's device state.  The
+        ONE download starts with its `head`: seqlen | status (the decoders put seq | qual | mods behind it)."""
+        nread, lens = len(sigs), np.array([len(s) for s in sigs], dtype=np.int64)
         nsig = int(lens.sum())
-        o_off = _align(4 * nsig)
-        o_shift = o_off + _align(8 * (nread + 1))
-        o_scale = o_shift + _align(4 * nread)
-        host = np.zeros(o_scale + _align(4 * nread), dtype=np.uint8)
-        host[:4 * nsig].view(np.float32)[:] = np.concatenate(sigs) if nsig else 0
-        host[o_off:o_off + 8 * (nread + 1)].view(np.int64)[:] = np.concatenate([[0], np.cumsum(lens)])
-        host[o_shift:o_shift + 4 * nread].view(np.float32)[:] = [p[0] if p is not None else 0 for p in params]
-        host[o_scale:o_scale + 4 * nread].view(np.float32)[:] = [p[1] if p is not None else 1 for p in params]
-        plan = self.plan(lens)
-        counts = chunk_counts(lens, self.chunk_size, self.overlap)
-        total = int(counts.sum())
-        with torch.cuda.device(dev), torch.no_grad():
-            stream = _lib.stream_ptr()
-            up = torch.from_numpy(host).to(dev)
-            signal, sig_off = up[:4 * max(nsig, 1)].view(torch.float32), up[o_off:o_off + 8 * (nread + 1)].view(torch.int64)
-            shift = up[o_shift:o_shift + 4 * nread].view(torch.float32)
-            scale = up[o_scale:o_scale + 4 * nread].view(torch.float32)
-            # the ONE download comes from here: seqlen | status | seq | qual (sized once the block counts are known)
-            head = torch.zeros(_align(4 * nread) + 16, dtype=torch.uint8, device=dev)
-            seqlen, status = head[:4 * nread].view(torch.int32), head[_align(4 * nread):]
-            # 2. median / MAD where no parameters were given
-            if not given.all():
-                medmad = torch.empty(2, nread, dtype=torch.float32, device=dev)
-                _lib.check(L.tk_signal_med_mad_dev(_lib.ptr(signal), _lib.ptr(sig_off), nread, _lib.ptr(medmad[0]),
-                                                   _lib.ptr(medmad[1]), _lib.ptr(status), stream), "tk_signal_med_mad_dev")
-                if given.any():
-                    mask = torch.from_numpy(given).to(dev)
-                    shift, scale = torch.where(mask, shift, medmad[0]), torch.where(mask, scale, medmad[1])
-                else:
-                    shift, scale = medmad[0], medmad[1]
-            # 3. normalise + chunk: the batch's chunk tensor, and each short read as one chunk of its own length
-            starts = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
-            ends = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
-            read_chunk_off = torch.empty(nread + 1, dtype=torch.int64, device=dev)
-            chunks = torch.empty(self.chunk_size, total, 1, dtype=torch.float32, device=dev)
-            ws = torch.empty(max(L.tk_basecall_gather_workspace_bytes(total), 16), dtype=torch.uint8, device=dev)
-            _lib.check(L.tk_basecall_gather_chunks_dev(
-                _lib.ptr(signal), _lib.ptr(sig_off), nread, nsig, _lib.ptr(shift), _lib.ptr(scale), self.chunk_size,
-                self.overlap, total, _lib.ptr(chunks), _lib.ptr(starts), _lib.ptr(ends), _lib.ptr(read_chunk_off),
-                _lib.ptr(ws), ws.numel(), _lib.ptr(status), stream), "tk_basecall_gather_chunks_dev")
-            one = torch.tensor([0, 1], dtype=torch.int64, device=dev)      # read_chunk_off of a read called alone
-            outs, short, short_w = [], [], {}
-            for sl in plan:
-                if not sl.short:
-                    # 4. the network on column slices of at most max_concurrent_chunks
-                    outs.append(self._run(chunks[:, sl.first:sl.first + sl.ncol].contiguous()))
-                    continue
-                r, n = sl.first, int(lens[sl.first])
-                own = torch.empty(n, 1, 1, dtype=torch.float32, device=dev)
-                geo = torch.empty(3, 2, dtype=torch.int64, device=dev)     # starts, ends, read_chunk_off
-                w1 = torch.empty(16, dtype=torch.uint8, device=dev)
-                _lib.check(L.tk_basecall_gather_chunks_dev(
-                    _lib.ptr(signal), _lib._vp(sig_off.data_ptr() + 8 * r), 1, nsig, _lib._vp(shift.data_ptr() + 4 * r),
-                    _lib._vp(scale.data_ptr() + 4 * r), n, 0, 1, _lib.ptr(own), _lib.ptr(geo[0]), _lib.ptr(geo[1]),
-                    _lib.ptr(geo[2]), _lib.ptr(w1), w1.numel(), _lib.ptr(status), stream), "tk_basecall_gather_chunks_dev")
-                if self.beam:
-                    short.append((r, self._trans([self._run(own)]).contiguous(), None, geo))
-                    continue
-                out = self._run(own)
-                path, err = self._decode([out])
-                short.append((r, path, err, geo))
-                if want_mods:
-                    short_w[r] = self._mod_weights([out])
-            if self.beam:
-                return self._call_beam(outs, short, counts, lens, starts, ends, read_chunk_off, scale, head), None
-            # 5.-8. temperature, posterior, Viterbi, error probabilities on all the batch's chunks at once
-            path = err = None
-            if total:
-                path, err = self._decode(outs)
-            # room per read: its stitched row count bounds its call length
-            rows = np.zeros(nread, dtype=np.int64)
-            for r in range(nread):
-                if counts[r]:
-                    rows[r] = stitched_rows(int(counts[r]), int(lens[r]), self.chunk_size, self.overlap, self.stride,
-                                            path.shape[0])
-            for r, spath, _, _ in short:
-                rows[r] = spath.shape[0]
-            out_off_host = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
-            cap = max(int(out_off_host[-1]), 1)
-            out_off = torch.from_numpy(out_off_host).to(dev)
-            nmod = sum(self.can_nmods) if want_mods else 0
-            body = torch.empty(2 * _align(cap) + 4 * cap * nmod, dtype=torch.uint8, device=dev)
-            seq, qual = body[:cap], body[_align(cap):_align(cap) + cap]
-            if want_mods:       # behind seq | qual: read r's rows from row out_off[r], as its characters
-                mods = body[2 * _align(cap):].view(torch.float32)
-                nbase, can_nmods = len(self.alphabet), (ctypes.c_int * len(self.alphabet))(*self.can_nmods)
-                weights = self._mod_weights(outs) if total else None
-            qs, qo = self.qscore_scale, self.qscore_offset
-            # 9. the tail (reads without a chunk in `path` get seqlen 0 here; the short ones are written next)
-            if total:
-                _lib.check(L.tk_basecall_call_dev(
-                    _lib.ptr(path), _lib.ptr(err), path.shape[0] - 1, total, _lib.ptr(starts), _lib.ptr(ends),
-                    _lib.ptr(read_chunk_off), _lib.ptr(scale), nread, self.stride, len(self.alphabet), self.alphabet,
-                    qs, qo, _lib.ptr(out_off), _lib.ptr(seq), _lib.ptr(qual), _lib.ptr(seqlen), _lib.ptr(status),
-                    stream), "tk_basecall_call_dev")
-            for r, spath, serr, geo in short:
-                _lib.check(L.tk_basecall_call_dev(
-                    _lib.ptr(spath), _lib.ptr(serr), spath.shape[0] - 1, 1, _lib.ptr(geo[0]), _lib.ptr(geo[1]),
-                    _lib.ptr(one), _lib._vp(scale.data_ptr() + 4 * r), 1, self.stride, len(self.alphabet),
-                    self.alphabet, qs, qo, _lib._vp(out_off.data_ptr() + 8 * r), _lib.ptr(seq), _lib.ptr(qual),
-                    _lib._vp(seqlen.data_ptr() + 4 * r), _lib.ptr(status), stream), "tk_basecall_call_dev")
-            # 9b. the modified-base scores at the same moves: the same walk, the same offsets, the same seqlen
-            if want_mods and total:
-                _lib.check(L.tk_basecall_mod_weights_dev(
-                    _lib.ptr(path), _lib.ptr(weights), path.shape[0] - 1, total, _lib.ptr(starts), _lib.ptr(ends),
-                    _lib.ptr(read_chunk_off), _lib.ptr(scale), nread, self.stride, nbase, can_nmods, _lib.ptr(out_off),
-                    _lib.ptr(mods), _lib.ptr(seqlen), _lib.ptr(status), stream), "tk_basecall_mod_weights_dev")
-            for r, spath, _, geo in short if want_mods else ():
-                _lib.check(L.tk_basecall_mod_weights_dev(
-                    _lib.ptr(spath), _lib.ptr(short_w[r]), spath.shape[0] - 1, 1, _lib.ptr(geo[0]), _lib.ptr(geo[1]),
-                    _lib.ptr(one), _lib._vp(scale.data_ptr() + 4 * r), 1, self.stride, nbase, can_nmods,
-                    _lib._vp(out_off.data_ptr() + 8 * r), _lib.ptr(mods), _lib._vp(seqlen.data_ptr() + 4 * r),
-                    _lib.ptr(status), stream), "tk_basecall_mod_weights_dev")
-            # 10. ONE download
-            got = torch.cat([head, body]).cpu().numpy()
-        nhead = head.numel()
-        bits = int(got[_align(4 * nread):nhead].view(np.uint32)[0])
+        up = _Layout([("signal", np.float32, nsig), ("sig_off", np.int64, nread + 1), ("shift", np.float32, nread),
+                      ("scale", np.float32, nread)])
+        host = np.zeros(_align(up.nbytes), dtype=np.uint8)
+        up.view(host, "signal")[:] = np.concatenate(sigs) if nsig else 0
+        up.view(host, "sig_off")[:] = np.concatenate([[0], np.cumsum(lens)])
+        up.view(host, "shift")[:] = [p[0] if p is not None else 0 for p in params]
+        up.view(host, "scale")[:] = [p[1] if p is not None else 1 for p in params]
+        dev = torch.from_numpy(host).to(self.device)
+        head_layout = _Layout([("seqlen", np.int32, nread), ("status", np.uint8, 16)])
+        head = torch.zeros(head_layout.nbytes, dtype=torch.uint8, device=self.device)
+        return types.SimpleNamespace(
+            L=_lib.basecall_lib(), stream=_lib.stream_ptr(), nread=nread, lens=lens, nsig=nsig,
+            signal=up.view(dev, "signal", max(nsig, 1)), sig_off=up.view(dev, "sig_off"), shift=up.view(dev, "shift"),
+            scale=up.view(dev, "scale"), head_layout=head_layout, head=head, seqlen=head_layout.view(head, "seqlen"),
+            status=head_layout.view(head, "status"))
+
+    def _normalisation(self, c, given):
+        """Step 2: median / MAD where the caller gave no parameters, beside those it gave."""
+        if given.all():
+            return
+        medmad = torch.empty(2, c.nread, dtype=torch.float32, device=self.device)
+        _lib.check(c.L.tk_signal_med_mad_dev(_lib.ptr(c.signal), _lib.ptr(c.sig_off), c.nread, _lib.ptr(medmad[0]),
+                                             _lib.ptr(medmad[1]), _lib.ptr(c.status), c.stream),
+                   "tk_signal_med_mad_dev")
+        if given.any():
+            mask = torch.from_numpy(given).to(self.device)
+            c.shift, c.scale = torch.where(mask, c.shift, medmad[0]), torch.where(mask, c.scale, medmad[1])
+        else:
+            c.shift, c.scale = medmad[0], medmad[1]
+
+    def _gather(self, c, r0, nread, overlap, chunks, geo, ws):
+        """Normalise + chunk reads [r0, r0 + nread) into `chunks` (size, columns, 1); geo: starts, ends, offsets."""
+        _lib.check(c.L.tk_basecall_gather_chunks_dev(
+            _lib.ptr(c.signal), _at(c.sig_off, r0), nread, c.nsig, _at(c.shift, r0), _at(c.scale, r0), chunks.shape[0],
+            overlap, chunks.shape[1], _lib.ptr(chunks), _lib.ptr(geo[0]), _lib.ptr(geo[1]), _lib.ptr(geo[2]),
+            _lib.ptr(ws), ws.numel(), _lib.ptr(c.status), c.stream), "tk_basecall_gather_chunks_dev")
+
+    def _chunk(self, c, total):
+        """Step 3 for the reads of a chunk or more: the batch's chunk tensor and its starts, ends, read_chunk_off."""
+        dev = self.device
+        geo = [torch.empty(n, dtype=torch.int64, device=dev) for n in (max(total, 1), max(total, 1), c.nread + 1)]
+        chunks = torch.empty(self.chunk_size, total, 1, dtype=torch.float32, device=dev)
+        ws = torch.empty(max(c.L.tk_basecall_gather_workspace_bytes(total), 16), dtype=torch.uint8, device=dev)
+        self._gather(c, 0, c.nread, self.overlap, chunks, geo, ws)
+        return chunks, geo
+
+    def _network(self, c, plan, chunks, geo, want_mods):
+        """Steps 4-8 over the plan: the network on column slices of the batch's chunk tensor and on each short read as
+        one chunk of its own length (step 3 for it), then the operators -> (the batch's segment or None, the short)."""
+        dev, outs, short = self.device, [], []
+        one = torch.tensor([0, 1], dtype=torch.int64, device=dev)      # read_chunk_off of a read called alone
+        for sl in plan:
+            if not sl.short:
+                outs.append(self.model(chunks[:, sl.first:sl.first + sl.ncol].contiguous()))
+                continue
+            own = torch.empty(int(c.lens[sl.first]), 1, 1, dtype=torch.float32, device=dev)
+            own_geo = torch.empty(3, 2, dtype=torch.int64, device=dev)
+            self._gather(c, sl.first, 1, 0, own, own_geo, torch.empty(16, dtype=torch.uint8, device=dev))
+            short.append(Segment(sl.first, 1, 1, own_geo[0], own_geo[1], one,
+                                 *self._operators([self.model(own)], want_mods)))
+        batch = Segment(0, c.nread, chunks.shape[1], *geo, *self._operators(outs, want_mods)) if outs else None
+        return batch, short
+
+    def _operators(self, outs, want_mods):
+        """Steps 5-8 on the network's outputs for one chunk tensor (categorical columns lie behind the scores):
+        temperature, posterior, the Viterbi path and its error probabilities, or the scores for a beam -> a Segment's
+        last five fields."""
+        trans = torch.cat([o[:, :, :self.n_can_state] for o in outs], 1) * self.temperature
+        if self.posterior:
+            trans = (decode.flipflop_make_trans(trans) + 1e-8).log()
+        if self.beam:
+            return trans.shape[0], None, None, trans.contiguous(), None
+        path = decode.flipflop_viterbi_path(trans)
+        err = qscores.errprobs_from_trans(trans, path) if self.fastq else None
+        weights = torch.cat([o[:, :, self.n_can_state:] for o in outs], 1).contiguous() if want_mods else None
+        return path.shape[0], path, err, None, weights
+
+    def _launch_call(self, c, seg, out_off, seq, qual):
+        """The tail: stitch, collapse, quality characters of the segment's reads, each at its out_off."""
+        _lib.check(c.L.tk_basecall_call_dev(
+            _lib.ptr(seg.path), _lib.ptr(seg.err), seg.nrow - 1, seg.ncol, _lib.ptr(seg.starts), _lib.ptr(seg.ends),
+            _lib.ptr(seg.read_chunk_off), _at(c.scale, seg.r0), seg.nread, self.stride, len(self.alphabet),
+            self.alphabet, self.qscore_scale, self.qscore_offset, _at(out_off, seg.r0), _lib.ptr(seq), _lib.ptr(qual),
+            _at(c.seqlen, seg.r0), _lib.ptr(c.status), c.stream), "tk_basecall_call_dev")
+
+    def _launch_mods(self, c, seg, out_off, mods):
+        """The modified-base scores at the tail's moves: the same walk, the same offsets, the same seqlen."""
+        _lib.check(c.L.tk_basecall_mod_weights_dev(
+            _lib.ptr(seg.path), _lib.ptr(seg.weights), seg.nrow - 1, seg.ncol, _lib.ptr(seg.starts), _lib.ptr(seg.ends),
+            _lib.ptr(seg.read_chunk_off), _at(c.scale, seg.r0), seg.nread, self.stride, len(self.alphabet),
+            (ctypes.c_int * len(self.can_nmods))(*self.can_nmods), _at(out_off, seg.r0), _lib.ptr(mods),
+            _at(c.seqlen, seg.r0), _lib.ptr(c.status), c.stream), "tk_basecall_mod_weights_dev")
+
+    def _launch_stitch(self, c, seg, row_off, packed, nrows):
+        """The stitched scores of the segment's reads, each from row row_off of the packed buffer."""
+        _lib.check(c.L.tk_basecall_stitch_scores_dev(
+            _lib.ptr(seg.trans), seg.nrow, seg.ncol, seg.trans.shape[2], _lib.ptr(seg.starts), _lib.ptr(seg.ends),
+            _lib.ptr(seg.read_chunk_off), _at(c.scale, seg.r0), seg.nread, self.stride, _at(row_off, seg.r0),
+            packed.shape[0], _lib.ptr(packed), _at(nrows, seg.r0), _lib.ptr(c.status), c.stream),
+            "tk_basecall_stitch_scores_dev")
+
+    def _decode_viterbi(self, c, segs, off, want_mods):
+        """Step 9 on the Viterbi paths: seq | qual | mods, read r's characters (and rows of scores) from off[r].  The
+        mod launches read the seqlen of the tail's, so they follow all of them."""
+        cap, nmod = max(int(off[-1]), 1), sum(self.can_nmods) if want_mods else 0
+        layout = _Layout([("seq", np.uint8, cap), ("qual", np.uint8, cap), ("mods", np.float32, cap * nmod)])
+        out_off = torch.from_numpy(off).to(self.device)
+        body = torch.empty(layout.nbytes, dtype=torch.uint8, device=self.device)
+        for seg in segs:
+            self._launch_call(c, seg, out_off, layout.view(body, "seq"), layout.view(body, "qual"))
+        for seg in segs if want_mods else ():
+            self._launch_mods(c, seg, out_off, layout.view(body, "mods"))
+        return layout, body
+
+    def _decode_beam(self, c, segs, off):
+        """Step 9 with a beam (bin/basecall.py:216-221 for every read): the stitched scores of every segment in ONE
+        packed buffer, read r's rows from off[r], and ONE launch of the beam search, which also writes the calls."""
+        row_off = torch.from_numpy(off).to(self.device)
+        packed = torch.empty(int(off[-1]), self.n_can_state, dtype=torch.float32, device=self.device)
+        nrows = torch.zeros(c.nread, dtype=torch.int32, device=self.device)
+        for seg in segs:
+            self._launch_stitch(c, seg, row_off, packed, nrows)
+        seq = decodeutil.beamsearch_packed(packed, row_off, nrows, int(np.diff(off).max()), self.alphabet,
+                                           self.beam.width, self.beam_cut, self.beam.guided, c.status, c.seqlen)[3]
+        cap = max(int(off[-1]), 1)
+        return _Layout([("seq", np.uint8, cap)]), seq[:cap]
+
+    def _download(self, c, layout, body, off, want_mods):
+        """Step 10, the ONE download: head | body -> (results, every read's modified-base scores or None)."""
+        got = torch.cat([c.head, body]).cpu().numpy()
+        bits = int(c.head_layout.view(got, "status").view(np.uint32)[0])
         if bits & _lib.BASECALL_DEFINES["TK_STATUS_CHUNK_PLAN"]:
             raise RuntimeError("basecall: the device's chunk plan disagrees with the host's (status %#x)" % bits)
-        called, seq_h = got[:4 * nread].view(np.int32), got[nhead:nhead + cap]
-        qual_h = got[nhead + _align(cap):nhead + _align(cap) + cap]
-        results = []
-        for r in range(nread):
-            lo, hi = int(out_off_host[r]), int(out_off_host[r]) + int(called[r])
-            q = qual_h[lo:hi].tobytes().decode("ascii") if self.fastq else None
-            results.append((seq_h[lo:hi].tobytes().decode("ascii"), q, int(lens[r])))
-        if not want_mods:
-            return results, None
-        mods_h = got[nhead + 2 * _align(cap):].view(np.float32).reshape(cap, nmod)
-        return results, [mods_h[int(out_off_host[r]):int(out_off_host[r]) + int(called[r])].copy() for r in range(nread)]
-
-    def _call_beam(self, outs, short, counts, lens, starts, ends, read_chunk_off, scale, head):
-        """The rest of a call with a beam, inside `call`'s device context (bin/basecall.py:216-221 for every read):
-        stitch the scores of the batch's chunk tensor and of each short read's own chunk into ONE packed buffer, ONE
-        launch of the beam search, which also writes the calls, ONE download of seqlen | status | seq."""
-        L, dev, nread, stream = _lib.basecall_lib(), self.device, len(lens), _lib.stream_ptr()
-        seqlen, status = head[:4 * nread].view(torch.int32), head[_align(4 * nread):]
-        total = int(counts.sum())
-        trans = self._trans(outs).contiguous() if total else None
-        # room per read: its stitched row count
-        rows = np.zeros(nread, dtype=np.int64)
-        for r in range(nread):
-            if counts[r]:
-                rows[r] = stitched_rows(int(counts[r]), int(lens[r]), self.chunk_size, self.overlap, self.stride,
-                                        trans.shape[0])
-        for r, strans, _, _ in short:
-            rows[r] = strans.shape[0]
-        row_off_host = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
-        total_rows = int(row_off_host[-1])
-        row_off = torch.from_numpy(row_off_host).to(dev)
-        packed = torch.empty(total_rows, self.n_can_state, dtype=torch.float32, device=dev)
-        nrows = torch.zeros(nread, dtype=torch.int32, device=dev)
-        one = torch.tensor([0, 1], dtype=torch.int64, device=dev)
-        if total:       # (reads without a chunk in `trans` get 0 rows here; the short ones are written next)
-            _lib.check(L.tk_basecall_stitch_scores_dev(
-                _lib.ptr(trans), trans.shape[0], total, trans.shape[2], _lib.ptr(starts), _lib.ptr(ends),
-                _lib.ptr(read_chunk_off), _lib.ptr(scale), nread, self.stride, _lib.ptr(row_off), total_rows,
-                _lib.ptr(packed), _lib.ptr(nrows), _lib.ptr(status), stream), "tk_basecall_stitch_scores_dev")
-        for r, strans, _, geo in short:
-            _lib.check(L.tk_basecall_stitch_scores_dev(
-                _lib.ptr(strans), strans.shape[0], 1, strans.shape[2], _lib.ptr(geo[0]), _lib.ptr(geo[1]), _lib.ptr(one),
-                _lib._vp(scale.data_ptr() + 4 * r), 1, self.stride, _lib._vp(row_off.data_ptr() + 8 * r), total_rows,
-                _lib.ptr(packed), _lib._vp(nrows.data_ptr() + 4 * r), _lib.ptr(status), stream),
-                "tk_basecall_stitch_scores_dev")
-        _, _, _, seq, _ = decodeutil.beamsearch_packed(packed, row_off, nrows, int(rows.max()), self.alphabet,
-                                                       self.beam.width, self.beam_cut, self.beam.guided, status, seqlen)
-        got = torch.cat([head, seq[:max(total_rows, 1)]]).cpu().numpy()
-        nhead = head.numel()
-        bits = int(got[_align(4 * nread):nhead].view(np.uint32)[0])
-        if bits & _lib.BASECALL_DEFINES["TK_STATUS_CHUNK_PLAN"]:
-            raise RuntimeError("basecall: the device's chunk plan disagrees with the host's (status %#x)" % bits)
-        called, seq_h = got[:4 * nread].view(np.int32), got[nhead:]
-        return [(seq_h[int(row_off_host[r]):int(row_off_host[r]) + int(called[r])].tobytes().decode("ascii"), None,
-                 int(lens[r])) for r in range(nread)]
-
+        called, got = c.head_layout.view(got, "seqlen"), got[c.head.numel():]
+        spans = [slice(int(off[r]), int(off[r]) + int(called[r])) for r in range(c.nread)]
+        seq = [layout.view(got, "seq")[s].tobytes().decode("ascii") for s in spans]
+        qual = [layout.view(got, "qual")[s].tobytes().decode("ascii") if self.fastq else None for s in spans]
+        mods = layout.view(got, "mods").reshape(-1, sum(self.can_nmods)) if want_mods else None
+        return list(zip(seq, qual, (int(n) for n in c.lens))), ([mods[s].copy() for s in spans] if want_mods else None)
 
 def write_records(fh, ids, results, fastq, reverse=False):
     """The output loop of bin/basecall.py:280-291: one FASTA / FASTQ record per read with a non-empty call

@@ -359,6 +359,13 @@ def test_beam_basecaller_equals_the_chain_of_existing_operators(gpu_device, whic
     print(which, "posterior", posterior, "temperature", temperature, "bases called:", [len(r[0]) for r in alone])
     assert sum(len(r[0]) for r in alone) > 1000                     # (the comparison is not one of empty strings)
     assert caller.call(sigs) == alone                               # the same reads as ONE batch: one beam launch
+    # a short read and a read without samples BETWEEN reads of several chunks (the chain calls nothing without samples)
+    empty = np.zeros(0, dtype=np.float32)
+    assert _beam_chain(empty, model, stride, gpu_device, posterior, temperature, 5, True) == ("", None, 0)
+    order = ("len9500", "len4999", None, "len23456", "len2", "len5001")
+    want = [alone[READS.index(n)] if n else ("", None, 0) for n in order]
+    assert caller.call([sigs[READS.index(n)] if n else empty for n in order]) == want
+    assert all(len(want[i][0]) > 0 for i in (0, 1, 3, 5))           # (not a comparison of empty calls)
 
 
 @pytest.mark.gpu

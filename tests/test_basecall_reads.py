@@ -105,6 +105,40 @@ def test_packing_plan(pack, width):
     assert all(s.ncol == 1 and s.reads == (s.first,) for s in short_slices)
 
 
+def test_transfer_layouts_and_room_of_a_hand_written_batch():
+    """Three reads of 9500, 3 and 5002 samples at stride 5 (two chunks, a short read between, two chunks): the byte
+    layouts of the upload and of the download, and every read's room, as literals worked out by hand from 16-byte
+    alignment and the stitching cuts (9500: rows [0, 950) + [50, 1000); 5002: [0, 500) + [499, 1000); 3: its own 2)."""
+    from taiyaki_amd import basecall
+    offsets = lambda lay: {k: v[0] for k, v in lay.fields.items()}  # noqa: E731
+    up = basecall._Layout([("signal", np.float32, 14505), ("sig_off", np.int64, 4), ("shift", np.float32, 3),
+                           ("scale", np.float32, 3)])
+    assert offsets(up) == dict(signal=0, sig_off=58032, shift=58064, scale=58080)
+    assert up.nbytes == 58092 and basecall._align(up.nbytes) == 58096
+    head = basecall._Layout([("seqlen", np.int32, 3), ("status", np.uint8, 16)])
+    assert offsets(head) == dict(seqlen=0, status=16) and head.nbytes == 32
+    counts = basecall.chunk_counts([9500, 3, 5002], bs.CHUNK, bs.OVERLAP)
+    assert counts.tolist() == [2, 0, 2]
+    off = basecall.room_offsets(counts, [9500, 3, 5002], 1001, [(1, 2)], bs.CHUNK, bs.OVERLAP, bs.STRIDE)
+    assert off.dtype == np.int64 and off.tolist() == [0, 1900, 1902, 2903]
+    for nmod, nbytes in ((0, 5824), (2, 29048)):
+        body = basecall._Layout([("seq", np.uint8, 2903), ("qual", np.uint8, 2903), ("mods", np.float32, 2903 * nmod)])
+        assert offsets(body) == dict(seq=0, qual=2912, mods=5824) and body.nbytes == nbytes
+    assert basecall._Layout([("seq", np.uint8, 2903)]).nbytes == 2903                  # a beam's download
+    # typed views of a host block and, by the same names, of a tensor; `count` overrides the field's length
+    import torch
+    host = np.arange(up.nbytes, dtype=np.uint8)
+    sig_off = up.view(host, "sig_off")
+    assert sig_off.dtype == np.int64 and sig_off.shape == (4,) and sig_off.base is not None
+    assert sig_off.tobytes() == host[58032:58064].tobytes() and up.view(host, "scale").tobytes() == host[58080:].tobytes()
+    dev = torch.from_numpy(host)
+    assert up.view(dev, "shift").dtype == torch.float32 and up.view(dev, "shift").numpy().tobytes() == host[58064:58076].tobytes()
+    assert up.view(dev, "signal", 1).shape == (1,) and up.view(dev, "sig_off").data_ptr() == dev.data_ptr() + 58032
+    # no read of a chunk or more: only the short ones have room
+    assert basecall.room_offsets(np.zeros(3, dtype=np.int64), [0, 3, 7], 0, [(1, 2), (2, 3)], bs.CHUNK, bs.OVERLAP,
+                                 bs.STRIDE).tolist() == [0, 0, 2, 5]
+
+
 def test_write_records():
     import io
     from taiyaki_amd import basecall
@@ -399,9 +433,10 @@ def test_basecaller_equals_the_chain_of_existing_operators(gpu_device, which):
                                      posterior=posterior, temperature=temperature, fastq=fastq, qscore_scale=0.9,
                                      qscore_offset=0.3, pack=False)
         assert caller.stride == stride
-        called = {}
+        called, alone = {}, {}
         for n, x in sigs.items():
-            (seq, q, nsample), = caller.call([x])
+            alone[n], = caller.call([x])
+            seq, q, nsample = alone[n]
             wseq, wq, wn = _reference_chain(x, model, stride, gpu_device, posterior, temperature, fastq, 0.9, 0.3, 16)
             tag = (which, n, posterior, temperature, fastq)
             assert nsample == wn == len(x) and seq == wseq, tag
@@ -414,6 +449,15 @@ def test_basecaller_equals_the_chain_of_existing_operators(gpu_device, which):
             called[n] = len(seq)
         print(which, "posterior", posterior, "temperature", temperature, "fastq", fastq, "bases called:", called)
         assert sum(called.values()) > 1000                          # (the comparison is not one of empty strings)
+        # ONE batch with a short read and a read without samples between reads of several chunks: every read's call is
+        # the one it got alone, above, where it was held against the chain (which calls nothing without samples)
+        empty = np.zeros(0, dtype=np.float32)
+        assert _reference_chain(empty, model, stride, gpu_device, posterior, temperature, fastq, 0.9, 0.3, 16) == \
+            ("", "" if fastq else None, 0)
+        batch = caller.call([sigs["len9500"], sigs["len4999"], empty, sigs["len23456"], sigs["len2"], sigs["len5001"]])
+        assert batch == [alone["len9500"], alone["len4999"], ("", "" if fastq else None, 0), alone["len23456"],
+                         alone["len2"], alone["len5001"]]
+        assert all(len(batch[i][0]) > 0 for i in (0, 1, 3, 5))      # (the equality above is not one of empty calls)
 
 
 def _columnwise(dev):
