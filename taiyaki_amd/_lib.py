@@ -33,6 +33,9 @@ WGRAD_LAB_LIBNAME = "libtaiyaki_amd_lstm_wgrad_lab.so"      # ... and its lab bu
 VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
 VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
 
+DECODE_VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_decode_varlen.h")
+DECODE_VARLEN_LIBNAME = "libtaiyaki_amd_decode_varlen.so"   # csrc/decode_varlen.hip: the decode operators with per-column lengths, header and library of its own
+
 _vp = ctypes.c_void_p
 _SCALARS = {"size_t": ctypes.c_size_t, "int": ctypes.c_int, "float": ctypes.c_float}
 
@@ -116,6 +119,11 @@ def _read_varlen_header():
 
 # the sixth: include/taiyaki_amd_rnn_varlen.h (libtaiyaki_amd_rnn_varlen.so), and its TK_RNN_KIND_* values
 VARLEN_SIGNATURES, VARLEN_DEFINES = _read_varlen_header()
+
+
+# the seventh: include/taiyaki_amd_decode_varlen.h (libtaiyaki_amd_decode_varlen.so)
+DECODE_VARLEN_SIGNATURES = {n: (r, a) for n, (r, a, _) in
+                            parse_prototypes(_blank_comments(open(DECODE_VARLEN_HEADER).read())).items()}
 
 
 class SeqLabels(ctypes.Structure):
@@ -212,6 +220,12 @@ def varlen_lib():
     """The recurrences' forward with per-column lengths (include/taiyaki_amd_rnn_varlen.h).  No fallback: a missing
     library raises."""
     return _load(os.path.join(CSRC, VARLEN_LIBNAME), VARLEN_SIGNATURES)
+
+
+def decode_varlen_lib():
+    """The decode operators with per-column lengths (include/taiyaki_amd_decode_varlen.h).  No fallback: a missing
+    library raises."""
+    return _load(os.path.join(CSRC, DECODE_VARLEN_LIBNAME), DECODE_VARLEN_SIGNATURES)
 
 
 def check(rc, what):

@@ -23,8 +23,8 @@ from taiyaki_amd import _lib, basecall_helpers, decode, decodeutil, flipflopfing
 Beam = collections.namedtuple("Beam", "width guided")       # bin/basecall.py's --beam
 Slice = collections.namedtuple("Slice", "short first ncol reads")
 Slice.__doc__ = """One model invocation of the packing plan: `ncol` columns.  short=False: columns [first, first + ncol)
-of the batch's chunk tensor; short=True: the one chunk, of its own length, of read `first`.  `reads`: the read of
-every column."""
+of the batch's chunk tensor; short=True: reads shorter than a chunk, each one chunk of its own length -- read `first`
+alone, or (batch_short) the reads `reads` as zero-padded columns of one tensor.  `reads`: the read of every column."""
 
 
 def chunk_counts(lengths, chunk_size, overlap):
@@ -35,11 +35,12 @@ def chunk_counts(lengths, chunk_size, overlap):
     return np.where(lengths < chunk_size, 0, (lengths - chunk_size + step - 1) // step + 1)
 
 
-def packing_plan(lengths, chunk_size, overlap, max_concurrent_chunks, pack=True):
+def packing_plan(lengths, chunk_size, overlap, max_concurrent_chunks, pack=True, batch_short=False):
     """The model invocations for reads of `lengths` samples, host arithmetic on lengths alone.  Every chunk appears
     once, in read order; no slice is wider than `max_concurrent_chunks`.  pack=True fills every slice across read
     boundaries; pack=False splits per read, as `torch.split` does in bin/basecall.py:208.  Reads shorter than
-    `chunk_size` follow as slices of one column each (reads without samples get none)."""
+    `chunk_size` follow as slices of one column each (reads without samples get none) or -- batch_short -- in read
+    order as slices of up to `max_concurrent_chunks` columns."""
     counts = chunk_counts(lengths, chunk_size, overlap)
     owner = np.repeat(np.arange(len(counts)), counts)
     plan = []
@@ -52,9 +53,10 @@ def packing_plan(lengths, chunk_size, overlap, max_concurrent_chunks, pack=True)
         for first in range(lo, hi, max_concurrent_chunks):
             ncol = min(max_concurrent_chunks, hi - first)
             plan.append(Slice(False, first, ncol, tuple(int(r) for r in owner[first:first + ncol])))
-    for r, n in enumerate(lengths):
-        if 0 < n < chunk_size:
-            plan.append(Slice(True, r, 1, (r,)))
+    short = [r for r, n in enumerate(lengths) if 0 < n < chunk_size]
+    width = max_concurrent_chunks if batch_short else 1
+    for k in range(0, len(short), width):
+        plan.append(Slice(True, short[k], len(short[k:k + width]), tuple(short[k:k + width])))
     return plan
 
 
@@ -142,10 +144,14 @@ def room_offsets(counts, lens, nrow, short, chunk_size, overlap, stride):
     return np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
 
 
-Segment = collections.namedtuple("Segment", "r0 nread ncol starts ends read_chunk_off nrow path err trans weights")
+Segment = collections.namedtuple("Segment", "r0 nread ncol starts ends read_chunk_off nrow path err trans weights "
+                                 "rooms rows", defaults=(None, None))
 Segment.__doc__ = """A decoded chunk tensor of `ncol` columns and `nrow` rows, and the reads [r0, r0 + nread) it belongs
-to: the batch's chunk tensor (r0 = 0, all reads) or a short read's own chunk (nread = 1).  `path`, `err` (fastq),
-`weights` (call_mods) on the Viterbi path, `trans` with a beam; `starts`, `ends`, `read_chunk_off` from the gather."""
+to: the batch's chunk tensor (r0 = 0, all reads), a short read's own chunk (nread = 1), or -- batch_short -- a slice of
+short reads as padded columns (nread = ncol; r0 counts in the call's extended numbering, where the batched short reads
+follow the call's reads: see `_upload`).  `path`, `err` (fastq), `weights` (call_mods) on the Viterbi path, `trans` with
+a beam; `starts`, `ends`, `read_chunk_off` from the gather.  Padded columns only: `rooms`, every read's room in the
+output (host), and `rows`, every column's true row count (device int32)."""
 
 
 def _at(t, r0):     # &t[r0] of a per-read device array: where a segment's reads start in it
@@ -162,13 +168,25 @@ class Basecaller:
     splits them per read, exactly as the reference's loop does.  `beam`: (width, guided) decodes every read with the
     hash beam search on its stitched scores instead of the Viterbi path (`beam_cut` as decodeutil.beamsearch's); no
     quality strings then.  `mod_output`: the model is a cat-mod model (its last layer GlobalNormFlipFlopCatMod) and
-    `call_mods` is wanted; `call` gives what it gives without it."""
+    `call_mods` is wanted; `call` gives what it gives without it.  `batch_short`: the reads shorter than a chunk go
+    through the network and the decode operators as zero-padded columns of shared tensors (`layers.forward_varlen`, the
+    operators of include/taiyaki_amd_decode_varlen.h), up to max_concurrent_chunks of them at a time, instead of one by
+    one; the model must be one `forward_varlen` has a rule for (TypeError otherwise).  A read's call may differ from the
+    one it gets alone where the network's GEMMs round differently at another column count."""
 
     def __init__(self, model, stride=None, chunk_size=1000, overlap=100, max_concurrent_chunks=128, alphabet="ACGT",
                  posterior=True, temperature=1.0, fastq=False, qscore_scale=1.0, qscore_offset=0.0, reverse=False,
-                 pack=True, beam=None, beam_cut=0.0, mod_output=False):
+                 pack=True, beam=None, beam_cut=0.0, mod_output=False, batch_short=False):
         self.beam, self.beam_cut = check_beam(beam, beam_cut, len(alphabet), fastq), float(beam_cut)
         self.can_nmods = check_mods(model, mod_output, beam, len(alphabet))
+        self.batch_short = bool(batch_short)
+        if self.batch_short:
+            if not isinstance(model, layers.Serial):
+                raise TypeError("Basecaller: batch_short needs a layers.Serial that layers.forward_varlen has a rule "
+                                "for, not %s" % type(model).__name__)
+            # (TypeError for a layer forward_varlen does not know) -> the strides that turn samples into rows
+            self._row_strides = [layer.stride for layer, _, _ in layers._varlen_layers(model)
+                                 if isinstance(layer, layers.Convolution)]
         self.model = model
         self.device = basecall_helpers.get_model_device(model)
         if self.device.type != "cuda":
@@ -186,7 +204,8 @@ class Basecaller:
         self.reverse, self.pack = bool(reverse), bool(pack)
 
     def plan(self, lengths):
-        return packing_plan(lengths, self.chunk_size, self.overlap, self.max_concurrent_chunks, self.pack)
+        return packing_plan(lengths, self.chunk_size, self.overlap, self.max_concurrent_chunks, self.pack,
+                            self.batch_short)
 
     def call(self, signals, read_params=None):
         return self._call(signals, read_params, False)[0]
@@ -217,8 +236,10 @@ class Basecaller:
             counts = chunk_counts(c.lens, self.chunk_size, self.overlap)
             chunks, geo = self._chunk(c, int(counts.sum()))                             # 3.
             batch, short = self._network(c, self.plan(c.lens), chunks, geo, want_mods)  # 4.-8.
-            off = room_offsets(counts, c.lens, batch.nrow if batch else 0, [(s.r0, s.nrow) for s in short],
-                               self.chunk_size, self.overlap, self.stride)
+            rooms = [(s.r0 + i, n) for s in short for i, n in enumerate([s.nrow] if s.rooms is None else s.rooms)]
+            grow = np.zeros(c.nvirt - c.nread, dtype=np.int64)       # (the batched short reads: no chunk of the batch's)
+            off = room_offsets(np.concatenate([counts, grow]), np.concatenate([c.lens, grow]),
+                               batch.nrow if batch else 0, rooms, self.chunk_size, self.overlap, self.stride)
             # Order is behaviour: the batch's launch comes first and writes a length of 0 for every read without a
             # chunk in it; the short reads follow in plan order, each over its own slot.
             segs = ([batch] if batch else []) + short
@@ -228,27 +249,40 @@ class Basecaller:
 
     def _upload(self, sigs, params):
         """Step 1, the ONE upload: signals | offsets | the caller's shift and scale -> the call's device state.  The
-        ONE download starts with its `head`: seqlen | status (the decoders put seq | qual | mods behind it)."""
+        ONE download starts with its `head`: seqlen | status (the decoders put seq | qual | mods behind it).
+        batch_short: the reads shorter than a chunk, in read order, are numbered nread, nread + 1, ... as well (`nvirt`
+        entries in all): under those numbers they have their rooms, call lengths and scales, contiguous per slice, which
+        is what the tail's per-read arrays need; the upload carries their list, the download is mapped back."""
         nread, lens = len(sigs), np.array([len(s) for s in sigs], dtype=np.int64)
         nsig = int(lens.sum())
+        short = np.flatnonzero((lens > 0) & (lens < self.chunk_size)).astype(np.int32) if self.batch_short else None
+        nvirt = nread + (len(short) if self.batch_short else 0)
         up = _Layout([("signal", np.float32, nsig), ("sig_off", np.int64, nread + 1), ("shift", np.float32, nread),
-                      ("scale", np.float32, nread)])
+                      ("scale", np.float32, nread)] + ([("short", np.int32, len(short))] if self.batch_short else []))
         host = np.zeros(_align(up.nbytes), dtype=np.uint8)
         up.view(host, "signal")[:] = np.concatenate(sigs) if nsig else 0
         up.view(host, "sig_off")[:] = np.concatenate([[0], np.cumsum(lens)])
         up.view(host, "shift")[:] = [p[0] if p is not None else 0 for p in params]
         up.view(host, "scale")[:] = [p[1] if p is not None else 1 for p in params]
+        if self.batch_short:
+            up.view(host, "short")[:] = short
         dev = torch.from_numpy(host).to(self.device)
-        head_layout = _Layout([("seqlen", np.int32, nread), ("status", np.uint8, 16)])
+        head_layout = _Layout([("seqlen", np.int32, nvirt), ("status", np.uint8, 16)])
         head = torch.zeros(head_layout.nbytes, dtype=torch.uint8, device=self.device)
         return types.SimpleNamespace(
-            L=_lib.basecall_lib(), stream=_lib.stream_ptr(), nread=nread, lens=lens, nsig=nsig,
+            L=_lib.basecall_lib(), stream=_lib.stream_ptr(), nread=nread, lens=lens, nsig=nsig, nvirt=nvirt,
+            short=short, short_dev=up.view(dev, "short") if self.batch_short else None,
             signal=up.view(dev, "signal", max(nsig, 1)), sig_off=up.view(dev, "sig_off"), shift=up.view(dev, "shift"),
             scale=up.view(dev, "scale"), head_layout=head_layout, head=head, seqlen=head_layout.view(head, "seqlen"),
             status=head_layout.view(head, "status"))
 
     def _normalisation(self, c, given):
         """Step 2: median / MAD where the caller gave no parameters, beside those it gave."""
+        self._med_mad(c, given)
+        if self.batch_short:        # the scales in the extended numbering (a refused read is refused under either number)
+            c.scale = torch.cat([c.scale, c.scale.index_select(0, c.short_dev)])
+
+    def _med_mad(self, c, given):
         if given.all():
             return
         medmad = torch.empty(2, c.nread, dtype=torch.float32, device=self.device)
@@ -280,11 +314,15 @@ class Basecaller:
     def _network(self, c, plan, chunks, geo, want_mods):
         """Steps 4-8 over the plan: the network on column slices of the batch's chunk tensor and on each short read as
         one chunk of its own length (step 3 for it), then the operators -> (the batch's segment or None, the short)."""
-        dev, outs, short = self.device, [], []
+        dev, outs, short, k0 = self.device, [], [], 0
         one = torch.tensor([0, 1], dtype=torch.int64, device=dev)      # read_chunk_off of a read called alone
         for sl in plan:
             if not sl.short:
                 outs.append(self.model(chunks[:, sl.first:sl.first + sl.ncol].contiguous()))
+                continue
+            if self.batch_short:
+                short.append(self._short_slice(c, sl, k0, want_mods))
+                k0 += sl.ncol
                 continue
             own = torch.empty(int(c.lens[sl.first]), 1, 1, dtype=torch.float32, device=dev)
             own_geo = torch.empty(3, 2, dtype=torch.int64, device=dev)
@@ -294,16 +332,36 @@ class Basecaller:
         batch = Segment(0, c.nread, chunks.shape[1], *geo, *self._operators(outs, want_mods)) if outs else None
         return batch, short
 
-    def _operators(self, outs, want_mods):
+    def _short_slice(self, c, sl, k0, want_mods):
+        """Steps 3-8 for a slice of short reads, the k0-th .. of the call's, as zero-padded columns: ONE gather, ONE
+        network pass, the operators with the columns' lengths -> a Segment in the extended numbering.  Every column is
+        a read of one chunk: starts 0, ends its length, and a path whose rows behind the length repeat the last state."""
+        dev, lens = self.device, c.lens[list(sl.reads)]
+        x = torch.empty(int(lens.max()), sl.ncol, 1, dtype=torch.float32, device=dev)
+        samples = torch.empty(sl.ncol, dtype=torch.int32, device=dev)
+        _lib.check(_lib.decode_varlen_lib().tk_basecall_gather_columns_dev(
+            _lib.ptr(c.signal), _lib.ptr(c.sig_off), c.nread, c.nsig, _lib.ptr(c.shift), _lib.ptr(c.scale),
+            _at(c.short_dev, k0), sl.ncol, x.shape[0], _lib.ptr(x), _lib.ptr(samples), _lib.ptr(c.status), c.stream),
+            "tk_basecall_gather_columns_dev")
+        out, out_lens = layers.forward_varlen(self.model, x, lens)
+        rows = samples
+        for stride in self._row_strides:
+            rows = layers.conv_out_lengths(rows, stride)
+        ops = self._operators([out], want_mods, rows)
+        rooms = np.full(sl.ncol, ops[0], dtype=np.int64) if self.beam else np.asarray(out_lens, dtype=np.int64) + 1
+        return Segment(c.nread + k0, sl.ncol, sl.ncol, torch.zeros(sl.ncol, dtype=torch.int64, device=dev),
+                       samples.long(), torch.arange(sl.ncol + 1, dtype=torch.int64, device=dev), *ops, rooms, rows)
+
+    def _operators(self, outs, want_mods, lengths=None):
         """Steps 5-8 on the network's outputs for one chunk tensor (categorical columns lie behind the scores):
         temperature, posterior, the Viterbi path and its error probabilities, or the scores for a beam -> a Segment's
-        last five fields."""
+        nrow, path, err, trans, weights.  `lengths`: the rows of every column of a padded tensor."""
         trans = torch.cat([o[:, :, :self.n_can_state] for o in outs], 1) * self.temperature
         if self.posterior:
-            trans = (decode.flipflop_make_trans(trans) + 1e-8).log()
+            trans = (decode.flipflop_make_trans(trans, lengths=lengths) + 1e-8).log()
         if self.beam:
             return trans.shape[0], None, None, trans.contiguous(), None
-        path = decode.flipflop_viterbi_path(trans)
+        path = decode.flipflop_viterbi_path(trans, lengths=lengths)
         err = qscores.errprobs_from_trans(trans, path) if self.fastq else None
         weights = torch.cat([o[:, :, self.n_can_state:] for o in outs], 1).contiguous() if want_mods else None
         return path.shape[0], path, err, None, weights
@@ -350,9 +408,12 @@ class Basecaller:
         packed buffer, read r's rows from off[r], and ONE launch of the beam search, which also writes the calls."""
         row_off = torch.from_numpy(off).to(self.device)
         packed = torch.empty(int(off[-1]), self.n_can_state, dtype=torch.float32, device=self.device)
-        nrows = torch.zeros(c.nread, dtype=torch.int32, device=self.device)
+        nrows = torch.zeros(c.nvirt, dtype=torch.int32, device=self.device)
         for seg in segs:
             self._launch_stitch(c, seg, row_off, packed, nrows)
+            if seg.rows is not None:        # padded columns: the search stops at every read's own last row
+                own = nrows[seg.r0:seg.r0 + seg.nread]
+                own.copy_(torch.minimum(own, seg.rows))
         seq = decodeutil.beamsearch_packed(packed, row_off, nrows, int(np.diff(off).max()), self.alphabet,
                                            self.beam.width, self.beam_cut, self.beam.guided, c.status, c.seqlen)[3]
         cap = max(int(off[-1]), 1)
@@ -365,7 +426,10 @@ class Basecaller:
         if bits & _lib.BASECALL_DEFINES["TK_STATUS_CHUNK_PLAN"]:
             raise RuntimeError("basecall: the device's chunk plan disagrees with the host's (status %#x)" % bits)
         called, got = c.head_layout.view(got, "seqlen"), got[c.head.numel():]
-        spans = [slice(int(off[r]), int(off[r]) + int(called[r])) for r in range(c.nread)]
+        where = np.arange(c.nread)
+        if self.batch_short:
+            where[c.short] = c.nread + np.arange(len(c.short))      # the batched short reads: back to read order
+        spans = [slice(int(off[v]), int(off[v]) + int(called[v])) for v in where]
         seq = [layout.view(got, "seq")[s].tobytes().decode("ascii") for s in spans]
         qual = [layout.view(got, "qual")[s].tobytes().decode("ascii") if self.fastq else None for s in spans]
         mods = layout.view(got, "mods").reshape(-1, sum(self.can_nmods)) if want_mods else None

@@ -31,8 +31,15 @@ each ending in its downloads:
 All at pack=False, so the three sides give equal calls and call_mods and chain equal scores (compared first, bit for
 bit; a mismatch ends the run).  Prints one JSON line.
 
+--short times, instead of all the above, batches of 1, 8 and 64 reads of 300 - 4 900 samples (every one shorter than
+a chunk) on the two seeded models, excited so that they call bases: whole calls ending in their downloads, with
+batch_short=False (a network pass and three or four decode launches per read) against batch_short=True (the reads as
+padded columns of one tensor), alternating --short-steps times after one warm-up each.  Checked first: both sides
+report every read's sample count and well-formed records (the sequences may differ where the network's GEMMs round
+differently at another column count; how many are equal is reported).  Prints one JSON line.
+
     python tools/basecallbench.py [--chunks 128] [--blocks 1000] [--reads-per-batch 8] [--steps 20] [--warmup 3]
-                                  [--beam 5] [--beam-steps 5] [--mods] [--mods-steps 5]
+                                  [--beam 5] [--beam-steps 5] [--mods] [--mods-steps 5] [--short] [--short-steps 5]
 """
 import argparse
 import json
@@ -188,6 +195,42 @@ def mods_rows(size, steps, dev):
                 pack=False, rows=rows)
 
 
+def short_rows(size, steps, dev):
+    rs = np.random.RandomState(19)
+    sigs = [(90 + 12 * rs.standard_normal(int(n))).astype(np.float32) for n in rs.randint(300, 4901, size=64)]
+    out = {}
+    for name, make in (("mGru_flipflop", models.mGru_flipflop), ("mLstm_flipflop", models.mLstm_flipflop)):
+        torch.manual_seed(17)
+        net = synth.excite_network(make(size=size)).to(dev).eval()
+        callers = {k: basecall.Basecaller(net, fastq=True, batch_short=v) for k, v in (("alone", False), ("batched", True))}
+        rows = {}
+        for nread in (1, 8, 64):
+            batch = sigs[:nread]
+            sides = {k: (lambda c=c: c.call(batch)) for k, c in callers.items()}
+            first = {k: fn() for k, fn in sides.items()}                       # (the warm-up at the timed shapes)
+            for k, res in first.items():
+                if [r[2] for r in res] != [len(x) for x in batch] or not all(
+                        len(q) == len(s) and set(s) <= set("ACGT") for s, q, _ in res):
+                    raise SystemExit("basecallbench --short: %s gives a malformed record; nothing timed" % k)
+            same = sum(a[0] == b[0] for a, b in zip(first["alone"], first["batched"]))
+            times = {k: [] for k in sides}
+            for _ in range(steps):
+                for k, fn in sides.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()                                                        # ends in its download
+                    times[k].append(time.perf_counter() - t0)
+            row = dict(reads=nread, samples=int(sum(map(len, batch))), samples_longest=int(max(map(len, batch))),
+                       bases=sum(len(r[0]) for r in first["batched"]), reads_with_equal_sequences=same)
+            for k, t in times.items():
+                row[k] = dict(median_ms=round(1e3 * float(np.median(t)), 2), min_ms=round(1e3 * float(np.min(t)), 2),
+                              max_ms=round(1e3 * float(np.max(t)), 2), reads_per_s=round(nread / float(np.median(t)), 2))
+            row["alone_over_batched"] = round(float(np.median(times["alone"]) / np.median(times["batched"])), 2)
+            rows[str(nread)] = row
+        out[name] = dict(size=size, stride=callers["alone"].stride, steps=steps, rows=rows)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chunks", type=int, default=128)
@@ -203,12 +246,18 @@ def main():
     ap.add_argument("--mods", action="store_true",
                     help="time call_mods, call and the host chain on a cat-mod model at 1, 8, 64 reads (nothing else)")
     ap.add_argument("--mods-steps", type=int, default=5)
+    ap.add_argument("--short", action="store_true",
+                    help="time batch_short False against True at 1, 8, 64 reads shorter than a chunk (nothing else)")
+    ap.add_argument("--short-steps", type=int, default=5)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("basecallbench needs a GPU (the basecaller has no CPU fallback)")
     dev = torch.device("cuda:0")
     if a.mods:
         print(json.dumps(dict(mods=mods_rows(a.size, a.mods_steps, dev))))
+        return
+    if a.short:
+        print(json.dumps(dict(short=short_rows(a.size, a.short_steps, dev))))
         return
     L = _lib.basecall_lib()
     T, N = a.blocks, a.chunks
