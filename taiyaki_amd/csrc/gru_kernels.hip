@@ -178,7 +178,14 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
             const float rg = sigmoidf(gq[0] + acc[0][0] + bh[0]), zg = sigmoidf(gq[1] + acc[1][0] + bh[1]);
             const float qv = acc[2][0] + bh[2];
             const float ng = tanhf(gq[2] + rg * qv);
-            float h = (1.f - zg) * ng + zg * hprev;
+            // (two products and a sum, no contraction: left to the compiler, the saving kernel at H 32 and 64 took
+            // fma(zg, hprev, (1 - zg) ng) where its VL twin, like every instantiation at H >= 96, multiplies the pair
+            // with one v_pk_mul_f32 and adds -- lengths = NULL then differed from the saving forward in the last bit)
+            float h;
+            {
+#pragma clang fp contract(off)
+                h = (1.f - zg) * ng + zg * hprev;
+            }
             if constexpr (VL) {
                 if (t >= len) h = 0.f;
             }
