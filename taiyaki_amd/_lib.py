@@ -33,6 +33,8 @@ WGRAD_LAB_LIBNAME = "libtaiyaki_amd_lstm_wgrad_lab.so"      # ... and its lab bu
 VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
 VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
 
+VARLEN_TRAIN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen_train.h")
+VARLEN_TRAIN_LIBNAME = "libtaiyaki_amd_rnn_varlen_train.so"     # the same two sources built -DTK_RNN_VARLEN_TRAIN: the training pair with per-column lengths
 DECODE_VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_decode_varlen.h")
 DECODE_VARLEN_LIBNAME = "libtaiyaki_amd_decode_varlen.so"   # csrc/decode_varlen.hip: the decode operators with per-column lengths, header and library of its own
 
@@ -124,6 +126,11 @@ VARLEN_SIGNATURES, VARLEN_DEFINES = _read_varlen_header()
 # the seventh: include/taiyaki_amd_decode_varlen.h (libtaiyaki_amd_decode_varlen.so)
 DECODE_VARLEN_SIGNATURES = {n: (r, a) for n, (r, a, _) in
                             parse_prototypes(_blank_comments(open(DECODE_VARLEN_HEADER).read())).items()}
+
+
+# the eighth: include/taiyaki_amd_rnn_varlen_train.h (libtaiyaki_amd_rnn_varlen_train.so)
+VARLEN_TRAIN_SIGNATURES = {n: (r, a) for n, (r, a, _) in
+                           parse_prototypes(_blank_comments(open(VARLEN_TRAIN_HEADER).read())).items()}
 
 
 class SeqLabels(ctypes.Structure):
@@ -220,6 +227,12 @@ def varlen_lib():
     """The recurrences' forward with per-column lengths (include/taiyaki_amd_rnn_varlen.h).  No fallback: a missing
     library raises."""
     return _load(os.path.join(CSRC, VARLEN_LIBNAME), VARLEN_SIGNATURES)
+
+
+def varlen_train_lib():
+    """The recurrences' training pair with per-column lengths (include/taiyaki_amd_rnn_varlen_train.h).  No fallback: a
+    missing library raises."""
+    return _load(os.path.join(CSRC, VARLEN_TRAIN_LIBNAME), VARLEN_TRAIN_SIGNATURES)
 
 
 def decode_varlen_lib():

@@ -100,6 +100,24 @@ int gru_forward_varlen_dispatch(const float *gx, const float *whh, const float *
                                 size_t N, size_t H, int reverse, int cu_count, float *y, void *ws, size_t wsb,
                                 uint32_t *status, hipStream_t stream);
 
+// ... and their -DTK_RNN_VARLEN_TRAIN build (libtaiyaki_amd_rnn_varlen_train.so; rnn_varlen_train_api.hip defines the C
+// entries)
+size_t lstm_varlen_train_workspace_bytes(size_t N, size_t H, int cu_count);
+int lstm_forward_varlen_save_dispatch(const float *gx, const float *whh, const int32_t *lengths, size_t T, size_t N,
+                                      size_t H, int reverse, int cu_count, float *y, float *gates, float *cell,
+                                      void *ws, size_t wsb, uint32_t *status, hipStream_t stream);
+int lstm_backward_varlen_dispatch(const float *whh, const float *gates, const float *cell, const float *dy,
+                                  const int32_t *lengths, size_t T, size_t N, size_t H, int reverse, int cu_count,
+                                  float *dgates, void *ws, size_t wsb, uint32_t *status, hipStream_t stream);
+size_t gru_varlen_train_workspace_bytes(size_t N, size_t H, int cu_count);
+int gru_forward_varlen_save_dispatch(const float *gx, const float *whh, const float *bhh, const int32_t *lengths,
+                                     size_t T, size_t N, size_t H, int reverse, int cu_count, float *y, float *gates,
+                                     float *q, void *ws, size_t wsb, uint32_t *status, hipStream_t stream);
+int gru_backward_varlen_dispatch(const float *whh, const float *y, const float *gates, const float *q,
+                                 const float *dy, const int32_t *lengths, size_t T, size_t N, size_t H, int reverse,
+                                 int cu_count, float *dgates, float *dq, void *ws, size_t wsb, uint32_t *status,
+                                 hipStream_t stream);
+
 // conv_kernels.hip
 bool conv_small_supported(size_t cin, size_t cout, size_t winlen, size_t stride);
 size_t conv_small_workspace_bytes(size_t T, size_t N, size_t cin, size_t cout, size_t winlen, int cu_count);

@@ -20,8 +20,9 @@
 // in registers and stored right after step s + 1's.  Both drain under the matvec; the granule publish is the last
 // memory operation of a step.  Every sum runs in a fixed order: a launch is bit-reproducible.
 //
-// Two builds of this one source, as for lstm_kernels.hip: the flip-flop library takes the forward and the backward,
-// -DTK_RNN_VARLEN (libtaiyaki_amd_rnn_varlen.so) the forward alone in its VL form.
+// Three builds of this one source, as for lstm_kernels.hip: the flip-flop library takes the forward and the backward,
+// -DTK_RNN_VARLEN (libtaiyaki_amd_rnn_varlen.so) the forward alone in its VL form with nothing saved,
+// -DTK_RNN_VARLEN_TRAIN (libtaiyaki_amd_rnn_varlen_train.so) the saving forward and the backward in their VL form.
 #include "dispatch.h"
 #include "ff_common.h"
 #include "rnn_common.h"
@@ -45,8 +46,9 @@ constexpr int gru_threads() { return U == H ? 4 * U : 512; }
 // the 3 hidden-side sums of column col(kp) and runs its cell update.
 //
 // VL: column n has lengths[n] steps (NULL: T).  A step at t >= lengths[n] leaves h = 0, writes y = 0 and hands h = 0
-// on like any other step; gates and qout are not written (the pointers are not read).
-template <int H, int U, int C, bool VL = false>
+// on like any other step.  SAVE: gates and qout are written where they are not NULL (with VL: 0 on a step at or beyond
+// the length); not SAVE: they are not written (the pointers are not read).
+template <int H, int U, int C, bool VL = false, bool SAVE = !VL>
 __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
     const float *__restrict__ gx, const float *__restrict__ whh, const float *__restrict__ bhh, int T, int N,
     int reverse, int ngroups, float *__restrict__ y, float *__restrict__ gates, float *__restrict__ qout, u64 *hbuf,
@@ -124,7 +126,7 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
             if (valid) {
                 const size_t row = (size_t)(reverse ? t + 1 : t - 1) * N + n;
                 y[row * H + j0 + u] = held[0];
-                if constexpr (!VL) {
+                if constexpr (SAVE) {
                     if (gates) {
                         float *gp = gates + row * H3 + j0 + u;
 #pragma unroll
@@ -175,9 +177,9 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
         }
 
         if (cell_lane) {
-            const float rg = sigmoidf(gq[0] + acc[0][0] + bh[0]), zg = sigmoidf(gq[1] + acc[1][0] + bh[1]);
-            const float qv = acc[2][0] + bh[2];
-            const float ng = tanhf(gq[2] + rg * qv);
+            float rg = sigmoidf(gq[0] + acc[0][0] + bh[0]), zg = sigmoidf(gq[1] + acc[1][0] + bh[1]);
+            float qv = acc[2][0] + bh[2];
+            float ng = tanhf(gq[2] + rg * qv);
             // (two products and a sum, no contraction: left to the compiler, the saving kernel at H 32 and 64 took
             // fma(zg, hprev, (1 - zg) ng) where its VL twin, like every instantiation at H >= 96, multiplies the pair
             // with one v_pk_mul_f32 and adds -- lengths = NULL then differed from the saving forward in the last bit)
@@ -187,7 +189,10 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
                 h = (1.f - zg) * ng + zg * hprev;
             }
             if constexpr (VL) {
-                if (t >= len) h = 0.f;
+                if (t >= len) {
+                    h = 0.f;
+                    if constexpr (SAVE) rg = zg = ng = qv = 0.f;
+                }
             }
             hprev = h;
             if (s + 1 < T) {
@@ -209,7 +214,7 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
     if (valid && T > 0) {
         const size_t row = (size_t)(reverse ? 0 : T - 1) * N + n;
         y[row * H + j0 + u] = held[0];
-        if constexpr (!VL) {
+        if constexpr (SAVE) {
             if (gates) {
                 float *gp = gates + row * H3 + j0 + u;
 #pragma unroll
@@ -227,11 +232,16 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
 //   dh_rec of the step before = dh z + W_hh^T [dr_pre, dz_pre, dq]
 // Lane (k, rp), rp < RP = threads / H, holds W_hh[every RP-th owned row from rp, k] of the owned 3 U rows; the RP partial sums meet in
 // LDS.  G = 1: the cell lane of (column, unit) adds them there.  G > 1: pbuf [2][ngroups][G producers][C][H] granules.
-template <int H, int U, int C>
+//
+// VL: column n has lengths[n] steps (NULL: T).  A step at t >= lengths[n] writes dgates = 0 and dq = 0 and hands on
+// dh = 0 (its rows in LDS are 0, so is what it publishes; the carried dh z is 0), like any other step.  The mask is a
+// select behind the cell update: dy and the saved rows beyond the length are loaded and never used.
+template <int H, int U, int C, bool VL = false>
 __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_bwd_kernel(
     const float *__restrict__ whh, const float *__restrict__ y, const float *__restrict__ gates,
     const float *__restrict__ qin, const float *__restrict__ dy, int T, int N, int reverse, int ngroups,
-    float *__restrict__ dgates, float *__restrict__ dqout, u64 *pbuf, uint32_t *status) {
+    float *__restrict__ dgates, float *__restrict__ dqout, u64 *pbuf, uint32_t *status,
+    const int32_t *__restrict__ lengths) {
     constexpr int NT = gru_threads<H, U>();
     constexpr int G = H / U;
     constexpr int RP = NT / H;                        // row partitions
@@ -267,6 +277,8 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_bwd_kernel(
     const int n = n0 + cc;
     const bool valid = cell_lane && n < N;
     float carry = 0.f;                                // dh z of the step before
+    int len = 0;                                       // VL: the steps of this lane's column
+    if constexpr (VL) len = !valid ? 0 : lengths ? lengths[n] : T;
     if (tid == 0) give_up = 0;
 
     // this step's inputs, loaded one step ahead: dy, r, z, n, q and h_prev (y of the recurrence's previous step)
@@ -335,13 +347,20 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_bwd_kernel(
         asm volatile("" ::: "memory");                   // the deferred stores and the prefetch stay here
 
         if (cell_lane) {
-            const float rg = in[1], zg = in[2], ng = in[3], qv = in[4], hp = in[5];
+            const float rg = in[1], zg = in[2], ng = in[3], qv = in[4];
+            float hp = in[5];
+            if constexpr (VL) {
+                if (tp >= len) hp = 0.f;                  // (reverse: the column's first step starts from h = 0)
+            }
             const float dh = in[0] + dhr + carry;
-            const float dn = dh * (1.f - zg) * (1.f - ng * ng);
-            const float dz = dh * (hp - ng) * zg * (1.f - zg);
-            const float dq = dn * rg;
-            const float dr = dn * qv * rg * (1.f - rg);
+            float dn = dh * (1.f - zg) * (1.f - ng * ng);
+            float dz = dh * (hp - ng) * zg * (1.f - zg);
+            float dq = dn * rg;
+            float dr = dn * qv * rg * (1.f - rg);
             carry = dh * zg;
+            if constexpr (VL) {
+                if (t >= len) carry = dn = dz = dq = dr = 0.f;
+            }
             held[0] = dr;
             held[1] = dz;
             held[2] = dn;
@@ -387,7 +406,7 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_bwd_kernel(
     }
 }
 
-#endif  // TK_RNN_VARLEN
+#endif  // TK_RNN_VARLEN: no backward
 
 // A launch: U units and C columns per workgroup, groups of G = H / U workgroups; false where the kernels do not
 // run.  H <= 128 is one workgroup per group (any N); H = 256 hands h between the 4 members of a group, so its grid
@@ -434,12 +453,12 @@ size_t gru_ws_bytes(size_t H, const Plan &p, bool backward) {
         default: return TK_ERR_UNSUPPORTED;                                                                       \
     }
 
-template <bool VL>
+template <bool VL, bool SAVE>
 int launch_fwd(const Plan &p, size_t H, hipStream_t st, const float *gx, const float *whh, const float *bhh, int T,
                int N, int rev, float *y, float *gates, float *q, u64 *ws, uint32_t *status, const int32_t *lengths) {
 #define TK_GRU_FWD(HH, UU, CC)                                                                                    \
     case HH * 10 + CC:                                                                                            \
-        hipLaunchKernelGGL((gru_fwd_kernel<HH, UU, CC, VL>), dim3(p.grid), dim3(gru_threads<HH, UU>()), 0, st,    \
+        hipLaunchKernelGGL((gru_fwd_kernel<HH, UU, CC, VL, SAVE>), dim3(p.grid), dim3(gru_threads<HH, UU>()), 0, st,    \
                            gx, whh, bhh, T, N, rev, p.groups, y, gates, q, ws, status, lengths);                  \
         break;
     TK_GRU_SWITCH(TK_GRU_FWD)
@@ -448,13 +467,14 @@ int launch_fwd(const Plan &p, size_t H, hipStream_t st, const float *gx, const f
 }
 
 #ifndef TK_RNN_VARLEN
+template <bool VL>
 int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const float *y, const float *gates,
                const float *q, const float *dy, int T, int N, int rev, float *dg, float *dq, u64 *ws,
-               uint32_t *status) {
+               uint32_t *status, const int32_t *lengths) {
 #define TK_GRU_BWD(HH, UU, CC)                                                                                    \
     case HH * 10 + CC:                                                                                            \
-        hipLaunchKernelGGL((gru_bwd_kernel<HH, UU, CC>), dim3(p.grid), dim3(gru_threads<HH, UU>()), 0, st,        \
-                           whh, y, gates, q, dy, T, N, rev, p.groups, dg, dq, ws, status);                        \
+        hipLaunchKernelGGL((gru_bwd_kernel<HH, UU, CC, VL>), dim3(p.grid), dim3(gru_threads<HH, UU>()), 0, st,    \
+                           whh, y, gates, q, dy, T, N, rev, p.groups, dg, dq, ws, status, lengths);               \
         break;
     TK_GRU_SWITCH(TK_GRU_BWD)
 #undef TK_GRU_BWD
@@ -490,7 +510,56 @@ int gru_forward_varlen_dispatch(const float *gx, const float *whh, const float *
         int rc = zero_ws(ws, need, stream);
         if (rc != TK_OK) return rc;
     }
-    return launch_fwd<true>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, nullptr, nullptr,
+    return launch_fwd<true, false>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, nullptr, nullptr,
+                            static_cast<u64 *>(ws), status, lengths);
+}
+#elif defined(TK_RNN_VARLEN_TRAIN)
+// The training pair with per-column lengths (include/taiyaki_amd_rnn_varlen_train.h): the plans, grids and granule
+// buffers of gru_forward_dispatch / gru_backward_dispatch at the same (N, H, cu_count); the workspace is the
+// backward's, as tk_gru_workspace_bytes is.  Never 0 where the kernels run.
+size_t gru_varlen_train_workspace_bytes(size_t N, size_t H, int cu_count) {
+    Plan p;
+    if (!gru_plan(N, H, cu_count, &p)) return 0;
+    const size_t need = gru_ws_bytes(H, p, true);
+    return need ? need : 16;
+}
+
+int gru_forward_varlen_save_dispatch(const float *gx, const float *whh, const float *bhh, const int32_t *lengths,
+                                     size_t T, size_t N, size_t H, int reverse, int cu_count, float *y, float *gates,
+                                     float *q, void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
+    if (!gx || !whh || !bhh || !y || !gates || !q || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX ||
+        N > (size_t)INT32_MAX)
+        return TK_ERR_BAD_ARG;
+    Plan p;
+    if (!gru_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+    const size_t need = gru_ws_bytes(H, p, false);
+    if (wsb < (need ? need : 16)) return TK_ERR_WORKSPACE;
+    if (T == 0) return TK_OK;
+    if (need) {
+        int rc = zero_ws(ws, need, stream);
+        if (rc != TK_OK) return rc;
+    }
+    return launch_fwd<true, true>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, gates, q,
+                                  static_cast<u64 *>(ws), status, lengths);
+}
+
+int gru_backward_varlen_dispatch(const float *whh, const float *y, const float *gates, const float *q,
+                                 const float *dy, const int32_t *lengths, size_t T, size_t N, size_t H, int reverse,
+                                 int cu_count, float *dgates, float *dq, void *ws, size_t wsb, uint32_t *status,
+                                 hipStream_t stream) {
+    if (!whh || !y || !gates || !q || !dy || !dgates || !dq || !ws || !status || !aligned16(ws) ||
+        T > (size_t)INT32_MAX || N > (size_t)INT32_MAX)
+        return TK_ERR_BAD_ARG;
+    Plan p;
+    if (!gru_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+    const size_t need = gru_ws_bytes(H, p, true);
+    if (wsb < (need ? need : 16)) return TK_ERR_WORKSPACE;
+    if (T == 0) return TK_OK;
+    if (need) {
+        int rc = zero_ws(ws, need, stream);
+        if (rc != TK_OK) return rc;
+    }
+    return launch_bwd<true>(p, H, stream, whh, y, gates, q, dy, (int)T, (int)N, reverse, dgates, dq,
                             static_cast<u64 *>(ws), status, lengths);
 }
 #else
@@ -517,8 +586,8 @@ int gru_forward_dispatch(const float *gx, const float *whh, const float *bhh, si
         int rc = zero_ws(ws, need, stream);
         if (rc != TK_OK) return rc;
     }
-    return launch_fwd<false>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, gates, q,
-                             static_cast<u64 *>(ws), status, nullptr);
+    return launch_fwd<false, true>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, gates, q,
+                                   static_cast<u64 *>(ws), status, nullptr);
 }
 
 int gru_backward_dispatch(const float *whh, const float *y, const float *gates, const float *q, const float *dy,
@@ -536,8 +605,8 @@ int gru_backward_dispatch(const float *whh, const float *y, const float *gates, 
         int rc = zero_ws(ws, need, stream);
         if (rc != TK_OK) return rc;
     }
-    return launch_bwd(p, H, stream, whh, y, gates, q, dy, (int)T, (int)N, reverse, dgates, dq,
-                      static_cast<u64 *>(ws), status);
+    return launch_bwd<false>(p, H, stream, whh, y, gates, q, dy, (int)T, (int)N, reverse, dgates, dq,
+                             static_cast<u64 *>(ws), status, nullptr);
 }
 
 #ifdef TK_LAB

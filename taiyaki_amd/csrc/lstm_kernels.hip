@@ -22,9 +22,11 @@
 // in LDS and the workgroup stores the block as whole rows, 16 bytes per lane (rows_to_global, rnn_common.h): 3 store
 // instructions per workgroup and step at H 256, U 64, C 2 where the cell lanes issued 48.
 //
-// Two builds of this one source.  The flip-flop library takes the training pair: the forward that saves the gates
-// and c, and the backward.  -DTK_RNN_VARLEN (libtaiyaki_amd_rnn_varlen.so) takes the forward alone in its VL form:
-// per-column lengths, y the only output (DESIGN.md "Variable-length recurrences").
+// Three builds of this one source.  The flip-flop library takes the training pair: the forward that saves the gates
+// and c, and the backward.  -DTK_RNN_VARLEN (libtaiyaki_amd_rnn_varlen.so) takes the forward alone in its VL form with
+// nothing saved: per-column lengths, y the only output (DESIGN.md "Variable-length recurrences").
+// -DTK_RNN_VARLEN_TRAIN (libtaiyaki_amd_rnn_varlen_train.so) takes the training pair in its VL form: the saving forward
+// and the backward with per-column lengths (DESIGN.md "Training through variable-length batches").
 #include "dispatch.h"
 #include "ff_common.h"
 #include "rnn_common.h"
@@ -49,8 +51,9 @@ constexpr int threads_for() { return U <= 32 ? 256 : 512; }
 //
 // VL: column n has lengths[n] steps (NULL: T).  A step at t >= lengths[n] leaves h = c = 0, writes y = 0 and
 // publishes h = 0 like any other step: every workgroup runs all T steps, so the hand-off is that of a full batch.
-// gates and cell are not written (the pointers are not read); y goes out from the cell lane's register, one step late.
-template <int H, int C, int U, bool VL = false>
+// SAVE: gates and cell are written, through the staging block (with VL: 0 on a step at or beyond the length).  Not SAVE:
+// they are not written (the pointers are not read); y goes out from the cell lane's register, one step late.
+template <int H, int C, int U, bool VL = false, bool SAVE = !VL>
 __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const float *__restrict__ gx,
                                                                        const float *__restrict__ whh, int T, int N,
                                                                        int reverse, int ngroups,
@@ -66,12 +69,12 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
     constexpr int NG = (H * C + NT - 1) / NT;
     static_assert(KS >= 1 && KP <= 64 && C <= KP, "lane (u, kp) inside one wave; one cell lane per (u, column)");
     constexpr int U4 = U / 4;
-    constexpr int NQ = VL ? 1 : (6 * C * U4 + NT - 1) / NT;        // 16-byte chunks of a staging block per lane
+    constexpr int NQ = SAVE ? (6 * C * U4 + NT - 1) / NT : 1;        // 16-byte chunks of a staging block per lane
     static_assert(U % 4 == 0, "a row of the staging block is whole 16-byte chunks");
     __shared__ __attribute__((aligned(16))) float hs[2][H * C];      // h_{t-1} as [k][c], by step parity
     // a step's h, c, i, f, g, o as [value][column][unit], by step parity: written by the cell lanes at the end of step
     // s, read behind step s + 1's barrier, written again behind step s + 2's
-    __shared__ __attribute__((aligned(16))) float stg[VL ? 1 : 2][VL ? 4 : 6 * C * U];
+    __shared__ __attribute__((aligned(16))) float stg[SAVE ? 2 : 1][SAVE ? 6 * C * U : 4];
     __shared__ int give_up;
 
     int group, member;
@@ -105,7 +108,7 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
     // the chunks of the staging block this lane stores: rows (value, column) of y, cell and the gates' four slabs
     float *rp[NQ];
     size_t rpitch[NQ];
-    if constexpr (!VL) {
+    if constexpr (SAVE) {
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
             const int q = tid + i * NT, row = q / U4, v = row / C, nn = n0 + row % C;
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
 #pragma unroll
         for (int g = 0; g < 4; ++g) gq[g] = p[(size_t)g * H];
     }
-    float held = 0.f;                                  // VL: h of the previous step, stored one step late
+    float held = 0.f;                                  // not SAVE: h of the previous step, stored one step late
     __syncthreads();
 
     for (int s = 0; s < T; ++s) {
@@ -140,7 +143,7 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
             __syncthreads();
             if (give_up) return;
             const int tl = reverse ? t + 1 : t - 1;
-            if constexpr (VL) {
+            if constexpr (!SAVE) {
                 if (valid) y[((size_t)tl * N + n) * H + j0 + u] = held;
             } else {
                 rows_to_global<NQ>(stg[(s - 1) & 1], tid, NT, rp, rpitch, (size_t)tl);
@@ -187,20 +190,23 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
         }
 
         if (cell_lane) {
-            const float ig = sigmoidf(acc[0][0] + gq[0]), fg = sigmoidf(acc[1][0] + gq[1]);
-            const float gg = tanhf(acc[2][0] + gq[2]), og = sigmoidf(acc[3][0] + gq[3]);
+            float ig = sigmoidf(acc[0][0] + gq[0]), fg = sigmoidf(acc[1][0] + gq[1]);
+            float gg = tanhf(acc[2][0] + gq[2]), og = sigmoidf(acc[3][0] + gq[3]);
             // (the contraction written out: left to the compiler, which product the fma takes depends on the code around
             // it -- the VL mask's select, the staging stores -- and a column's rows then differ in the last bit between
             // the builds)
             cst = fmaf(ig, gg, fg * cst);
             float h = og * tanhf(cst);
             if constexpr (VL) {
-                if (t >= len) cst = h = 0.f;
+                if (t >= len) {
+                    cst = h = 0.f;
+                    if constexpr (SAVE) ig = fg = gg = og = 0.f;
+                }
             }
             if (s + 1 < T)
                 store_granule(hbuf + ((size_t)(s & 1) * ngroups + group) * (H * C) + col * H + j0 + u,
                               (unsigned)(s + 1), h);
-            if constexpr (VL) {
+            if constexpr (!SAVE) {
                 held = h;
             } else {
                 float *sp = stg[s & 1] + col * U + u;
@@ -217,7 +223,7 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
     }
     if (T > 0) {
         const int tl = reverse ? 0 : T - 1;
-        if constexpr (VL) {
+        if constexpr (!SAVE) {
             if (valid) y[((size_t)tl * N + n) * H + j0 + u] = held;
         } else {
             __syncthreads();                             // the last step's block: no poll, so no barrier, is behind it
@@ -229,14 +235,20 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
 #ifndef TK_RNN_VARLEN
 // Backward.  From the saved gate activations and c, and dy = dL/dy (T, N, H), writes dgates = dL/d(pre-activation)
 // (T, N, 4H) walking the recurrence from its last step.  pbuf: [2][ngroups][G producers][C][H] granules.
-template <int H, int C, int U>
+//
+// VL: column n has lengths[n] steps (NULL: T).  A step at t >= lengths[n] writes dgates = 0 and hands on dh = 0 and
+// dc = 0 (its dG rows in LDS are 0, so is what it publishes; dc_next = f_next = 0), like any other step.  The mask is a
+// select behind the cell update, as in the forward: dy, the gates and c beyond the length are loaded and never used.
+// (With reverse != 0 the walk reaches the padding after the column's real steps, with a dh and a dc f that are not 0.)
+template <int H, int C, int U, bool VL = false>
 __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_bwd_kernel(const float *__restrict__ whh,
                                                                        const float *__restrict__ gates,
                                                                        const float *__restrict__ cell,
                                                                        const float *__restrict__ dy, int T, int N,
                                                                        int reverse, int ngroups,
                                                                        float *__restrict__ dgates, u64 *pbuf,
-                                                                       uint32_t *status) {
+                                                                       uint32_t *status,
+                                                                       const int32_t *__restrict__ lengths) {
     constexpr int NT = threads_for<U>();
     constexpr int G = H / U;
     constexpr int RP = NT / H;                        // row partitions: lane (k, rp) holds W_hh[rows of rp, k]
@@ -270,6 +282,8 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_bwd_kernel(const flo
     const int n = n0 + cc;
     const bool valid = cell_lane && n < N;
     float dc_next = 0.f, f_next = 0.f;
+    int len = 0;                                       // VL: the steps of this lane's column
+    if constexpr (VL) len = !valid ? 0 : lengths ? lengths[n] : T;
     if (tid == 0) give_up = 0;
 
     // this step's inputs, loaded one step ahead: dy, c_t, c_{t-1}, the four gates (c_t of a step is the c_{t-1}
@@ -332,15 +346,23 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_bwd_kernel(const flo
         asm volatile("" ::: "memory");                   // the deferred stores and the prefetch stay here
 
         if (cell_lane) {
-            const float ct = in[1], cp = in[2];
-            const float ig = in[3], fg = in[4], gg = in[5], og = in[6];
+            const float ct = in[1];
+            float cp = in[2];
+            if constexpr (VL) {
+                if (tp >= len) cp = 0.f;                  // (reverse: the column's first step starts from c = 0)
+            }
+            const float ig = in[3], gg = in[5], og = in[6];
+            float fg = in[4];
             const float dh = in[0] + dhr;
             const float tc = tanhf(ct);
-            const float dc = dh * og * (1.f - tc * tc) + dc_next * f_next;
-            const float di = dc * gg * ig * (1.f - ig);
-            const float df = dc * cp * fg * (1.f - fg);
-            const float dg = dc * ig * (1.f - gg * gg);
-            const float dout = dh * tc * og * (1.f - og);
+            float dc = dh * og * (1.f - tc * tc) + dc_next * f_next;
+            float di = dc * gg * ig * (1.f - ig);
+            float df = dc * cp * fg * (1.f - fg);
+            float dg = dc * ig * (1.f - gg * gg);
+            float dout = dh * tc * og * (1.f - og);
+            if constexpr (VL) {
+                if (t >= len) dc = fg = di = df = dg = dout = 0.f;
+            }
             dc_next = dc;
             f_next = fg;
             held[0] = di;
@@ -391,7 +413,7 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_bwd_kernel(const flo
     }
 }
 
-#endif  // TK_RNN_VARLEN
+#endif  // TK_RNN_VARLEN: no backward
 
 int g_lab_cols = 0;     // lab build: force the admitted batch columns, 8 or 16 (0 = the rule below)
 int g_lab_units = 0;    // lab build: force the hidden units per workgroup, 16, 32 or 64 (0 = the rule in lstm_plan)
@@ -451,12 +473,12 @@ bool lstm_plan(size_t N, size_t H, int cu_count, Plan *p) {
         default: return TK_ERR_UNSUPPORTED;                                                                       \
     }
 
-template <bool VL>
+template <bool VL, bool SAVE>
 int launch_fwd(const Plan &p, size_t H, hipStream_t st, const float *gx, const float *whh, int T, int N, int rev,
                float *y, float *gates, float *cell, u64 *ws, uint32_t *status, const int32_t *lengths) {
 #define TK_LSTM_FWD(HH, UU, CC)                                                                                  \
     case HH * 100000 + UU * 1000 + CC:                                                                           \
-        hipLaunchKernelGGL((lstm_fwd_kernel<HH, CC, UU, VL>), dim3(p.grid), dim3(threads_for<UU>()), 0, st, gx,  \
+        hipLaunchKernelGGL((lstm_fwd_kernel<HH, CC, UU, VL, SAVE>), dim3(p.grid), dim3(threads_for<UU>()), 0, st, gx,  \
                            whh, T, N, rev, p.groups, y, gates, cell, ws, status, lengths);                       \
         break;
     TK_LSTM_SWITCH(TK_LSTM_FWD)
@@ -465,12 +487,13 @@ int launch_fwd(const Plan &p, size_t H, hipStream_t st, const float *gx, const f
 }
 
 #ifndef TK_RNN_VARLEN
+template <bool VL>
 int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const float *gates, const float *cell,
-               const float *dy, int T, int N, int rev, float *dg, u64 *ws, uint32_t *status) {
+               const float *dy, int T, int N, int rev, float *dg, u64 *ws, uint32_t *status, const int32_t *lengths) {
 #define TK_LSTM_BWD(HH, UU, CC)                                                                                   \
     case HH * 100000 + UU * 1000 + CC:                                                                            \
-        hipLaunchKernelGGL((lstm_bwd_kernel<HH, CC, UU>), dim3(p.grid), dim3(threads_for<UU>()), 0, st, whh,      \
-                           gates, cell, dy, T, N, rev, p.groups, dg, ws, status);                                 \
+        hipLaunchKernelGGL((lstm_bwd_kernel<HH, CC, UU, VL>), dim3(p.grid), dim3(threads_for<UU>()), 0, st, whh,  \
+                           gates, cell, dy, T, N, rev, p.groups, dg, ws, status, lengths);                        \
         break;
     TK_LSTM_SWITCH(TK_LSTM_BWD)
 #undef TK_LSTM_BWD
@@ -502,7 +525,50 @@ int lstm_forward_varlen_dispatch(const float *gx, const float *whh, const int32_
     if (T == 0) return TK_OK;
     int rc = zero_ws(ws, need, stream);
     if (rc != TK_OK) return rc;
-    return launch_fwd<true>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, nullptr, nullptr,
+    return launch_fwd<true, false>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, nullptr, nullptr,
+                            static_cast<u64 *>(ws), status, lengths);
+}
+#elif defined(TK_RNN_VARLEN_TRAIN)
+// The training pair with per-column lengths (include/taiyaki_amd_rnn_varlen_train.h): the plans, grids and granule
+// buffers of lstm_forward_dispatch / lstm_backward_dispatch at the same (N, H, cu_count); the workspace is the
+// backward's bound, as tk_lstm_workspace_bytes is.
+size_t lstm_varlen_train_workspace_bytes(size_t N, size_t H, int cu_count) {
+    int C = 0, groups = 0;
+    if (!lstm_geometry(N, H, cu_count, &C, &groups)) return 0;
+    return ws_bytes(H, C, groups, 16, true);
+}
+
+int lstm_forward_varlen_save_dispatch(const float *gx, const float *whh, const int32_t *lengths, size_t T, size_t N,
+                                      size_t H, int reverse, int cu_count, float *y, float *gates, float *cell,
+                                      void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
+    if (!gx || !whh || !y || !gates || !cell || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX ||
+        N > (size_t)INT32_MAX)
+        return TK_ERR_BAD_ARG;
+    Plan p;
+    if (!lstm_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+    const size_t need = ws_bytes(H, p.C, p.groups, p.U, false);
+    if (wsb < need) return TK_ERR_WORKSPACE;
+    if (T == 0) return TK_OK;
+    int rc = zero_ws(ws, need, stream);
+    if (rc != TK_OK) return rc;
+    return launch_fwd<true, true>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, gates, cell,
+                                  static_cast<u64 *>(ws), status, lengths);
+}
+
+int lstm_backward_varlen_dispatch(const float *whh, const float *gates, const float *cell, const float *dy,
+                                  const int32_t *lengths, size_t T, size_t N, size_t H, int reverse, int cu_count,
+                                  float *dgates, void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
+    if (!whh || !gates || !cell || !dy || !dgates || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX ||
+        N > (size_t)INT32_MAX)
+        return TK_ERR_BAD_ARG;
+    Plan p;
+    if (!lstm_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+    const size_t need = ws_bytes(H, p.C, p.groups, p.U, true);
+    if (wsb < need) return TK_ERR_WORKSPACE;
+    if (T == 0) return TK_OK;
+    int rc = zero_ws(ws, need, stream);
+    if (rc != TK_OK) return rc;
+    return launch_bwd<true>(p, H, stream, whh, gates, cell, dy, (int)T, (int)N, reverse, dgates,
                             static_cast<u64 *>(ws), status, lengths);
 }
 #else
@@ -525,8 +591,8 @@ int lstm_forward_dispatch(const float *gx, const float *whh, size_t T, size_t N,
     if (T == 0) return TK_OK;
     int rc = zero_ws(ws, need, stream);
     if (rc != TK_OK) return rc;
-    return launch_fwd<false>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, gates, cell, static_cast<u64 *>(ws),
-                             status, nullptr);
+    return launch_fwd<false, true>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, gates, cell,
+                                   static_cast<u64 *>(ws), status, nullptr);
 }
 
 int lstm_backward_dispatch(const float *whh, const float *gates, const float *cell, const float *dy, size_t T,
@@ -542,8 +608,8 @@ int lstm_backward_dispatch(const float *whh, const float *gates, const float *ce
     if (T == 0) return TK_OK;
     int rc = zero_ws(ws, need, stream);
     if (rc != TK_OK) return rc;
-    return launch_bwd(p, H, stream, whh, gates, cell, dy, (int)T, (int)N, reverse, dgates, static_cast<u64 *>(ws),
-                      status);
+    return launch_bwd<false>(p, H, stream, whh, gates, cell, dy, (int)T, (int)N, reverse, dgates,
+                             static_cast<u64 *>(ws), status, nullptr);
 }
 
 #ifdef TK_LAB

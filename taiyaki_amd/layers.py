@@ -14,7 +14,7 @@ that feeds them.
   (`SmallConvolution`).
 * ``forward_varlen`` runs a ``Serial`` on a batch whose columns have different lengths: every column's rows are what
   the column gives run alone (``Lstm`` / ``GruMod`` ``forward(x, reverse, lengths)`` on the forward-only launches of
-  include/taiyaki_amd_rnn_varlen.h).
+  include/taiyaki_amd_rnn_varlen.h; under grad mode on the training pair of include/taiyaki_amd_rnn_varlen_train.h).
 """
 import numpy as np
 import torch
@@ -241,6 +241,13 @@ class _Rnn(nn.Module):
 
 # False: every Lstm runs nn.LSTM (MIOpen on the GPU), for comparisons against the HIP recurrence
 USE_HIP_LSTM = True
+# True: `Lstm` / `GruMod` `forward(x, reverse, lengths)` and `forward_varlen` are differentiable under grad mode (the
+# training pair of include/taiyaki_amd_rnn_varlen_train.h where a HIP launch takes the tensors).  False, the default: such
+# a call under grad mode raises, as it always has: a caller that trains through variable-length batches says so.
+TRAIN_VARLEN = False
+# HIP launches of `Lstm` / `GruMod` `forward(x, reverse, lengths)` by kind: "saved" wrote the activations for a backward
+# pass (include/taiyaki_amd_rnn_varlen_train.h), "inference" saved nothing (include/taiyaki_amd_rnn_varlen.h)
+rnn_varlen_calls = {"saved": 0, "inference": 0}
 # False: the parameter gradients of LstmRecurrence.backward are two GEMMs and a sum over dG (what they are wherever
 # tk_lstm_weight_grad_workspace_bytes is 0), for comparisons against the fused kernel
 USE_HIP_LSTM_WGRAD = True
@@ -305,33 +312,88 @@ class LstmRecurrence(torch.autograd.Function):
                                              ctx.wsb, _lib.ptr(status), _lib.stream_ptr())
         _lib.check(rc, "tk_lstm_backward_dev")
         _lib.finish(status)
-        dg2 = dg.view(T * N, 4 * H)
-        need = ctx.needs_input_grad
-        dx = (dg2 @ w_ih).view(T, N, I) if need[0] else None
-        if USE_HIP_LSTM_WGRAD and need[1] and need[2] and (need[3] or need[4]):
-            # the three parameter gradients in one pass over dG: dG^T [x | y shifted by a step | 1]
-            W = _lib.wgrad_lib()
-            wgb = W.tk_lstm_weight_grad_workspace_bytes(T, N, H, I, _cu_count(dev))
-            if wgb:
-                dw_ih, dw_hh = torch.empty_like(w_ih, memory_format=torch.contiguous_format), torch.empty_like(w_hh)
-                db = torch.empty(4 * H, dtype=torch.float32, device=dev)
-                wws = _lib.workspace(wgb, dev, "lstm_wgrad")
-                rc = W.tk_lstm_weight_grad_dev(_lib.ptr(dg), _lib.ptr(x), _lib.ptr(y), T, N, H, I, int(ctx.reverse),
-                                               _cu_count(dev), _lib.ptr(dw_ih), _lib.ptr(dw_hh), _lib.ptr(db),
-                                               _lib.ptr(wws), wgb, _lib.stream_ptr())
-                _lib.check(rc, "tk_lstm_weight_grad_dev")
-                return dx, dw_ih, dw_hh, db if need[3] else None, db if need[4] else None, None, None
-        dw_ih = dg2.t() @ x.view(T * N, I) if need[1] else None
-        dw_hh = None
-        if need[2]:
-            # dW_hh = sum over steps of dG_t^T h_prev, h_prev = the output of the recurrence's previous step
-            if T > 1:
-                dgs, hp = (dg[:-1], y[1:]) if ctx.reverse else (dg[1:], y[:-1])
-                dw_hh = dgs.reshape(-1, 4 * H).t() @ hp.reshape(-1, H)
-            else:
-                dw_hh = torch.zeros_like(w_hh)
-        db = dg2.sum(0) if (need[3] or need[4]) else None
-        return dx, dw_ih, dw_hh, db if need[3] else None, db if need[4] else None, None, None
+        return _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None, None)
+
+
+def _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, reverse, need):
+    """(dx, dW_ih, dW_hh, db_ih, db_hh) of one LSTM layer from dG = dL/d(pre-activation) (T, N, 4H), its input x and
+    its output y; need[0..4]: which of them are wanted.  With per-column lengths dG and y are 0 beyond every length, so
+    the same sums over the whole padded tensors are the sums over every column's own steps (x finite in the padding)."""
+    T, N, I = x.shape
+    H = w_hh.shape[1]
+    dev = x.device
+    dg2 = dg.view(T * N, 4 * H)
+    dx = (dg2 @ w_ih).view(T, N, I) if need[0] else None
+    if USE_HIP_LSTM_WGRAD and need[1] and need[2] and (need[3] or need[4]):
+        # the three parameter gradients in one pass over dG: dG^T [x | y shifted by a step | 1]
+        W = _lib.wgrad_lib()
+        wgb = W.tk_lstm_weight_grad_workspace_bytes(T, N, H, I, _cu_count(dev))
+        if wgb:
+            dw_ih, dw_hh = torch.empty_like(w_ih, memory_format=torch.contiguous_format), torch.empty_like(w_hh)
+            db = torch.empty(4 * H, dtype=torch.float32, device=dev)
+            wws = _lib.workspace(wgb, dev, "lstm_wgrad")
+            rc = W.tk_lstm_weight_grad_dev(_lib.ptr(dg), _lib.ptr(x), _lib.ptr(y), T, N, H, I, int(reverse),
+                                           _cu_count(dev), _lib.ptr(dw_ih), _lib.ptr(dw_hh), _lib.ptr(db),
+                                           _lib.ptr(wws), wgb, _lib.stream_ptr())
+            _lib.check(rc, "tk_lstm_weight_grad_dev")
+            return dx, dw_ih, dw_hh, db if need[3] else None, db if need[4] else None
+    dw_ih = dg2.t() @ x.view(T * N, I) if need[1] else None
+    dw_hh = None
+    if need[2]:
+        # dW_hh = sum over steps of dG_t^T h_prev, h_prev = the output of the recurrence's previous step
+        if T > 1:
+            dgs, hp = (dg[:-1], y[1:]) if reverse else (dg[1:], y[:-1])
+            dw_hh = dgs.reshape(-1, 4 * H).t() @ hp.reshape(-1, H)
+        else:
+            dw_hh = torch.zeros_like(w_hh)
+    db = dg2.sum(0) if (need[3] or need[4]) else None
+    return dx, dw_ih, dw_hh, db if need[3] else None, db if need[4] else None
+
+
+class LstmVarlenRecurrence(torch.autograd.Function):
+    """`LstmRecurrence` on a batch whose column n has lens[n] steps (a device int32 tensor): the saving forward and the
+    backward of include/taiyaki_amd_rnn_varlen_train.h.  y, the gates, c and dG are 0 at and beyond every length, so the
+    input and parameter gradients are those of `LstmRecurrence.backward` on the whole padded tensors."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, lens, reverse, wsb):
+        T, N, _ = x.shape
+        H = w_hh.shape[1]
+        dev = x.device
+        x = x.contiguous()
+        w_hh = w_hh.contiguous()
+        rnn_varlen_calls["saved"] += 1
+        gx = torch.addmm(b_ih + b_hh, x.view(T * N, -1), w_ih.t())
+        y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
+        gates = torch.empty(T, N, 4 * H, dtype=torch.float32, device=dev)
+        cell = torch.empty(T, N, H, dtype=torch.float32, device=dev)
+        ws = _lib.workspace(wsb, dev, "rnn_varlen_train")
+        status = _lib.status_word(dev)
+        rc = _lib.varlen_train_lib().tk_lstm_forward_varlen_save_dev(
+            _lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(lens), T, N, H, int(reverse), _cu_count(dev), _lib.ptr(y),
+            _lib.ptr(gates), _lib.ptr(cell), _lib.ptr(ws), wsb, _lib.ptr(status), _lib.stream_ptr())
+        _lib.check(rc, "tk_lstm_forward_varlen_save_dev")
+        _lib.finish(status)
+        ctx.save_for_backward(x, w_ih, w_hh, y, gates, cell, lens)
+        ctx.reverse, ctx.wsb = reverse, wsb
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w_ih, w_hh, y, gates, cell, lens = ctx.saved_tensors
+        T, N, _ = x.shape
+        H = w_hh.shape[1]
+        dev = x.device
+        dy = dy.contiguous()
+        dg = torch.empty_like(gates)
+        ws = _lib.workspace(ctx.wsb, dev, "rnn_varlen_train")
+        status = _lib.status_word(dev)
+        rc = _lib.varlen_train_lib().tk_lstm_backward_varlen_dev(
+            _lib.ptr(w_hh), _lib.ptr(gates), _lib.ptr(cell), _lib.ptr(dy), _lib.ptr(lens), T, N, H, int(ctx.reverse),
+            _cu_count(dev), _lib.ptr(dg), _lib.ptr(ws), ctx.wsb, _lib.ptr(status), _lib.stream_ptr())
+        _lib.check(rc, "tk_lstm_backward_varlen_dev")
+        _lib.finish(status)
+        return _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None, None, None)
 
 
 class Lstm(_Rnn):
@@ -447,22 +509,79 @@ class GruRecurrence(torch.autograd.Function):
                                             _lib.ptr(ws), ctx.wsb, _lib.ptr(status), _lib.stream_ptr())
         _lib.check(rc, "tk_gru_backward_dev")
         _lib.finish(status)
-        dg2 = dg.view(T * N, 3 * H)
-        need = ctx.needs_input_grad
-        dx = (dg2 @ w_ih).view(T, N, I) if need[0] else None
-        dw_ih = _time_sum_tn(dg, x) if need[1] else None
-        dw_hh = None
-        if need[2]:
-            # dW_hh = sum over steps of [dr_pre, dz_pre, dq]_t^T h_prev, h_prev = the output of the recurrence's
-            # previous step (0 at its first)
-            if T > 1:
-                sl, hp = (slice(0, T - 1), y[1:]) if ctx.reverse else (slice(1, T), y[:-1])
-                dw_hh = torch.cat([_time_sum_tn(dg[sl][:, :, :2 * H], hp), _time_sum_tn(dq[sl], hp)])
-            else:
-                dw_hh = torch.zeros_like(w_hh)
-        db_ih = dg2.sum(0) if (need[3] or need[4]) else None
-        db_hh = torch.cat([db_ih[:2 * H], dq.view(T * N, H).sum(0)]) if need[4] else None
-        return dx, dw_ih, dw_hh, db_ih if need[3] else None, db_hh, None, None, None
+        return _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None, None, None)
+
+
+def _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, reverse, need):
+    """(dx, dW_ih, dW_hh, db_ih, db_hh) of one GRU layer from dG = dL/dG_x (T, N, 3H) and dq (T, N, H), its input x and
+    its output y; need[0..4]: which of them are wanted.  With per-column lengths dG, dq and y are 0 beyond every length,
+    so the same sums over the whole padded tensors are the sums over every column's own steps (x finite in the padding)."""
+    T, N, I = x.shape
+    H = w_hh.shape[1]
+    dg2 = dg.view(T * N, 3 * H)
+    dx = (dg2 @ w_ih).view(T, N, I) if need[0] else None
+    dw_ih = _time_sum_tn(dg, x) if need[1] else None
+    dw_hh = None
+    if need[2]:
+        # dW_hh = sum over steps of [dr_pre, dz_pre, dq]_t^T h_prev, h_prev = the output of the recurrence's
+        # previous step (0 at its first)
+        if T > 1:
+            sl, hp = (slice(0, T - 1), y[1:]) if reverse else (slice(1, T), y[:-1])
+            dw_hh = torch.cat([_time_sum_tn(dg[sl][:, :, :2 * H], hp), _time_sum_tn(dq[sl], hp)])
+        else:
+            dw_hh = torch.zeros_like(w_hh)
+    db_ih = dg2.sum(0) if (need[3] or need[4]) else None
+    db_hh = torch.cat([db_ih[:2 * H], dq.view(T * N, H).sum(0)]) if need[4] else None
+    return dx, dw_ih, dw_hh, db_ih if need[3] else None, db_hh
+
+
+class GruVarlenRecurrence(torch.autograd.Function):
+    """`GruRecurrence` (saving) on a batch whose column n has lens[n] steps (a device int32 tensor): the saving forward
+    and the backward of include/taiyaki_amd_rnn_varlen_train.h.  y, the activations, q, dG and dq are 0 at and beyond
+    every length, so the input and parameter gradients are those of `GruRecurrence.backward` on the padded tensors."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, lens, reverse, wsb):
+        T, N, _ = x.shape
+        H = w_hh.shape[1]
+        dev = x.device
+        x = x.contiguous()
+        w_hh, b_hh = w_hh.contiguous(), b_hh.contiguous()
+        gru_forward_calls["saved"] += 1
+        rnn_varlen_calls["saved"] += 1
+        gx = torch.addmm(b_ih, x.view(T * N, -1), w_ih.t())
+        y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
+        gates = torch.empty(T, N, 3 * H, dtype=torch.float32, device=dev)
+        q = torch.empty(T, N, H, dtype=torch.float32, device=dev)
+        ws = _lib.workspace(wsb, dev, "rnn_varlen_train")
+        status = _lib.status_word(dev)
+        rc = _lib.varlen_train_lib().tk_gru_forward_varlen_save_dev(
+            _lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(b_hh), _lib.ptr(lens), T, N, H, int(reverse), _cu_count(dev),
+            _lib.ptr(y), _lib.ptr(gates), _lib.ptr(q), _lib.ptr(ws), wsb, _lib.ptr(status), _lib.stream_ptr())
+        _lib.check(rc, "tk_gru_forward_varlen_save_dev")
+        _lib.finish(status)
+        ctx.save_for_backward(x, w_ih, w_hh, y, gates, q, lens)
+        ctx.reverse, ctx.wsb = reverse, wsb
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w_ih, w_hh, y, gates, q, lens = ctx.saved_tensors
+        T, N, _ = x.shape
+        H = w_hh.shape[1]
+        dev = x.device
+        dy = dy.contiguous()
+        dg = torch.empty_like(gates)
+        dq = torch.empty_like(q)
+        ws = _lib.workspace(ctx.wsb, dev, "rnn_varlen_train")
+        status = _lib.status_word(dev)
+        rc = _lib.varlen_train_lib().tk_gru_backward_varlen_dev(
+            _lib.ptr(w_hh), _lib.ptr(y), _lib.ptr(gates), _lib.ptr(q), _lib.ptr(dy), _lib.ptr(lens), T, N, H,
+            int(ctx.reverse), _cu_count(dev), _lib.ptr(dg), _lib.ptr(dq), _lib.ptr(ws), ctx.wsb, _lib.ptr(status),
+            _lib.stream_ptr())
+        _lib.check(rc, "tk_gru_backward_varlen_dev")
+        _lib.finish(status)
+        return _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None, None, None)
 
 
 class GruMod(_Rnn):
@@ -497,22 +616,43 @@ def hip_rnn_varlen_workspace_bytes(rnn, x):
     return _lib.varlen_lib().tk_rnn_varlen_workspace_bytes(kind, x.shape[1], rnn.hidden_size, _cu_count(x.device))
 
 
+def hip_rnn_varlen_train_workspace_bytes(rnn, x):
+    """Workspace of the training pair with per-column lengths (include/taiyaki_amd_rnn_varlen_train.h) for this nn.LSTM
+    or nn.GRU and input, 0 where it does not run: the rule of `hip_rnn_varlen_workspace_bytes`."""
+    lstm = isinstance(rnn, nn.LSTM)
+    if not (_hip_lstm_takes(rnn, x) if lstm else _hip_gru_takes(rnn, x)):
+        return 0
+    kind = _lib.VARLEN_DEFINES["TK_RNN_KIND_LSTM" if lstm else "TK_RNN_KIND_GRU"]
+    return _lib.varlen_train_lib().tk_rnn_varlen_train_workspace_bytes(kind, x.shape[1], rnn.hidden_size,
+                                                                       _cu_count(x.device))
+
+
 def _needs_grad(x, module):
     return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
 
 
 def _rnn_forward_varlen(layer, x, reverse, lengths):
     """`Lstm` / `GruMod` forward on a batch whose column n has lengths[n] steps: rows [0, lengths[n]) of column n are
-    what `layer(x[:lengths[n], n:n + 1], reverse)` gives, the rows beyond are 0.  One launch of
-    tk_lstm_forward_varlen_dev / tk_gru_forward_varlen_dev where `hip_rnn_varlen_workspace_bytes` admits the tensors
-    (nothing is saved: inference only); every column alone at its own length otherwise."""
-    if _needs_grad(x, layer):
-        raise RuntimeError("%s.forward with lengths is inference only: call it under torch.no_grad() (training "
-                           "through variable-length batches is not implemented)" % type(layer).__name__)
+    what `layer(x[:lengths[n], n:n + 1], reverse)` gives, the rows beyond are 0.  Where a HIP launch admits the
+    tensors: under grad mode with something that requires a gradient, `LstmVarlenRecurrence` / `GruVarlenRecurrence`
+    (x must be finite in the padding: the parameter gradients are sums over the whole padded tensors); otherwise one
+    launch of tk_lstm_forward_varlen_dev / tk_gru_forward_varlen_dev, which saves nothing.  Every column alone at its
+    own length otherwise (differentiable like any other call of the layer).  Under grad mode the call needs
+    layers.TRAIN_VARLEN = True; without it it raises, as it did before there was a backward with lengths."""
     rnn = layer.rnn
     T, N, _ = x.shape
     H = rnn.hidden_size
-    wsb = hip_rnn_varlen_workspace_bytes(rnn, x) if T and N else 0
+    train = _needs_grad(x, layer)
+    if train and not TRAIN_VARLEN:
+        raise RuntimeError("%s.forward with lengths is inference only unless layers.TRAIN_VARLEN is set: call it under "
+                           "torch.no_grad(), or set layers.TRAIN_VARLEN = True to train through variable-length "
+                           "batches" % type(layer).__name__)
+    if not (T and N):
+        wsb = 0
+    elif train:
+        wsb = hip_rnn_varlen_train_workspace_bytes(rnn, x)
+    else:
+        wsb = hip_rnn_varlen_workspace_bytes(rnn, x)
     if not wsb:
         host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
         assert len(host) == N and (N == 0 or (host.min() >= 0 and host.max() <= T)), "lengths: one per column, 0..T"
@@ -523,7 +663,15 @@ def _rnn_forward_varlen(layer, x, reverse, lengths):
         return y
     dev = x.device
     lstm = isinstance(rnn, nn.LSTM)
+    if train:
+        with torch.cuda.device(dev):
+            lens = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).reshape(-1).clamp(0, T).contiguous()
+            assert lens.numel() == N, "lengths: one per column"
+            fn = LstmVarlenRecurrence if lstm else GruVarlenRecurrence
+            return fn.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0, lens,
+                            bool(reverse), wsb)
     with torch.no_grad(), torch.cuda.device(dev):
+        rnn_varlen_calls["inference"] += 1
         lens = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).reshape(-1).clamp(0, T).contiguous()
         assert lens.numel() == N, "lengths: one per column"
         x = x.contiguous()
@@ -643,8 +791,11 @@ def conv_out_lengths(lengths, stride):
 
 
 def _zero_beyond(y, lens_dev):
-    """Rows t >= lens[n] of column n of y (T, N, C) set to 0, in place."""
+    """Rows t >= lens[n] of column n of y (T, N, C) set to 0: in place, or, under grad mode, in a new tensor (autograd
+    may have saved y: tanh's output is its own saved tensor)."""
     keep = torch.arange(y.shape[0], device=y.device)[:, None] < lens_dev[None, :]
+    if torch.is_grad_enabled():
+        return y.masked_fill(~keep[:, :, None], 0)
     return y.masked_fill_(~keep[:, :, None], 0)
 
 
@@ -667,6 +818,9 @@ def _varlen_layers(model):
 def _varlen_batched(plan, x, lens):
     """The whole batch through every layer once; None where a recurrent layer has no HIP launch for its input."""
     h, lens_dev = x, torch.from_numpy(lens).to(x.device)
+    if torch.is_grad_enabled():
+        # the rows of x beyond a column's length belong to no column: their gradient is 0, whatever a window reads
+        h = _zero_beyond(h, lens_dev)
     for layer, rnn_layer, rev in plan:
         if rnn_layer is not None:
             if not hip_rnn_varlen_workspace_bytes(rnn_layer.rnn, h):
@@ -684,7 +838,10 @@ def _varlen_batched(plan, x, lens):
 def forward_varlen(model, x, lengths):
     """`model` (a `Serial` of this module's layers) on x (T, N, C) whose column n has lengths[n] rows (zero beyond):
     -> (out, out_lengths), where out[:out_lengths[n], n] is what `model(x[:lengths[n], n:n + 1])` gives and every row
-    beyond is 0.  out_lengths is a host int64 array (`conv_out_lengths` through every Convolution).  Inference only.
+    beyond is 0.  out_lengths is a host int64 array (`conv_out_lengths` through every Convolution).  Under grad mode
+    (layers.TRAIN_VARLEN = True; a RuntimeError without it) the result is differentiable: the gradient of every parameter, and of x, is the sum over the columns of the gradients
+    of those per-column passes (rows of x beyond a column's length get 0).  The time length per column of the CRF loss
+    is not part of this: the caller masks or slices `out` by `out_lengths`.
 
     On the GPU the batch goes through every layer once: a Convolution's rows beyond the column's output length are
     zeroed (the next window then sees the zeros its own padding would have supplied), the recurrences take the
@@ -694,8 +851,9 @@ def forward_varlen(model, x, lengths):
     if not isinstance(model, Serial):
         raise TypeError("forward_varlen: the model must be a layers.Serial, not %s" % type(model).__name__)
     plan = _varlen_layers(model)
-    if _needs_grad(x, model):
-        raise RuntimeError("forward_varlen is inference only: call it under torch.no_grad()")
+    if _needs_grad(x, model) and not TRAIN_VARLEN:
+        raise RuntimeError("forward_varlen is inference only unless layers.TRAIN_VARLEN is set: call it under "
+                           "torch.no_grad(), or set layers.TRAIN_VARLEN = True")
     T, N, _ = x.shape
     lens = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
     if len(lens) != N or (N and (lens.min() < 0 or lens.max() > T)):
@@ -707,7 +865,7 @@ def forward_varlen(model, x, lengths):
     last = plan[-1][1] or plan[-1][0]
     nout = last.rnn.hidden_size if isinstance(last, _Rnn) else last.conv.out_channels if isinstance(last, Convolution) \
         else getattr(last, "nout", last.size)
-    with torch.no_grad():
+    with torch.enable_grad() if _needs_grad(x, model) else torch.no_grad():
         out = _varlen_batched(plan, x, lens) if T and N else None
         if out is None:
             out = x.new_zeros(t_out, N, nout)

@@ -12,7 +12,9 @@ record is --T 800 --N 128 --H 256.
 
 --varlen also times tk_gru_forward_varlen_dev (include/taiyaki_amd_rnn_varlen.h, the release rule) with every length
 equal to T, in turns with the forward above, five turns each: the mask's cost per step against the same run's forward
-and the spread of that forward between its turns.
+and the spread of that forward between its turns.  It then times the training pair with per-column lengths
+(include/taiyaki_amd_rnn_varlen_train.h) the same way, forward and backward, at lengths = NULL and at a half-full
+pattern (lengths[n] spread evenly over 0..T), in turns with tk_gru_forward_dev / tk_gru_backward_dev.
 """
 import argparse
 import json
@@ -107,6 +109,32 @@ def main():
         turns = [(timed(fwd, a.steps, a.warmup)[0], timed(vfwd, a.steps, a.warmup)[0]) for _ in range(5)]
         out.update(fwd_turns_us_per_step=[round(1e3 * f / T, 3) for f, _ in turns],
                    varlen_turns_us_per_step=[round(1e3 * v / T, 3) for _, v in turns])
+        # the training pair with lengths: NULL, and half full (its backward on what its own forward saved)
+        VT = _lib.varlen_train_lib()
+        twsb = VT.tk_rnn_varlen_train_workspace_bytes(_lib.VARLEN_DEFINES["TK_RNN_KIND_GRU"], N, H, cus)
+        tws = torch.empty(max(twsb // 4, 4), dtype=torch.float32, device=dev)
+        half = ((torch.arange(N) * T) // max(N - 1, 1)).to(dtype=torch.int32, device=dev)
+        y2, gates2, q2 = torch.empty_like(y), torch.empty_like(gates), torch.empty_like(q)
+
+        def tfwd(lens, yy, gg, qq):
+            _lib.check(VT.tk_gru_forward_varlen_save_dev(_lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(b_hh), _lib.ptr(lens), T,
+                                                         N, H, int(a.reverse), cus, _lib.ptr(yy), _lib.ptr(gg),
+                                                         _lib.ptr(qq), _lib.ptr(tws), twsb, _lib.ptr(status), stream),
+                       "tk_gru_forward_varlen_save_dev")
+
+        def tbwd(lens, yy, gg, qq):
+            _lib.check(VT.tk_gru_backward_varlen_dev(_lib.ptr(w_hh), _lib.ptr(yy), _lib.ptr(gg), _lib.ptr(qq),
+                                                     _lib.ptr(dy), _lib.ptr(lens), T, N, H, int(a.reverse), cus,
+                                                     _lib.ptr(dg), _lib.ptr(dq), _lib.ptr(tws), twsb, _lib.ptr(status),
+                                                     stream), "tk_gru_backward_varlen_dev")
+        fwd()
+        tfwd(half, y2, gates2, q2)
+        legs = {"fwd": fwd, "bwd": bwd, "train_null_fwd": lambda: tfwd(None, y, gates, q),
+                "train_null_bwd": lambda: tbwd(None, y, gates, q), "train_half_fwd": lambda: tfwd(half, y2, gates2, q2),
+                "train_half_bwd": lambda: tbwd(half, y2, gates2, q2)}
+        tt = [{k: timed(fn, a.steps, a.warmup)[0] for k, fn in legs.items()} for _ in range(5)]
+        out.update(train_half_mean_length=float(half.float().mean().item()),
+                   train_turns_us_per_step={k: [round(1e3 * t[k] / T, 3) for t in tt] for k in legs})
     f_med, f_min = timed(fwd, a.steps, a.warmup)
     b_med, b_min = timed(bwd, a.steps, a.warmup)
     _lib.finish(status)

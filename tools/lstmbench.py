@@ -7,6 +7,10 @@ units setting (microseconds per timestep and direction, median and min over --st
 
     python tools/lstmbench.py [--T 800] [--N 128] [--H 256] [--steps 20] [--warmup 3] [--units 0 16 32 64] [--varlen]
 
+--varlen also times, in turns of five, tk_lstm_forward_varlen_dev with every length = T beside the forward, and the
+training pair with per-column lengths (include/taiyaki_amd_rnn_varlen_train.h), forward and backward, at lengths = NULL
+and at a half-full pattern (lengths[n] spread evenly over 0..T) beside tk_lstm_forward_dev / tk_lstm_backward_dev.
+
 --units (lab build) forces the hidden units per workgroup; 0 is the release rule.  Without --units the
 release library is timed.
 """
@@ -100,6 +104,33 @@ def main():
             turns = [(timed(fwd, a.steps, a.warmup)[0], timed(vfwd, a.steps, a.warmup)[0]) for _ in range(5)]
             varlen = {"fwd_turns_us_per_step": [round(1e3 * f / T, 3) for f, _ in turns],
                       "varlen_turns_us_per_step": [round(1e3 * v / T, 3) for _, v in turns]}
+            # the training pair with lengths: NULL, and half full (its backward on what its own forward saved)
+            VT = _lib.varlen_train_lib()
+            twsb = VT.tk_rnn_varlen_train_workspace_bytes(_lib.VARLEN_DEFINES["TK_RNN_KIND_LSTM"], N, H, cus)
+            tws = torch.empty(twsb // 4, dtype=torch.float32, device=dev)
+            half = ((torch.arange(N) * T) // max(N - 1, 1)).to(dtype=torch.int32, device=dev)
+            y2, gates2, cell2 = torch.empty_like(y), torch.empty_like(gates), torch.empty_like(cell)
+
+            def tfwd(ln, yy, gg, cc):
+                _lib.check(VT.tk_lstm_forward_varlen_save_dev(_lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(ln), T, N, H,
+                                                              int(a.reverse), cus, _lib.ptr(yy), _lib.ptr(gg),
+                                                              _lib.ptr(cc), _lib.ptr(tws), twsb, _lib.ptr(status),
+                                                              stream), "tk_lstm_forward_varlen_save_dev")
+
+            def tbwd(ln, gg, cc):
+                _lib.check(VT.tk_lstm_backward_varlen_dev(_lib.ptr(w_hh), _lib.ptr(gg), _lib.ptr(cc), _lib.ptr(dy),
+                                                          _lib.ptr(ln), T, N, H, int(a.reverse), cus, _lib.ptr(dg),
+                                                          _lib.ptr(tws), twsb, _lib.ptr(status), stream),
+                           "tk_lstm_backward_varlen_dev")
+            fwd()
+            tfwd(half, y2, gates2, cell2)
+            legs = {"fwd": fwd, "bwd": bwd, "train_null_fwd": lambda: tfwd(None, y, gates, cell),
+                    "train_null_bwd": lambda: tbwd(None, gates, cell),
+                    "train_half_fwd": lambda: tfwd(half, y2, gates2, cell2),
+                    "train_half_bwd": lambda: tbwd(half, gates2, cell2)}
+            tt = [{k: timed(fn, a.steps, a.warmup)[0] for k, fn in legs.items()} for _ in range(5)]
+            varlen["train_half_mean_length"] = float(half.float().mean().item())
+            varlen["train_turns_us_per_step"] = {k: [round(1e3 * t[k] / T, 3) for t in tt] for k in legs}
         f_med, f_min = timed(fwd, a.steps, a.warmup)
         b_med, b_min = timed(bwd, a.steps, a.warmup)
 
