@@ -11,10 +11,22 @@
  *                    reverse != 0 t_prev = t + 1 (t = T - 1 adds nothing); all zeros at T = 1
  *   db     (4H)    = sum over (t, n) of dgates[t, n, :]
  *
- * One GEMM dG^T [x | y shifted | 1] over the T N rows on the float32 matrix cores (csrc/lstm_wgrad.hip): the rows are
+ * One GEMM dG^T [x | y shifted | 1] over the T N rows on the bf16 matrix cores (csrc/lstm_wgrad.hip): the rows are
  * cut into runs, one workgroup per (output tile, run), whose partial results go to the workspace; a second launch
  * adds them in a fixed order.  No atomics: two calls on the same inputs give the same bits, whatever the workspace
- * held.  Every product chain is a k-ordered float32 fmaf chain of at most 8192 rows.  dgates is read from HBM once.
+ * held.  dgates is read from HBM once.
+ *
+ * Arithmetic: every float32 operand a is split as it is staged, a = a1 + a2 + a3 with a1 = bf16(a), a2 = bf16(a - a1),
+ * a3 = bf16(a - a1 - a2) (round to nearest even; 24 significant bits in three parts of 8), and a product is
+ * a1 b1 + a1 b2 + a2 b1 + a2 b2 + a1 b3 + a3 b1: six bf16 MFMAs with float32 accumulation, each part product exact
+ * in float32, the three dropped ones below 2^-26 |a b|.  The results are as close to float64 as a float32 GEMM's
+ * (tests/test_lstm_wgrad.py, tests/test_lstm_split_gemm.py), at 6/16 of the matrix-core time of the float32 MFMA.
+ * No accumulation chain is longer than 8192 rows.  db is the float32 sum of the float32 values.
+ *   - A zero splits into three zeros: rows of dgates that are exactly 0 add exactly 0 whatever x and y hold there.
+ *   - A non-finite input gives NaN where a float32 product would give an infinity (Inf - Inf in the split); either
+ *     trips the trainer's non-finite check.
+ *   - Values below about 2^-108 in magnitude lose their third part, and the second below 2^-117, to bf16 underflow:
+ *     their products are then only as accurate as the parts that are left.
  *
  * tk_lstm_weight_grad_workspace_bytes: the workspace at this shape on a device with cu_count CUs (a function of its
  * five arguments only), 0 where the kernels do not run (a zero size, T N rows or an output beyond 32-bit indices): the

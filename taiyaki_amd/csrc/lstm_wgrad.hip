@@ -1,15 +1,24 @@
 // lstm_wgrad.hip -- the parameter gradients of one LSTM layer, dG^T [x | y shifted | 1], as one split-K GEMM on the
-// float32 matrix cores and one reduction (include/taiyaki_amd_lstm_wgrad.h; libtaiyaki_amd_lstm_wgrad.so).
+// bf16 matrix cores, every float32 operand split into three bf16 parts, and one reduction
+// (include/taiyaki_amd_lstm_wgrad.h; libtaiyaki_amd_lstm_wgrad.so).
 //
-// dG (K = T N rows of M = 4H), x (K x I) and y (K x H) are row-major with the summed index as the row, so a block of
-// WG_KB rows of either is staged into LDS as it lies in memory, [k][m], and v_mfma_f32_32x32x2_f32 takes its operands
-// from there one float per lane: lane l reads [k + (l >> 5)][m0 + (l & 31)], 32 consecutive floats per half wave.
-// A workgroup of four waves owns a 128 x 128 output tile (each wave 64 x 64: 2 x 2 accumulators) over one run of
-// rows.  The output's columns are tiled per operand -- x's columns, then y's -- so a tile reads one of the two; a y
+// dG (K = T N rows of M = 4H), x (K x I) and y (K x H) are row-major with the summed index as the row.  A block of
+// WG_KB = 16 rows, one k-step of v_mfma_f32_32x32x16_bf16, is staged as it lies in memory, [k][m]: each thread
+// splits its float4s a = a1 + a2 + a3 (a1 = bf16(a), a2 = bf16(a - a1), a3 = bf16(a - a1 - a2), round to nearest even,
+// both differences exact) and writes 8 bytes into each of three bf16 images per operand.  An image row is 128 bf16 =
+// 256 bytes = one LDS bank row, its 16-byte chunk c stored at chunk c ^ ((k & 3) << 2): the four rows that one
+// ds_read_b64_tr_b16 gathers per 16 lanes then lie in four different 64-byte bank groups, so the operand reads (the
+// summed index is the row in both operands, so both are transposed reads, two per 8-element fragment) are
+// conflict-free.  The product is a1 b1 + (a1 b2 + a2 b1 + a2 b2 + a1 b3 + a3 b1): products of bf16 values are exact
+// in float32 and the three dropped terms lie below 2^-26 |a b|.  The first term and the five corrections have an
+// accumulator set each (WG_ACC_SETS), added once per partial result.  A zero splits into three zeros: rows of dG that
+// are 0 add exactly 0.
+// A workgroup of eight waves owns a 128 x 128 output tile (each wave 64 x 32: 2 x 1 accumulators, twice) over one run
+// of rows.  The output's columns are tiled per operand -- x's columns, then y's -- so a tile reads one of the two; a y
 // tile reads y at row k -/+ N (the previous step's h of the same batch element), rows outside [0, K) as zeros.  The
-// workgroups of the first column of tiles add up the columns of the dG block they stage anyway: db.
+// workgroups of the first column of tiles add up the columns of the float32 dG block they stage anyway: db.
 // Rows per run are a multiple of WG_KB, so only the last block of all is ragged.  A run longer than WG_CHAIN rows is
-// cut again, inside its workgroup, into partial results of their own: no fmaf chain is longer than that.
+// cut again, inside its workgroup, into partial results of their own: no accumulation chain is longer than that.
 // blockIdx = column tile * rstride + (row tile * runs + run) with rstride a multiple of 8: the workgroups that
 // read the same rows of dG sit on one XCD and share its L2.
 #include "dispatch.h"
@@ -21,10 +30,23 @@ namespace {
 
 constexpr int WG_TILE = 128;        // output tile edge
 constexpr int WG_KB = 16;           // rows per staged block
-constexpr int WG_THREADS = 256;
-constexpr size_t WG_CHAIN = 8192;   // the longest fmaf chain, in rows
+constexpr int WG_THREADS = 512;     // two waves per SIMD: one wave's split (VALU) runs under the other's MFMAs
+constexpr int WG_SROWS = WG_THREADS / 32;           // rows of a block staged per pass of the workgroup
+constexpr int WG_SPASS = WG_KB / WG_SROWS;          // ... and passes per block
+constexpr int WG_NJ = WG_TILE / 32 / (WG_THREADS / 128);    // 32-column accumulators per wave across (two down)
+constexpr size_t WG_CHAIN = 8192;   // the longest accumulation chain, in rows
+// accumulator sets: 2 = a1 b1 and the five corrections accumulate apart, 1 = in one set.  Measured at the same speed;
+// error against float64 of dW_ih at (T, N, H, I) = (800, 128, 256, 256) 6.3e-7 with two, 1.6e-6 with one (the float32
+// MFMA kernel before: 1.6e-6; rocBLAS: 5.3e-6), and 2.7e-5 against 8.5e-5 on the cancelling input of
+// tests/test_lstm_split_gemm.py
+constexpr int WG_ACC_SETS = 2;
+constexpr int WG_IMAGE = WG_KB * WG_TILE * 2;       // bytes of one bf16 image of a block
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct WgradPlan {
     int tiles_m, tiles_x, tiles_y;  // output tiles down (4H) and across (I, then H)
@@ -88,18 +110,58 @@ __device__ __forceinline__ float4 load4(const float *src, int ld, int row, bool 
     return v;
 }
 
+// two floats -> their three bf16 parts, the first float's in the low halves (v_cvt_pk_bf16_f32; bf16 -> float is a shift)
+__device__ __forceinline__ void split2(float u, float v, uint32_t &p1, uint32_t &p2, uint32_t &p3) {
+    p1 = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{u, v}, bf16x2));
+    u -= __uint_as_float(p1 << 16), v -= __uint_as_float(p1 & 0xffff0000u);
+    p2 = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{u, v}, bf16x2));
+    u -= __uint_as_float(p2 << 16), v -= __uint_as_float(p2 & 0xffff0000u);
+    p3 = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{u, v}, bf16x2));
+}
+
+// the three parts of four floats into the three images of one operand, 8 bytes each
+__device__ __forceinline__ void stage4(unsigned char *img, float4 v) {
+    uint2 p1, p2, p3;
+    split2(v.x, v.y, p1.x, p2.x, p3.x);
+    split2(v.z, v.w, p1.y, p2.y, p3.y);
+    *reinterpret_cast<uint2 *>(img) = p1;
+    *reinterpret_cast<uint2 *>(img + WG_IMAGE) = p2;
+    *reinterpret_cast<uint2 *>(img + 2 * WG_IMAGE) = p3;
+}
+
+// rows 8 (lane >> 5) ... + 7 of 32 columns of an image as one operand fragment: `at` is the lane's address for the
+// first four rows (lstm_wgrad_kernel), the next four are 4 image rows on
+__device__ __forceinline__ bf16x8 frag(const unsigned char *at) {
+    typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
+    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)at);
+    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(at + 4 * WG_TILE * 2));
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
 template <bool FAST>
 __global__ __launch_bounds__(WG_THREADS) void lstm_wgrad_kernel(const WgradArgs a) {
-    __shared__ __attribute__((aligned(16))) float As[2][WG_KB][WG_TILE];
-    __shared__ __attribute__((aligned(16))) float Bs[2][WG_KB][WG_TILE];
+    __shared__ __attribute__((aligned(16))) unsigned char img[2][2][3][WG_IMAGE];    // [buffer][dG, x / y][part]
     __shared__ __attribute__((aligned(16))) float colsum[WG_THREADS / 32][WG_TILE];
 
     const int tnx = blockIdx.x / a.rstride, q = blockIdx.x % a.rstride;
     if (q >= a.tiles_m * a.splits) return;      // (the padding of rstride)
     const int run = q % a.splits, tmx = q / a.splits;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, lhalf = lane >> 5, wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+    const int l31 = lane & 31, lhalf = lane >> 5;
+    const int wm = (wave / (WG_THREADS / 128)) * 64, wn = (wave % (WG_THREADS / 128)) * 32 * WG_NJ;
     const int c4 = (tid & 31) * 4, r0 = tid >> 5;       // staging: this thread's four columns and first row of a block
+    // ... and where they go in an image: chunk c4 / 8 of row r0, swizzled; rows r0 and r0 + 8 swizzle alike
+    const int woff = 256 * r0 + 16 * (((tid & 31) >> 1) ^ ((r0 & 3) << 2)) + 8 * (tid & 1);
+    // the transposed read: lane 4 tq + tp of each 16 gives the address of row tq, columns 4 tp ... + 3 of its block of
+    // 4 rows x 16 columns; the wave's four blocks are columns 0-15 / 16-31 of rows 8 lhalf ... + 3
+    const int tq = (lane >> 2) & 3, tp = lane & 3;
+    int aoff[2], boff[WG_NJ];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = 256 * (8 * lhalf + tq) + 8 * (tp & 1), chunk = 4 * i + 2 * ((lane >> 4) & 1) + (tp >> 1);
+        aoff[i] = row + 16 * ((wm / 8 + chunk) ^ (tq << 2));
+        if (i < WG_NJ) boff[i] = row + 16 * ((wn / 8 + chunk) ^ (tq << 2));
+    }
 
     const bool is_x = tnx < a.tiles_x;
     const float *bsrc = is_x ? a.x : a.y;
@@ -119,68 +181,77 @@ __global__ __launch_bounds__(WG_THREADS) void lstm_wgrad_kernel(const WgradArgs 
         const int k1 = min(k0 + a.sub_rows, run_end);
         const int nkb = k1 > k0 ? (k1 - k0 + WG_KB - 1) / WG_KB : 0;
 
-        f32x16 acc[2][2];
+        f32x16 acc[WG_ACC_SETS][2][WG_NJ];
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+        for (int s = 0; s < WG_ACC_SETS; ++s)
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+            for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+                for (int j = 0; j < WG_NJ; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[s][i][j][r] = 0.f;
         float4 dbacc = make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 ra[2], rb[2];
-        bool oka[2], okb[2];
+        // two blocks are in flight from memory: block kb + 2 is requested before the MFMAs of block kb, block kb + 1
+        // is split and written to LDS after them
+        float4 ra[2][WG_SPASS], rb[2][WG_SPASS];
+        bool oka[2][WG_SPASS], okb[2][WG_SPASS];
 
-        auto fetch = [&](int kb) {
+        auto fetch = [&](int kb, int set) {
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int k = k0 + kb * WG_KB + r0 + 8 * j;
+            for (int j = 0; j < WG_SPASS; ++j) {
+                const int k = k0 + kb * WG_KB + r0 + WG_SROWS * j;
                 const int kk = k + shift;
-                oka[j] = k < k1, okb[j] = oka[j] && kk >= 0 && kk < a.K;
-                ra[j] = load4<FAST>(a.dg, a.M, k, oka[j], acol);
-                rb[j] = load4<FAST>(bsrc, bld, kk, okb[j], bcol);
+                oka[set][j] = k < k1, okb[set][j] = oka[set][j] && kk >= 0 && kk < a.K;
+                ra[set][j] = load4<FAST>(a.dg, a.M, k, oka[set][j], acol);
+                rb[set][j] = load4<FAST>(bsrc, bld, kk, okb[set][j], bcol);
             }
         };
-        auto stash = [&](int buf) {
+        auto stash = [&](int set, int buf) {
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                if (!oka[j]) ra[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (!okb[j]) rb[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                *reinterpret_cast<float4 *>(&As[buf][r0 + 8 * j][c4]) = ra[j];
-                *reinterpret_cast<float4 *>(&Bs[buf][r0 + 8 * j][c4]) = rb[j];
-                if (sum_cols) {
-                    dbacc.x += ra[j].x, dbacc.y += ra[j].y, dbacc.z += ra[j].z, dbacc.w += ra[j].w;
-                }
+            for (int j = 0; j < WG_SPASS; ++j) {
+                float4 va = ra[set][j], vb = rb[set][j];
+                if (!oka[set][j]) va = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (!okb[set][j]) vb = make_float4(0.f, 0.f, 0.f, 0.f);
+                stage4(&img[buf][0][0][woff + 256 * WG_SROWS * j], va);
+                stage4(&img[buf][1][0][woff + 256 * WG_SROWS * j], vb);
+                dbacc.x += va.x, dbacc.y += va.y, dbacc.z += va.z, dbacc.w += va.w;     // (used where sum_cols)
             }
         };
 
-        if (nkb > 0) {
-            fetch(0);
-            stash(0);
-        }
+        // no branch inside the loop: a block past the end is fetched as zeros (row 0 where the loads are unguarded)
+        // and adds nothing, so the blocks go in pairs and every fetch and stash is unconditional
+        fetch(0, 0);
+        fetch(1, 1);
+        stash(0, 0);
         __syncthreads();
-        for (int kb = 0; kb < nkb; ++kb) {
-            const int cur = kb & 1;
-            const bool more = kb + 1 < nkb;
-            if (more) fetch(kb + 1);        // in flight under the block's MFMAs
-            // the operands of the next pair of rows are read from LDS under the four MFMAs of this one
-            float a0 = As[cur][lhalf][wm + l31], a1 = As[cur][lhalf][wm + 32 + l31];
-            float b0 = Bs[cur][lhalf][wn + l31], b1 = Bs[cur][lhalf][wn + 32 + l31];
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+        for (int kb2 = 0; kb2 < nkb; kb2 += 2) {
 #pragma unroll
-            for (int kk = 0; kk < WG_KB; kk += 2) {
-                const int kn = (kk + 2 < WG_KB ? kk + 2 : kk) + lhalf;
-                const float na0 = As[cur][kn][wm + l31], na1 = As[cur][kn][wm + 32 + l31];
-                const float nb0 = Bs[cur][kn][wn + l31], nb1 = Bs[cur][kn][wn + 32 + l31];
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);      // the next pair's two LDS reads, then the four MFMAs
-                __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-                a0 = na0, a1 = na1, b0 = nb0, b1 = nb1;
+            for (int cur = 0; cur < 2; ++cur) {     // block kb is in LDS buffer kb & 1 and came through register set kb & 1
+                const int kb = kb2 + cur;
+                fetch(kb + 2, cur);
+                bf16x8 fa[2][3], fb[WG_NJ][3];
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) {
+                        fa[i][p] = frag(&img[cur][0][p][aoff[i]]);
+                        if (i < WG_NJ) fb[i][p] = frag(&img[cur][1][p][boff[i]]);
+                    }
+                // a1 b1, then the corrections, the smallest first
+                constexpr int PA[6] = {0, 2, 0, 1, 1, 0}, PB[6] = {0, 0, 2, 1, 0, 1};
+#pragma unroll
+                for (int t = 0; t < 6; ++t) {
+                    const int s = t > 0 ? WG_ACC_SETS - 1 : 0;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < WG_NJ; ++j)
+                            acc[s][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][PA[t]], fb[j][PB[t]],
+                                                                                    acc[s][i][j], 0, 0, 0);
+                }
+                stash(cur ^ 1, cur ^ 1);    // (its last readers passed the barrier of block kb - 1)
+                __syncthreads();
             }
-            if (more) stash(cur ^ 1);       // (its last readers passed the barrier of block kb - 1)
-            __syncthreads();
         }
 
         // this partial result: C[m][n] of accumulator register r sits at row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31
@@ -188,12 +259,13 @@ __global__ __launch_bounds__(WG_THREADS) void lstm_wgrad_kernel(const WgradArgs 
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
+            for (int j = 0; j < WG_NJ; ++j) {
                 const int n = wn + 32 * j + l31;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int m = tmx * WG_TILE + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
-                    if (m < a.M && bcol0 + n < bld) slab[(size_t)m * W + out_col0 + n] = acc[i][j][r];
+                    const float v = WG_ACC_SETS == 2 ? acc[0][i][j][r] + acc[WG_ACC_SETS - 1][i][j][r] : acc[0][i][j][r];
+                    if (m < a.M && bcol0 + n < bld) slab[(size_t)m * W + out_col0 + n] = v;
                 }
             }
         if (sum_cols) {
