@@ -483,130 +483,102 @@ int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const 
 #endif  // TK_RNN_VARLEN
 #undef TK_GRU_SWITCH
 
-}  // namespace
-
-#ifdef TK_RNN_VARLEN
-// The forward-only launch with per-column lengths (include/taiyaki_amd_rnn_varlen.h): the plan, and so the grid and
-// the granule buffers, of gru_forward_dispatch at the same (N, H, cu_count).  Never 0 where the kernels run.
-size_t gru_varlen_workspace_bytes(size_t N, size_t H, int cu_count) {
-    Plan p;
-    if (!gru_plan(N, H, cu_count, &p)) return 0;
-    const size_t need = gru_ws_bytes(H, p, false);
-    return need ? need : 16;
-}
-
-int gru_forward_varlen_dispatch(const float *gx, const float *whh, const float *bhh, const int32_t *lengths, size_t T,
-                                size_t N, size_t H, int reverse, int cu_count, float *y, void *ws, size_t wsb,
-                                uint32_t *status, hipStream_t stream) {
-    if (!gx || !whh || !bhh || !y || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX ||
-        N > (size_t)INT32_MAX)
+// What every dispatcher below does around its launch, written once: the pointer and range checks (`pointers_ok`: the
+// entry's own required pointers), the plan, the workspace's size, nothing to do at T == 0, the granules zeroed where
+// there are any, then `launch(plan)`.
+template <class Launch>
+int checked(bool pointers_ok, size_t T, size_t N, size_t H, int cu_count, void *ws, size_t wsb, uint32_t *status,
+            hipStream_t stream, bool backward, Launch launch) {
+    if (!pointers_ok || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX || N > (size_t)INT32_MAX)
         return TK_ERR_BAD_ARG;
     Plan p;
     if (!gru_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    const size_t need = gru_ws_bytes(H, p, false);
+    const size_t need = gru_ws_bytes(H, p, backward);
     if (wsb < (need ? need : 16)) return TK_ERR_WORKSPACE;
     if (T == 0) return TK_OK;
     if (need) {
         int rc = zero_ws(ws, need, stream);
         if (rc != TK_OK) return rc;
     }
-    return launch_fwd<true, false>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, nullptr, nullptr,
-                            static_cast<u64 *>(ws), status, lengths);
+    return launch(p);
+}
+
+// Never 0 where the kernels run (0 means "does not run here"): one granule pair at G = 1, which needs none.
+size_t workspace_bytes(size_t N, size_t H, int cu_count, bool backward) {
+    Plan p;
+    if (!gru_plan(N, H, cu_count, &p)) return 0;
+    const size_t need = gru_ws_bytes(H, p, backward);
+    return need ? need : 16;
+}
+
+}  // namespace
+
+#ifdef TK_RNN_VARLEN
+// The forward-only launch with per-column lengths (include/taiyaki_amd_rnn_varlen.h): the plan, and so the grid and
+// the granule buffers, of gru_forward_dispatch at the same (N, H, cu_count).
+size_t gru_varlen_workspace_bytes(size_t N, size_t H, int cu_count) { return workspace_bytes(N, H, cu_count, false); }
+
+int gru_forward_varlen_dispatch(const float *gx, const float *whh, const float *bhh, const int32_t *lengths, size_t T,
+                                size_t N, size_t H, int reverse, int cu_count, float *y, void *ws, size_t wsb,
+                                uint32_t *status, hipStream_t stream) {
+    auto launch = [&](const Plan &p) {
+        return launch_fwd<true, false>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, nullptr, nullptr,
+                                       static_cast<u64 *>(ws), status, lengths);
+    };
+    return checked(gx && whh && bhh && y, T, N, H, cu_count, ws, wsb, status, stream, false, launch);
 }
 #elif defined(TK_RNN_VARLEN_TRAIN)
 // The training pair with per-column lengths (include/taiyaki_amd_rnn_varlen_train.h): the plans, grids and granule
 // buffers of gru_forward_dispatch / gru_backward_dispatch at the same (N, H, cu_count); the workspace is the
-// backward's, as tk_gru_workspace_bytes is.  Never 0 where the kernels run.
+// backward's, as tk_gru_workspace_bytes is.
 size_t gru_varlen_train_workspace_bytes(size_t N, size_t H, int cu_count) {
-    Plan p;
-    if (!gru_plan(N, H, cu_count, &p)) return 0;
-    const size_t need = gru_ws_bytes(H, p, true);
-    return need ? need : 16;
+    return workspace_bytes(N, H, cu_count, true);
 }
 
 int gru_forward_varlen_save_dispatch(const float *gx, const float *whh, const float *bhh, const int32_t *lengths,
                                      size_t T, size_t N, size_t H, int reverse, int cu_count, float *y, float *gates,
                                      float *q, void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
-    if (!gx || !whh || !bhh || !y || !gates || !q || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX ||
-        N > (size_t)INT32_MAX)
-        return TK_ERR_BAD_ARG;
-    Plan p;
-    if (!gru_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    const size_t need = gru_ws_bytes(H, p, false);
-    if (wsb < (need ? need : 16)) return TK_ERR_WORKSPACE;
-    if (T == 0) return TK_OK;
-    if (need) {
-        int rc = zero_ws(ws, need, stream);
-        if (rc != TK_OK) return rc;
-    }
-    return launch_fwd<true, true>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, gates, q,
-                                  static_cast<u64 *>(ws), status, lengths);
+    auto launch = [&](const Plan &p) {
+        return launch_fwd<true, true>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, gates, q,
+                                      static_cast<u64 *>(ws), status, lengths);
+    };
+    return checked(gx && whh && bhh && y && gates && q, T, N, H, cu_count, ws, wsb, status, stream, false, launch);
 }
 
 int gru_backward_varlen_dispatch(const float *whh, const float *y, const float *gates, const float *q,
                                  const float *dy, const int32_t *lengths, size_t T, size_t N, size_t H, int reverse,
                                  int cu_count, float *dgates, float *dq, void *ws, size_t wsb, uint32_t *status,
                                  hipStream_t stream) {
-    if (!whh || !y || !gates || !q || !dy || !dgates || !dq || !ws || !status || !aligned16(ws) ||
-        T > (size_t)INT32_MAX || N > (size_t)INT32_MAX)
-        return TK_ERR_BAD_ARG;
-    Plan p;
-    if (!gru_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    const size_t need = gru_ws_bytes(H, p, true);
-    if (wsb < (need ? need : 16)) return TK_ERR_WORKSPACE;
-    if (T == 0) return TK_OK;
-    if (need) {
-        int rc = zero_ws(ws, need, stream);
-        if (rc != TK_OK) return rc;
-    }
-    return launch_bwd<true>(p, H, stream, whh, y, gates, q, dy, (int)T, (int)N, reverse, dgates, dq,
-                            static_cast<u64 *>(ws), status, lengths);
+    auto launch = [&](const Plan &p) {
+        return launch_bwd<true>(p, H, stream, whh, y, gates, q, dy, (int)T, (int)N, reverse, dgates, dq,
+                                static_cast<u64 *>(ws), status, lengths);
+    };
+    return checked(whh && y && gates && q && dy && dgates && dq, T, N, H, cu_count, ws, wsb, status, stream, true,
+                   launch);
 }
 #else
-// Never 0 where the kernels run (0 means "does not run here"): one granule pair at G = 1, which needs none.
-size_t gru_workspace_bytes(size_t N, size_t H, int cu_count) {
-    Plan p;
-    if (!gru_plan(N, H, cu_count, &p)) return 0;
-    const size_t need = gru_ws_bytes(H, p, true);
-    return need ? need : 16;
-}
+size_t gru_workspace_bytes(size_t N, size_t H, int cu_count) { return workspace_bytes(N, H, cu_count, true); }
 
+// gates and q may be NULL: the activations are then not saved
 int gru_forward_dispatch(const float *gx, const float *whh, const float *bhh, size_t T, size_t N, size_t H,
                          int reverse, int cu_count, float *y, float *gates, float *q, void *ws, size_t wsb,
                          uint32_t *status, hipStream_t stream) {
-    if (!gx || !whh || !bhh || !y || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX ||
-        N > (size_t)INT32_MAX)
-        return TK_ERR_BAD_ARG;
-    Plan p;
-    if (!gru_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    const size_t need = gru_ws_bytes(H, p, false);
-    if (wsb < (need ? need : 16)) return TK_ERR_WORKSPACE;
-    if (T == 0) return TK_OK;
-    if (need) {
-        int rc = zero_ws(ws, need, stream);
-        if (rc != TK_OK) return rc;
-    }
-    return launch_fwd<false, true>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, gates, q,
-                                   static_cast<u64 *>(ws), status, nullptr);
+    auto launch = [&](const Plan &p) {
+        return launch_fwd<false, true>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, gates, q,
+                                       static_cast<u64 *>(ws), status, nullptr);
+    };
+    return checked(gx && whh && bhh && y, T, N, H, cu_count, ws, wsb, status, stream, false, launch);
 }
 
 int gru_backward_dispatch(const float *whh, const float *y, const float *gates, const float *q, const float *dy,
                           size_t T, size_t N, size_t H, int reverse, int cu_count, float *dgates, float *dq, void *ws,
                           size_t wsb, uint32_t *status, hipStream_t stream) {
-    if (!whh || !y || !gates || !q || !dy || !dgates || !dq || !ws || !status || !aligned16(ws) ||
-        T > (size_t)INT32_MAX || N > (size_t)INT32_MAX)
-        return TK_ERR_BAD_ARG;
-    Plan p;
-    if (!gru_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    const size_t need = gru_ws_bytes(H, p, true);
-    if (wsb < (need ? need : 16)) return TK_ERR_WORKSPACE;
-    if (T == 0) return TK_OK;
-    if (need) {
-        int rc = zero_ws(ws, need, stream);
-        if (rc != TK_OK) return rc;
-    }
-    return launch_bwd<false>(p, H, stream, whh, y, gates, q, dy, (int)T, (int)N, reverse, dgates, dq,
-                             static_cast<u64 *>(ws), status, nullptr);
+    auto launch = [&](const Plan &p) {
+        return launch_bwd<false>(p, H, stream, whh, y, gates, q, dy, (int)T, (int)N, reverse, dgates, dq,
+                                 static_cast<u64 *>(ws), status, nullptr);
+    };
+    return checked(whh && y && gates && q && dy && dgates && dq, T, N, H, cu_count, ws, wsb, status, stream, true,
+                   launch);
 }
 
 #ifdef TK_LAB

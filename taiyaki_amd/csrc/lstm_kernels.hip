@@ -502,6 +502,31 @@ int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const 
 #endif  // TK_RNN_VARLEN
 #undef TK_LSTM_SWITCH
 
+// What every dispatcher below does around its launch, written once: the pointer and range checks (`pointers_ok`: the
+// entry's own required pointers), the plan, the workspace's size, nothing to do at T == 0, the granules zeroed, then
+// `launch(plan)`.
+template <class Launch>
+int checked(bool pointers_ok, size_t T, size_t N, size_t H, int cu_count, void *ws, size_t wsb, uint32_t *status,
+            hipStream_t stream, bool backward, Launch launch) {
+    if (!pointers_ok || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX || N > (size_t)INT32_MAX)
+        return TK_ERR_BAD_ARG;
+    Plan p;
+    if (!lstm_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+    const size_t need = ws_bytes(H, p.C, p.groups, p.U, backward);
+    if (wsb < need) return TK_ERR_WORKSPACE;
+    if (T == 0) return TK_OK;
+    int rc = zero_ws(ws, need, stream);
+    if (rc != TK_OK) return rc;
+    return launch(p);
+}
+
+// the backward's granule bytes at U = 16: they bound every plan's, forward and backward
+size_t train_workspace_bytes(size_t N, size_t H, int cu_count) {
+    int C = 0, groups = 0;
+    if (!lstm_geometry(N, H, cu_count, &C, &groups)) return 0;
+    return ws_bytes(H, C, groups, 16, true);
+}
+
 }  // namespace
 
 #ifdef TK_RNN_VARLEN
@@ -516,100 +541,60 @@ size_t lstm_varlen_workspace_bytes(size_t N, size_t H, int cu_count) {
 int lstm_forward_varlen_dispatch(const float *gx, const float *whh, const int32_t *lengths, size_t T, size_t N,
                                  size_t H, int reverse, int cu_count, float *y, void *ws, size_t wsb,
                                  uint32_t *status, hipStream_t stream) {
-    if (!gx || !whh || !y || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX || N > (size_t)INT32_MAX)
-        return TK_ERR_BAD_ARG;
-    Plan p;
-    if (!lstm_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    const size_t need = ws_bytes(H, p.C, p.groups, p.U, false);
-    if (wsb < need) return TK_ERR_WORKSPACE;
-    if (T == 0) return TK_OK;
-    int rc = zero_ws(ws, need, stream);
-    if (rc != TK_OK) return rc;
-    return launch_fwd<true, false>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, nullptr, nullptr,
-                            static_cast<u64 *>(ws), status, lengths);
+    auto launch = [&](const Plan &p) {
+        return launch_fwd<true, false>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, nullptr, nullptr,
+                                       static_cast<u64 *>(ws), status, lengths);
+    };
+    return checked(gx && whh && y, T, N, H, cu_count, ws, wsb, status, stream, false, launch);
 }
 #elif defined(TK_RNN_VARLEN_TRAIN)
 // The training pair with per-column lengths (include/taiyaki_amd_rnn_varlen_train.h): the plans, grids and granule
 // buffers of lstm_forward_dispatch / lstm_backward_dispatch at the same (N, H, cu_count); the workspace is the
 // backward's bound, as tk_lstm_workspace_bytes is.
 size_t lstm_varlen_train_workspace_bytes(size_t N, size_t H, int cu_count) {
-    int C = 0, groups = 0;
-    if (!lstm_geometry(N, H, cu_count, &C, &groups)) return 0;
-    return ws_bytes(H, C, groups, 16, true);
+    return train_workspace_bytes(N, H, cu_count);
 }
 
 int lstm_forward_varlen_save_dispatch(const float *gx, const float *whh, const int32_t *lengths, size_t T, size_t N,
                                       size_t H, int reverse, int cu_count, float *y, float *gates, float *cell,
                                       void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
-    if (!gx || !whh || !y || !gates || !cell || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX ||
-        N > (size_t)INT32_MAX)
-        return TK_ERR_BAD_ARG;
-    Plan p;
-    if (!lstm_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    const size_t need = ws_bytes(H, p.C, p.groups, p.U, false);
-    if (wsb < need) return TK_ERR_WORKSPACE;
-    if (T == 0) return TK_OK;
-    int rc = zero_ws(ws, need, stream);
-    if (rc != TK_OK) return rc;
-    return launch_fwd<true, true>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, gates, cell,
-                                  static_cast<u64 *>(ws), status, lengths);
+    auto launch = [&](const Plan &p) {
+        return launch_fwd<true, true>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, gates, cell,
+                                      static_cast<u64 *>(ws), status, lengths);
+    };
+    return checked(gx && whh && y && gates && cell, T, N, H, cu_count, ws, wsb, status, stream, false, launch);
 }
 
 int lstm_backward_varlen_dispatch(const float *whh, const float *gates, const float *cell, const float *dy,
                                   const int32_t *lengths, size_t T, size_t N, size_t H, int reverse, int cu_count,
                                   float *dgates, void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
-    if (!whh || !gates || !cell || !dy || !dgates || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX ||
-        N > (size_t)INT32_MAX)
-        return TK_ERR_BAD_ARG;
-    Plan p;
-    if (!lstm_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    const size_t need = ws_bytes(H, p.C, p.groups, p.U, true);
-    if (wsb < need) return TK_ERR_WORKSPACE;
-    if (T == 0) return TK_OK;
-    int rc = zero_ws(ws, need, stream);
-    if (rc != TK_OK) return rc;
-    return launch_bwd<true>(p, H, stream, whh, gates, cell, dy, (int)T, (int)N, reverse, dgates,
-                            static_cast<u64 *>(ws), status, lengths);
+    auto launch = [&](const Plan &p) {
+        return launch_bwd<true>(p, H, stream, whh, gates, cell, dy, (int)T, (int)N, reverse, dgates,
+                                static_cast<u64 *>(ws), status, lengths);
+    };
+    return checked(whh && gates && cell && dy && dgates, T, N, H, cu_count, ws, wsb, status, stream, true, launch);
 }
 #else
-size_t lstm_workspace_bytes(size_t N, size_t H, int cu_count) {
-    int C = 0, groups = 0;
-    if (!lstm_geometry(N, H, cu_count, &C, &groups)) return 0;
-    return ws_bytes(H, C, groups, 16, true);    // the backward's at U = 16 bounds every plan's
-}
+size_t lstm_workspace_bytes(size_t N, size_t H, int cu_count) { return train_workspace_bytes(N, H, cu_count); }
 
 int lstm_forward_dispatch(const float *gx, const float *whh, size_t T, size_t N, size_t H, int reverse,
                           int cu_count, float *y, float *gates, float *cell, void *ws, size_t wsb,
                           uint32_t *status, hipStream_t stream) {
-    if (!gx || !whh || !y || !gates || !cell || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX ||
-        N > (size_t)INT32_MAX)
-        return TK_ERR_BAD_ARG;
-    Plan p;
-    if (!lstm_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    const size_t need = ws_bytes(H, p.C, p.groups, p.U, false);
-    if (wsb < need) return TK_ERR_WORKSPACE;
-    if (T == 0) return TK_OK;
-    int rc = zero_ws(ws, need, stream);
-    if (rc != TK_OK) return rc;
-    return launch_fwd<false, true>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, gates, cell,
-                                   static_cast<u64 *>(ws), status, nullptr);
+    auto launch = [&](const Plan &p) {
+        return launch_fwd<false, true>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, gates, cell,
+                                       static_cast<u64 *>(ws), status, nullptr);
+    };
+    return checked(gx && whh && y && gates && cell, T, N, H, cu_count, ws, wsb, status, stream, false, launch);
 }
 
 int lstm_backward_dispatch(const float *whh, const float *gates, const float *cell, const float *dy, size_t T,
                            size_t N, size_t H, int reverse, int cu_count, float *dgates, void *ws, size_t wsb,
                            uint32_t *status, hipStream_t stream) {
-    if (!whh || !gates || !cell || !dy || !dgates || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX ||
-        N > (size_t)INT32_MAX)
-        return TK_ERR_BAD_ARG;
-    Plan p;
-    if (!lstm_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    const size_t need = ws_bytes(H, p.C, p.groups, p.U, true);
-    if (wsb < need) return TK_ERR_WORKSPACE;
-    if (T == 0) return TK_OK;
-    int rc = zero_ws(ws, need, stream);
-    if (rc != TK_OK) return rc;
-    return launch_bwd<false>(p, H, stream, whh, gates, cell, dy, (int)T, (int)N, reverse, dgates,
-                             static_cast<u64 *>(ws), status, nullptr);
+    auto launch = [&](const Plan &p) {
+        return launch_bwd<false>(p, H, stream, whh, gates, cell, dy, (int)T, (int)N, reverse, dgates,
+                                 static_cast<u64 *>(ws), status, nullptr);
+    };
+    return checked(whh && gates && cell && dy && dgates, T, N, H, cu_count, ws, wsb, status, stream, true, launch);
 }
 
 #ifdef TK_LAB

@@ -268,51 +268,73 @@ def _hip_lstm_takes(rnn, x):
     return not (rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or rnn.batch_first or rnn.proj_size)
 
 
+# What a recurrence launches, by (per-column lengths given, activations saved): the library (its accessor in _lib), the
+# forward and the backward entry ("%s": lstm / gru) and the workspace's tag (None: the cell's own).
+_RNN_LAUNCHES = {
+    (False, True): ("lib", "tk_%s_forward_dev", "tk_%s_backward_dev", None),
+    (False, False): ("lib", "tk_%s_forward_dev", None, None),       # the GRU alone: NULL for the activations
+    (True, True): ("varlen_train_lib", "tk_%s_forward_varlen_save_dev", "tk_%s_backward_varlen_dev",
+                   "rnn_varlen_train"),
+    (True, False): ("varlen_lib", "tk_%s_forward_varlen_dev", None, "rnn_varlen"),
+}
+
+
+def _rnn_launch(cell, lens, save, backward, ins, shape, reverse, outs, wsb, dev):
+    """One launch of a recurrence, checked: the entry of _RNN_LAUNCHES on `ins` (the lengths behind them where given),
+    T, N, H, the direction and the CU count, `outs`, then the workspace, the status word and the stream."""
+    libname, fwd, bwd, tag = _RNN_LAUNCHES[lens is not None, bool(save)]
+    name = (bwd if backward else fwd) % cell
+    ws = _lib.workspace(wsb, dev, tag or cell)
+    status = _lib.status_word(dev)
+    ptrs = [_lib.ptr(t) for t in ins + (() if lens is None else (lens,))]
+    rc = getattr(getattr(_lib, libname)(), name)(*ptrs, *shape, int(reverse), _cu_count(dev),
+                                                 *[_lib.ptr(t) for t in outs], _lib.ptr(ws), wsb, _lib.ptr(status),
+                                                 _lib.stream_ptr())
+    _lib.check(rc, name)
+    _lib.finish(status)
+
+
 class LstmRecurrence(torch.autograd.Function):
     """One nn.LSTM layer (h0 = c0 = 0) with its recurrence on the HIP kernels.  Forward: G_x = x W_ih^T + b_ih +
     b_hh as one GEMM, then tk_lstm_forward_dev.  Backward: tk_lstm_backward_dev gives dG (the gates'
     pre-activation gradient, T x N x 4H), the parameter and input gradients are GEMMs / a sum over it.
-    `reverse` runs the recurrence from the last time step (layers.Reverse) on tensors in time order."""
+    `reverse` runs the recurrence from the last time step (layers.Reverse) on tensors in time order.
+    `lens` (a device int32 tensor, one entry per column): column n has lens[n] steps, and the launches are those of
+    include/taiyaki_amd_rnn_varlen_train.h.  y, the gates, c and dG are 0 at and beyond every length, so the input and
+    parameter gradients are the same sums over the whole padded tensors.  `save` False (only with `lens`) is the launch
+    of include/taiyaki_amd_rnn_varlen.h: nothing but y is allocated or written, and the call cannot be differentiated."""
 
     @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, wsb):
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, wsb, lens=None, save=True):
+        if lens is None and not save:
+            raise RuntimeError("the LSTM has no launch without lengths that saves nothing")
         T, N, _ = x.shape
         H = w_hh.shape[1]
         dev = x.device
-        L = _lib.lib()
         x = x.contiguous()
         w_hh = w_hh.contiguous()
+        if lens is not None:
+            rnn_varlen_calls["saved" if save else "inference"] += 1
         gx = torch.addmm(b_ih + b_hh, x.view(T * N, -1), w_ih.t())
         y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
-        gates = torch.empty(T, N, 4 * H, dtype=torch.float32, device=dev)
-        cell = torch.empty(T, N, H, dtype=torch.float32, device=dev)
-        ws = _lib.workspace(wsb, dev, "lstm")
-        status = _lib.status_word(dev)
-        rc = L.tk_lstm_forward_dev(_lib.ptr(gx), _lib.ptr(w_hh), T, N, H, int(reverse), _cu_count(dev),
-                                   _lib.ptr(y), _lib.ptr(gates), _lib.ptr(cell), _lib.ptr(ws), wsb,
-                                   _lib.ptr(status), _lib.stream_ptr())
-        _lib.check(rc, "tk_lstm_forward_dev")
-        _lib.finish(status)
-        ctx.save_for_backward(x, w_ih, w_hh, y, gates, cell)
+        gates = torch.empty(T, N, 4 * H, dtype=torch.float32, device=dev) if save else None
+        cell = torch.empty(T, N, H, dtype=torch.float32, device=dev) if save else None
+        _rnn_launch("lstm", lens, save, False, (gx, w_hh), (T, N, H), reverse, (y, gates, cell) if save else (y,), wsb,
+                    dev)
+        if save:
+            ctx.save_for_backward(x, w_ih, w_hh, y, gates, cell, lens)
         ctx.reverse, ctx.wsb = reverse, wsb
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, w_ih, w_hh, y, gates, cell = ctx.saved_tensors
+        x, w_ih, w_hh, y, gates, cell, lens = ctx.saved_tensors
         T, N, I = x.shape
         H = w_hh.shape[1]
-        dev = x.device
         dy = dy.contiguous()
         dg = torch.empty_like(gates)
-        ws = _lib.workspace(ctx.wsb, dev, "lstm")
-        status = _lib.status_word(dev)
-        rc = _lib.lib().tk_lstm_backward_dev(_lib.ptr(w_hh), _lib.ptr(gates), _lib.ptr(cell), _lib.ptr(dy), T, N,
-                                             H, int(ctx.reverse), _cu_count(dev), _lib.ptr(dg), _lib.ptr(ws),
-                                             ctx.wsb, _lib.ptr(status), _lib.stream_ptr())
-        _lib.check(rc, "tk_lstm_backward_dev")
-        _lib.finish(status)
-        return _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None, None)
+        _rnn_launch("lstm", lens, True, True, (w_hh, gates, cell, dy), (T, N, H), ctx.reverse, (dg,), ctx.wsb, x.device)
+        return _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None,) * 4
 
 
 def _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, reverse, need):
@@ -348,52 +370,6 @@ def _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, reverse, need):
             dw_hh = torch.zeros_like(w_hh)
     db = dg2.sum(0) if (need[3] or need[4]) else None
     return dx, dw_ih, dw_hh, db if need[3] else None, db if need[4] else None
-
-
-class LstmVarlenRecurrence(torch.autograd.Function):
-    """`LstmRecurrence` on a batch whose column n has lens[n] steps (a device int32 tensor): the saving forward and the
-    backward of include/taiyaki_amd_rnn_varlen_train.h.  y, the gates, c and dG are 0 at and beyond every length, so the
-    input and parameter gradients are those of `LstmRecurrence.backward` on the whole padded tensors."""
-
-    @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, lens, reverse, wsb):
-        T, N, _ = x.shape
-        H = w_hh.shape[1]
-        dev = x.device
-        x = x.contiguous()
-        w_hh = w_hh.contiguous()
-        rnn_varlen_calls["saved"] += 1
-        gx = torch.addmm(b_ih + b_hh, x.view(T * N, -1), w_ih.t())
-        y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
-        gates = torch.empty(T, N, 4 * H, dtype=torch.float32, device=dev)
-        cell = torch.empty(T, N, H, dtype=torch.float32, device=dev)
-        ws = _lib.workspace(wsb, dev, "rnn_varlen_train")
-        status = _lib.status_word(dev)
-        rc = _lib.varlen_train_lib().tk_lstm_forward_varlen_save_dev(
-            _lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(lens), T, N, H, int(reverse), _cu_count(dev), _lib.ptr(y),
-            _lib.ptr(gates), _lib.ptr(cell), _lib.ptr(ws), wsb, _lib.ptr(status), _lib.stream_ptr())
-        _lib.check(rc, "tk_lstm_forward_varlen_save_dev")
-        _lib.finish(status)
-        ctx.save_for_backward(x, w_ih, w_hh, y, gates, cell, lens)
-        ctx.reverse, ctx.wsb = reverse, wsb
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w_ih, w_hh, y, gates, cell, lens = ctx.saved_tensors
-        T, N, _ = x.shape
-        H = w_hh.shape[1]
-        dev = x.device
-        dy = dy.contiguous()
-        dg = torch.empty_like(gates)
-        ws = _lib.workspace(ctx.wsb, dev, "rnn_varlen_train")
-        status = _lib.status_word(dev)
-        rc = _lib.varlen_train_lib().tk_lstm_backward_varlen_dev(
-            _lib.ptr(w_hh), _lib.ptr(gates), _lib.ptr(cell), _lib.ptr(dy), _lib.ptr(lens), T, N, H, int(ctx.reverse),
-            _cu_count(dev), _lib.ptr(dg), _lib.ptr(ws), ctx.wsb, _lib.ptr(status), _lib.stream_ptr())
-        _lib.check(rc, "tk_lstm_backward_varlen_dev")
-        _lib.finish(status)
-        return _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None, None, None)
 
 
 class Lstm(_Rnn):
@@ -465,10 +441,14 @@ class GruRecurrence(torch.autograd.Function):
     they are neither allocated nor written, and the call cannot be differentiated.  Backward: tk_gru_backward_dev gives
     dG = dL/dG_x (T x N x 3H) and dq; the hidden side's pre-activation gradient is dG with dq as its third slab,
     and the parameter and input gradients are GEMMs / sums over the two.  `reverse` runs the recurrence from the
-    last time step (layers.Reverse) on tensors in time order."""
+    last time step (layers.Reverse) on tensors in time order.
+    `lens` (a device int32 tensor, one entry per column): column n has lens[n] steps, and the launches are those of
+    include/taiyaki_amd_rnn_varlen_train.h (`save`) or include/taiyaki_amd_rnn_varlen.h (not `save`).  y, the
+    activations, q, dG and dq are 0 at and beyond every length, so the input and parameter gradients are the same sums
+    over the whole padded tensors."""
 
     @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, wsb, save):
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, wsb, save, lens=None):
         T, N, _ = x.shape
         H = w_hh.shape[1]
         dev = x.device
@@ -476,40 +456,32 @@ class GruRecurrence(torch.autograd.Function):
         w_hh, b_hh = w_hh.contiguous(), b_hh.contiguous()
         # (grad mode is off inside forward and ctx.needs_input_grad ignores it: the caller decides)
         train = bool(save)
-        gru_forward_calls["saved" if train else "inference"] += 1
+        if lens is not None:
+            rnn_varlen_calls["saved" if train else "inference"] += 1
+        if lens is None or train:
+            gru_forward_calls["saved" if train else "inference"] += 1
         gx = torch.addmm(b_ih, x.view(T * N, -1), w_ih.t())
         y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
         gates = torch.empty(T, N, 3 * H, dtype=torch.float32, device=dev) if train else None
         q = torch.empty(T, N, H, dtype=torch.float32, device=dev) if train else None
-        ws = _lib.workspace(wsb, dev, "gru")
-        status = _lib.status_word(dev)
-        rc = _lib.lib().tk_gru_forward_dev(_lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(b_hh), T, N, H, int(reverse),
-                                           _cu_count(dev), _lib.ptr(y), _lib.ptr(gates), _lib.ptr(q), _lib.ptr(ws),
-                                           wsb, _lib.ptr(status), _lib.stream_ptr())
-        _lib.check(rc, "tk_gru_forward_dev")
-        _lib.finish(status)
+        _rnn_launch("gru", lens, train, False, (gx, w_hh, b_hh), (T, N, H), reverse,
+                    (y, gates, q) if train or lens is None else (y,), wsb, dev)
         if train:
-            ctx.save_for_backward(x, w_ih, w_hh, y, gates, q)
+            ctx.save_for_backward(x, w_ih, w_hh, y, gates, q, lens)
         ctx.reverse, ctx.wsb = reverse, wsb
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, w_ih, w_hh, y, gates, q = ctx.saved_tensors
+        x, w_ih, w_hh, y, gates, q, lens = ctx.saved_tensors
         T, N, I = x.shape
         H = w_hh.shape[1]
-        dev = x.device
         dy = dy.contiguous()
         dg = torch.empty_like(gates)
         dq = torch.empty_like(q)
-        ws = _lib.workspace(ctx.wsb, dev, "gru")
-        status = _lib.status_word(dev)
-        rc = _lib.lib().tk_gru_backward_dev(_lib.ptr(w_hh), _lib.ptr(y), _lib.ptr(gates), _lib.ptr(q), _lib.ptr(dy),
-                                            T, N, H, int(ctx.reverse), _cu_count(dev), _lib.ptr(dg), _lib.ptr(dq),
-                                            _lib.ptr(ws), ctx.wsb, _lib.ptr(status), _lib.stream_ptr())
-        _lib.check(rc, "tk_gru_backward_dev")
-        _lib.finish(status)
-        return _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None, None, None)
+        _rnn_launch("gru", lens, True, True, (w_hh, y, gates, q, dy), (T, N, H), ctx.reverse, (dg, dq), ctx.wsb,
+                    x.device)
+        return _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None,) * 4
 
 
 def _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, reverse, need):
@@ -535,55 +507,6 @@ def _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, reverse, need):
     return dx, dw_ih, dw_hh, db_ih if need[3] else None, db_hh
 
 
-class GruVarlenRecurrence(torch.autograd.Function):
-    """`GruRecurrence` (saving) on a batch whose column n has lens[n] steps (a device int32 tensor): the saving forward
-    and the backward of include/taiyaki_amd_rnn_varlen_train.h.  y, the activations, q, dG and dq are 0 at and beyond
-    every length, so the input and parameter gradients are those of `GruRecurrence.backward` on the padded tensors."""
-
-    @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, lens, reverse, wsb):
-        T, N, _ = x.shape
-        H = w_hh.shape[1]
-        dev = x.device
-        x = x.contiguous()
-        w_hh, b_hh = w_hh.contiguous(), b_hh.contiguous()
-        gru_forward_calls["saved"] += 1
-        rnn_varlen_calls["saved"] += 1
-        gx = torch.addmm(b_ih, x.view(T * N, -1), w_ih.t())
-        y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
-        gates = torch.empty(T, N, 3 * H, dtype=torch.float32, device=dev)
-        q = torch.empty(T, N, H, dtype=torch.float32, device=dev)
-        ws = _lib.workspace(wsb, dev, "rnn_varlen_train")
-        status = _lib.status_word(dev)
-        rc = _lib.varlen_train_lib().tk_gru_forward_varlen_save_dev(
-            _lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(b_hh), _lib.ptr(lens), T, N, H, int(reverse), _cu_count(dev),
-            _lib.ptr(y), _lib.ptr(gates), _lib.ptr(q), _lib.ptr(ws), wsb, _lib.ptr(status), _lib.stream_ptr())
-        _lib.check(rc, "tk_gru_forward_varlen_save_dev")
-        _lib.finish(status)
-        ctx.save_for_backward(x, w_ih, w_hh, y, gates, q, lens)
-        ctx.reverse, ctx.wsb = reverse, wsb
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w_ih, w_hh, y, gates, q, lens = ctx.saved_tensors
-        T, N, _ = x.shape
-        H = w_hh.shape[1]
-        dev = x.device
-        dy = dy.contiguous()
-        dg = torch.empty_like(gates)
-        dq = torch.empty_like(q)
-        ws = _lib.workspace(ctx.wsb, dev, "rnn_varlen_train")
-        status = _lib.status_word(dev)
-        rc = _lib.varlen_train_lib().tk_gru_backward_varlen_dev(
-            _lib.ptr(w_hh), _lib.ptr(y), _lib.ptr(gates), _lib.ptr(q), _lib.ptr(dy), _lib.ptr(lens), T, N, H,
-            int(ctx.reverse), _cu_count(dev), _lib.ptr(dg), _lib.ptr(dq), _lib.ptr(ws), ctx.wsb, _lib.ptr(status),
-            _lib.stream_ptr())
-        _lib.check(rc, "tk_gru_backward_varlen_dev")
-        _lib.finish(status)
-        return _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None, None, None)
-
-
 class GruMod(_Rnn):
     """layers.py:609-725 (wraps nn.GRU, bias_hh frozen).  On the GPU the recurrence runs on the HIP kernels
     (`GruRecurrence`); nn.GRU evaluates CPU tensors, sizes the kernels do not cover, and USE_HIP_GRU = False."""
@@ -605,26 +528,27 @@ class GruMod(_Rnn):
         return rnn(x)[0]
 
 
-def hip_rnn_varlen_workspace_bytes(rnn, x):
-    """Workspace of the forward-only launch with per-column lengths (include/taiyaki_amd_rnn_varlen.h) for this nn.LSTM
-    or nn.GRU and input, 0 where it does not run: what `hip_lstm_workspace_bytes` / `hip_gru_workspace_bytes` rule
-    out, under the same switches."""
+def _rnn_varlen_workspace_bytes(rnn, x, train):
     lstm = isinstance(rnn, nn.LSTM)
     if not (_hip_lstm_takes(rnn, x) if lstm else _hip_gru_takes(rnn, x)):
         return 0
     kind = _lib.VARLEN_DEFINES["TK_RNN_KIND_LSTM" if lstm else "TK_RNN_KIND_GRU"]
-    return _lib.varlen_lib().tk_rnn_varlen_workspace_bytes(kind, x.shape[1], rnn.hidden_size, _cu_count(x.device))
+    query = (_lib.varlen_train_lib().tk_rnn_varlen_train_workspace_bytes if train
+             else _lib.varlen_lib().tk_rnn_varlen_workspace_bytes)
+    return query(kind, x.shape[1], rnn.hidden_size, _cu_count(x.device))
+
+
+def hip_rnn_varlen_workspace_bytes(rnn, x):
+    """Workspace of the forward-only launch with per-column lengths (include/taiyaki_amd_rnn_varlen.h) for this nn.LSTM
+    or nn.GRU and input, 0 where it does not run: what `hip_lstm_workspace_bytes` / `hip_gru_workspace_bytes` rule
+    out, under the same switches."""
+    return _rnn_varlen_workspace_bytes(rnn, x, False)
 
 
 def hip_rnn_varlen_train_workspace_bytes(rnn, x):
     """Workspace of the training pair with per-column lengths (include/taiyaki_amd_rnn_varlen_train.h) for this nn.LSTM
     or nn.GRU and input, 0 where it does not run: the rule of `hip_rnn_varlen_workspace_bytes`."""
-    lstm = isinstance(rnn, nn.LSTM)
-    if not (_hip_lstm_takes(rnn, x) if lstm else _hip_gru_takes(rnn, x)):
-        return 0
-    kind = _lib.VARLEN_DEFINES["TK_RNN_KIND_LSTM" if lstm else "TK_RNN_KIND_GRU"]
-    return _lib.varlen_train_lib().tk_rnn_varlen_train_workspace_bytes(kind, x.shape[1], rnn.hidden_size,
-                                                                       _cu_count(x.device))
+    return _rnn_varlen_workspace_bytes(rnn, x, True)
 
 
 def _needs_grad(x, module):
@@ -634,10 +558,11 @@ def _needs_grad(x, module):
 def _rnn_forward_varlen(layer, x, reverse, lengths):
     """`Lstm` / `GruMod` forward on a batch whose column n has lengths[n] steps: rows [0, lengths[n]) of column n are
     what `layer(x[:lengths[n], n:n + 1], reverse)` gives, the rows beyond are 0.  Where a HIP launch admits the
-    tensors: under grad mode with something that requires a gradient, `LstmVarlenRecurrence` / `GruVarlenRecurrence`
-    (x must be finite in the padding: the parameter gradients are sums over the whole padded tensors); otherwise one
-    launch of tk_lstm_forward_varlen_dev / tk_gru_forward_varlen_dev, which saves nothing.  Every column alone at its
-    own length otherwise (differentiable like any other call of the layer).  Under grad mode the call needs
+    tensors, `LstmRecurrence` / `GruRecurrence` with the lengths: under grad mode with something that requires a
+    gradient they save the activations (x must be finite in the padding: the parameter gradients are sums over the
+    whole padded tensors); otherwise it is one launch of tk_lstm_forward_varlen_dev / tk_gru_forward_varlen_dev, which
+    saves nothing.  Every column alone at its own length otherwise (differentiable like any other call of the layer).
+    Under grad mode the call needs
     layers.TRAIN_VARLEN = True; without it it raises, as it did before there was a backward with lengths."""
     rnn = layer.rnn
     T, N, _ = x.shape
@@ -661,35 +586,13 @@ def _rnn_forward_varlen(layer, x, reverse, lengths):
             if ln:
                 y[:ln, n:n + 1] = layer(x[:ln, n:n + 1], reverse=reverse)
         return y
-    dev = x.device
-    lstm = isinstance(rnn, nn.LSTM)
-    if train:
-        with torch.cuda.device(dev):
-            lens = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).reshape(-1).clamp(0, T).contiguous()
-            assert lens.numel() == N, "lengths: one per column"
-            fn = LstmVarlenRecurrence if lstm else GruVarlenRecurrence
-            return fn.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0, lens,
-                            bool(reverse), wsb)
-    with torch.no_grad(), torch.cuda.device(dev):
-        rnn_varlen_calls["inference"] += 1
-        lens = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).reshape(-1).clamp(0, T).contiguous()
+    with torch.cuda.device(x.device):
+        lens = torch.as_tensor(lengths).to(device=x.device, dtype=torch.int32).reshape(-1).clamp(0, T).contiguous()
         assert lens.numel() == N, "lengths: one per column"
-        x = x.contiguous()
-        w_hh, b_hh = rnn.weight_hh_l0.contiguous(), rnn.bias_hh_l0.contiguous()
-        gx = torch.addmm(rnn.bias_ih_l0 + b_hh if lstm else rnn.bias_ih_l0, x.view(T * N, -1), rnn.weight_ih_l0.t())
-        y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
-        ws = _lib.workspace(wsb, dev, "rnn_varlen")
-        status = _lib.status_word(dev)
-        tail = (T, N, H, int(bool(reverse)), _cu_count(dev), _lib.ptr(y), _lib.ptr(ws), wsb, _lib.ptr(status),
-                _lib.stream_ptr())
-        if lstm:
-            rc = _lib.varlen_lib().tk_lstm_forward_varlen_dev(_lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(lens), *tail)
-        else:
-            rc = _lib.varlen_lib().tk_gru_forward_varlen_dev(_lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(b_hh),
-                                                             _lib.ptr(lens), *tail)
-        _lib.check(rc, "tk_lstm_forward_varlen_dev" if lstm else "tk_gru_forward_varlen_dev")
-        _lib.finish(status)
-    return y
+        args = (x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0, bool(reverse), wsb)
+        if isinstance(rnn, nn.LSTM):
+            return LstmRecurrence.apply(*args, lens, train)
+        return GruRecurrence.apply(*args, train, lens)
 
 
 class Reverse(nn.Module):

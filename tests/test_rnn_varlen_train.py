@@ -587,3 +587,48 @@ def test_captured_forward_and_backward_replay_bit_identical(gpu_device, cell, T,
         _lib.raise_if_nonfinite()
     finally:
         _lib.set_strict(strict)
+
+
+# --- 9. one Function per cell: full lengths are the call without lengths, bit for bit --------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("reverse", [False, True])
+@pytest.mark.parametrize("cell,H", [("lstm", 128), ("lstm", 32), ("gru", 256), ("gru", 32)])
+def test_full_lengths_are_the_call_without_lengths(gpu_device, cell, H, reverse):
+    """`LstmRecurrence` / `GruRecurrence` take the lengths as an argument: layer(x, lengths=[T] * N) and layer(x) differ
+    in the library, the entry points, the workspace tag and the counters, and in nothing that is computed.  The kernels
+    with lengths = [T] * N are the kernels without, bit for bit (pinned at the C ABI above); the GEMMs and the
+    weight-gradient kernel are the same calls on the same tensors.  So y, dx and every parameter gradient are
+    torch.equal; a second run of the call without lengths, asserted equal to the first here, shows that the path is
+    reproducible run to run, which is what makes torch.equal the right comparison.  Sizes: 128 is two LSTM workgroups
+    that hand h over, 256 the GRU's four members, 32 one workgroup."""
+    T, N, I, dev = 5, 3, 8, gpu_device
+    torch.manual_seed(77)
+    layer = _make_layer(cell, I, H).to(dev)
+    x, w = torch.randn(T, N, I, device=dev), torch.randn(T, N, H, device=dev)
+    gru = int(cell == "gru")
+
+    before, gbefore = dict(layers.rnn_varlen_calls), dict(layers.gru_forward_calls)
+    plain = _grads(layer, lambda v: layer(v, reverse=reverse), x, w)
+    again = _grads(layer, lambda v: layer(v, reverse=reverse), x, w)
+    assert layers.rnn_varlen_calls == before
+    assert layers.gru_forward_calls == dict(gbefore, saved=gbefore["saved"] + 2 * gru)
+    assert set(plain) == set(again) and len(plain) == 5           # y, x, weight_ih, weight_hh, bias_ih
+    for k in plain:
+        assert bool(torch.isfinite(plain[k]).all()) and plain[k].abs().max().item() > 0, k
+        assert torch.equal(plain[k], again[k]), ("run to run", k, (plain[k] - again[k]).abs().max().item())
+
+    before, gbefore = dict(layers.rnn_varlen_calls), dict(layers.gru_forward_calls)
+    full = _grads(layer, lambda v: layer(v, reverse=reverse, lengths=[T] * N), x, w)
+    assert layers.rnn_varlen_calls == dict(before, saved=before["saved"] + 1)
+    assert layers.gru_forward_calls == dict(gbefore, saved=gbefore["saved"] + gru)
+    assert set(full) == set(plain)
+    for k in plain:
+        assert torch.equal(full[k], plain[k]), (cell, H, reverse, k, (full[k] - plain[k]).abs().max().item())
+
+    # nothing to differentiate: the launch with lengths that saves nothing, counted as such and nowhere else
+    before, gbefore = dict(layers.rnn_varlen_calls), dict(layers.gru_forward_calls)
+    with torch.no_grad():
+        y = layer(x, reverse=reverse, lengths=[T] * N)
+    assert layers.rnn_varlen_calls == dict(before, inference=before["inference"] + 1)
+    assert layers.gru_forward_calls == gbefore
+    assert not y.requires_grad and y.shape == plain["y"].shape
