@@ -1,13 +1,16 @@
 #!/usr/bin/env python
 """Writes tests/golden/squiggle_small.npz: the reference squiggle match's answers on the cases of
-tests/golden/squiggle_cases.py, so that tests/test_squiggle_match.py stands without the reference.
+tests/golden/squiggle_cases.py, so that tests/test_squiggle_match.py stands without the reference; and
+tests/golden/squiggle_lanes.npz: its answers alone (cost, grad, vcost, path and a digest of the inputs, which
+squiggle_cases.make_lane_case regenerates from their seeds) on the second table there, for
+tests/test_squiggle_instantiations.py.
 
 The reference C (taiyaki/squiggle_match/c_squiggle_match.c) is compiled with its own flags
 (setup.py: -O3 -fopenmp -std=c99) into a temporary directory outside the tree and called through
 ctypes; nothing compiled is kept.  The arrays of the reference's SQUIGGLE_TEST harness are read from
 that source file and stored as data.
 
-    python tests/golden/make_golden_squiggle.py /path/to/taiyaki
+    python tests/golden/make_golden_squiggle.py /path/to/taiyaki [small] [lanes]        (default: both)
 """
 import ctypes
 import os
@@ -25,6 +28,8 @@ if ROOT not in sys.path:
 from tests.golden import squiggle_cases  # noqa: E402
 
 PATH = os.path.join(HERE, "squiggle_small.npz")
+LANES_PATH = os.path.join(HERE, "squiggle_lanes.npz")
+MAX_BYTES = 1 << 20             # the limit for a committed file
 LARGE_LOG_VAL = 50000.0
 
 
@@ -90,8 +95,29 @@ def embed_expected(seq):
     return verts[["ACGT".index(b) for b in seq]]
 
 
-def main(reference_root):
+def write_lanes(src):
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        so = _compile(src, tmp)
+        for name in squiggle_cases.LANE_NAMES:
+            case = squiggle_cases.make_lane_case(name)
+            cost, grad, vcost, path = run_reference(so, case)
+            out[name + "/siglen"], out[name + "/sums"] = squiggle_cases.digest(case)
+            out[name + "/cost"], out[name + "/grad"] = cost, grad
+            out[name + "/vcost"], out[name + "/path"] = vcost, path
+            print("%-10s npos %4d siglen %s cost %s" % (name, case["params"].shape[0], case["siglen"], cost))
+    np.savez_compressed(LANES_PATH, **out)
+    size = os.path.getsize(LANES_PATH)
+    print("wrote %s (%d bytes)" % (LANES_PATH, size))
+    assert size < MAX_BYTES, "the fixture must stay under 1 MiB"
+
+
+def main(reference_root, which=("small", "lanes")):
     src = os.path.join(reference_root, "taiyaki", "squiggle_match", "c_squiggle_match.c")
+    if "lanes" in which:
+        write_lanes(src)
+    if "small" not in which:
+        return
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
         so = _compile(src, tmp)
@@ -115,4 +141,5 @@ def main(reference_root):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else os.environ.get("TAIYAKI_REFERENCE", "../taiyaki"))
+    main(sys.argv[1] if len(sys.argv) > 1 else os.environ.get("TAIYAKI_REFERENCE", "../taiyaki"),
+         tuple(sys.argv[2:]) or ("small", "lanes"))

@@ -67,11 +67,13 @@ def cost(params, signal, back_prob):
     return -forward(params, signal, back_prob)[-1, 0, -1]
 
 
-def grad(params, signal, back_prob):
+def grad(params, signal, back_prob, f=None):
     """Negated gradient (npos, 3) as :591-694 write it: per-sample normaliser over all states; the
-    move-logit term without the transition penalty in its exponent (:661-685)."""
+    move-logit term without the transition penalty in its exponent (:661-685).  `f`: the forward
+    lattice of the same arguments, where the caller has it already."""
     loc, logsc, sc, mpen, spen = tables(params, back_prob)
-    f, g = forward(params, signal, back_prob), backward(params, signal, back_prob)
+    f = forward(params, signal, back_prob) if f is None else f
+    g = backward(params, signal, back_prob)
     m = 0.5 * (1.0 + np.tanh(np.asarray(params, dtype=np.float64)[:, 2] / 2.0))
     dl = (1.0 - back_prob) * m * (1.0 - m)
     out = np.zeros((len(loc), 3))

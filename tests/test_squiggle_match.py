@@ -166,6 +166,9 @@ def test_hip_matches_the_float64_restatement(gpu_device, npos, nbatch, seed, bac
     case = C.random_batch(npos, nbatch, seed, back_prob)
     args = (case["params"], case["signal"], case["siglen"], case["back_prob"])
     np.testing.assert_allclose(sm.squiggle_match_cost(*args), M.batch(M.cost, case), rtol=COST_RTOL)
+    # The gradient of the 8409-sample read at npos 1024 is compared in tests/test_squiggle_instantiations.py (its
+    # case "long1024", with every other positions-per-lane instantiation): the reference's own gradient is 7e-4 off
+    # float64 there, beyond GRAD_COL_TOL, so that module's allowance follows the reference's error per case.
     if npos <= 130:
         err = _grad_err(sm.squiggle_match_grad(*args), np.stack(M.batch(M.grad, case), axis=1))
         assert np.all(err < GRAD_COL_TOL), err
