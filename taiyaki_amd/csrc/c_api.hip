@@ -478,6 +478,14 @@ int tk_lab_lstm_geometry(size_t nbatch, size_t size, int cu_count, size_t *out) 
     return tk::lstm_lab_geometry(nbatch, size, cu_count, out) ? 1 : 0;
 }
 void tk_lab_gru_cols(int cols) { tk::gru_lab_cols(cols); }
+int tk_lab_logz_plan(size_t nblk, size_t nbatch, size_t nbase, size_t score_bytes, size_t *out) {
+    tk::LogzPlan p;
+    if (!tk::logz_lab_plan(nblk, nbatch, nbase, score_bytes, &p)) return 0;
+    const size_t v[4] = {(size_t)p.ch, (size_t)p.transfer, (size_t)p.super, p.chain_tail ? (size_t)1 : (size_t)0};
+    for (int i = 0; i < 4; ++i) out[i] = v[i];
+    return 1;
+}
+int tk_lab_viterbi_plan(size_t nbatch) { return tk::viterbi_lab_waves(nbatch); }
 #endif
 
 size_t tk_lstm_workspace_bytes(size_t nbatch, size_t size, int cu_count) {

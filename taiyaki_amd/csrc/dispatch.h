@@ -14,6 +14,14 @@ namespace tk {
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // logz_kernels.hip, viterbi_kernels.hip
+// What the logZ launcher makes of a shape: rows per chunk after the LDS fallback (8 / 16 / 32), the form of the
+// transfer kernel, the middle kernel's chunks per super (8 / 16), and whether the posterior kernel keeps the hand-off
+// slots of its chains in a tail behind the waves' buffers (or inside them)
+enum { LOGZ_COOP = 0, LOGZ_RING = 1, LOGZ_PLAIN = 2, LOGZ_STREAM = 3 };
+struct LogzPlan {
+    int ch, transfer, super;
+    bool chain_tail;
+};
 size_t logz_workspace_bytes(size_t T, size_t N, size_t nbase);
 int logz_dispatch(const float *scores, size_t T, size_t N, size_t nbase, float *logz, float *grad, void *workspace,
                   size_t workspace_bytes, uint32_t *status, hipStream_t stream, float *loss_acc = nullptr,
@@ -151,6 +159,8 @@ void lstm_lab_cols(int cols);
 void lstm_lab_units(int units);
 bool lstm_lab_geometry(size_t N, size_t H, int cu_count, size_t *out);
 void gru_lab_cols(int cols);
+bool logz_lab_plan(size_t T, size_t N, size_t nbase, size_t score_bytes, LogzPlan *p);
+int viterbi_lab_waves(size_t N);
 #endif
 
 }  // namespace tk
@@ -170,5 +180,12 @@ void tk_lab_lstm_units(int units);
 int tk_lab_lstm_geometry(size_t nbatch, size_t size, int cu_count, size_t *out);
 /* the GRU recurrence's batch columns per workgroup at sizes <= 128: 1 or 2 (0: the launcher's rule; gru_kernels.hip) */
 void tk_lab_gru_cols(int cols);
+/* the logZ launch plan at (nblk, nbatch, nbase) for a score tensor of score_bytes: out[4] = rows per chunk after the
+ * LDS fallback, the transfer form (0 cooperative, 1 LDS ring, 2 one wave per chunk through registers, 3 its
+ * streaming-load instantiation), chunks per super, 1 where the posterior kernel keeps its chains in the tail;
+ * 0 where the launch refuses the shape (logz_kernels.hip) */
+int tk_lab_logz_plan(size_t nblk, size_t nbatch, size_t nbase, size_t score_bytes, size_t *out);
+/* the Viterbi's waves per read at nbatch reads: 5, 3 or 1 (viterbi_kernels.hip) */
+int tk_lab_viterbi_plan(size_t nbatch);
 }
 #endif

@@ -204,6 +204,12 @@ __host__ __device__ constexpr int k3_buf_f4() {
     constexpr int b = (CH / K3_WAVES) * FF<NB>::NS * WAVE / 4;
     return a > b ? a : b;
 }
+// ... and whether the hand-off slots of its two chains fit the unused tail of each wave's buffer (false: they sit
+// in a tail behind the buffers, 2 x NS x 64 floats more of dynamic LDS)
+template <int NB, int CH>
+__host__ __device__ constexpr bool k3_chain_in_buf() {
+    return (CH / K3_WAVES + 2) * FF<NB>::NS * WAVE <= k3_buf_f4<NB, CH>() * 4;
+}
 
 // ---------------------------------------------------------------------------
 // K1: chunk transfer matrices.  ONE WAVE PER CHUNK: the wave folds all CH rows of its
@@ -987,7 +993,7 @@ __global__ __launch_bounds__(K3_WAVES *WAVE, (CH / K3_WAVES <= 2 ? 4 : 2)) void 
     // it are over (stage barriers) long before that wave transposes its output.  (A slot in
     // another wave's buffer would race with that wave's load-phase transposes, which no
     // barrier separates from the first chain stage.)
-    constexpr bool CHAIN_IN_BUF = (K3_ROWS + 2) * F::NS * WAVE <= BUF_F4 * 4;
+    constexpr bool CHAIN_IN_BUF = k3_chain_in_buf<NB, CH>();
     float *const chain_tail = reinterpret_cast<float *>(reinterpret_cast<f4 *>(smem) + K3_WAVES * BUF_F4);
     auto chainF_of = [&](int w) {       // slot written by wave w for wave w + 1
         return CHAIN_IN_BUF ? reinterpret_cast<float *>(reinterpret_cast<f4 *>(smem) + w * BUF_F4) +
@@ -1155,6 +1161,21 @@ static bool logz_use_ring(size_t nchunks) {
     return nchunks <= 900;
 }
 
+// The form of the transfer kernel (LogzPlan::transfer in dispatch.h).  `nchunks_all`: chunk count of the whole
+// operator call; `nchunks`: of the reads this launch covers; `score_bytes`: of the whole score tensor.
+// One wave per chunk needs about a wave per SIMD to stream at full rate; below that the cooperative form (4 waves
+// per chunk) is faster.  A score tensor that fits the Infinity Cache is read with plain loads: the posterior
+// kernel's second read then hits (T=4000 x N=256: 99.5 us for the op against 110 with streaming loads here); a
+// bigger one is streamed (N=1024: transfer 130 us instead of 157, the op 385 instead of 412; break-even ~300 MB).
+// Two instantiations, not a runtime flag: a branch in the load stream costs the whole gain
+static int logz_transfer_form(size_t nchunks_all, size_t nchunks, size_t score_bytes) {
+    if (nchunks_all < 640) return LOGZ_COOP;
+    if (logz_use_ring(nchunks)) return LOGZ_RING;
+    bool nt_load = score_bytes > ((size_t)300 << 20);
+    if (const char *e = TK_LAB_ENV("TK_K1_NT")) nt_load = atoi(e) != 0;     // tuning / test override
+    return nt_load ? LOGZ_STREAM : LOGZ_PLAIN;
+}
+
 // chunk size = rows per K3 block.  16 rows (two per wave) keep K3 at 128 VGPRs = two
 // blocks per CU, so one block's serial chain overlaps the other's loads and stores;
 // 8 when a 16-row grid would leave CUs without a block.  32 is kept for the env override.
@@ -1183,6 +1204,20 @@ static size_t logz_ws_layout(size_t T, size_t N, void *base, LogzWs *ws) {
     return off;
 }
 
+// ... after the override and the fallback: the middle kernel keeps one read's chunk matrices in LDS, so a long
+// T falls back to bigger chunks (at 32 rows the launch itself refuses what still does not fit)
+template <int NB>
+static int logz_ch(size_t T, size_t N) {
+    int ch = logz_pick_ch(T, N);
+    if (const char *e = TK_LAB_ENV("TK_LOGZ_CH")) ch = atoi(e);         // tuning override
+    auto middle_lds = [&](int c) {
+        const int C = (int)((T + c - 1) / c);
+        return logz_middle_lds_bytes<NB>(C, (C + logz_super(C) - 1) / logz_super(C));
+    };
+    while (ch < 32 && middle_lds(ch) > 160 * 1024) ch *= 2;
+    return ch;
+}
+
 constexpr int PH_TRANSFER = 1, PH_MIDDLE = 2, PH_POSTERIOR = 4, PH_ALL = 7;
 
 // `phases`: which of the three launches to enqueue (the two-queue pipeline of logz_launch issues
@@ -1206,32 +1241,19 @@ static int logz_launch_ch(const float *scores, size_t T, size_t N, float *logz, 
             raise_dynamic_lds(reinterpret_cast<const void *>(&logz_transfer_kernel<NB, CH, K1_RING, false>)) ||
             raise_dynamic_lds(reinterpret_cast<const void *>(&logz_transfer_coop_kernel<NB, CH>)))
             return 4;
-        // one wave per chunk needs about a wave per SIMD to stream at full rate; below that
-        // the cooperative form (4 waves per chunk) is faster
-        if (nchunks_all >= 640) {
-            if (logz_use_ring((size_t)ncols * C)) {
-                const size_t ringlds = K1_WAVES * (size_t)K1_RING * WAVE * F::PIECES * sizeof(f4);
-                hipLaunchKernelGGL((logz_transfer_kernel<NB, CH, K1_RING, false>), dim3(ncols, (C + K1_WAVES - 1) / K1_WAVES),
-                                   dim3(K1_WAVES * WAVE), ringlds > lds ? ringlds : lds, stream, scores, (int)T,
-                                   (int)N, C, Npad, ws);
-            } else {
-                // a score tensor that fits the Infinity Cache is read with plain loads: the
-                // posterior kernel's second read then hits (T=4000 x N=256: 99.5 us for the op
-                // against 110 with streaming loads here); a bigger one is streamed (N=1024:
-                // transfer 130 us instead of 157, the op 385 instead of 412; break-even ~300 MB).
-                // Two instantiations, not a runtime flag: a branch in the load stream costs the
-                // whole gain
-                bool nt_load = (size_t)T * ws.nstride * F::S * sizeof(float) > ((size_t)300 << 20);
-                if (const char *e = TK_LAB_ENV("TK_K1_NT")) nt_load = atoi(e) != 0;     // tuning / test override
-                const dim3 grid(ncols, (C + K1_WAVES - 1) / K1_WAVES);
-                if (nt_load)
-                    hipLaunchKernelGGL((logz_transfer_kernel<NB, CH, 0, true>), grid, dim3(K1_WAVES * WAVE), lds, stream,
-                                       scores, (int)T, (int)N, C, Npad, ws);
-                else
-                    hipLaunchKernelGGL((logz_transfer_kernel<NB, CH, 0, false>), grid, dim3(K1_WAVES * WAVE), lds, stream,
-                                       scores, (int)T, (int)N, C, Npad, ws);
-            }
-        } else
+        const int form = logz_transfer_form(nchunks_all, (size_t)ncols * C, (size_t)T * ws.nstride * F::S * sizeof(float));
+        const dim3 grid(ncols, (C + K1_WAVES - 1) / K1_WAVES);
+        if (form == LOGZ_RING) {
+            const size_t ringlds = K1_WAVES * (size_t)K1_RING * WAVE * F::PIECES * sizeof(f4);
+            hipLaunchKernelGGL((logz_transfer_kernel<NB, CH, K1_RING, false>), grid, dim3(K1_WAVES * WAVE),
+                               ringlds > lds ? ringlds : lds, stream, scores, (int)T, (int)N, C, Npad, ws);
+        } else if (form == LOGZ_STREAM)
+            hipLaunchKernelGGL((logz_transfer_kernel<NB, CH, 0, true>), grid, dim3(K1_WAVES * WAVE), lds, stream,
+                               scores, (int)T, (int)N, C, Npad, ws);
+        else if (form == LOGZ_PLAIN)
+            hipLaunchKernelGGL((logz_transfer_kernel<NB, CH, 0, false>), grid, dim3(K1_WAVES * WAVE), lds, stream,
+                               scores, (int)T, (int)N, C, Npad, ws);
+        else
             hipLaunchKernelGGL((logz_transfer_coop_kernel<NB, CH>), dim3(ncols, C), dim3(K1_WAVES * WAVE),
                                lds, stream, scores, (int)T, (int)N, C, Npad, ws);
     }
@@ -1250,8 +1272,7 @@ static int logz_launch_ch(const float *scores, size_t T, size_t N, float *logz, 
     }
     if (grad != nullptr && (phases & PH_POSTERIOR)) {
         dim3 grid(ncols, C), block(K3_WAVES * WAVE);
-        constexpr bool chain_in_buf =
-            ((CH / K3_WAVES) + 2) * F::NS * WAVE <= k3_buf_f4<NB, CH>() * 4;
+        constexpr bool chain_in_buf = k3_chain_in_buf<NB, CH>();
         const size_t lds = K3_WAVES * (size_t)k3_buf_f4<NB, CH>() * sizeof(f4) +
                            (chain_in_buf ? 0 : 2 * F::NS * WAVE * sizeof(float));
         if (raise_dynamic_lds(reinterpret_cast<const void *>(&logz_posterior_kernel<NB, CH, false>)) ||
@@ -1355,6 +1376,21 @@ static int logz_launch_split(const float *scores, size_t T, size_t N, float *log
     return hipStreamWaitEvent(stream, sd->join, 0) == hipSuccess ? 0 : 4;
 }
 
+// What logz_launch makes of a shape (LogzPlan, dispatch.h): the chunk size it switches on, and what logz_launch_ch
+// then takes from the same functions for a launch over all reads.  False: too many chunks for one LDS image
+template <int NB>
+static bool logz_plan_nb(size_t T, size_t N, size_t score_bytes, LogzPlan *p) {
+    const int picked = logz_ch<NB>(T, N), ch = picked == 8 || picked == 16 ? picked : 32;
+    const int C = (int)((T + ch - 1) / ch);
+    if (logz_middle_lds_bytes<NB>(C, (C + logz_super(C) - 1) / logz_super(C)) > 160 * 1024) return false;
+    const size_t nchunks = (N + WAVE - 1) / WAVE * (size_t)C;
+    p->ch = ch;
+    p->transfer = logz_transfer_form(nchunks, nchunks, score_bytes);
+    p->super = logz_super(C);
+    p->chain_tail = ch == 8 ? !k3_chain_in_buf<NB, 8>() : ch == 16 ? !k3_chain_in_buf<NB, 16>() : !k3_chain_in_buf<NB, 32>();
+    return true;
+}
+
 template <int NB>
 static int logz_launch(const float *scores, size_t T, size_t N, float *logz, float *grad,
                        void *workspace, size_t workspace_bytes, uint32_t *status,
@@ -1368,14 +1404,9 @@ static int logz_launch(const float *scores, size_t T, size_t N, float *logz, flo
     ws.grad_scale = grad_scale;
     ws.grad_scale_vec = grad_scale_vec;
     ws.nstride = (int)N;
-    int ch = logz_pick_ch(T, N);
-    if (const char *e = TK_LAB_ENV("TK_LOGZ_CH")) ch = atoi(e);         // tuning override
-    // the middle kernel keeps one read's chunk matrices in LDS: fall back to bigger chunks
-    auto middle_lds = [&](int c) {
-        const int C = (int)((T + c - 1) / c);
-        return logz_middle_lds_bytes<NB>(C, (C + logz_super(C) - 1) / logz_super(C));
-    };
-    while (ch < 32 && middle_lds(ch) > 160 * 1024) ch *= 2;
+    LogzPlan plan;
+    if (!logz_plan_nb<NB>(T, N, T * N * FF<NB>::S * sizeof(float), &plan)) return 2;
+    const int ch = plan.ch;
     {
         // OFF by default -- measured (round 3, T=4000): N=256 134.8 us staggered / 119.4 us side by side
         // against 101.0 us for the plain chain, N=512 229 / 221 against 204.  A half's kernels do not
@@ -1399,6 +1430,19 @@ static int logz_launch(const float *scores, size_t T, size_t N, float *logz, flo
         default: return logz_launch_ch<NB, 32>(scores, T, N, logz, grad, ws, status, stream);
     }
 }
+
+#ifdef TK_LAB
+bool logz_lab_plan(size_t T, size_t N, size_t nbase, size_t score_bytes, LogzPlan *p) {
+    if (T == 0 || N == 0) return false;
+    switch (nbase) {
+        case 1: return logz_plan_nb<1>(T, N, score_bytes, p);
+        case 2: return logz_plan_nb<2>(T, N, score_bytes, p);
+        case 3: return logz_plan_nb<3>(T, N, score_bytes, p);
+        case 4: return logz_plan_nb<4>(T, N, score_bytes, p);
+        default: return false;
+    }
+}
+#endif
 
 size_t logz_workspace_bytes(size_t T, size_t N, size_t nbase) {
     switch (nbase) {

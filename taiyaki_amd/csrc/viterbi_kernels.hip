@@ -643,23 +643,34 @@ size_t viterbi_workspace_bytes(size_t T, size_t N, size_t nbase) {
     return (T > 0 ? T : 1) * npad * VIT_GRP;        // one byte per state and step
 }
 
-template <int NB>
-static int viterbi_launch(const float *scores, size_t T, size_t N, float *fwd, int64_t *tb,
-                          int64_t *path, void *workspace, hipStream_t stream) {
-    const int npad = (int)((N + VIT_GRP - 1) / VIT_GRP * VIT_GRP);
-    if (N == 0) return 0;
+// Waves per read: 1 (viterbi_kernel), or 1 + 2 x the trace waves per step parity of viterbi3_kernel (3, 5; lab: 9).
+static int viterbi_waves(size_t N) {
     // Three waves per read while the reads do not fill the chip's wave slots anyway (a read is bound by its serial
     // chain: T 4000 / N 256 342 -> 217 us path only, 404 -> 224 with the full outputs; N 1024 529 -> 345); at 2048
     // reads the two forms measure the same (743 / 733 us) and beyond the launch is bound by throughput, where
     // three waves per read cost more slots than the chain saves (tools/vitbench.py, profiles/r5_vitbench.txt)
     const char *v1 = TK_LAB_ENV("TK_VIT_V1");                   // lab: 1 = the one-wave kernel of rounds 1-4, 0 = three waves, for A/B
     const bool three = v1 ? v1[0] != '1' : N <= 1536;
-    if (three) {
-        // trace waves per step parity: 2 (five waves per read) while a read has a CU nearly to itself -- T 4000 / N 256 193 -> 180 us
-        // path only, 233 -> 184 with the full outputs, N 512 230 -> 215; beyond ~2 reads per CU the extra waves share SIMDs with chain
-        // waves (N 1024: 326 -> 427 us) and the three-wave form stays (profiles/r6_viterbi_fill_split_ab.txt).  TK_VIT_SPLIT = 1 | 2 | 4 (lab)
-        int split = N <= 640 ? 2 : 1;
-        if (const char *e = TK_LAB_ENV("TK_VIT_SPLIT")) split = atoi(e);
+    if (!three) return 1;
+    // trace waves per step parity: 2 (five waves per read) while a read has a CU nearly to itself -- T 4000 / N 256 193 -> 180 us
+    // path only, 233 -> 184 with the full outputs, N 512 230 -> 215; beyond ~2 reads per CU the extra waves share SIMDs with chain
+    // waves (N 1024: 326 -> 427 us) and the three-wave form stays (profiles/r6_viterbi_fill_split_ab.txt).  TK_VIT_SPLIT = 1 | 2 | 4 (lab)
+    int split = N <= 640 ? 2 : 1;
+    if (const char *e = TK_LAB_ENV("TK_VIT_SPLIT")) split = atoi(e);
+    return vit_waves(split == 4 || split == 2 ? split : 1);
+}
+
+#ifdef TK_LAB
+int viterbi_lab_waves(size_t N) { return viterbi_waves(N); }
+#endif
+
+template <int NB>
+static int viterbi_launch(const float *scores, size_t T, size_t N, float *fwd, int64_t *tb,
+                          int64_t *path, void *workspace, hipStream_t stream) {
+    const int npad = (int)((N + VIT_GRP - 1) / VIT_GRP * VIT_GRP);
+    if (N == 0) return 0;
+    const int waves = viterbi_waves(N);
+    if (waves > 1) {
         auto go = [&](auto sp) {
             constexpr int SP = decltype(sp)::value;
             if (fwd != nullptr && tb != nullptr)
@@ -669,8 +680,8 @@ static int viterbi_launch(const float *scores, size_t T, size_t N, float *fwd, i
                 hipLaunchKernelGGL((viterbi3_kernel<NB, false, SP>), dim3((unsigned)N), dim3(vit_waves(SP) * WAVE), 0, stream, scores,
                                    (int)T, (int)N, fwd, tb, path, static_cast<unsigned char *>(workspace), npad);
         };
-        if (split == 4) go(std::integral_constant<int, 4>{});
-        else if (split == 2) go(std::integral_constant<int, 2>{});
+        if (waves == vit_waves(4)) go(std::integral_constant<int, 4>{});
+        else if (waves == vit_waves(2)) go(std::integral_constant<int, 2>{});
         else go(std::integral_constant<int, 1>{});
         return hipGetLastError() == hipSuccess ? 0 : 4;
     }

@@ -4,7 +4,8 @@
 CPU: the header is the ABI, the binding has its argument types, lengths are checked before anything is launched, and the
 float64 forward-backward restated here (the reference of the GPU tests) agrees with the oracle at full-length columns.
 GPU: every column against the existing fixed-length operator on the column alone -- the Viterbi bit for bit, the
-posterior under the project's rule against float64 -- and the gather against numpy, bit for bit."""
+posterior under the project's rule against float64 -- and the gather against numpy, bit for bit.  Every alphabet size the
+library is built for (nbase 1 .. 4: viterbi_varlen_kernel<NB>, posterior_varlen_kernel<NB>) runs the same batches."""
 import ctypes
 import os
 import re
@@ -14,10 +15,10 @@ import numpy as np
 import pytest
 import torch
 
-from taiyaki_amd import _lib, decode, synth
+from taiyaki_amd import _lib, decode, flipflopfings, synth
 from tests import basecall_support as bs
 
-T, NBASE = 130, 4
+T, NBASES = 130, [1, 2, 3, 4]
 LENGTHS = [130, 129, 65, 64, 63, 1, 0]          # both sides of the 64-step traceback batch, the ends, an empty column
 
 
@@ -30,16 +31,24 @@ def forward_backward(scores, lengths):
     to = np.concatenate([np.repeat(np.arange(nb), ns), nb + np.arange(ns) % nb])
     frm = np.concatenate([np.tile(np.arange(ns), nb), np.arange(ns)])
     trans, logz = np.zeros((Tn, N, S)), np.zeros(N)
-    lse = lambda v: v.max() + np.log(np.exp(v - v.max()).sum())  # noqa: E731
+
+    def lse(v, axis=0):
+        m = v.max(axis, keepdims=True)
+        return m.squeeze(axis) + np.log(np.exp(v - m).sum(axis))
+
     for n, L in enumerate(lengths):
         sc = scores[:L, n].astype(np.float64)
         fwd = np.full((L + 1, ns), -1e30)
         fwd[0, :nb] = 0.0
         for t in range(L):
-            fwd[t + 1] = [lse((fwd[t, frm] + sc[t])[to == s]) for s in range(ns)]
+            v = fwd[t, frm] + sc[t]
+            # into flip b: transitions b ns .. b ns + ns - 1; into flop b: nb ns + b (from flip b) and nb ns + nb + b (stay)
+            fwd[t + 1, :nb] = lse(v[:nb * ns].reshape(nb, ns), 1)
+            fwd[t + 1, nb:] = lse(v[nb * ns:].reshape(2, nb))
         bwd = np.zeros((L + 1, ns))
         for t in range(L, 0, -1):
-            bwd[t - 1] = [lse((sc[t - 1] + bwd[t, to])[frm == s]) for s in range(ns)]
+            # out of state s: transitions b ns + s into every flip b, then nb ns + s into its flop
+            bwd[t - 1] = lse((sc[t - 1] + bwd[t, to]).reshape(nb + 1, ns))
         logz[n] = lse(fwd[L])
         trans[:L, n] = np.exp(fwd[:L, frm] + sc + bwd[1:, to] - logz[n])
     return trans, logz
@@ -106,16 +115,22 @@ def test_float64_restatement_agrees_with_the_oracle_at_full_length(oracle_mod):
 # ----------------------------------------------------------------------------------------------------------------------
 # GPU
 # ----------------------------------------------------------------------------------------------------------------------
-def _scores(n, seed):
+def _scores(n, seed, nbase=4):
     """Half the columns a trained network's confident scores, half a fresh one's."""
-    inp = synth.crf_case(T, n, seed, seqlens=np.full(n, 40, dtype=np.int32))
+    inp = synth.crf_case(T, n, seed, nbase=nbase, seqlens=np.full(n, 40, dtype=np.int32))
     plain = inp["scores"].copy()
-    sharp = synth.confident_scores(inp, seed + 1)["scores"]
+    sharp = synth.confident_scores(inp, seed + 1, nbase=nbase)["scores"]
     sharp[:, 1::2] = plain[:, 1::2]
     return np.ascontiguousarray(sharp)
 
 
 BATCHES = {"seven": (LENGTHS, 11), "one": ([2], 12)}
+
+
+def _over_alphabets(*cases):
+    """Every case at every alphabet size; the nbase = 4 cases keep the ids they had before the others joined them."""
+    return [pytest.param(*c, nb, id="-".join(str(v) for v in c) + ("" if nb == 4 else "-nb%d" % nb))
+            for nb in reversed(NBASES) for c in cases]
 
 
 def _p(t):
@@ -125,7 +140,8 @@ def _p(t):
 def _viterbi_abi(sc, lengths):
     """tk_flipflop_viterbi_varlen_dev on NaN-like filled outputs (int64: a pattern no state has)."""
     V, dev = _lib.decode_varlen_lib(), sc.device
-    Tn, N, _ = sc.shape
+    Tn, N, S = sc.shape
+    NBASE = flipflopfings.nbase_flipflop(S)
     path = torch.full((Tn + 1, N), -7777, dtype=torch.int64, device=dev)
     wsb = V.tk_decode_varlen_workspace_bytes(Tn, N, NBASE)
     ws = torch.full((wsb,), 0xAB, dtype=torch.uint8, device=dev)
@@ -136,7 +152,8 @@ def _viterbi_abi(sc, lengths):
 
 def _posterior_abi(sc, lengths):
     V, dev = _lib.decode_varlen_lib(), sc.device
-    Tn, N, _ = sc.shape
+    Tn, N, S = sc.shape
+    NBASE = flipflopfings.nbase_flipflop(S)
     trans = torch.full_like(sc, float("nan"))
     logz = torch.full((N,), float("nan"), dtype=torch.float32, device=dev)
     wsb = V.tk_decode_varlen_workspace_bytes(Tn, N, NBASE)
@@ -149,10 +166,10 @@ def _posterior_abi(sc, lengths):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("batch", list(BATCHES))
-def test_viterbi_columns_equal_the_column_alone(gpu_device, batch):
+@pytest.mark.parametrize("batch,nbase", _over_alphabets(*((b,) for b in BATCHES)))
+def test_viterbi_columns_equal_the_column_alone(gpu_device, batch, nbase):
     lengths, seed = BATCHES[batch]
-    sc = torch.from_numpy(_scores(len(lengths), seed)).to(gpu_device)
+    sc = torch.from_numpy(_scores(len(lengths), seed, nbase)).to(gpu_device)
     path = _viterbi_abi(sc, lengths)
     assert torch.equal(path, decode.flipflop_viterbi_path(sc, lengths=lengths))       # the operator is the entry point
     assert torch.equal(path, decode.flipflop_viterbi_path(sc, lengths=torch.tensor(lengths, device=gpu_device)))
@@ -175,12 +192,12 @@ def test_viterbi_columns_equal_the_column_alone(gpu_device, batch):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("batch,sharpen", [("seven", 1.0), ("seven", 2.5), ("one", 1.0)])
-def test_posterior_columns_against_float64(gpu_device, batch, sharpen):
+@pytest.mark.parametrize("batch,sharpen,nbase", _over_alphabets(("seven", 1.0), ("seven", 2.5), ("one", 1.0)))
+def test_posterior_columns_against_float64(gpu_device, batch, sharpen, nbase):
     """Per column, in max-norm: |got - ref| <= 2 |alone - ref| + 2e-6 max|ref| (the rule of tests/test_gru_hip.py and
     tests/test_forward_varlen.py): ref the float64 restatement above, alone the existing operator on the column."""
     lengths, seed = BATCHES[batch]
-    host = _scores(len(lengths), seed) * np.float32(sharpen)
+    host = _scores(len(lengths), seed, nbase) * np.float32(sharpen)
     sc = torch.from_numpy(host).to(gpu_device)
     trans, logz, status = _posterior_abi(sc, lengths)
     assert status == 0 and bool(torch.isfinite(trans).all()) and bool(torch.isfinite(logz).all())
@@ -194,7 +211,7 @@ def test_posterior_columns_against_float64(gpu_device, batch, sharpen):
         alone = decode.flipflop_make_trans(sc[:L, n:n + 1].contiguous())[:, 0].cpu().numpy()
         e_got, e_alone = np.abs(got[:L, n] - ref[:L, n]).max(), np.abs(alone - ref[:L, n]).max()
         bound = 2 * e_alone + 2e-6 * np.abs(ref[:L, n]).max()
-        print("column %d (%d rows, x%.1f): batched %.3g, alone %.3g, bound %.3g" % (n, L, sharpen, e_got, e_alone, bound))
+        print("nbase %d column %d (%d rows, x%.1f): batched %.3g, alone %.3g, bound %.3g" % (nbase, n, L, sharpen, e_got, e_alone, bound))
         ok &= bool(e_got <= bound)
     assert ok
     # logZ: float32 of a sum of up to 130 terms of magnitude <= 12.5
@@ -207,11 +224,12 @@ def test_posterior_columns_against_float64(gpu_device, batch, sharpen):
 
 @pytest.mark.gpu
 def test_posterior_flags_a_non_finite_result(gpu_device):
-    host = _scores(2, 13)
-    host[7, 1, 3] = np.nan
-    trans, logz, status = _posterior_abi(torch.from_numpy(host).to(gpu_device), [T, T])
-    assert status & _lib.DEFINES["TK_STATUS_NONFINITE_GRAD"] and status & _lib.DEFINES["TK_STATUS_NONFINITE_SCORE"]
-    assert bool(torch.isfinite(trans[:, 0]).all()) and bool(torch.isfinite(logz[0]))      # the neighbour is untouched
+    for nbase in reversed(NBASES):
+        host = _scores(2, 13, nbase)
+        host[7, 1, 3] = np.nan
+        trans, logz, status = _posterior_abi(torch.from_numpy(host).to(gpu_device), [T, T])
+        assert status & _lib.DEFINES["TK_STATUS_NONFINITE_GRAD"] and status & _lib.DEFINES["TK_STATUS_NONFINITE_SCORE"], nbase
+        assert bool(torch.isfinite(trans[:, 0]).all()) and bool(torch.isfinite(logz[0])), nbase     # the neighbour is untouched
 
 
 def _gather_abi(sigs, shift, scale, read_index, tmax, dev):

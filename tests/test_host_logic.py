@@ -372,7 +372,8 @@ def test_release_library_carries_no_lab_switch():
     import re
     assert set(re.findall(r"\bTK_[A-Z0-9_]{3,}\b", rel)) == {"TK_LOSS_OVERLAP"}
     assert "tk_lab_" not in dynsyms(_lib.LIBPATH)
-    assert "tk_lab_crf_band_phase" in dynsyms(_lib.LAB_LIBPATH)
+    lab_syms = dynsyms(_lib.LAB_LIBPATH)
+    assert all(name in lab_syms for name in _lib.LAB_SIGNATURES) and "tk_lab_logz_plan" in _lib.LAB_SIGNATURES
     # no source file of the library calls getenv outside the macro and that one static
     for fn in os.listdir(_lib.CSRC):
         if fn.endswith((".hip", ".h", ".cpp")) and fn != "rccl_api.cpp":
@@ -523,7 +524,8 @@ def test_binding_read_from_the_header_is_the_hand_typed_one():
     """tests/golden/abi_signatures.json is the dump of the three tables `_lib.py` held, typed by hand, before it read
     them from the headers: {name: [restype, [argtypes]]}.  The parsed tables equal it, keys and every code.  One entry
     of the dump was corrected: the last parameter of tk_lab_lstm_geometry (`size_t *out`) was POINTER(c_size_t) there
-    and is c_void_p by the rule every other pointer follows (its callers pass a ctypes array, which both accept)."""
+    and is c_void_p by the rule every other pointer follows (its callers pass a ctypes array, which both accept).  Two
+    entries were added with the decode side's plan queries, tk_lab_logz_plan and tk_lab_viterbi_plan."""
     import json
     from taiyaki_amd import _lib
     golden = json.load(open(os.path.join(ROOT, "tests", "golden", "abi_signatures.json")))
@@ -532,7 +534,7 @@ def test_binding_read_from_the_header_is_the_hand_typed_one():
         got = _ctype_names(getattr(_lib, table))
         assert set(got) == set(want), table
         assert [k for k in want if got[k] != want[k]] == [], table
-    assert len(golden["SIGNATURES"]) == 43 and len(golden["RCCL_SIGNATURES"]) == 8 and len(golden["LAB_SIGNATURES"]) == 5
+    assert len(golden["SIGNATURES"]) == 43 and len(golden["RCCL_SIGNATURES"]) == 8 and len(golden["LAB_SIGNATURES"]) == 7
     assert _lib.ERRORS.keys() == {1, 2, 3, 4} and all(_lib.ERRORS.values())
 
 
