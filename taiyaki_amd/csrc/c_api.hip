@@ -486,6 +486,10 @@ int tk_lab_logz_plan(size_t nblk, size_t nbatch, size_t nbase, size_t score_byte
     return 1;
 }
 int tk_lab_viterbi_plan(size_t nbatch) { return tk::viterbi_lab_waves(nbatch); }
+int tk_lab_crf_plan(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, size_t bulk_seqlen, int form,
+                    int want_grad, float sharp, size_t workspace_bytes, size_t *out) {
+    return tk::crf_lab_plan(ntrans, nblk, nbatch, max_seqlen, bulk_seqlen, form, want_grad, sharp, workspace_bytes, out) ? 1 : 0;
+}
 #endif
 
 size_t tk_lstm_workspace_bytes(size_t nbatch, size_t size, int cu_count) {

@@ -119,6 +119,11 @@ BandLayout crf_band_layout(size_t ntrans, size_t nblk, size_t nbatch, size_t max
                            bool want_grad, int bk, int force_R = 0);
 // cells per lane of the RETRY: the smallest that leaves 2 W <= 16 waves, so that the tail launch's workgroup runs both sweeps at once
 int crf_band_retry_R(size_t max_seqlen);
+// the sweep launch's feed (a row-maker wave or every wave for itself) and, at four cells per lane, its wave-count class
+bool crf_band_use_rows(int W, int S, bool mod, bool colw, int bk);
+int crf_band_wave_class(int R, int bk, int nw);
+// the tail launch's workgroup runs the retry's two sweeps side by side (else one after the other)
+bool crf_band_tail_side_by_side(int W);
 int crf_band_dispatch(const BandArgs &a, int R, bool mod, int bk, hipStream_t stream);
 // (the tail launch -- retry, then the log domain: crf_log.h: crf_band_tail_dispatch)
 

@@ -1448,13 +1448,23 @@ constexpr int g_band_lab_phase = 0;
 // Does this launch run with a row maker (band_rowmaker)?  Whenever W + 1 waves fit a workgroup and the weights
 // are gathers from an exponentiated row (the plain CRF; cat-mod with per-column factors); 4-step blocks (sharpened
 // calls) keep the plain feed.  TK_CRF_FEED = self | rows forces one (lab, tests).
-static bool band_use_rows(const BandArgs &a, bool mod, int bk) {
-    if (bk < 8 || a.W + 1 > BAND_MAXW || (mod && a.colw == nullptr)) return false;
-    if (a.S > ROW_PITCH) return false;      // a row image holds ROW_PITCH columns: wider rows (cat-mod with >= 5
+bool crf_band_use_rows(int W, int S, bool mod, bool colw, int bk) {
+    if (bk < 8 || W + 1 > BAND_MAXW || (mod && !colw)) return false;
+    if (S > ROW_PITCH) return false;        // a row image holds ROW_PITCH columns: wider rows (cat-mod with >= 5
                                             // modifications, nbase 5) gather from their own exponentiated rows
     if (const char *e = TK_LAB_ENV("TK_CRF_FEED")) return e[0] == 'r';
     return true;
 }
+
+// The sweep kernel's wave-count class: four cells per lane at 8- and 12-step blocks are compiled per launch bound (8, 12 and
+// 16 waves: 155 registers where the bound allows them); `nw` = the launch's waves, the row maker among them.
+int crf_band_wave_class(int R, int bk, int nw) {
+    if (R != 4 || bk < 8) return BAND_MAXW;
+    return nw <= 8 ? 8 : nw <= 12 ? 12 : BAND_MAXW;
+}
+
+// Does the tail launch's workgroup run the retry's two sweeps side by side?  (crf_band_tail_kernel: 2 W <= its waves)
+bool crf_band_tail_side_by_side(int W) { return 2 * W <= BAND_MAXW; }
 
 template <int R, bool MOD, bool CW, int BK, bool ROWS>
 static int band_launch_sweep(const BandArgs &a, hipStream_t stream) {
@@ -1462,14 +1472,14 @@ static int band_launch_sweep(const BandArgs &a, hipStream_t stream) {
     const int nw = a.W + (ROWS ? 1 : 0);
     const size_t lds = ROWS ? (size_t)(a.W + 1) * BK * ROW_PITCH * sizeof(float) : 0;
     const dim3 grid((want_grad ? 3 : 2) * a.N), block(nw * WAVE);
-    // (R = 4 is compiled per wave-count class: 155 registers where the launch bounds allow them)
     auto go = [&](auto cap) {
         constexpr int WCAP = decltype(cap)::value;
         hipLaunchKernelGGL((crf_band_sweep_kernel<R, MOD, WCAP, ROWS, CW, BK>), grid, block, lds, stream, a);
     };
     if constexpr (R == 4 && BK >= 8) {
-        if (nw <= 8) go(std::integral_constant<int, 8>{});
-        else if (nw <= 12) go(std::integral_constant<int, 12>{});
+        const int cap = crf_band_wave_class(R, BK, nw);
+        if (cap == 8) go(std::integral_constant<int, 8>{});
+        else if (cap == 12) go(std::integral_constant<int, 12>{});
         else go(std::integral_constant<int, BAND_MAXW>{});
     } else {
         go(std::integral_constant<int, BAND_MAXW>{});
@@ -1483,7 +1493,7 @@ static int band_launch(const BandArgs &a, hipStream_t stream) {
     if (g_band_lab_phase != 2) {
         int rc;
         if constexpr (BK >= 8 && (!MOD || CW)) {
-            rc = band_use_rows(a, MOD, BK) ? band_launch_sweep<R, MOD, CW, BK, true>(a, stream)
+            rc = crf_band_use_rows(a.W, a.S, MOD, a.colw != nullptr, BK) ? band_launch_sweep<R, MOD, CW, BK, true>(a, stream)
                                            : band_launch_sweep<R, MOD, CW, BK, false>(a, stream);
         } else {
             rc = band_launch_sweep<R, MOD, CW, BK, false>(a, stream);

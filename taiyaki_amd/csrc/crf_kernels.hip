@@ -409,6 +409,88 @@ static void crf_gate_dump(const BandArgs &b, const BandBlock *rblk, size_t nbatc
     }
 }
 
+// WHAT crf_dispatch MAKES OF A CALL, before it touches a pointer: the form (linear path or log domain on every read), the
+// linear path's block configuration and its retry's, and the workspace plan.  rc != 0: the call is refused (2: no
+// instantiation for the shape, 3: the workspace holds neither form).  The lab build's plan query reports the same choice.
+struct CrfChoice {
+    int rc;
+    bool band;
+    BandBlock blk, rblk;
+    CrfPlan p;
+};
+static CrfChoice crf_choose(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, size_t bulk_seqlen, bool mod, bool colw,
+                            bool g, float sharp, size_t workspace_bytes) {
+    CrfChoice ch{};
+    const CrfShape sh = crf_pick_shape(max_seqlen);
+    if ((size_t)sh.R * sh.W * WAVE < max_seqlen || sh.R > 4) {
+        ch.rc = 2;
+        return ch;
+    }
+    // the linear path's block length for this sharpening factor; when the workspace the caller brought is
+    // too small for it (sized without the factor: tk_crf_flipflop_workspace_bytes) but large enough for the
+    // log-domain kernel on every read, that kernel does the call
+    ch.blk = crf_band_pick_block(sharp, mod, max_seqlen, mod && colw, nblk, bulk_seqlen);
+    ch.band = crf_pick_mode(ntrans, nblk, nbatch, max_seqlen, g, ch.blk.bk) == CRF_BAND;
+    // the second chance for what the batch's launch disowns (round 6); left out when the workspace the caller brought has no
+    // room for it (sized by an older query): such reads go straight to the log-domain kernel, as in round 5
+    ch.rblk = ch.band ? crf_band_pick_retry(sharp, ch.blk) : BandBlock{0, 0.f, 0};
+    auto plan = [&](int bk, int rbk) { return crf_plan(ntrans, nblk, nbatch, max_seqlen, mod, g, bk, rbk); };
+    ch.p = plan(ch.band ? ch.blk.bk : 0, ch.rblk.bk);
+    if (ch.band && ch.p.total > workspace_bytes) {
+        ch.rblk.bk = 0;
+        ch.p = plan(ch.blk.bk, 0);
+    }
+    if (ch.band && ch.p.total > workspace_bytes) {
+        ch.band = false;
+        ch.p = plan(0, 0);
+    }
+    if (!ch.band && ch.p.total > workspace_bytes) ch.rc = 3;
+    return ch;
+}
+
+#ifdef TK_LAB
+// tk_lab_crf_plan (dispatch.h): the choice above and what the launchers behind it make of it, as numbers
+bool crf_lab_plan(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, size_t bulk_seqlen, int form, int want_grad,
+                  float sharp, size_t workspace_bytes, size_t *out) {
+    for (int i = 0; i < 20; ++i) out[i] = 0;
+    if (ntrans > 62 || ntrans == 0 || form < 0 || form > 2) return false;
+    if (max_seqlen == 0) max_seqlen = nblk + 1;
+    const bool mod = form > 0, colw = form == 1;
+    const CrfChoice ch = crf_choose(ntrans, nblk, nbatch, max_seqlen, bulk_seqlen, mod, colw, want_grad != 0, sharp, workspace_bytes);
+    if (ch.rc != 0) return false;
+    const int kinds = mod ? 3 : 2;
+    if (!ch.band && crf_lds_bytes(ch.p.sh.R, ch.p.sh.W, (int)ntrans, kinds) > 160 * 1024) return false;     // (crf_launch_one)
+    auto halves = [](float bias) { return (size_t)(bias * 2.f + 0.5f); };
+    out[0] = ch.band ? 0 : 1;
+    out[1] = (size_t)ch.p.sh.R;
+    out[2] = (size_t)ch.p.sh.W;
+    out[3] = (size_t)crf_ck(ch.p.sh.R, ch.p.sh.W, kinds);
+    out[18] = ch.p.nslots;
+    if (!ch.band) return true;
+    const BandLayout &l = ch.p.band;
+    const bool rows = crf_band_use_rows(l.W, (int)ntrans, mod, colw, ch.blk.bk);
+    out[4] = (size_t)l.R;
+    out[5] = (size_t)l.W;
+    out[6] = (size_t)ch.blk.bk;
+    out[7] = halves(ch.blk.wbias);
+    out[8] = (size_t)ch.blk.klip;
+    out[9] = rows ? 1 : 0;
+    out[10] = (size_t)crf_band_wave_class(l.R, ch.blk.bk, l.W + (rows ? 1 : 0));
+    const int rR = crf_band_retry_R(max_seqlen);
+    if (ch.rblk.bk > 0) {
+        out[11] = (size_t)ch.rblk.bk;
+        out[12] = halves(ch.rblk.wbias);
+        out[13] = (size_t)ch.rblk.klip;
+        out[14] = (size_t)ch.p.retry.R;
+        out[15] = (size_t)ch.p.retry.W;
+        out[16] = crf_band_tail_side_by_side(ch.p.retry.W) ? 1 : 0;
+    }
+    out[17] = (size_t)crf_tail_log_R(rR);
+    out[19] = (size_t)rR;       // the tail launch's instantiation (crf_band_tail_dispatch), with or without a retry
+    return true;
+}
+#endif
+
 int crf_dispatch(const CrfCall &c) {
     const SeqLabels *labels = c.labels;
     if (c.ntrans > 62 || c.ncan > c.ntrans || c.ncan == 0) return 2;
@@ -418,29 +500,13 @@ int crf_dispatch(const CrfCall &c) {
                               (labels->mod_cats != nullptr && (labels->can_mods_offsets == nullptr || labels->mod_cat_weights == nullptr))))
         return 1;
     const size_t max_seqlen = c.max_seqlen != 0 ? c.max_seqlen : c.nblk + 1;
-    const CrfShape sh = crf_pick_shape(max_seqlen);
-    if ((size_t)sh.R * sh.W * WAVE < max_seqlen || sh.R > 4) return 2;
     const bool mod = c.mod != nullptr, g = c.grad != nullptr;
-    // the linear path's block length for this sharpening factor; when the workspace the caller brought is
-    // too small for it (sized without the factor: tk_crf_flipflop_workspace_bytes) but large enough for the
-    // log-domain kernel on every read, that kernel does the call
-    const BandBlock blk = crf_band_pick_block(c.sharp_can, mod, max_seqlen, mod && c.mod_col_weights != nullptr, c.nblk,
-                                              labels != nullptr ? labels->bulk_seqlen : 0);
-    bool band = crf_pick_mode(c.ntrans, c.nblk, c.nbatch, max_seqlen, g, blk.bk) == CRF_BAND;
-    // the second chance for what the batch's launch disowns (round 6); left out when the workspace the caller brought has no
-    // room for it (sized by an older query): such reads go straight to the log-domain kernel, as in round 5
-    BandBlock rblk = band ? crf_band_pick_retry(c.sharp_can, blk) : BandBlock{0, 0.f, 0};
-    auto plan = [&](int bk, int rbk) { return crf_plan(c.ntrans, c.nblk, c.nbatch, max_seqlen, mod, g, bk, rbk); };
-    CrfPlan p = plan(band ? blk.bk : 0, rblk.bk);
-    if (band && p.total > c.workspace_bytes) {
-        rblk.bk = 0;
-        p = plan(blk.bk, 0);
-    }
-    if (band && p.total > c.workspace_bytes) {
-        band = false;
-        p = plan(0, 0);
-    }
-    if (!band && p.total > c.workspace_bytes) return 3;
+    const CrfChoice ch = crf_choose(c.ntrans, c.nblk, c.nbatch, max_seqlen, labels != nullptr ? labels->bulk_seqlen : 0, mod,
+                                    c.mod_col_weights != nullptr, g, c.sharp_can, c.workspace_bytes);
+    if (ch.rc != 0) return ch.rc;
+    const bool band = ch.band;
+    const BandBlock &blk = ch.blk, &rblk = ch.rblk;
+    const CrfPlan &p = ch.p;
     if (labels != nullptr && !band) {
         // the index arrays are OUTPUTS of this call; the band launch builds them itself, this path takes the
         // stand-alone kernel (tk_flipflop_build_indices_dev's)

@@ -42,7 +42,8 @@ struct CrfArgs {
 };
 
 __host__ __device__ inline int crf_ck(int R, int W, int kinds) {
-    // recompute tile + sorted-posterior tile <= 112 KiB of LDS
+    // recompute tile + sorted-posterior tile <= 112 KiB of LDS -- except at (4, 16) cat-mod, where the quotient is 1 and the
+    // spacing is clamped to 2: 134 KiB, inside the 160 a workgroup has (crf_launch_one, band_tail_launch check)
     const int c = 28672 / (R * W * WAVE * (kinds + 1));
     return c >= 16 ? 16 : (c >= 8 ? 8 : (c >= 4 ? 4 : 2));
 }

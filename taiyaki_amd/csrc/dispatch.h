@@ -161,6 +161,8 @@ bool lstm_lab_geometry(size_t N, size_t H, int cu_count, size_t *out);
 void gru_lab_cols(int cols);
 bool logz_lab_plan(size_t T, size_t N, size_t nbase, size_t score_bytes, LogzPlan *p);
 int viterbi_lab_waves(size_t N);
+bool crf_lab_plan(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, size_t bulk_seqlen, int form, int want_grad,
+                  float sharp, size_t workspace_bytes, size_t *out);
 #endif
 
 }  // namespace tk
@@ -187,5 +189,13 @@ void tk_lab_gru_cols(int cols);
 int tk_lab_logz_plan(size_t nblk, size_t nbatch, size_t nbase, size_t score_bytes, size_t *out);
 /* the Viterbi's waves per read at nbatch reads: 5, 3 or 1 (viterbi_kernels.hip) */
 int tk_lab_viterbi_plan(size_t nbatch);
+/* kernel A's choices for a call under the environment as it stands (crf_kernels.hip: crf_choose; form 0 the plain CRF,
+ * 1 cat-mod with per-column factors, 2 cat-mod with per-position factors; max_seqlen 0: nblk + 1; bulk_seqlen 0: unknown):
+ * out[20] = 0 the linear path / 1 the log-domain kernel on every read; the log-domain form's R, W and checkpoint spacing
+ * (behind the linear path: the tail launch's); the batch launch's R, W, block length, 2 x weight bias, frame slope, 1 with
+ * a row maker, wave-count class; the retry's block length (0: none), 2 x bias, slope, R, W, 1 where its sweeps run side by
+ * side; the tail's log-domain R; the slots; the tail launch's R.  0 where the call is refused */
+int tk_lab_crf_plan(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, size_t bulk_seqlen, int form,
+                    int want_grad, float sharp, size_t workspace_bytes, size_t *out);
 }
 #endif

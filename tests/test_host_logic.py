@@ -374,6 +374,7 @@ def test_release_library_carries_no_lab_switch():
     assert "tk_lab_" not in dynsyms(_lib.LIBPATH)
     lab_syms = dynsyms(_lib.LAB_LIBPATH)
     assert all(name in lab_syms for name in _lib.LAB_SIGNATURES) and "tk_lab_logz_plan" in _lib.LAB_SIGNATURES
+    assert "tk_lab_crf_plan" in _lib.LAB_SIGNATURES and "tk_lab_crf_plan" in lab_syms
     # no source file of the library calls getenv outside the macro and that one static
     for fn in os.listdir(_lib.CSRC):
         if fn.endswith((".hip", ".h", ".cpp")) and fn != "rccl_api.cpp":
@@ -525,7 +526,8 @@ def test_binding_read_from_the_header_is_the_hand_typed_one():
     them from the headers: {name: [restype, [argtypes]]}.  The parsed tables equal it, keys and every code.  One entry
     of the dump was corrected: the last parameter of tk_lab_lstm_geometry (`size_t *out`) was POINTER(c_size_t) there
     and is c_void_p by the rule every other pointer follows (its callers pass a ctypes array, which both accept).  Two
-    entries were added with the decode side's plan queries, tk_lab_logz_plan and tk_lab_viterbi_plan."""
+    entries were added with the decode side's plan queries, tk_lab_logz_plan and tk_lab_viterbi_plan, and one with
+    kernel A's, tk_lab_crf_plan."""
     import json
     from taiyaki_amd import _lib
     golden = json.load(open(os.path.join(ROOT, "tests", "golden", "abi_signatures.json")))
@@ -534,7 +536,7 @@ def test_binding_read_from_the_header_is_the_hand_typed_one():
         got = _ctype_names(getattr(_lib, table))
         assert set(got) == set(want), table
         assert [k for k in want if got[k] != want[k]] == [], table
-    assert len(golden["SIGNATURES"]) == 43 and len(golden["RCCL_SIGNATURES"]) == 8 and len(golden["LAB_SIGNATURES"]) == 7
+    assert len(golden["SIGNATURES"]) == 43 and len(golden["RCCL_SIGNATURES"]) == 8 and len(golden["LAB_SIGNATURES"]) == 8
     assert _lib.ERRORS.keys() == {1, 2, 3, 4} and all(_lib.ERRORS.values())
 
 
