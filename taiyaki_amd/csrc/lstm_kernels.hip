@@ -5,7 +5,8 @@
 // C batch columns.  The G = H / U workgroups that share C columns form a group; a group needs nothing from another
 // group.  The admission rule and the workspace size are those of U = 16 with 8 or 16 columns (lstm_geometry); a
 // launch at U = 32 or 64 takes C * 16 / U columns per workgroup, so its grid and its granule buffers are never
-// larger than the admitted ones (lstm_plan).
+// larger than the admitted ones (lstm_plan).  H = 192 and 384 are not multiples of 64: there a workgroup owns U = 48
+// units and 4 (H 192: or 8) columns, and the admission geometry is the launch's own (lstm_geometry).
 //
 // Hand-off.  Inside a group every step is an all-to-all: forward, each member needs the whole h_{t-1} of its
 // columns; backward, each member needs the sum over members of W_hh[rows(m), J]^T dG_{t+1}[rows(m)] for its units J
@@ -34,9 +35,13 @@
 namespace tk {
 namespace {
 
-// threads per workgroup at U units: 4 U H / threads W_hh floats per lane, <= 128 at H = 256
+// threads per workgroup at U units: 4 U H / threads W_hh floats per lane, <= 128 at H = 256; U = 48 (H 192, 384): the
+// forward's lanes (u, kp) at KP = 8, 192 floats per lane at H = 384
 template <int U>
-constexpr int threads_for() { return U <= 32 ? 256 : 512; }
+constexpr int threads_for() { return U == 48 ? 384 : U <= 32 ? 256 : 512; }
+// ... of the backward: two lanes per column of W_hh at U = 48, 96 floats per lane at either size
+template <int H, int U>
+constexpr int bwd_threads_for() { return U == 48 ? 2 * H : threads_for<U>(); }
 
 // Forward.  gx (T, N, 4H) = x W_ih^T + b_ih + b_hh.  Writes y = h (T, N, H), the gate activations (T, N, 4H) and
 // c (T, N, H).  Recurrence step s runs time t = s (reverse: T - 1 - s).  hbuf: [2][ngroups][C][H] granules.
@@ -240,8 +245,13 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
 // dc = 0 (its dG rows in LDS are 0, so is what it publishes; dc_next = f_next = 0), like any other step.  The mask is a
 // select behind the cell update, as in the forward: dy, the gates and c beyond the length are loaded and never used.
 // (With reverse != 0 the walk reaches the padding after the column's real steps, with a dh and a dc f that are not 0.)
+//
+// Lane (k, rp), rp < RP = threads / H, holds column k of R = 4 U / RP owned rows of W_hh: rows rp R + i (i < R); at
+// U = 48 rows i RP + rp, as the GRU backward takes them.  RP divides U, so row i RP + rp is unit (i RP) % U + rp of gate
+// (i RP) / U, a compile-time offset from the lane's first weight: with U and H no powers of two, r / U and r % U of a
+// run-time row keep an address per weight live, and the kernel spills.
 template <int H, int C, int U, bool VL = false>
-__global__ __launch_bounds__(threads_for<U>(), 1) void lstm_bwd_kernel(const float *__restrict__ whh,
+__global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(const float *__restrict__ whh,
                                                                        const float *__restrict__ gates,
                                                                        const float *__restrict__ cell,
                                                                        const float *__restrict__ dy, int T, int N,
@@ -249,14 +259,17 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_bwd_kernel(const flo
                                                                        float *__restrict__ dgates, u64 *pbuf,
                                                                        uint32_t *status,
                                                                        const int32_t *__restrict__ lengths) {
-    constexpr int NT = threads_for<U>();
+    constexpr int NT = bwd_threads_for<H, U>();
     constexpr int G = H / U;
+    constexpr bool STRIDED = U == 48;                 // a lane's rows: every RP-th, not R in a run
     constexpr int RP = NT / H;                        // row partitions: lane (k, rp) holds W_hh[rows of rp, k]
     constexpr int R = 4 * U / RP;                     // floats per lane
     constexpr int PAIRS = U * C;                      // (c, u) pairs of the cell update
     constexpr int PL = NT / PAIRS;                    // producer planes of the gather
     constexpr int NP = (G + PL - 1) / PL;
     static_assert(RP >= 1 && R >= 1 && PL >= 1 && PL * PAIRS == NT, "every lane polls; one cell lane per pair");
+    static_assert(!STRIDED || (RP * H == NT && R * RP == 4 * U && U % RP == 0),
+                  "a lane's rows keep their gate index at compile time");
     __shared__ __attribute__((aligned(16))) float dgs[4 * U * C];      // dG_t of the owned rows as [row][c]
     __shared__ float gath[PL * PAIRS];
     __shared__ __attribute__((aligned(16))) float red[RP > 1 ? RP * C * H : 1];
@@ -269,10 +282,16 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_bwd_kernel(const flo
 
     const int k = tid % H, rp = tid / H;
     float w[R];
+    if constexpr (STRIDED) {
+        const float *wbase = whh + (size_t)(j0 + rp) * H + k;
 #pragma unroll
-    for (int i = 0; i < R; ++i) {
-        const int r = rp * R + i;
-        w[i] = whh[((size_t)(r / U) * H + j0 + (r % U)) * H + k];
+        for (int i = 0; i < R; ++i) w[i] = wbase[(unsigned)((((i * RP) / U) * H + (i * RP) % U) * H)];
+    } else {
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const int r = rp * R + i;
+            w[i] = whh[((size_t)(r / U) * H + j0 + (r % U)) * H + k];
+        }
     }
     settle(w);
 
@@ -385,7 +404,7 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_bwd_kernel(const flo
 #pragma unroll
         for (int i = 0; i < R; ++i) {
             float d[C];
-            lds_row<C>(dgs + (rp * R + i) * C, d);
+            lds_row<C>(dgs + (STRIDED ? i * RP + rp : rp * R + i) * C, d);
 #pragma unroll
             for (int c = 0; c < C; ++c) acc[c] = fmaf(w[i], d[c], acc[c]);
         }
@@ -415,15 +434,24 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_bwd_kernel(const flo
 
 #endif  // TK_RNN_VARLEN: no backward
 
-int g_lab_cols = 0;     // lab build: force the admitted batch columns, 8 or 16 (0 = the rule below)
+int g_lab_cols = 0;     // lab build: force the admitted batch columns, 8 or 16; H = 192: 4 or 8 (0 = the rule below)
 int g_lab_units = 0;    // lab build: force the hidden units per workgroup, 16, 32 or 64 (0 = the rule in lstm_plan)
 
-// The admission geometry: batch columns C per group of H / 16 workgroups and the number of groups; false where the
-// kernels do not run.  It fixes the workspace (tk_lstm_workspace_bytes) and bounds every launch plan.
+// units per workgroup of the sizes that are no power of two (0: a power of two, planned from U = 16)
+int units48(size_t H) { return H == 192 || H == 384 ? 48 : 0; }
+
+// The admission geometry: batch columns C per group and the number of groups; false where the kernels do not run.  It
+// fixes the workspace (tk_lstm_workspace_bytes) and bounds every launch plan.  H = 16 ... 256, powers of two: groups of
+// H / 16 workgroups with 8 columns where they fit one workgroup per CU, else with 16.  H = 192 and 384: groups of H / 48
+// workgroups with 4 columns where they fit, else, at H = 192 only, with 8 (at H = 384 the forward at 8 columns does not
+// fit its registers); this is the launch itself.  Every kernel waits on the other members of its group, so a grid
+// larger than the CU count is never admitted.
 bool lstm_geometry(size_t N, size_t H, int cu_count, int *C_out, int *groups_out) {
-    if (!(H == 16 || H == 32 || H == 64 || H == 128 || H == 256) || N == 0 || cu_count <= 0) return false;
-    const size_t G = H / 16;
-    for (int C : {8, 16}) {
+    const int U48 = units48(H);
+    if (!(U48 || H == 16 || H == 32 || H == 64 || H == 128 || H == 256) || N == 0 || cu_count <= 0) return false;
+    const size_t G = H / (U48 ? U48 : 16);
+    const int first = U48 ? 4 : 8, last = H == 384 ? 4 : 2 * first;
+    for (int C = first; C <= last; C *= 2) {
         if (g_lab_cols != 0 && C != g_lab_cols) continue;
         const size_t groups = (N + C - 1) / C;
         if (groups * G <= (size_t)cu_count) {
@@ -442,7 +470,8 @@ size_t ws_bytes(size_t H, int C, int groups, int U, bool backward) {
 // A launch: U units and C = C_admitted * 16 / U columns per workgroup, groups of H / U workgroups.  Release rule:
 // U = 64, or H where H < 64 (config 2's layer when the rule was set: 2.85 / 2.54 us per forward / backward step at U = 64, 2.84 / 3.58 at
 // U = 32, 3.44 / 4.02 at U = 16; tools/lstmbench.py).  C divides the admitted column count, so the grid and both granule buffers are never
-// larger than those of the admission geometry.
+// larger than those of the admission geometry.  H = 192 and 384: U = 48 and the admitted columns and groups as they are
+// (the lab's forced units do not apply).
 struct Plan {
     int U, C, groups;
     unsigned grid;
@@ -451,6 +480,10 @@ struct Plan {
 bool lstm_plan(size_t N, size_t H, int cu_count, Plan *p) {
     int C16 = 0, groups16 = 0;
     if (!lstm_geometry(N, H, cu_count, &C16, &groups16)) return false;
+    if (const int U48 = units48(H)) {
+        *p = Plan{U48, C16, groups16, (unsigned)(groups16 * (H / U48))};
+        return true;
+    }
     int U = g_lab_units != 0 ? g_lab_units : 64;
     if ((size_t)U > H) U = (int)H;
     if (U != 16 && U != 32 && U != 64) return false;
@@ -461,7 +494,8 @@ bool lstm_plan(size_t N, size_t H, int cu_count, Plan *p) {
     return true;
 }
 
-// (H, U, C) -> one instantiation: U = 16 takes 8 or 16 columns, U = 32 4 or 8, U = 64 2 or 4; U <= H
+// (H, U, C) -> one instantiation: U = 16 takes 8 or 16 columns, U = 32 4 or 8, U = 64 2 or 4; U <= H; U = 48 takes 4,
+// and 8 at H = 192
 #define TK_LSTM_SWITCH(LAUNCH)                                                                                    \
     switch ((int)H * 100000 + p.U * 1000 + p.C) {                                                                 \
         LAUNCH(16, 16, 8) LAUNCH(16, 16, 16) LAUNCH(32, 16, 8) LAUNCH(32, 16, 16) LAUNCH(64, 16, 8)                \
@@ -469,7 +503,7 @@ bool lstm_plan(size_t N, size_t H, int cu_count, Plan *p) {
         LAUNCH(32, 32, 4) LAUNCH(32, 32, 8) LAUNCH(64, 32, 4) LAUNCH(64, 32, 8) LAUNCH(128, 32, 4)                 \
         LAUNCH(128, 32, 8) LAUNCH(256, 32, 4) LAUNCH(256, 32, 8)                                                  \
         LAUNCH(64, 64, 2) LAUNCH(64, 64, 4) LAUNCH(128, 64, 2) LAUNCH(128, 64, 4) LAUNCH(256, 64, 2)               \
-        LAUNCH(256, 64, 4)                                                                                        \
+        LAUNCH(256, 64, 4) LAUNCH(192, 48, 4) LAUNCH(192, 48, 8) LAUNCH(384, 48, 4)                               \
         default: return TK_ERR_UNSUPPORTED;                                                                       \
     }
 
@@ -492,8 +526,8 @@ int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const 
                const float *dy, int T, int N, int rev, float *dg, u64 *ws, uint32_t *status, const int32_t *lengths) {
 #define TK_LSTM_BWD(HH, UU, CC)                                                                                   \
     case HH * 100000 + UU * 1000 + CC:                                                                            \
-        hipLaunchKernelGGL((lstm_bwd_kernel<HH, CC, UU, VL>), dim3(p.grid), dim3(threads_for<UU>()), 0, st, whh,  \
-                           gates, cell, dy, T, N, rev, p.groups, dg, ws, status, lengths);                        \
+        hipLaunchKernelGGL((lstm_bwd_kernel<HH, CC, UU, VL>), dim3(p.grid), dim3(bwd_threads_for<HH, UU>()), 0,   \
+                           st, whh, gates, cell, dy, T, N, rev, p.groups, dg, ws, status, lengths);               \
         break;
     TK_LSTM_SWITCH(TK_LSTM_BWD)
 #undef TK_LSTM_BWD
@@ -520,11 +554,13 @@ int checked(bool pointers_ok, size_t T, size_t N, size_t H, int cu_count, void *
     return launch(p);
 }
 
-// the backward's granule bytes at U = 16: they bound every plan's, forward and backward
+// the backward's granule bytes at U = 16 (H = 192, 384: at the launch's U = 48): they bound every plan's, forward and
+// backward
 size_t train_workspace_bytes(size_t N, size_t H, int cu_count) {
     int C = 0, groups = 0;
     if (!lstm_geometry(N, H, cu_count, &C, &groups)) return 0;
-    return ws_bytes(H, C, groups, 16, true);
+    const int U48 = units48(H);
+    return ws_bytes(H, C, groups, U48 ? U48 : 16, true);
 }
 
 }  // namespace

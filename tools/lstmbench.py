@@ -6,15 +6,22 @@ units setting (microseconds per timestep and direction, median and min over --st
 (csrc/lstm_wgrad.hip) at (T, N, H, I = H), `wgrad_gemm_ms` the two GEMMs and the sum over dG that it replaces.
 
     python tools/lstmbench.py [--T 800] [--N 128] [--H 256] [--steps 20] [--warmup 3] [--units 0 16 32 64] [--varlen]
+                              [--fallback PAIRS]
 
 --varlen also times, in turns of five, tk_lstm_forward_varlen_dev with every length = T beside the forward, and the
 training pair with per-column lengths (include/taiyaki_amd_rnn_varlen_train.h), forward and backward, at lengths = NULL
 and at a half-full pattern (lengths[n] spread evenly over 0..T) beside tk_lstm_forward_dev / tk_lstm_backward_dev.
 
 --units (lab build) forces the hidden units per workgroup; 0 is the release rule.  Without --units the
-release library is timed.
+release library is timed.  H = 192 and 384 run at 48 units whatever is forced: a setting other than 0 is reported as
+skipped there, with the units of the plan.
+
+--fallback PAIRS times layers.Lstm(H, H) on one input, forward (grad mode) and backward, PAIRS times in turns: the HIP
+recurrence, then nn.LSTM (layers.USE_HIP_LSTM = False: MIOpen, what a size the kernels refuse runs).  Both sides include
+the input GEMM and the weight gradients; one JSON line, microseconds per timestep, in front of the others.
 """
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -41,6 +48,37 @@ def timed(fn, steps, warmup):
     return float(np.median(times)), float(np.min(times))
 
 
+def layer_turns(T, N, H, pairs, steps, warmup, dev):
+    """[(hip fwd, hip bwd, nn.LSTM fwd, nn.LSTM bwd)] * pairs, median microseconds per timestep."""
+    torch.manual_seed(12)
+    layer = layers.Lstm(H, H).to(dev)
+    x = torch.randn(T, N, H, device=dev).requires_grad_(True)
+    dy = torch.randn(T, N, H, device=dev).div_((T * N) ** 0.5)
+    if layers.hip_lstm_workspace_bytes(layer.rnn, x) == 0:
+        raise SystemExit("(N, H) = (%d, %d) is not admitted on %d CUs" % (N, H, layers._cu_count(dev)))
+
+    def one(use_hip):
+        layers.USE_HIP_LSTM = use_hip
+        f, b = [], []
+        for i in range(warmup + steps):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            e[0].record()
+            y = layer(x)
+            e[1].record()
+            y.backward(dy)
+            e[2].record()
+            e[2].synchronize()
+            if i >= warmup:
+                f.append(e[0].elapsed_time(e[1]))
+                b.append(e[1].elapsed_time(e[2]))
+        return 1e3 * float(np.median(f)) / T, 1e3 * float(np.median(b)) / T
+
+    try:
+        return [one(True) + one(False) for _ in range(pairs)]
+    finally:
+        layers.USE_HIP_LSTM = True
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=800)
@@ -52,6 +90,8 @@ def main():
     ap.add_argument("--varlen", action="store_true",
                     help="also time tk_lstm_forward_varlen_dev (release rule) with every length = T, in turns with the forward")
     ap.add_argument("--units", type=int, nargs="*", default=None, help="(lab) units per workgroup; 0 = release rule")
+    ap.add_argument("--fallback", type=int, default=0, metavar="PAIRS",
+                    help="also time layers.Lstm(H, H) forward and backward, HIP and nn.LSTM in turns, PAIRS times")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("lstmbench needs a GPU (the LSTM recurrence has no CPU fallback)")
@@ -68,6 +108,11 @@ def main():
     x_in = torch.randn(T, N, H, generator=g).to(dev)
     cus = layers._cu_count(dev)
     _lib.set_strict(False)
+    if a.fallback:
+        turns = layer_turns(T, N, H, a.fallback, a.steps, a.warmup, dev)
+        keys = ("hip_fwd", "hip_bwd", "nn_lstm_fwd", "nn_lstm_bwd")
+        print(json.dumps({"T": T, "N": N, "H": H, "layer_turns_us_per_step": {k: [round(t[i], 3) for t in turns]
+                                                                              for i, k in enumerate(keys)}}))
     for units in (a.units if a.units is not None else [None]):
         L = _lib.use_lab(units is not None)
         if units is not None:
@@ -75,6 +120,13 @@ def main():
         wsb = L.tk_lstm_workspace_bytes(N, H, cus)
         if wsb == 0:
             raise SystemExit("(N, H) = (%d, %d) is not admitted on %d CUs" % (N, H, cus))
+        if units:
+            plan = (ctypes.c_size_t * 8)()
+            L.tk_lab_lstm_geometry(N, H, cus, plan)
+            if plan[2] not in (16, 32, 64):  # H = 192, 384: the forced units do not apply
+                L.tk_lab_lstm_units(0)
+                print(json.dumps({"T": T, "N": N, "H": H, "units": units, "skipped": "the plan runs %d units" % plan[2]}))
+                continue
         ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
         status = _lib.status_word(dev)
         stream = _lib.stream_ptr()

@@ -1,0 +1,72 @@
+#!/usr/bin/env python
+"""Times one eager train step of mLstm_flipflop at a hidden size (default 384, the reference trainer's own default) with
+the LSTM layers on the HIP recurrence and on nn.LSTM (layers.USE_HIP_LSTM = False: what a size the kernels refuse runs),
+in turns on one model and one batch; prints one JSON line, milliseconds per step (median over --steps per turn).
+
+    python tools/sizebench.py [--size 384] [--chunk-len 4000] [--chunks 128] [--pairs 3] [--steps 5] [--warmup 2]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from taiyaki_amd import _lib, layers, models, parallel, synth, train  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=384)
+    ap.add_argument("--chunk-len", type=int, default=4000)
+    ap.add_argument("--chunks", type=int, default=128)
+    ap.add_argument("--pairs", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("sizebench needs a GPU")
+    dev = torch.device("cuda:0")
+    stride = 5
+    torch.manual_seed(0)
+    net = models.mLstm_flipflop(size=a.size, stride=stride).to(dev)
+    probe = torch.zeros(a.chunk_len // stride, a.chunks, a.size, device=dev)
+    lstms = [m for m in net.modules() if isinstance(m, layers.Lstm)]
+    if not all(layers.hip_lstm_workspace_bytes(m.rnn, probe) > 0 for m in lstms):
+        raise SystemExit("size %d x %d chunks is not admitted on %d CUs" % (a.size, a.chunks, layers._cu_count(dev)))
+    sl = synth.realistic_seqlens(a.chunk_len // stride, a.chunks, 8, a.chunk_len, 9.0)
+    sq, _ = synth.sequences(sl, 8)
+    batch = dict(indata=torch.from_numpy(synth.signal_chunks(a.chunk_len, a.chunks, 8)).to(dev),
+                 seqs=torch.from_numpy(sq), seqlens=torch.from_numpy(sl))
+    trainer = train.Trainer(net, parallel.FlatGradArena(net), clip_num_mads=0)
+    _lib.set_strict(False)
+
+    def turn(use_hip):
+        layers.USE_HIP_LSTM = use_hip
+        times = []
+        for i in range(a.warmup + a.steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            loss = trainer.step(batch)
+            e1.record()
+            e1.synchronize()
+            if i >= a.warmup:
+                times.append(e0.elapsed_time(e1))
+        return float(np.median(times)), float(loss.detach())
+
+    try:
+        turns = [turn(True) + turn(False) for _ in range(a.pairs)]
+    finally:
+        layers.USE_HIP_LSTM = True
+    _lib.raise_if_nonfinite()
+    print(json.dumps({"model": "mLstm_flipflop", "size": a.size, "chunk_len": a.chunk_len, "chunks": a.chunks,
+                      "cus": layers._cu_count(dev), "hip_ms_per_step": [round(t[0], 2) for t in turns],
+                      "nn_lstm_ms_per_step": [round(t[2], 2) for t in turns],
+                      "last_loss": [round(turns[-1][1], 4), round(turns[-1][3], 4)],
+                      "device": torch.cuda.get_device_name(dev)}))
+
+
+if __name__ == "__main__":
+    main()
