@@ -323,7 +323,9 @@ int tk_lstm_backward_dev(const float *w_hh, const float *gates, const float *cel
  * tk_gru_workspace_bytes: the workspace either call needs at (nbatch, size) on a device with
  * cu_count CUs, 0 where the kernels do not run (the caller falls back to nn.GRU); never 0
  * where they do.  Sizes 32, 64, 96 and 128 run at any nbatch >= 1; size 256 where
- * ceil(nbatch / 4) * 4 <= cu_count.  The same cu_count goes to both calls.
+ * ceil(nbatch / 4) * 4 <= cu_count; sizes 192 and 384 where ceil(nbatch / 4) * size / 48 <= cu_count
+ * or, failing that, ceil(nbatch / 8) * size / 48 <= cu_count (on 256 CUs: nbatch <= 512 at 192,
+ * <= 256 at 384).  The same cu_count goes to both calls.
  * TK_STATUS_RNN_TIMEOUT in *status if a workgroup's wait for its group ran out of time.
  * ------------------------------------------------------------------------- */
 size_t tk_gru_workspace_bytes(size_t nbatch, size_t size, int cu_count);

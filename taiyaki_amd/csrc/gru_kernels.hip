@@ -14,6 +14,10 @@
 //     of W_hh[rows(m), J]^T dG[rows(m)] for its units J (summed in producer order: bit-reproducible).  Both go
 //     through the tagged granules of rnn_common.h.  Such a grid is co-resident by construction: it is admitted
 //     only where groups * G <= cu_count, at one workgroup per CU (__launch_bounds__(threads, 1)).
+//   H = 192, 384: U = 48, G = H / 48 (4, 8), as in lstm_kernels.hip, handed on through the granules like H = 256.
+//     C = 4 where ceil(N / 4) * G <= cu_count, else 8 where ceil(N / 8) * G <= cu_count, else the batch is refused.
+//     Forward 384 lanes (u, kp) at KP = 8: 72 weight floats per lane at H = 192, 144 at 384.  Backward 2 H lanes
+//     (384, 768), two per column of W_hh, 72 floats each at either size.
 //
 // Step schedule (lstm_kernels.hip's rule).  Nothing bound for HBM is issued ahead of a poll in the same step: the
 // inputs of step s + 1 are loaded right after step s's poll (G = 1: barrier), the bulk outputs of step s are held
@@ -30,11 +34,15 @@
 namespace tk {
 namespace {
 
-constexpr int kCols = 4;        // batch columns per workgroup at H = 256
+constexpr int kCols = 4;        // batch columns per workgroup at H = 256, and where they fit at H = 192 and 384
 
-// threads per workgroup: 4 per unit where one workgroup owns every unit, 8 per unit at U = 64 of H = 256
+// threads per workgroup: 4 per unit where one workgroup owns every unit, 8 per unit at U = 64 of H = 256 and at U = 48
+// of H = 192 and 384
 template <int H, int U>
-constexpr int gru_threads() { return U == H ? 4 * U : 512; }
+constexpr int gru_threads() { return U == H ? 4 * U : U == 48 ? 384 : 512; }
+// ... of the backward: two lanes per column of W_hh at U = 48, 72 floats per lane at either size
+template <int H, int U>
+constexpr int bwd_threads_for() { return U == 48 ? 2 * H : gru_threads<H, U>(); }
 
 // Forward.  Writes y = h (T, N, H) and, where the pointers are not NULL, the activations r, z, n as gates (T, N, 3H)
 // and q (T, N, H).  Recurrence step s runs time t = s (reverse: T - 1 - s).  hbuf (G > 1): [2][ngroups][C][H]
@@ -237,12 +245,12 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
 // dh = 0 (its rows in LDS are 0, so is what it publishes; the carried dh z is 0), like any other step.  The mask is a
 // select behind the cell update: dy and the saved rows beyond the length are loaded and never used.
 template <int H, int U, int C, bool VL = false>
-__global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_bwd_kernel(
+__global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void gru_bwd_kernel(
     const float *__restrict__ whh, const float *__restrict__ y, const float *__restrict__ gates,
     const float *__restrict__ qin, const float *__restrict__ dy, int T, int N, int reverse, int ngroups,
     float *__restrict__ dgates, float *__restrict__ dqout, u64 *pbuf, uint32_t *status,
     const int32_t *__restrict__ lengths) {
-    constexpr int NT = gru_threads<H, U>();
+    constexpr int NT = bwd_threads_for<H, U>();
     constexpr int G = H / U;
     constexpr int RP = NT / H;                        // row partitions
     constexpr int R = 3 * U / RP;                     // floats per lane
@@ -410,7 +418,8 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_bwd_kernel(
 
 // A launch: U units and C columns per workgroup, groups of G = H / U workgroups; false where the kernels do not
 // run.  H <= 128 is one workgroup per group (any N); H = 256 hands h between the 4 members of a group, so its grid
-// must be co-resident: groups * 4 <= cu_count at one workgroup per CU.
+// must be co-resident: groups * 4 <= cu_count at one workgroup per CU.  H = 192 and 384: groups of H / 48 members with
+// 4 columns where such a grid is co-resident, else with 8, else refused.
 struct Plan {
     int U, G, C, groups;
     unsigned grid;
@@ -419,10 +428,11 @@ struct Plan {
 int g_lab_cols = 0;     // lab build: force the batch columns per workgroup at H <= 128: 1 or 2 (0 = the rule below)
 
 bool gru_plan(size_t N, size_t H, int cu_count, Plan *p) {
-    if (!(H == 32 || H == 64 || H == 96 || H == 128 || H == 256) || N == 0 || N > (size_t)INT32_MAX ||
+    const bool u48 = H == 192 || H == 384;
+    if (!(u48 || H == 32 || H == 64 || H == 96 || H == 128 || H == 256) || N == 0 || N > (size_t)INT32_MAX ||
         cu_count <= 0)
         return false;
-    p->U = H == 256 ? 64 : (int)H;
+    p->U = u48 ? 48 : H == 256 ? 64 : (int)H;
     p->G = (int)H / p->U;
     // one workgroup per group: 1 column where every column gets a CU of its own, else 2 (tools/grubench.py, us per
     // forward / backward step at H = 96: N = 64 0.88 / 0.81 at 1 column, 1.08 / 1.15 at 2, 1.45 / 1.72 at 4;
@@ -432,6 +442,7 @@ bool gru_plan(size_t N, size_t H, int cu_count, Plan *p) {
         if (g_lab_cols != 1 && g_lab_cols != 2) return false;
         p->C = g_lab_cols;
     }
+    if (u48 && (N + 3) / 4 * p->G > (size_t)cu_count) p->C = 8;
     const size_t groups = (N + p->C - 1) / p->C;
     if (p->G > 1 && groups * p->G > (size_t)cu_count) return false;
     p->groups = (int)groups;
@@ -447,7 +458,7 @@ size_t gru_ws_bytes(size_t H, const Plan &p, bool backward) {
 
 #define TK_GRU_SWITCH(LAUNCH)                                                                                     \
     switch ((int)H * 10 + p.C) {                                                                                  \
-        LAUNCH(256, 64, 4)                                                                                        \
+        LAUNCH(256, 64, 4) LAUNCH(192, 48, 4) LAUNCH(192, 48, 8) LAUNCH(384, 48, 4) LAUNCH(384, 48, 8)            \
         LAUNCH(32, 32, 2) LAUNCH(64, 64, 2) LAUNCH(96, 96, 2) LAUNCH(128, 128, 2)                                 \
         LAUNCH(32, 32, 1) LAUNCH(64, 64, 1) LAUNCH(96, 96, 1) LAUNCH(128, 128, 1)                                 \
         default: return TK_ERR_UNSUPPORTED;                                                                       \
@@ -473,8 +484,8 @@ int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const 
                uint32_t *status, const int32_t *lengths) {
 #define TK_GRU_BWD(HH, UU, CC)                                                                                    \
     case HH * 10 + CC:                                                                                            \
-        hipLaunchKernelGGL((gru_bwd_kernel<HH, UU, CC, VL>), dim3(p.grid), dim3(gru_threads<HH, UU>()), 0, st,    \
-                           whh, y, gates, q, dy, T, N, rev, p.groups, dg, dq, ws, status, lengths);               \
+        hipLaunchKernelGGL((gru_bwd_kernel<HH, UU, CC, VL>), dim3(p.grid), dim3(bwd_threads_for<HH, UU>()), 0,    \
+                           st, whh, y, gates, q, dy, T, N, rev, p.groups, dg, dq, ws, status, lengths);           \
         break;
     TK_GRU_SWITCH(TK_GRU_BWD)
 #undef TK_GRU_BWD

@@ -5,8 +5,13 @@ direction, median and min over --steps).  bench.py --config 1's layer is the def
 record is --T 800 --N 128 --H 256.
 
     python tools/grubench.py [--T 1000] [--N 64] [--H 96] [--steps 20] [--warmup 3] [--reverse] [--infer] [--varlen] [--cols C]
+                             [--fallback PAIRS]
 
 --cols (lab build) forces the batch columns per workgroup at H <= 128; without it the release library is timed.
+
+--fallback PAIRS times layers.GruMod(H, H) on one input, forward (grad mode) and backward, PAIRS times in turns: the HIP
+recurrence, then nn.GRU (layers.USE_HIP_GRU = False: MIOpen, what a size the kernels refuse runs).  Both sides include
+the input GEMM and the weight gradients; one JSON line, microseconds per timestep, in front of the other.
 
 --infer also times the forward with NULL for gates and q (what a torch.no_grad() call launches).
 
@@ -43,6 +48,37 @@ def timed(fn, steps, warmup):
     return float(np.median(times)), float(np.min(times))
 
 
+def layer_turns(T, N, H, pairs, steps, warmup, dev):
+    """[(hip fwd, hip bwd, nn.GRU fwd, nn.GRU bwd)] * pairs, median microseconds per timestep."""
+    torch.manual_seed(12)
+    layer = layers.GruMod(H, H).to(dev)
+    x = torch.randn(T, N, H, device=dev).requires_grad_(True)
+    dy = torch.randn(T, N, H, device=dev).div_((T * N) ** 0.5)
+    if layers.hip_gru_workspace_bytes(layer.rnn, x) == 0:
+        raise SystemExit("(N, H) = (%d, %d) is not admitted on %d CUs" % (N, H, layers._cu_count(dev)))
+
+    def one(use_hip):
+        layers.USE_HIP_GRU = use_hip
+        f, b = [], []
+        for i in range(warmup + steps):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            e[0].record()
+            y = layer(x)
+            e[1].record()
+            y.backward(dy)
+            e[2].record()
+            e[2].synchronize()
+            if i >= warmup:
+                f.append(e[0].elapsed_time(e[1]))
+                b.append(e[1].elapsed_time(e[2]))
+        return 1e3 * float(np.median(f)) / T, 1e3 * float(np.median(b)) / T
+
+    try:
+        return [one(True) + one(False) for _ in range(pairs)]
+    finally:
+        layers.USE_HIP_GRU = True
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--T", type=int, default=1000)
@@ -54,6 +90,8 @@ def main():
     ap.add_argument("--infer", action="store_true", help="also time the forward that saves nothing (gates = q = NULL)")
     ap.add_argument("--varlen", action="store_true", help="also time the forward with per-column lengths, all = T")
     ap.add_argument("--cols", type=int, default=None, help="(lab build) batch columns per workgroup at H <= 128")
+    ap.add_argument("--fallback", type=int, default=0, metavar="PAIRS",
+                    help="also time layers.GruMod(H, H) forward and backward, HIP and nn.GRU in turns, PAIRS times")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("grubench needs a GPU (the GRU recurrence has no CPU fallback)")
@@ -71,6 +109,11 @@ def main():
     dq = torch.empty(T, N, H, device=dev)
     cus = layers._cu_count(dev)
     _lib.set_strict(False)
+    if a.fallback:
+        turns = layer_turns(T, N, H, a.fallback, a.steps, a.warmup, dev)
+        keys = ("hip_fwd", "hip_bwd", "nn_gru_fwd", "nn_gru_bwd")
+        print(json.dumps({"T": T, "N": N, "H": H, "layer_turns_us_per_step": {k: [round(t[i], 3) for t in turns]
+                                                                              for i, k in enumerate(keys)}}))
     L = _lib.use_lab(a.cols is not None)
     if a.cols is not None:
         L.tk_lab_gru_cols(a.cols)

@@ -1,9 +1,11 @@
 #!/usr/bin/env python
-"""Times one eager train step of mLstm_flipflop at a hidden size (default 384, the reference trainer's own default) with
-the LSTM layers on the HIP recurrence and on nn.LSTM (layers.USE_HIP_LSTM = False: what a size the kernels refuse runs),
-in turns on one model and one batch; prints one JSON line, milliseconds per step (median over --steps per turn).
+"""Times one eager train step of mLstm_flipflop or mGru_flipflop at a hidden size (default 384, the reference trainer's
+own default) with the recurrent layers on the HIP recurrence and on nn.LSTM / nn.GRU (layers.USE_HIP_LSTM / USE_HIP_GRU =
+False: what a size the kernels refuse runs), in turns on one model and one batch; prints one JSON line, milliseconds per
+step (median over --steps per turn).  Both models are built with the trainer's stride, 5: chunk_len 4000 is T = 800.
 
-    python tools/sizebench.py [--size 384] [--chunk-len 4000] [--chunks 128] [--pairs 3] [--steps 5] [--warmup 2]
+    python tools/sizebench.py [--model mLstm_flipflop] [--size 384] [--chunk-len 4000] [--chunks 128] [--pairs 3]
+                              [--steps 5] [--warmup 2]
 """
 import argparse
 import json
@@ -19,6 +21,7 @@ from taiyaki_amd import _lib, layers, models, parallel, synth, train  # noqa: E4
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("mLstm_flipflop", "mGru_flipflop"), default="mLstm_flipflop")
     ap.add_argument("--size", type=int, default=384)
     ap.add_argument("--chunk-len", type=int, default=4000)
     ap.add_argument("--chunks", type=int, default=128)
@@ -31,10 +34,13 @@ def main():
     dev = torch.device("cuda:0")
     stride = 5
     torch.manual_seed(0)
-    net = models.mLstm_flipflop(size=a.size, stride=stride).to(dev)
+    gru = a.model == "mGru_flipflop"
+    switch, fallback = ("USE_HIP_GRU", "nn_gru") if gru else ("USE_HIP_LSTM", "nn_lstm")
+    net = getattr(models, a.model)(size=a.size, stride=stride).to(dev)
     probe = torch.zeros(a.chunk_len // stride, a.chunks, a.size, device=dev)
-    lstms = [m for m in net.modules() if isinstance(m, layers.Lstm)]
-    if not all(layers.hip_lstm_workspace_bytes(m.rnn, probe) > 0 for m in lstms):
+    rnns = [m for m in net.modules() if isinstance(m, layers.GruMod if gru else layers.Lstm)]
+    query = layers.hip_gru_workspace_bytes if gru else layers.hip_lstm_workspace_bytes
+    if not (len(rnns) == 5 and all(query(m.rnn, probe) > 0 for m in rnns)):
         raise SystemExit("size %d x %d chunks is not admitted on %d CUs" % (a.size, a.chunks, layers._cu_count(dev)))
     sl = synth.realistic_seqlens(a.chunk_len // stride, a.chunks, 8, a.chunk_len, 9.0)
     sq, _ = synth.sequences(sl, 8)
@@ -44,7 +50,7 @@ def main():
     _lib.set_strict(False)
 
     def turn(use_hip):
-        layers.USE_HIP_LSTM = use_hip
+        setattr(layers, switch, use_hip)
         times = []
         for i in range(a.warmup + a.steps):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -59,11 +65,11 @@ def main():
     try:
         turns = [turn(True) + turn(False) for _ in range(a.pairs)]
     finally:
-        layers.USE_HIP_LSTM = True
+        setattr(layers, switch, True)
     _lib.raise_if_nonfinite()
-    print(json.dumps({"model": "mLstm_flipflop", "size": a.size, "chunk_len": a.chunk_len, "chunks": a.chunks,
+    print(json.dumps({"model": a.model, "size": a.size, "chunk_len": a.chunk_len, "chunks": a.chunks,
                       "cus": layers._cu_count(dev), "hip_ms_per_step": [round(t[0], 2) for t in turns],
-                      "nn_lstm_ms_per_step": [round(t[2], 2) for t in turns],
+                      fallback + "_ms_per_step": [round(t[2], 2) for t in turns],
                       "last_loss": [round(turns[-1][1], 4), round(turns[-1][3], 4)],
                       "device": torch.cuda.get_device_name(dev)}))
 
