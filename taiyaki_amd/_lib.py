@@ -29,6 +29,9 @@ BASECALL_LIBNAME = "libtaiyaki_amd_basecall.so"     # csrc/basecall_kernels.hip:
 WGRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_lstm_wgrad.h")
 WGRAD_LIBNAME = "libtaiyaki_amd_lstm_wgrad.so"      # csrc/lstm_wgrad.hip: the LSTM's parameter gradients, header and library of its own
 WGRAD_LAB_LIBNAME = "libtaiyaki_amd_lstm_wgrad_lab.so"      # ... and its lab build (tk_lab_lstm_wgrad_*)
+GRU_WGRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_gru_wgrad.h")
+GRU_WGRAD_LIBNAME = "libtaiyaki_amd_gru_wgrad.so"   # csrc/gru_wgrad.hip: the GRU's parameter gradients, header and library of its own
+GRU_WGRAD_LAB_LIBNAME = "libtaiyaki_amd_gru_wgrad_lab.so"   # ... and its lab build (tk_lab_gru_wgrad_*)
 
 VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
 VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
@@ -103,14 +106,16 @@ def _read_basecall_header():
 BASECALL_SIGNATURES, BASECALL_DEFINES = _read_basecall_header()
 
 
-def _read_wgrad_header():
-    sigs = {n: (r, a) for n, (r, a, _) in parse_prototypes(_blank_comments(open(WGRAD_HEADER).read())).items()}
+def _read_wgrad_header(header=WGRAD_HEADER):
+    sigs = {n: (r, a) for n, (r, a, _) in parse_prototypes(_blank_comments(open(header).read())).items()}
     return ({n: v for n, v in sigs.items() if not n.startswith("tk_lab_")},
             {n: v for n, v in sigs.items() if n.startswith("tk_lab_")})
 
 
 # the fifth: include/taiyaki_amd_lstm_wgrad.h (libtaiyaki_amd_lstm_wgrad.so), and the hooks its lab build adds
 WGRAD_SIGNATURES, WGRAD_LAB_SIGNATURES = _read_wgrad_header()
+# the ninth: include/taiyaki_amd_gru_wgrad.h (libtaiyaki_amd_gru_wgrad.so), and the hooks its lab build adds
+GRU_WGRAD_SIGNATURES, GRU_WGRAD_LAB_SIGNATURES = _read_wgrad_header(GRU_WGRAD_HEADER)
 
 
 def _read_varlen_header():
@@ -221,6 +226,15 @@ def wgrad_lib():
     if is_lab():
         return _load(os.path.join(CSRC, WGRAD_LAB_LIBNAME), dict(WGRAD_SIGNATURES, **WGRAD_LAB_SIGNATURES))
     return _load(os.path.join(CSRC, WGRAD_LIBNAME), WGRAD_SIGNATURES)
+
+
+def gru_wgrad_lib():
+    """The GRU's parameter gradients (include/taiyaki_amd_gru_wgrad.h): the lab build of that library while the
+    process runs on the lab build (`use_lab`), the release one otherwise.  No fallback: a missing library raises."""
+    if is_lab():
+        return _load(os.path.join(CSRC, GRU_WGRAD_LAB_LIBNAME),
+                     dict(GRU_WGRAD_SIGNATURES, **GRU_WGRAD_LAB_SIGNATURES))
+    return _load(os.path.join(CSRC, GRU_WGRAD_LIBNAME), GRU_WGRAD_SIGNATURES)
 
 
 def varlen_lib():

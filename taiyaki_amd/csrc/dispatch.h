@@ -141,6 +141,12 @@ int lstm_wgrad_dispatch(const float *dgates, const float *x, const float *y, siz
                         int reverse, int cu_count, float *dw_ih, float *dw_hh, float *db, void *ws, size_t wsb,
                         hipStream_t stream);
 
+// gru_wgrad.hip (a library of its own too, include/taiyaki_amd_gru_wgrad.h; db_hh may be NULL)
+size_t gru_wgrad_workspace_bytes(size_t T, size_t N, size_t H, size_t I, int cu_count);
+int gru_wgrad_dispatch(const float *dgates, const float *dq, const float *x, const float *y, size_t T, size_t N,
+                       size_t H, size_t I, int reverse, int cu_count, float *dw_ih, float *dw_hh, float *db_ih,
+                       float *db_hh, void *ws, size_t wsb, hipStream_t stream);
+
 // basecall_mods.hip (libtaiyaki_amd_basecall.so; basecall_kernels.hip defines the C entry and fills the column map)
 struct ModColumns {
     uint8_t base[TK_BASECALL_MAX_NMOD];     // the canonical base that output column j belongs to

@@ -1,340 +1,40 @@
 // lstm_wgrad.hip -- the parameter gradients of one LSTM layer, dG^T [x | y shifted | 1], as one split-K GEMM on the
 // bf16 matrix cores, every float32 operand split into three bf16 parts, and one reduction
-// (include/taiyaki_amd_lstm_wgrad.h; libtaiyaki_amd_lstm_wgrad.so).
-//
-// dG (K = T N rows of M = 4H), x (K x I) and y (K x H) are row-major with the summed index as the row.  A block of
-// WG_KB = 16 rows, one k-step of v_mfma_f32_32x32x16_bf16, is staged as it lies in memory, [k][m]: each thread
-// splits its float4s a = a1 + a2 + a3 (a1 = bf16(a), a2 = bf16(a - a1), a3 = bf16(a - a1 - a2), round to nearest even,
-// both differences exact) and writes 8 bytes into each of three bf16 images per operand.  An image row is 128 bf16 =
-// 256 bytes = one LDS bank row, its 16-byte chunk c stored at chunk c ^ ((k & 3) << 2): the four rows that one
-// ds_read_b64_tr_b16 gathers per 16 lanes then lie in four different 64-byte bank groups, so the operand reads (the
-// summed index is the row in both operands, so both are transposed reads, two per 8-element fragment) are
-// conflict-free.  The product is a1 b1 + (a1 b2 + a2 b1 + a2 b2 + a1 b3 + a3 b1): products of bf16 values are exact
-// in float32 and the three dropped terms lie below 2^-26 |a b|.  The first term and the five corrections have an
-// accumulator set each (WG_ACC_SETS), added once per partial result.  A zero splits into three zeros: rows of dG that
-// are 0 add exactly 0.
-// A workgroup of eight waves owns a 128 x 128 output tile (each wave 64 x 32: 2 x 1 accumulators, twice) over one run
-// of rows.  The output's columns are tiled per operand -- x's columns, then y's -- so a tile reads one of the two; a y
-// tile reads y at row k -/+ N (the previous step's h of the same batch element), rows outside [0, K) as zeros.  The
-// workgroups of the first column of tiles add up the columns of the float32 dG block they stage anyway: db.
-// Rows per run are a multiple of WG_KB, so only the last block of all is ragged.  A run longer than WG_CHAIN rows is
-// cut again, inside its workgroup, into partial results of their own: no accumulation chain is longer than that.
-// blockIdx = column tile * rstride + (row tile * runs + run) with rstride a multiple of 8: the workgroups that
-// read the same rows of dG sit on one XCD and share its L2.
-#include "dispatch.h"
+// (include/taiyaki_amd_lstm_wgrad.h; libtaiyaki_amd_lstm_wgrad.so).  The plan, the kernel and the reduction are
+// wgrad_common.h's, shared with gru_wgrad.hip; this file is the LSTM's cell and its entries.
+#include "wgrad_common.h"
 
 #include "../../include/taiyaki_amd_lstm_wgrad.h"
 
 namespace tk {
 namespace {
 
-constexpr int WG_TILE = 128;        // output tile edge
-constexpr int WG_KB = 16;           // rows per staged block
-constexpr int WG_THREADS = 512;     // two waves per SIMD: one wave's split (VALU) runs under the other's MFMAs
-constexpr int WG_SROWS = WG_THREADS / 32;           // rows of a block staged per pass of the workgroup
-constexpr int WG_SPASS = WG_KB / WG_SROWS;          // ... and passes per block
-constexpr int WG_NJ = WG_TILE / 32 / (WG_THREADS / 128);    // 32-column accumulators per wave across (two down)
-constexpr size_t WG_CHAIN = 8192;   // the longest accumulation chain, in rows
-// accumulator sets: 2 = a1 b1 and the five corrections accumulate apart, 1 = in one set.  Measured at the same speed;
-// error against float64 of dW_ih at (T, N, H, I) = (800, 128, 256, 256) 6.3e-7 with two, 1.6e-6 with one (the float32
-// MFMA kernel before: 1.6e-6; rocBLAS: 5.3e-6), and 2.7e-5 against 8.5e-5 on the cancelling input of
-// tests/test_lstm_split_gemm.py
-constexpr int WG_ACC_SETS = 2;
-constexpr int WG_IMAGE = WG_KB * WG_TILE * 2;       // bytes of one bf16 image of a block
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-struct WgradPlan {
-    int tiles_m, tiles_x, tiles_y;  // output tiles down (4H) and across (I, then H)
-    int splits, nsub;               // runs of rows, partial results per run
-    int run_rows, sub_rows;         // rows per run and per partial result (multiples of WG_KB)
-    int rstride, grid;
-    size_t slab_floats, slabs;      // one partial result [4H][I + H] | [4H], and how many there are
+// A is dG (K x 4H) for every tile; the bias sum is db (4H)
+struct LstmCell {
+    static constexpr int GATES = 4;
+    static constexpr bool SEAM = false;
+    static constexpr int EXTRA_BIAS = 0;
+    static constexpr bool VEC4_EDGE = false;    // the two instantiations it has always had
+    typedef WgradArgs Args;
+    typedef float *Bias;
+    static bool takes(size_t) { return true; }
+    static __device__ __forceinline__ void store_bias(float *db, size_t i, float v, int, int) { db[i] = v; }
 };
-
-int g_lab_splits = 0;   // lab build: force the number of runs (0 = the rule below)
-
-size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
-
-// The plan: a function of the shape and the CU count only.  tiles * runs <= cu_count where the tiles alone fit.
-bool wgrad_plan(size_t T, size_t N, size_t H, size_t I, int cu_count, WgradPlan *p) {
-    if (T == 0 || N == 0 || H == 0 || I == 0 || cu_count <= 0) return false;
-    if (H > (1u << 20) || I > (1u << 20) || N > (1u << 28) || T > (size_t(1) << 30) / N) return false;
-    const size_t K = T * N, M = 4 * H, W = I + H;
-    if (M * W + M >= (size_t(1) << 31)) return false;
-    const size_t tm = ceil_div(M, WG_TILE), tx = ceil_div(I, WG_TILE), ty = ceil_div(H, WG_TILE);
-    const size_t tiles = tm * (tx + ty);
-    size_t G = g_lab_splits > 0 ? (size_t)g_lab_splits : (size_t)cu_count / tiles;
-    if (G < 1) G = 1;
-    const size_t run = ceil_div(ceil_div(K, G), WG_KB) * WG_KB;
-    G = ceil_div(K, run);           // (no empty runs)
-    const size_t nsub = ceil_div(run, WG_CHAIN);
-    const size_t sub = ceil_div(ceil_div(run, nsub), WG_KB) * WG_KB;
-    const size_t rstride = ceil_div(tm * G, 8) * 8;
-    if (rstride * (tx + ty) >= (size_t(1) << 31)) return false;
-    p->tiles_m = (int)tm, p->tiles_x = (int)tx, p->tiles_y = (int)ty;
-    p->splits = (int)G, p->nsub = (int)nsub, p->run_rows = (int)run, p->sub_rows = (int)sub;
-    p->rstride = (int)rstride, p->grid = (int)(rstride * (tx + ty));
-    p->slab_floats = (M * W + M + 3) / 4 * 4;
-    p->slabs = G * nsub;
-    return true;
-}
-
-struct WgradArgs {
-    const float *dg, *x, *y;
-    float *ws;
-    int K, N, M, I, H, reverse;
-    int tiles_m, tiles_x, splits, nsub, run_rows, sub_rows, rstride;
-    size_t slab_floats;
-};
-
-// four floats of row `row` from column `col` on.  FAST (every tile lies inside its matrix and takes 16-byte loads) is
-// one unconditional load, of row 0 where the row is not there: the caller zeroes it when it stages the value, so
-// nothing branches or waits for memory before the block's MFMAs.  Otherwise zeros where the row is not there or the
-// column is past the edge.
-template <bool FAST>
-__device__ __forceinline__ float4 load4(const float *src, int ld, int row, bool row_ok, int col) {
-    if (FAST) return *reinterpret_cast<const float4 *>(src + (size_t)(row_ok ? row : 0) * (size_t)ld + col);
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (row_ok) {
-        const float *p = src + (size_t)row * (size_t)ld + col;
-        if (col < ld) v.x = p[0];
-        if (col + 1 < ld) v.y = p[1];
-        if (col + 2 < ld) v.z = p[2];
-        if (col + 3 < ld) v.w = p[3];
-    }
-    return v;
-}
-
-// two floats -> their three bf16 parts, the first float's in the low halves (v_cvt_pk_bf16_f32; bf16 -> float is a shift)
-__device__ __forceinline__ void split2(float u, float v, uint32_t &p1, uint32_t &p2, uint32_t &p3) {
-    p1 = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{u, v}, bf16x2));
-    u -= __uint_as_float(p1 << 16), v -= __uint_as_float(p1 & 0xffff0000u);
-    p2 = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{u, v}, bf16x2));
-    u -= __uint_as_float(p2 << 16), v -= __uint_as_float(p2 & 0xffff0000u);
-    p3 = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{u, v}, bf16x2));
-}
-
-// the three parts of four floats into the three images of one operand, 8 bytes each
-__device__ __forceinline__ void stage4(unsigned char *img, float4 v) {
-    uint2 p1, p2, p3;
-    split2(v.x, v.y, p1.x, p2.x, p3.x);
-    split2(v.z, v.w, p1.y, p2.y, p3.y);
-    *reinterpret_cast<uint2 *>(img) = p1;
-    *reinterpret_cast<uint2 *>(img + WG_IMAGE) = p2;
-    *reinterpret_cast<uint2 *>(img + 2 * WG_IMAGE) = p3;
-}
-
-// rows 8 (lane >> 5) ... + 7 of 32 columns of an image as one operand fragment: `at` is the lane's address for the
-// first four rows (lstm_wgrad_kernel), the next four are 4 image rows on
-__device__ __forceinline__ bf16x8 frag(const unsigned char *at) {
-    typedef bf16x4 __attribute__((address_space(3))) * lds_ptr;
-    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)at);
-    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_ptr)(at + 4 * WG_TILE * 2));
-    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-template <bool FAST>
-__global__ __launch_bounds__(WG_THREADS) void lstm_wgrad_kernel(const WgradArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned char img[2][2][3][WG_IMAGE];    // [buffer][dG, x / y][part]
-    __shared__ __attribute__((aligned(16))) float colsum[WG_THREADS / 32][WG_TILE];
-
-    const int tnx = blockIdx.x / a.rstride, q = blockIdx.x % a.rstride;
-    if (q >= a.tiles_m * a.splits) return;      // (the padding of rstride)
-    const int run = q % a.splits, tmx = q / a.splits;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, lhalf = lane >> 5;
-    const int wm = (wave / (WG_THREADS / 128)) * 64, wn = (wave % (WG_THREADS / 128)) * 32 * WG_NJ;
-    const int c4 = (tid & 31) * 4, r0 = tid >> 5;       // staging: this thread's four columns and first row of a block
-    // ... and where they go in an image: chunk c4 / 8 of row r0, swizzled; rows r0 and r0 + 8 swizzle alike
-    const int woff = 256 * r0 + 16 * (((tid & 31) >> 1) ^ ((r0 & 3) << 2)) + 8 * (tid & 1);
-    // the transposed read: lane 4 tq + tp of each 16 gives the address of row tq, columns 4 tp ... + 3 of its block of
-    // 4 rows x 16 columns; the wave's four blocks are columns 0-15 / 16-31 of rows 8 lhalf ... + 3
-    const int tq = (lane >> 2) & 3, tp = lane & 3;
-    int aoff[2], boff[WG_NJ];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = 256 * (8 * lhalf + tq) + 8 * (tp & 1), chunk = 4 * i + 2 * ((lane >> 4) & 1) + (tp >> 1);
-        aoff[i] = row + 16 * ((wm / 8 + chunk) ^ (tq << 2));
-        if (i < WG_NJ) boff[i] = row + 16 * ((wn / 8 + chunk) ^ (tq << 2));
-    }
-
-    const bool is_x = tnx < a.tiles_x;
-    const float *bsrc = is_x ? a.x : a.y;
-    const int bld = is_x ? a.I : a.H;
-    const int bcol0 = (is_x ? tnx : tnx - a.tiles_x) * WG_TILE;
-    const int shift = is_x ? 0 : (a.reverse ? a.N : -a.N);
-    const int out_col0 = is_x ? bcol0 : a.I + bcol0;
-    const int W = a.I + a.H;
-    const bool sum_cols = tnx == 0;
-    const int acol = tmx * WG_TILE + c4, bcol = bcol0 + c4;
-
-    const int run_begin = run * a.run_rows;
-    const int run_end = min(run_begin + a.run_rows, a.K);
-
-    for (int sub = 0; sub < a.nsub; ++sub) {
-        const int k0 = run_begin + sub * a.sub_rows;
-        const int k1 = min(k0 + a.sub_rows, run_end);
-        const int nkb = k1 > k0 ? (k1 - k0 + WG_KB - 1) / WG_KB : 0;
-
-        f32x16 acc[WG_ACC_SETS][2][WG_NJ];
-#pragma unroll
-        for (int s = 0; s < WG_ACC_SETS; ++s)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < WG_NJ; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[s][i][j][r] = 0.f;
-        float4 dbacc = make_float4(0.f, 0.f, 0.f, 0.f);
-        // two blocks are in flight from memory: block kb + 2 is requested before the MFMAs of block kb, block kb + 1
-        // is split and written to LDS after them
-        float4 ra[2][WG_SPASS], rb[2][WG_SPASS];
-        bool oka[2][WG_SPASS], okb[2][WG_SPASS];
-
-        auto fetch = [&](int kb, int set) {
-#pragma unroll
-            for (int j = 0; j < WG_SPASS; ++j) {
-                const int k = k0 + kb * WG_KB + r0 + WG_SROWS * j;
-                const int kk = k + shift;
-                oka[set][j] = k < k1, okb[set][j] = oka[set][j] && kk >= 0 && kk < a.K;
-                ra[set][j] = load4<FAST>(a.dg, a.M, k, oka[set][j], acol);
-                rb[set][j] = load4<FAST>(bsrc, bld, kk, okb[set][j], bcol);
-            }
-        };
-        auto stash = [&](int set, int buf) {
-#pragma unroll
-            for (int j = 0; j < WG_SPASS; ++j) {
-                float4 va = ra[set][j], vb = rb[set][j];
-                if (!oka[set][j]) va = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (!okb[set][j]) vb = make_float4(0.f, 0.f, 0.f, 0.f);
-                stage4(&img[buf][0][0][woff + 256 * WG_SROWS * j], va);
-                stage4(&img[buf][1][0][woff + 256 * WG_SROWS * j], vb);
-                dbacc.x += va.x, dbacc.y += va.y, dbacc.z += va.z, dbacc.w += va.w;     // (used where sum_cols)
-            }
-        };
-
-        // no branch inside the loop: a block past the end is fetched as zeros (row 0 where the loads are unguarded)
-        // and adds nothing, so the blocks go in pairs and every fetch and stash is unconditional
-        fetch(0, 0);
-        fetch(1, 1);
-        stash(0, 0);
-        __syncthreads();
-        for (int kb2 = 0; kb2 < nkb; kb2 += 2) {
-#pragma unroll
-            for (int cur = 0; cur < 2; ++cur) {     // block kb is in LDS buffer kb & 1 and came through register set kb & 1
-                const int kb = kb2 + cur;
-                fetch(kb + 2, cur);
-                bf16x8 fa[2][3], fb[WG_NJ][3];
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) {
-                        fa[i][p] = frag(&img[cur][0][p][aoff[i]]);
-                        if (i < WG_NJ) fb[i][p] = frag(&img[cur][1][p][boff[i]]);
-                    }
-                // a1 b1, then the corrections, the smallest first
-                constexpr int PA[6] = {0, 2, 0, 1, 1, 0}, PB[6] = {0, 0, 2, 1, 0, 1};
-#pragma unroll
-                for (int t = 0; t < 6; ++t) {
-                    const int s = t > 0 ? WG_ACC_SETS - 1 : 0;
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int j = 0; j < WG_NJ; ++j)
-                            acc[s][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][PA[t]], fb[j][PB[t]],
-                                                                                    acc[s][i][j], 0, 0, 0);
-                }
-                stash(cur ^ 1, cur ^ 1);    // (its last readers passed the barrier of block kb - 1)
-                __syncthreads();
-            }
-        }
-
-        // this partial result: C[m][n] of accumulator register r sits at row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31
-        float *slab = a.ws + (size_t)(run * a.nsub + sub) * a.slab_floats;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < WG_NJ; ++j) {
-                const int n = wn + 32 * j + l31;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = tmx * WG_TILE + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
-                    const float v = WG_ACC_SETS == 2 ? acc[0][i][j][r] + acc[WG_ACC_SETS - 1][i][j][r] : acc[0][i][j][r];
-                    if (m < a.M && bcol0 + n < bld) slab[(size_t)m * W + out_col0 + n] = v;
-                }
-            }
-        if (sum_cols) {
-            *reinterpret_cast<float4 *>(&colsum[r0][c4]) = dbacc;
-            __syncthreads();
-            if (tid < WG_TILE) {
-                float v = colsum[0][tid];
-#pragma unroll
-                for (int r = 1; r < WG_THREADS / 32; ++r) v += colsum[r][tid];
-                const int m = tmx * WG_TILE + tid;
-                if (m < a.M) slab[(size_t)a.M * W + m] = v;
-            }
-        }
-    }
-}
-
-// dw_ih | dw_hh | db = the partial results added in their order
-__global__ __launch_bounds__(256) void lstm_wgrad_reduce_kernel(const float *ws, size_t slab_floats, int slabs, int M,
-                                                                int I, int H, int zero_hh, float *dw_ih, float *dw_hh,
-                                                                float *db) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t W = (size_t)I + H, MW = (size_t)M * W;
-    if (idx >= MW + M) return;
-    float v = ws[idx];
-#pragma unroll 4
-    for (int p = 1; p < slabs; ++p) v += ws[(size_t)p * slab_floats + idx];
-    if (idx >= MW) {
-        db[idx - MW] = v;
-        return;
-    }
-    const size_t m = idx / W, c = idx % W;
-    if (c < (size_t)I)
-        dw_ih[m * I + c] = v;
-    else
-        dw_hh[m * H + (c - I)] = zero_hh ? 0.f : v;
-}
 
 }  // namespace
 
 size_t lstm_wgrad_workspace_bytes(size_t T, size_t N, size_t H, size_t I, int cu_count) {
-    WgradPlan p;
-    if (!wgrad_plan(T, N, H, I, cu_count, &p)) return 0;
-    return p.slabs * p.slab_floats * sizeof(float);
+    return wgrad_workspace_bytes<LstmCell>(T, N, H, I, cu_count);
 }
 
 int lstm_wgrad_dispatch(const float *dgates, const float *x, const float *y, size_t T, size_t N, size_t H, size_t I,
                         int reverse, int cu_count, float *dw_ih, float *dw_hh, float *db, void *ws, size_t wsb,
                         hipStream_t stream) {
     if (!dgates || !x || !y || !dw_ih || !dw_hh || !db || !ws || !aligned16(ws)) return TK_ERR_BAD_ARG;
-    WgradPlan p;
-    if (!wgrad_plan(T, N, H, I, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    if (wsb < p.slabs * p.slab_floats * sizeof(float)) return TK_ERR_WORKSPACE;
     WgradArgs a;
-    a.dg = dgates, a.x = x, a.y = y, a.ws = static_cast<float *>(ws);
-    a.K = (int)(T * N), a.N = (int)N, a.M = (int)(4 * H), a.I = (int)I, a.H = (int)H, a.reverse = reverse != 0;
-    a.tiles_m = p.tiles_m, a.tiles_x = p.tiles_x, a.splits = p.splits, a.nsub = p.nsub;
-    a.run_rows = p.run_rows, a.sub_rows = p.sub_rows, a.rstride = p.rstride;
-    a.slab_floats = p.slab_floats;
-    // whole tiles and 16-byte loads everywhere, or the guarded loads
-    if (aligned16(dgates) && aligned16(x) && aligned16(y) && H % WG_TILE == 0 && I % WG_TILE == 0)
-        hipLaunchKernelGGL(lstm_wgrad_kernel<true>, dim3(p.grid), dim3(WG_THREADS), 0, stream, a);
-    else
-        hipLaunchKernelGGL(lstm_wgrad_kernel<false>, dim3(p.grid), dim3(WG_THREADS), 0, stream, a);
-    if (hipGetLastError() != hipSuccess) return TK_ERR_LAUNCH;
-    const size_t total = (size_t)a.M * (I + H) + a.M;
-    hipLaunchKernelGGL(lstm_wgrad_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,
-                       static_cast<const float *>(ws), p.slab_floats, (int)p.slabs, a.M, a.I, a.H, T == 1 ? 1 : 0,
-                       dw_ih, dw_hh, db);
-    return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
+    a.dg = dgates, a.x = x, a.y = y;
+    return wgrad_launch<LstmCell>(a, aligned16(dgates) && aligned16(x) && aligned16(y), T, N, H, I, reverse, cu_count,
+                                  dw_ih, dw_hh, db, ws, wsb, stream);
 }
 
 }  // namespace tk
@@ -356,12 +56,7 @@ int tk_lstm_weight_grad_dev(const float *dgates, const float *x, const float *y,
 void tk_lab_lstm_wgrad_splits(int splits) { tk::g_lab_splits = splits; }
 
 int tk_lab_lstm_wgrad_plan(size_t nblk, size_t nbatch, size_t size, size_t insize, int cu_count, size_t *out) {
-    tk::WgradPlan p;
-    if (!tk::wgrad_plan(nblk, nbatch, size, insize, cu_count, &p)) return 0;
-    const size_t v[8] = {(size_t)p.tiles_m, (size_t)(p.tiles_x + p.tiles_y), (size_t)p.splits, (size_t)p.nsub,
-                         (size_t)p.run_rows, (size_t)p.sub_rows, (size_t)p.grid, p.slabs};
-    for (int i = 0; i < 8; ++i) out[i] = v[i];
-    return 1;
+    return tk::wgrad_lab_plan<tk::LstmCell>(nblk, nbatch, size, insize, cu_count, out);
 }
 #endif
 

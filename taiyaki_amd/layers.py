@@ -434,13 +434,22 @@ def _time_sum_tn(a, b, rows=2048):
 gru_forward_calls = {"saved": 0, "inference": 0}
 
 
+# False: the parameter gradients of GruRecurrence.backward are the batched GEMMs and sums of `_gru_grads_from_dgates`
+# (what they are wherever tk_gru_weight_grad_workspace_bytes is 0), for comparisons against the fused kernel
+USE_HIP_GRU_WGRAD = True
+# calls of `_gru_grads_from_dgates` that wanted parameter gradients, by what computed them: tk_gru_weight_grad_dev or
+# the GEMMs
+gru_wgrad_calls = {"kernel": 0, "gemm": 0}
+
+
 class GruRecurrence(torch.autograd.Function):
     """One nn.GRU layer (h0 = 0) with its recurrence on the HIP kernels.  Forward: G_x = x W_ih^T + b_ih as one
     GEMM, then tk_gru_forward_dev (b_hh goes to the kernel: its third slab sits inside the reset gate's product).
     `save` False (GruMod.forward: grad mode off, or nothing that requires a gradient) hands NULL for the activations:
     they are neither allocated nor written, and the call cannot be differentiated.  Backward: tk_gru_backward_dev gives
     dG = dL/dG_x (T x N x 3H) and dq; the hidden side's pre-activation gradient is dG with dq as its third slab,
-    and the parameter and input gradients are GEMMs / sums over the two.  `reverse` runs the recurrence from the
+    and the input gradient is a GEMM over dG, the parameter gradients one fused pass over the two
+    (`_gru_grads_from_dgates`).  `reverse` runs the recurrence from the
     last time step (layers.Reverse) on tensors in time order.
     `lens` (a device int32 tensor, one entry per column): column n has lens[n] steps, and the launches are those of
     include/taiyaki_amd_rnn_varlen_train.h (`save`) or include/taiyaki_amd_rnn_varlen.h (not `save`).  y, the
@@ -487,11 +496,35 @@ class GruRecurrence(torch.autograd.Function):
 def _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, reverse, need):
     """(dx, dW_ih, dW_hh, db_ih, db_hh) of one GRU layer from dG = dL/dG_x (T, N, 3H) and dq (T, N, H), its input x and
     its output y; need[0..4]: which of them are wanted.  With per-column lengths dG, dq and y are 0 beyond every length,
-    so the same sums over the whole padded tensors are the sums over every column's own steps (x finite in the padding)."""
+    so the same sums over the whole padded tensors are the sums over every column's own steps (x finite in the padding).
+    The parameter gradients are one call of tk_gru_weight_grad_dev (include/taiyaki_amd_gru_wgrad.h) where both weight
+    gradients and a bias gradient are wanted, the tensors are float32 on the GPU and the call has a workspace at the
+    shape -- at every shape it was measured at it is faster than the GEMMs below (profiles/r30_gru_wgrad.txt), so no
+    shape is excluded here -- and the GEMMs, sums and cats below otherwise (USE_HIP_GRU_WGRAD = False: always)."""
     T, N, I = x.shape
     H = w_hh.shape[1]
     dg2 = dg.view(T * N, 3 * H)
     dx = (dg2 @ w_ih).view(T, N, I) if need[0] else None
+    if (USE_HIP_GRU_WGRAD and need[1] and need[2] and (need[3] or need[4]) and dg.is_cuda
+            and all(t.dtype == torch.float32 for t in (dg, dq, x, y, w_ih, w_hh))):
+        # the four parameter gradients in one pass: [dG | dq]^T [x | y shifted by a step | 1]
+        dev = x.device
+        W = _lib.gru_wgrad_lib()
+        wgb = W.tk_gru_weight_grad_workspace_bytes(T, N, H, I, _cu_count(dev))
+        if wgb:
+            dg, dq, x, y = dg.contiguous(), dq.contiguous(), x.contiguous(), y.contiguous()
+            dw_ih, dw_hh = torch.empty_like(w_ih, memory_format=torch.contiguous_format), torch.empty_like(w_hh)
+            db_ih = torch.empty(3 * H, dtype=torch.float32, device=dev)
+            db_hh = torch.empty(3 * H, dtype=torch.float32, device=dev) if need[4] else None
+            wws = _lib.workspace(wgb, dev, "gru_wgrad")
+            rc = W.tk_gru_weight_grad_dev(_lib.ptr(dg), _lib.ptr(dq), _lib.ptr(x), _lib.ptr(y), T, N, H, I,
+                                          int(reverse), _cu_count(dev), _lib.ptr(dw_ih), _lib.ptr(dw_hh),
+                                          _lib.ptr(db_ih), _lib.ptr(db_hh), _lib.ptr(wws), wgb, _lib.stream_ptr())
+            _lib.check(rc, "tk_gru_weight_grad_dev")
+            gru_wgrad_calls["kernel"] += 1
+            return dx, dw_ih, dw_hh, db_ih if need[3] else None, db_hh
+    if any(need[1:5]):
+        gru_wgrad_calls["gemm"] += 1
     dw_ih = _time_sum_tn(dg, x) if need[1] else None
     dw_hh = None
     if need[2]:

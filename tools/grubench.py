@@ -2,10 +2,13 @@
 """Times one layer's GRU recurrence (csrc/gru_kernels.hip) on the GPU: tk_gru_forward_dev and tk_gru_backward_dev
 at (T, N, H), each timed with device events after warm-up; prints one JSON line (microseconds per timestep and
 direction, median and min over --steps).  bench.py --config 1's layer is the default shape; the other shape on
-record is --T 800 --N 128 --H 256.
+record is --T 800 --N 128 --H 256.  The weight-gradient leg follows: `wgrad_ms` is tk_gru_weight_grad_dev
+(csrc/gru_wgrad.hip) at (T, N, H, I = H) on that dG, dq and y, `wgrad_gemm_ms` the lines of
+layers._gru_grads_from_dgates that it replaces (the batched GEMMs, the sums and the two cats), `--wgrad-turns` times
+in turns; `wgrad_vs_gemm_maxrel` is the largest difference between the two relative to a result's largest entry.
 
     python tools/grubench.py [--T 1000] [--N 64] [--H 96] [--steps 20] [--warmup 3] [--reverse] [--infer] [--varlen] [--cols C]
-                             [--fallback PAIRS]
+                             [--fallback PAIRS] [--wgrad-turns 3]
 
 --cols (lab build) forces the batch columns per workgroup at H <= 128; without it the release library is timed.
 
@@ -90,6 +93,7 @@ def main():
     ap.add_argument("--infer", action="store_true", help="also time the forward that saves nothing (gates = q = NULL)")
     ap.add_argument("--varlen", action="store_true", help="also time the forward with per-column lengths, all = T")
     ap.add_argument("--cols", type=int, default=None, help="(lab build) batch columns per workgroup at H <= 128")
+    ap.add_argument("--wgrad-turns", type=int, default=3, help="turns of the weight-gradient leg, kernel then GEMMs")
     ap.add_argument("--fallback", type=int, default=0, metavar="PAIRS",
                     help="also time layers.GruMod(H, H) forward and backward, HIP and nn.GRU in turns, PAIRS times")
     a = ap.parse_args()
@@ -180,6 +184,35 @@ def main():
                    train_turns_us_per_step={k: [round(1e3 * t[k] / T, 3) for t in tt] for k in legs})
     f_med, f_min = timed(fwd, a.steps, a.warmup)
     b_med, b_min = timed(bwd, a.steps, a.warmup)
+
+    # the parameter gradients from that dG, dq and y and an input of the layer's size
+    W = _lib.gru_wgrad_lib()
+    wgb = W.tk_gru_weight_grad_workspace_bytes(T, N, H, H, cus)
+    if wgb == 0:
+        raise SystemExit("(T, N, H, I) = (%d, %d, %d, %d) has no weight-gradient plan on %d CUs" % (T, N, H, H, cus))
+    x_in = torch.randn(T, N, H, generator=g).to(dev)
+    wws = torch.empty(wgb // 4, dtype=torch.float32, device=dev)
+    res = [torch.empty(3 * H, H, device=dev), torch.empty(3 * H, H, device=dev), torch.empty(3 * H, device=dev),
+           torch.empty(3 * H, device=dev)]
+
+    def wgrad():
+        _lib.check(W.tk_gru_weight_grad_dev(_lib.ptr(dg), _lib.ptr(dq), _lib.ptr(x_in), _lib.ptr(y), T, N, H, H,
+                                            int(a.reverse), cus, *[_lib.ptr(t) for t in res], _lib.ptr(wws), wgb,
+                                            stream), "tk_gru_weight_grad_dev")
+
+    def wgrad_gemm():
+        dw_ih = layers._time_sum_tn(dg, x_in)
+        sl, hp = (slice(0, T - 1), y[1:]) if a.reverse else (slice(1, T), y[:-1])
+        dw_hh = torch.cat([layers._time_sum_tn(dg[sl][:, :, :2 * H], hp), layers._time_sum_tn(dq[sl], hp)])
+        db_ih = dg.view(T * N, 3 * H).sum(0)
+        return dw_ih, dw_hh, db_ih, torch.cat([db_ih[:2 * H], dq.view(T * N, H).sum(0)])
+
+    turns = [timed(wgrad, a.steps, a.warmup) + timed(wgrad_gemm, a.steps, a.warmup) for _ in range(a.wgrad_turns)]
+    ref = wgrad_gemm()
+    wgrad_diff = max(((p - r).abs().max() / r.abs().max()).item() for p, r in zip(res, ref))
+    out.update(wgrad_ms=[round(t[0], 4) for t in turns], wgrad_min_ms=[round(t[1], 4) for t in turns],
+               wgrad_gemm_ms=[round(t[2], 4) for t in turns], wgrad_gemm_min_ms=[round(t[3], 4) for t in turns],
+               wgrad_vs_gemm_maxrel=wgrad_diff)
     _lib.finish(status)
     _lib.raise_if_nonfinite()
     out.update(fwd_ms=round(f_med, 3), bwd_ms=round(b_med, 3), fwd_us_per_step=round(1e3 * f_med / T, 3),

@@ -3,9 +3,12 @@
 own default) with the recurrent layers on the HIP recurrence and on nn.LSTM / nn.GRU (layers.USE_HIP_LSTM / USE_HIP_GRU =
 False: what a size the kernels refuse runs), in turns on one model and one batch; prints one JSON line, milliseconds per
 step (median over --steps per turn).  Both models are built with the trainer's stride, 5: chunk_len 4000 is T = 800.
+--switch NAME flips that switch of `layers` instead (USE_HIP_GRU_WGRAD, USE_HIP_LSTM_WGRAD: the fused weight-gradient
+kernel against the GEMMs, the recurrence on the HIP kernels in both turns); the lists are then `on_ms_per_step` and
+`off_ms_per_step`.
 
     python tools/sizebench.py [--model mLstm_flipflop] [--size 384] [--chunk-len 4000] [--chunks 128] [--pairs 3]
-                              [--steps 5] [--warmup 2]
+                              [--steps 5] [--warmup 2] [--switch NAME]
 """
 import argparse
 import json
@@ -28,6 +31,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--switch", default=None, help="the switch of `layers` to flip (default: the recurrence's)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sizebench needs a GPU")
@@ -36,6 +40,10 @@ def main():
     torch.manual_seed(0)
     gru = a.model == "mGru_flipflop"
     switch, fallback = ("USE_HIP_GRU", "nn_gru") if gru else ("USE_HIP_LSTM", "nn_lstm")
+    if a.switch:
+        if not isinstance(getattr(layers, a.switch, None), bool):
+            raise SystemExit("layers has no switch %s" % a.switch)
+        switch, fallback = a.switch, "off"
     net = getattr(models, a.model)(size=a.size, stride=stride).to(dev)
     probe = torch.zeros(a.chunk_len // stride, a.chunks, a.size, device=dev)
     rnns = [m for m in net.modules() if isinstance(m, layers.GruMod if gru else layers.Lstm)]
@@ -68,7 +76,7 @@ def main():
         setattr(layers, switch, True)
     _lib.raise_if_nonfinite()
     print(json.dumps({"model": a.model, "size": a.size, "chunk_len": a.chunk_len, "chunks": a.chunks,
-                      "cus": layers._cu_count(dev), "hip_ms_per_step": [round(t[0], 2) for t in turns],
+                      "cus": layers._cu_count(dev), ("on" if a.switch else "hip") + "_ms_per_step": [round(t[0], 2) for t in turns],
                       fallback + "_ms_per_step": [round(t[2], 2) for t in turns],
                       "last_loss": [round(turns[-1][1], 4), round(turns[-1][3], 4)],
                       "device": torch.cuda.get_device_name(dev)}))
