@@ -32,6 +32,9 @@ WGRAD_LAB_LIBNAME = "libtaiyaki_amd_lstm_wgrad_lab.so"      # ... and its lab bu
 GRU_WGRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_gru_wgrad.h")
 GRU_WGRAD_LIBNAME = "libtaiyaki_amd_gru_wgrad.so"   # csrc/gru_wgrad.hip: the GRU's parameter gradients, header and library of its own
 GRU_WGRAD_LAB_LIBNAME = "libtaiyaki_amd_gru_wgrad_lab.so"   # ... and its lab build (tk_lab_gru_wgrad_*)
+RNN_PROJ_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_proj.h")
+RNN_PROJ_LIBNAME = "libtaiyaki_amd_rnn_proj.so"     # csrc/rnn_proj.hip: the recurrent layers' projection GEMMs, header and library of its own
+RNN_PROJ_LAB_LIBNAME = "libtaiyaki_amd_rnn_proj_lab.so"     # ... and its lab build (tk_lab_rnn_proj_plan)
 
 VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
 VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
@@ -116,6 +119,8 @@ def _read_wgrad_header(header=WGRAD_HEADER):
 WGRAD_SIGNATURES, WGRAD_LAB_SIGNATURES = _read_wgrad_header()
 # the ninth: include/taiyaki_amd_gru_wgrad.h (libtaiyaki_amd_gru_wgrad.so), and the hooks its lab build adds
 GRU_WGRAD_SIGNATURES, GRU_WGRAD_LAB_SIGNATURES = _read_wgrad_header(GRU_WGRAD_HEADER)
+# the tenth: include/taiyaki_amd_rnn_proj.h (libtaiyaki_amd_rnn_proj.so), and the hook its lab build adds
+RNN_PROJ_SIGNATURES, RNN_PROJ_LAB_SIGNATURES = _read_wgrad_header(RNN_PROJ_HEADER)
 
 
 def _read_varlen_header():
@@ -235,6 +240,15 @@ def gru_wgrad_lib():
         return _load(os.path.join(CSRC, GRU_WGRAD_LAB_LIBNAME),
                      dict(GRU_WGRAD_SIGNATURES, **GRU_WGRAD_LAB_SIGNATURES))
     return _load(os.path.join(CSRC, GRU_WGRAD_LIBNAME), GRU_WGRAD_SIGNATURES)
+
+
+def rnn_proj_lib():
+    """The recurrent layers' projection GEMMs (include/taiyaki_amd_rnn_proj.h): the lab build of that library while the
+    process runs on the lab build (`use_lab`), the release one otherwise.  No fallback: a missing library raises."""
+    if is_lab():
+        return _load(os.path.join(CSRC, RNN_PROJ_LAB_LIBNAME),
+                     dict(RNN_PROJ_SIGNATURES, **RNN_PROJ_LAB_SIGNATURES))
+    return _load(os.path.join(CSRC, RNN_PROJ_LIBNAME), RNN_PROJ_SIGNATURES)
 
 
 def varlen_lib():

@@ -147,6 +147,12 @@ int gru_wgrad_dispatch(const float *dgates, const float *dq, const float *x, con
                        size_t H, size_t I, int reverse, int cu_count, float *dw_ih, float *dw_hh, float *db_ih,
                        float *db_hh, void *ws, size_t wsb, hipStream_t stream);
 
+// rnn_proj.hip (a library of its own too, include/taiyaki_amd_rnn_proj.h): out (rows, nout) = a (rows, k) B^T + bias, B
+// (nout, k) = w, or for transposed != 0 the transpose of w (k, nout); bias may be NULL
+size_t rnn_proj_workspace_bytes(size_t rows, size_t k, size_t nout, int cu_count);
+int rnn_proj_dispatch(const float *a, const float *w, const float *bias, int transposed, size_t rows, size_t k,
+                      size_t nout, int cu_count, float *out, void *ws, size_t wsb, hipStream_t stream);
+
 // basecall_mods.hip (libtaiyaki_amd_basecall.so; basecall_kernels.hip defines the C entry and fills the column map)
 struct ModColumns {
     uint8_t base[TK_BASECALL_MAX_NMOD];     // the canonical base that output column j belongs to

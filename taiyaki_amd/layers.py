@@ -251,6 +251,43 @@ rnn_varlen_calls = {"saved": 0, "inference": 0}
 # False: the parameter gradients of LstmRecurrence.backward are two GEMMs and a sum over dG (what they are wherever
 # tk_lstm_weight_grad_workspace_bytes is 0), for comparisons against the fused kernel
 USE_HIP_LSTM_WGRAD = True
+# True: the input projection x W_ih^T + b in front of a recurrence and the input gradient dG W_ih behind it run as
+# tk_rnn_input_proj_dev / tk_rnn_input_grad_dev (include/taiyaki_amd_rnn_proj.h) wherever tk_rnn_proj_workspace_bytes is
+# not 0.  That rule is the library's (csrc/rnn_proj.hip, proj_admitted: the shapes at which the kernel was measured faster
+# than rocBLAS, profiles/r31_lstmbench.txt, profiles/r31_grubench.txt): for the forward projection a function of the two
+# widths only, never of the number of rows, so training, inference and the variable-length paths of a layer all take the
+# same projection; the input gradient, which only training computes, also needs 64000 rows.
+# False: torch.addmm / `@` (rocBLAS), for comparisons against the kernel
+USE_HIP_RNN_PROJ = True
+# The workspace handed to those calls: one size for every shape (the widest pair of widths the rule admits needs 3.4 MiB),
+# so the cached buffer is allocated once per stream and never regrown or returned to the allocator in pieces
+_RNN_PROJ_WORKSPACE_BYTES = 4 << 20
+
+
+def _rnn_proj(a2, w_ih, bias, grad):
+    """The input projection a2 (rows, I) . w_ih^T + bias (grad False) or the input gradient a2 (rows, G H) . w_ih (grad
+    True) of a recurrent layer: the kernel of include/taiyaki_amd_rnn_proj.h where it runs, the rocBLAS GEMM otherwise."""
+    rows, k = a2.shape
+    nout = w_ih.shape[1] if grad else w_ih.shape[0]
+    dev = a2.device
+    if (USE_HIP_RNN_PROJ and a2.is_cuda and a2.dtype == torch.float32 and w_ih.dtype == torch.float32
+            and a2.is_contiguous()):
+        P = _lib.rnn_proj_lib()
+        wsb = P.tk_rnn_proj_workspace_bytes(rows, k, nout, _cu_count(dev))
+        if wsb:
+            w = w_ih.contiguous()
+            out = torch.empty(rows, nout, dtype=torch.float32, device=dev)
+            wsb = max(wsb, _RNN_PROJ_WORKSPACE_BYTES)
+            ws = _lib.workspace(wsb, dev, "rnn_proj")
+            if grad:
+                rc = P.tk_rnn_input_grad_dev(_lib.ptr(a2), _lib.ptr(w), rows, nout, k, _cu_count(dev), _lib.ptr(out),
+                                             _lib.ptr(ws), wsb, _lib.stream_ptr())
+            else:
+                rc = P.tk_rnn_input_proj_dev(_lib.ptr(a2), _lib.ptr(w), _lib.ptr(bias.contiguous()), rows, k, nout,
+                                             _cu_count(dev), _lib.ptr(out), _lib.ptr(ws), wsb, _lib.stream_ptr())
+            _lib.check(rc, "tk_rnn_input_grad_dev" if grad else "tk_rnn_input_proj_dev")
+            return out
+    return a2 @ w_ih if grad else torch.addmm(bias, a2, w_ih.t())
 
 
 def hip_lstm_workspace_bytes(rnn, x):
@@ -315,7 +352,7 @@ class LstmRecurrence(torch.autograd.Function):
         w_hh = w_hh.contiguous()
         if lens is not None:
             rnn_varlen_calls["saved" if save else "inference"] += 1
-        gx = torch.addmm(b_ih + b_hh, x.view(T * N, -1), w_ih.t())
+        gx = _rnn_proj(x.view(T * N, -1), w_ih, b_ih + b_hh, False)
         y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
         gates = torch.empty(T, N, 4 * H, dtype=torch.float32, device=dev) if save else None
         cell = torch.empty(T, N, H, dtype=torch.float32, device=dev) if save else None
@@ -345,7 +382,7 @@ def _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, reverse, need):
     H = w_hh.shape[1]
     dev = x.device
     dg2 = dg.view(T * N, 4 * H)
-    dx = (dg2 @ w_ih).view(T, N, I) if need[0] else None
+    dx = _rnn_proj(dg2, w_ih, None, True).view(T, N, I) if need[0] else None
     if USE_HIP_LSTM_WGRAD and need[1] and need[2] and (need[3] or need[4]):
         # the three parameter gradients in one pass over dG: dG^T [x | y shifted by a step | 1]
         W = _lib.wgrad_lib()
@@ -469,7 +506,7 @@ class GruRecurrence(torch.autograd.Function):
             rnn_varlen_calls["saved" if train else "inference"] += 1
         if lens is None or train:
             gru_forward_calls["saved" if train else "inference"] += 1
-        gx = torch.addmm(b_ih, x.view(T * N, -1), w_ih.t())
+        gx = _rnn_proj(x.view(T * N, -1), w_ih, b_ih, False)
         y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
         gates = torch.empty(T, N, 3 * H, dtype=torch.float32, device=dev) if train else None
         q = torch.empty(T, N, H, dtype=torch.float32, device=dev) if train else None
@@ -504,7 +541,7 @@ def _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, reverse, need):
     T, N, I = x.shape
     H = w_hh.shape[1]
     dg2 = dg.view(T * N, 3 * H)
-    dx = (dg2 @ w_ih).view(T, N, I) if need[0] else None
+    dx = _rnn_proj(dg2, w_ih, None, True).view(T, N, I) if need[0] else None
     if (USE_HIP_GRU_WGRAD and need[1] and need[2] and (need[3] or need[4]) and dg.is_cuda
             and all(t.dtype == torch.float32 for t in (dg, dq, x, y, w_ih, w_hh))):
         # the four parameter gradients in one pass: [dG | dq]^T [x | y shifted by a step | 1]

@@ -6,6 +6,8 @@ record is --T 800 --N 128 --H 256.  The weight-gradient leg follows: `wgrad_ms` 
 (csrc/gru_wgrad.hip) at (T, N, H, I = H) on that dG, dq and y, `wgrad_gemm_ms` the lines of
 layers._gru_grads_from_dgates that it replaces (the batched GEMMs, the sums and the two cats), `--wgrad-turns` times
 in turns; `wgrad_vs_gemm_maxrel` is the largest difference between the two relative to a result's largest entry.
+The projection legs of tools/lstmbench.py (`proj_ms` / `proj_gemm_ms`, `dx_ms` / `dx_gemm_ms`: csrc/rnn_proj.hip against
+the rocBLAS calls it replaces, five alternating turns) come last, at the GRU's three gates.
 
     python tools/grubench.py [--T 1000] [--N 64] [--H 96] [--steps 20] [--warmup 3] [--reverse] [--infer] [--varlen] [--cols C]
                              [--fallback PAIRS] [--wgrad-turns 3]
@@ -34,6 +36,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from taiyaki_amd import _lib, layers  # noqa: E402
+from lstmbench import proj_report  # noqa: E402  (tools/ is the script's directory)
 
 
 def timed(fn, steps, warmup):
@@ -213,6 +216,7 @@ def main():
     out.update(wgrad_ms=[round(t[0], 4) for t in turns], wgrad_min_ms=[round(t[1], 4) for t in turns],
                wgrad_gemm_ms=[round(t[2], 4) for t in turns], wgrad_gemm_min_ms=[round(t[3], 4) for t in turns],
                wgrad_vs_gemm_maxrel=wgrad_diff)
+    out.update(proj_report(T, N, H, 3, 5, a.steps, a.warmup, dev))
     _lib.finish(status)
     _lib.raise_if_nonfinite()
     out.update(fwd_ms=round(f_med, 3), bwd_ms=round(b_med, 3), fwd_us_per_step=round(1e3 * f_med / T, 3),

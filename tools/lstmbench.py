@@ -4,6 +4,10 @@ tk_lstm_backward_dev at (T, N, H), each timed with device events after warm-up; 
 units setting (microseconds per timestep and direction, median and min over --steps).  The flagship layer
 (config 2) is the default shape.  The weight-gradient leg follows: `wgrad_ms` is tk_lstm_weight_grad_dev
 (csrc/lstm_wgrad.hip) at (T, N, H, I = H), `wgrad_gemm_ms` the two GEMMs and the sum over dG that it replaces.
+The projection legs (csrc/rnn_proj.hip, include/taiyaki_amd_rnn_proj.h) come last: `proj_ms` is tk_rnn_input_proj_dev
+(x W_ih^T + b) and `proj_gemm_ms` the torch.addmm it replaces, `dx_ms` tk_rnn_input_grad_dev (dG W_ih) and `dx_gemm_ms`
+the `@` it replaces, each pair timed in --proj-turns alternating turns (the median of --steps calls per turn and the
+list of turns are both printed).
 
     python tools/lstmbench.py [--T 800] [--N 128] [--H 256] [--steps 20] [--warmup 3] [--units 0 16 32 64] [--varlen]
                               [--fallback PAIRS]
@@ -48,6 +52,56 @@ def timed(fn, steps, warmup):
     return float(np.median(times)), float(np.min(times))
 
 
+def proj_turns(T, N, H, gates, turns, steps, warmup, dev):
+    """The two projection GEMMs of one recurrent layer (I = H, `gates` H gate columns) as the kernel of
+    include/taiyaki_amd_rnn_proj.h and as the rocBLAS call it replaces, in alternating turns: {leg: [median ms per
+    turn]}, the largest difference between the two relative to the largest entry, and the GFLOP of one call."""
+    g = torch.Generator(device="cpu").manual_seed(13)
+    rows, G = T * N, gates * H
+    x = torch.randn(rows, H, generator=g).to(dev)
+    dgt = torch.randn(rows, G, generator=g).to(dev)
+    w = (torch.rand(G, H, generator=g) * 2 - 1).div_(H ** 0.5).to(dev)
+    b = torch.randn(G, generator=g).to(dev)
+    cus = layers._cu_count(dev)
+    P = _lib.rnn_proj_lib()
+    # (the workspace depends on the widths alone; below the rows the rule admits the legs are timed all the same)
+    big = max(rows, 1 << 16)
+    wsb = max(P.tk_rnn_proj_workspace_bytes(big, H, G, cus), P.tk_rnn_proj_workspace_bytes(big, G, H, cus))
+    if min(P.tk_rnn_proj_workspace_bytes(big, H, G, cus), P.tk_rnn_proj_workspace_bytes(big, G, H, cus)) == 0:
+        raise SystemExit("(H, gates) = (%d, %d) has no projection plan" % (H, gates))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    gx, dx = torch.empty(rows, G, device=dev), torch.empty(rows, H, device=dev)
+    stream = _lib.stream_ptr()
+    legs = {
+        "proj_ms": lambda: _lib.check(P.tk_rnn_input_proj_dev(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), rows, H, G, cus,
+                                                              _lib.ptr(gx), _lib.ptr(ws), wsb, stream), "proj"),
+        "proj_gemm_ms": lambda: torch.addmm(b, x, w.t()),
+        "dx_ms": lambda: _lib.check(P.tk_rnn_input_grad_dev(_lib.ptr(dgt), _lib.ptr(w), rows, H, G, cus, _lib.ptr(dx),
+                                                            _lib.ptr(ws), wsb, stream), "dx"),
+        "dx_gemm_ms": lambda: dgt @ w,
+    }
+    out = {k: [] for k in legs}
+    for _ in range(turns):
+        for k, fn in legs.items():
+            out[k].append(round(timed(fn, steps, warmup)[0], 4))
+    ref_gx, ref_dx = torch.addmm(b, x, w.t()), dgt @ w
+    diff = max(((gx - ref_gx).abs().max() / ref_gx.abs().max()).item(),
+               ((dx - ref_dx).abs().max() / ref_dx.abs().max()).item())
+    admitted = [P.tk_rnn_proj_workspace_bytes(rows, H, G, cus) > 0, P.tk_rnn_proj_workspace_bytes(rows, G, H, cus) > 0]
+    return out, diff, 2.0 * rows * H * G * 1e-9, admitted
+
+
+def proj_report(T, N, H, gates, turns, steps, warmup, dev):
+    """proj_turns as the keys of a result line: each leg's median over the turns, the turns, TFLOP/s of the medians."""
+    legs, diff, gflop, admitted = proj_turns(T, N, H, gates, turns, steps, warmup, dev)
+    rep = {k: float(np.median(v)) for k, v in legs.items()}
+    rep.update({k.replace("_ms", "_turns_ms"): v for k, v in legs.items()})
+    rep.update({k.replace("_ms", "_tflops"): round(gflop / np.median(v), 1) for k, v in legs.items()})
+    rep["proj_vs_gemm_maxrel"] = diff
+    rep["proj_admitted"], rep["dx_admitted"] = admitted
+    return rep
+
+
 def layer_turns(T, N, H, pairs, steps, warmup, dev):
     """[(hip fwd, hip bwd, nn.LSTM fwd, nn.LSTM bwd)] * pairs, median microseconds per timestep."""
     torch.manual_seed(12)
@@ -89,6 +143,7 @@ def main():
     ap.add_argument("--reverse", action="store_true")
     ap.add_argument("--varlen", action="store_true",
                     help="also time tk_lstm_forward_varlen_dev (release rule) with every length = T, in turns with the forward")
+    ap.add_argument("--proj-turns", type=int, default=5, help="alternating turns of the projection legs")
     ap.add_argument("--units", type=int, nargs="*", default=None, help="(lab) units per workgroup; 0 = release rule")
     ap.add_argument("--fallback", type=int, default=0, metavar="PAIRS",
                     help="also time layers.Lstm(H, H) forward and backward, HIP and nn.LSTM in turns, PAIRS times")
@@ -209,6 +264,7 @@ def main():
         ref = wgrad_gemm()
         wgrad_diff = max(((p - q).abs().max() / q.abs().max()).item() for p, q in zip((dw_ih, dw_hh, db), ref))
         gflop = 2.0 * T * N * 4 * H * (2 * H + 1) * 1e-9
+        proj = proj_report(T, N, H, 4, a.proj_turns, a.steps, a.warmup, dev)
         _lib.finish(status)
         _lib.raise_if_nonfinite()
         if units is not None:
@@ -219,7 +275,7 @@ def main():
                           "bwd_us_per_step": round(1e3 * b_med / T, 3), "bwd_min_us_per_step": round(1e3 * b_min / T, 3),
                           "wgrad_ms": round(w_med, 4), "wgrad_min_ms": round(w_min, 4), "wgrad_gemm_ms": round(g_med, 4),
                           "wgrad_gemm_min_ms": round(g_min, 4), "wgrad_tflops": round(gflop / w_med, 1),
-                          "wgrad_gemm_tflops": round(gflop / g_med, 1), "wgrad_vs_gemm_maxrel": wgrad_diff,
+                          "wgrad_gemm_tflops": round(gflop / g_med, 1), "wgrad_vs_gemm_maxrel": wgrad_diff, **proj,
                           "device": torch.cuda.get_device_name(dev)}))
     _lib.use_lab(False)
 
