@@ -70,6 +70,10 @@ void tk_lab_gru_wgrad_splits(int splits);
  * per partial result, grid, partial results in the workspace (each 3H (I + H) + 4H floats, rounded up to a multiple of
  * four); 0 where the kernels do not run */
 int tk_lab_gru_wgrad_plan(size_t nblk, size_t nbatch, size_t size, size_t insize, int cu_count, size_t *out);
+/* the loads a call takes at these widths, `aligned`: every operand is 16-byte aligned.  0 = guarded (any shape and
+ * alignment), 1 = 16-byte loads of whole tiles (both widths multiples of 128), 2 = 16-byte loads with ragged tiles
+ * (both multiples of 4) */
+int tk_lab_gru_wgrad_loads(size_t size, size_t insize, int aligned);
 #endif
 
 #ifdef __cplusplus

@@ -58,6 +58,10 @@ void tk_lab_lstm_wgrad_splits(int splits);
 /* the launch plan at a shape: out[8] = output tiles down and across, runs, partial results per run, rows per run, rows
  * per partial result, grid, partial results in the workspace; 0 where the kernels do not run */
 int tk_lab_lstm_wgrad_plan(size_t nblk, size_t nbatch, size_t size, size_t insize, int cu_count, size_t *out);
+/* the loads a call takes at these widths, `aligned`: every operand is 16-byte aligned.  0 = guarded (any shape and
+ * alignment), 1 = 16-byte loads of whole tiles (both widths multiples of 128); 2, 16-byte loads with ragged tiles, is
+ * the GRU's only */
+int tk_lab_lstm_wgrad_loads(size_t size, size_t insize, int aligned);
 #endif
 
 #ifdef __cplusplus

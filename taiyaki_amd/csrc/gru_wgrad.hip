@@ -78,6 +78,10 @@ void tk_lab_gru_wgrad_splits(int splits) { tk::g_lab_splits = splits; }
 int tk_lab_gru_wgrad_plan(size_t nblk, size_t nbatch, size_t size, size_t insize, int cu_count, size_t *out) {
     return tk::wgrad_lab_plan<tk::GruCell>(nblk, nbatch, size, insize, cu_count, out);
 }
+
+int tk_lab_gru_wgrad_loads(size_t size, size_t insize, int aligned) {
+    return tk::wgrad_loads<tk::GruCell>(aligned != 0, size, insize);
+}
 #endif
 
 }  // extern "C"

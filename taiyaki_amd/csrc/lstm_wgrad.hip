@@ -58,6 +58,10 @@ void tk_lab_lstm_wgrad_splits(int splits) { tk::g_lab_splits = splits; }
 int tk_lab_lstm_wgrad_plan(size_t nblk, size_t nbatch, size_t size, size_t insize, int cu_count, size_t *out) {
     return tk::wgrad_lab_plan<tk::LstmCell>(nblk, nbatch, size, insize, cu_count, out);
 }
+
+int tk_lab_lstm_wgrad_loads(size_t size, size_t insize, int aligned) {
+    return tk::wgrad_loads<tk::LstmCell>(aligned != 0, size, insize);
+}
 #endif
 
 }  // extern "C"

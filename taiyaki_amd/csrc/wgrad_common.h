@@ -353,6 +353,15 @@ size_t wgrad_workspace_bytes(size_t T, size_t N, size_t H, size_t I, int cu_coun
     return p.slabs * p.slab_floats * sizeof(float);
 }
 
+// Which loads a call takes (`aligned`: every operand is 16-byte aligned): whole tiles and 16-byte loads everywhere,
+// 16-byte loads and ragged tiles (a cell without that instantiation: the guarded loads), or the guarded loads
+template <class Cell>
+int wgrad_loads(bool aligned, size_t H, size_t I) {
+    if (aligned && H % WG_TILE == 0 && I % WG_TILE == 0) return WG_FAST;
+    if (aligned && H % 4 == 0 && I % 4 == 0) return Cell::VEC4_EDGE ? WG_VEC4 : WG_GUARDED;
+    return WG_GUARDED;
+}
+
 // The two launches.  `a` comes with its operand pointers set (the caller has refused NULLs); `aligned`: they are all
 // 16-byte aligned.
 template <class Cell>
@@ -366,15 +375,18 @@ int wgrad_launch(typename Cell::Args a, bool aligned, size_t T, size_t N, size_t
     a.tiles_m = p.tiles_m, a.tiles_x = p.tiles_x, a.splits = p.splits, a.nsub = p.nsub;
     a.run_rows = p.run_rows, a.sub_rows = p.sub_rows, a.rstride = p.rstride;
     a.slab_floats = p.slab_floats;
-    // whole tiles and 16-byte loads everywhere, 16-byte loads and ragged tiles (a cell without that instantiation:
-    // the guarded loads), or the guarded loads
+    // (a cell without the WG_VEC4 instantiation never gets that answer: its case launches the guarded loads again)
     constexpr int EDGE = Cell::VEC4_EDGE ? WG_VEC4 : WG_GUARDED;
-    if (aligned && H % WG_TILE == 0 && I % WG_TILE == 0)
+    switch (wgrad_loads<Cell>(aligned, H, I)) {
+    case WG_FAST:
         hipLaunchKernelGGL((wgrad_kernel<Cell, WG_FAST>), dim3(p.grid), dim3(WG_THREADS), 0, stream, a);
-    else if (aligned && H % 4 == 0 && I % 4 == 0)
+        break;
+    case WG_VEC4:
         hipLaunchKernelGGL((wgrad_kernel<Cell, EDGE>), dim3(p.grid), dim3(WG_THREADS), 0, stream, a);
-    else
+        break;
+    default:
         hipLaunchKernelGGL((wgrad_kernel<Cell, WG_GUARDED>), dim3(p.grid), dim3(WG_THREADS), 0, stream, a);
+    }
     if (hipGetLastError() != hipSuccess) return TK_ERR_LAUNCH;
     const size_t total = (size_t)a.M * (I + H) + a.M + Cell::EXTRA_BIAS * H;
     hipLaunchKernelGGL(wgrad_reduce_kernel<Cell>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream,

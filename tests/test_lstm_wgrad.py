@@ -28,7 +28,8 @@ def test_plan_and_workspace_arithmetic(labenv):
     workspace is one partial result [4H][I + H] | [4H] per (run, part)."""
     labenv.lib()
     W = _lib.wgrad_lib()
-    assert _lib.is_lab() and set(_lib.WGRAD_LAB_SIGNATURES) == {"tk_lab_lstm_wgrad_splits", "tk_lab_lstm_wgrad_plan"}
+    assert _lib.is_lab() and set(_lib.WGRAD_LAB_SIGNATURES) == {"tk_lab_lstm_wgrad_splits", "tk_lab_lstm_wgrad_plan",
+                                                                "tk_lab_lstm_wgrad_loads"}
     flagship = _plan(W, 800, 128, 256, 256)
     assert flagship == dict(tiles_m=8, tiles_n=4, runs=8, parts=2, run_rows=12800, part_rows=6400, grid=256, slabs=16)
     assert W.tk_lstm_weight_grad_workspace_bytes(800, 128, 256, 256, CUS) == 16 * (1024 * 512 + 1024) * 4

@@ -277,6 +277,24 @@ def test_rows_are_independent_of_the_batch_they_are_in(gpu_device, I, G, grad):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("M,I,G,grad,column_tiles", [(8 * RT + 1, 64, 256, False, 2), (8 * RT + 1, 64, 256, True, 1),
+                                                     (8 * RT + 1, 192, 768, True, 2), (17 * RT, 16, 64, False, 1),
+                                                     (17 * RT, 16, 64, True, 1)])
+def test_row_tiles_beyond_the_first_group_of_eight(gpu_device, M, I, G, grad, column_tiles):
+    """blockIdx walks the row tiles in groups of eight, the column tiles of a group inside it.  A ninth row tile of one
+    row under two column tiles (the projection at (64, 256), the gradient at (192, 768)) and under one; 17 row tiles:
+    three groups, the last with one tile.  Rows 0, 1023, 1024 and M - 1 are the bits of the same rows computed alone."""
+    assert -(-M // RT) > 8 and -(-(I if grad else G) // NT) == column_tiles
+    a, w, bias, _ = _inputs("randn", M, I, G, grad)
+    full = _check("randn", M, I, G, grad, gpu_device)
+    a, w = a.to(gpu_device), w.to(gpu_device)
+    bias = None if grad else bias.to(gpu_device)
+    for m in (0, 8 * RT - 1, 8 * RT, M - 1):
+        alone = _run(a[m:m + 1].contiguous(), w, bias, grad)
+        assert torch.equal(alone.view(torch.int32), full[m:m + 1].view(torch.int32)), m
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("grad", [False, True])
 def test_a_non_finite_element_stays_in_its_row(gpu_device, grad):
     M, I, G = RT + 1, 96, 288
