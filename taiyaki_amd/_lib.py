@@ -35,6 +35,9 @@ GRU_WGRAD_LAB_LIBNAME = "libtaiyaki_amd_gru_wgrad_lab.so"   # ... and its lab bu
 RNN_PROJ_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_proj.h")
 RNN_PROJ_LIBNAME = "libtaiyaki_amd_rnn_proj.so"     # csrc/rnn_proj.hip: the recurrent layers' projection GEMMs, header and library of its own
 RNN_PROJ_LAB_LIBNAME = "libtaiyaki_amd_rnn_proj_lab.so"     # ... and its lab build (tk_lab_rnn_proj_plan)
+CONV_STRIDED_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_conv_strided.h")
+CONV_STRIDED_LIBNAME = "libtaiyaki_amd_conv_strided.so"     # csrc/conv_strided.hip: the 16 -> Cout stride-5 convolution, header and library of its own
+CONV_STRIDED_LAB_LIBNAME = "libtaiyaki_amd_conv_strided_lab.so"     # ... and its lab build (tk_lab_conv_strided_*)
 
 VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
 VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
@@ -121,6 +124,8 @@ WGRAD_SIGNATURES, WGRAD_LAB_SIGNATURES = _read_wgrad_header()
 GRU_WGRAD_SIGNATURES, GRU_WGRAD_LAB_SIGNATURES = _read_wgrad_header(GRU_WGRAD_HEADER)
 # the tenth: include/taiyaki_amd_rnn_proj.h (libtaiyaki_amd_rnn_proj.so), and the hook its lab build adds
 RNN_PROJ_SIGNATURES, RNN_PROJ_LAB_SIGNATURES = _read_wgrad_header(RNN_PROJ_HEADER)
+# the eleventh: include/taiyaki_amd_conv_strided.h (libtaiyaki_amd_conv_strided.so), and the hooks its lab build adds
+CONV_STRIDED_SIGNATURES, CONV_STRIDED_LAB_SIGNATURES = _read_wgrad_header(CONV_STRIDED_HEADER)
 
 
 def _read_varlen_header():
@@ -249,6 +254,16 @@ def rnn_proj_lib():
         return _load(os.path.join(CSRC, RNN_PROJ_LAB_LIBNAME),
                      dict(RNN_PROJ_SIGNATURES, **RNN_PROJ_LAB_SIGNATURES))
     return _load(os.path.join(CSRC, RNN_PROJ_LIBNAME), RNN_PROJ_SIGNATURES)
+
+
+def conv_strided_lib():
+    """The 16 -> Cout, window 19, stride 5 convolution (include/taiyaki_amd_conv_strided.h): the lab build of that
+    library while the process runs on the lab build (`use_lab`), the release one otherwise.  No fallback: a missing
+    library raises."""
+    if is_lab():
+        return _load(os.path.join(CSRC, CONV_STRIDED_LAB_LIBNAME),
+                     dict(CONV_STRIDED_SIGNATURES, **CONV_STRIDED_LAB_SIGNATURES))
+    return _load(os.path.join(CSRC, CONV_STRIDED_LIBNAME), CONV_STRIDED_SIGNATURES)
 
 
 def varlen_lib():

@@ -172,6 +172,71 @@ class SmallConvolution(torch.autograd.Function):
         return dx, dw, db
 
 
+# False: the 16 -> Cout, window 19, stride 5 layer runs unfold + GEMM (exactly as with USE_HIP_CONV = False), for
+# comparisons against the kernels of include/taiyaki_amd_conv_strided.h
+USE_HIP_CONV_STRIDED = True
+# The workspace handed to those calls: one size, allocated once per stream, for every shape whose weight gradient has
+# one partial result per run, i.e. at most 8192 rows per run: 344 064 rows on 256 CUs, 3.4 x the models' 102 400.  The
+# need is then the weights' images (1.9 MB at most) + (CUs / tiles) partial results: 14.4 MB at 256 channels and 15.0 MB at
+# 384 on 256 CUs, 16.9 and 17.4 MB on 304 CUs.  Only a batch beyond those rows (its runs are cut into two or more partial
+# results each) or a device beyond about 440 CUs needs more; the cached buffer then regrows to that call's size.
+_CONV_STRIDED_WORKSPACE_BYTES = 24 << 20
+
+
+class StridedConvolution(torch.autograd.Function):
+    """swish(conv1d(x) + b) of the mLstm models' third layer (16 -> Cout channels, window 19, stride 5; the shapes
+    tk_conv_strided_supported names) on the kernels of csrc/conv_strided.hip.  Forward: one GEMM whose rows are read
+    straight from x writes z and y (`save` False, the caller under no_grad: y alone).  Backward: dz in one element-wise
+    launch, dx (when wanted) as a gather GEMM over dz, dW and db as one split-K launch and the fixed-order sum of its
+    partial results.  x and z are saved; no window matrix exists, forward or backward."""
+
+    @staticmethod
+    def _workspace(L, T, N, cout, dev):
+        wsb = max(L.tk_conv_strided_workspace_bytes(T, N, cout, _cu_count(dev)), _CONV_STRIDED_WORKSPACE_BYTES)
+        return _lib.workspace(wsb, dev, "conv_strided"), wsb
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, save):
+        T, N, _ = x.shape
+        cout = weight.shape[0]
+        dev = x.device
+        L = _lib.conv_strided_lib()
+        x = _aligned(x.detach())
+        weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+        with torch.cuda.device(dev):
+            y = torch.empty((T + 4) // 5, N, cout, dtype=torch.float32, device=dev)
+            z = torch.empty_like(y) if save else None
+            ws, wsb = StridedConvolution._workspace(L, T, N, cout, dev)
+            rc = L.tk_conv_strided_forward_dev(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), T, N, cout,
+                                               _cu_count(dev), _lib.ptr(z), _lib.ptr(y), _lib.ptr(ws), wsb,
+                                               _lib.stream_ptr())
+        _lib.check(rc, "tk_conv_strided_forward_dev")
+        if save:
+            ctx.save_for_backward(x, z, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, z, weight = ctx.saved_tensors
+        T, N, _ = x.shape
+        cout = weight.shape[0]
+        dev = x.device
+        L = _lib.conv_strided_lib()
+        dy = _aligned(dy)
+        with torch.cuda.device(dev):
+            dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+            dw = torch.empty_like(weight)
+            db = torch.empty(cout, dtype=torch.float32, device=dev)
+            dz = torch.empty_like(z)
+            ws, wsb = StridedConvolution._workspace(L, T, N, cout, dev)
+            rc = L.tk_conv_strided_backward_dev(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(z), _lib.ptr(weight), T, N, cout,
+                                                _cu_count(dev), _lib.ptr(dz), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db),
+                                                _lib.ptr(ws), wsb, _lib.stream_ptr())
+        _lib.check(rc, "tk_conv_strided_backward_dev")
+        return dx, dw, db, None
+
+
 class Convolution(nn.Module):
     """layers.py:744-850: TBF in/out, pad (winlen//2, (winlen-1)//2), then activation.
 
@@ -187,6 +252,10 @@ class Convolution(nn.Module):
     16 x 20 results over 512 000 rows, one macro tile on nine workgroups, 3 ms each.  With
     `use_gemm` set, a float32 CUDA input, swish and a shape `tk_conv1d_small_supported` names,
     the layer runs as the fused HIP operator `SmallConvolution` (USE_HIP_CONV = False: never).
+
+    The wide layer behind them (16 -> 192, 256 or 384 channels, window 19, stride 5, swish) runs as `StridedConvolution` where
+    `tk_conv_strided_supported` names the shape (USE_HIP_CONV or USE_HIP_CONV_STRIDED = False: never): its GEMMs
+    read x through the window's address map, so the 124 MB window matrix of the unfold path is never written.
     """
 
     def __init__(self, insize, size, winlen, stride=1, fun=torch.tanh, use_gemm=True):
@@ -206,12 +275,25 @@ class Convolution(nn.Module):
                 and w.is_cuda and w.dtype == torch.float32
                 and bool(_lib.lib().tk_conv1d_small_supported(w.shape[1], w.shape[0], self.winlen, self.stride)))
 
+    def _hip_strided(self, x):
+        w = self.conv.weight
+        if not (USE_HIP_CONV and USE_HIP_CONV_STRIDED and self.activation is swish and x.is_cuda and x.dim() == 3
+                and x.dtype == torch.float32 and w.is_cuda and w.dtype == torch.float32):
+            return False
+        L = _lib.conv_strided_lib()
+        return bool(L.tk_conv_strided_supported(w.shape[1], w.shape[0], self.winlen, self.stride)
+                    and L.tk_conv_strided_workspace_bytes(x.shape[0], x.shape[1], w.shape[0], _cu_count(x.device)))
+
     def forward(self, x):
         if not self.use_gemm:
             out = self.activation(self.conv(self.pad(x.permute(1, 2, 0))))
             return out.permute(2, 0, 1)
         if self._hip_small(x):
             return SmallConvolution.apply(x, self.conv.weight, self.conv.bias)
+        if self._hip_strided(x):
+            w, b = self.conv.weight, self.conv.bias
+            save = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or b.requires_grad)
+            return StridedConvolution.apply(x, w, b, save)
         # x: (T, N, C) -> pad time -> windows (Tout, N, C, winlen) -> GEMM with (C*winlen, size)
         xp = nn.functional.pad(x, (0, 0, 0, 0, self.winlen // 2, (self.winlen - 1) // 2))
         win = xp.unfold(0, self.winlen, self.stride)            # (Tout, N, C, winlen) view
