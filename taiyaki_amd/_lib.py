@@ -44,6 +44,8 @@ VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru
 
 VARLEN_TRAIN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen_train.h")
 VARLEN_TRAIN_LIBNAME = "libtaiyaki_amd_rnn_varlen_train.so"     # the same two sources built -DTK_RNN_VARLEN_TRAIN: the training pair with per-column lengths
+WIDE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_wide.h")
+WIDE_LIBNAME = "libtaiyaki_amd_rnn_wide.so"     # the same two sources built -DTK_RNN_WIDE: every batch width, as slabs of columns
 DECODE_VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_decode_varlen.h")
 DECODE_VARLEN_LIBNAME = "libtaiyaki_amd_decode_varlen.so"   # csrc/decode_varlen.hip: the decode operators with per-column lengths, header and library of its own
 
@@ -146,6 +148,10 @@ DECODE_VARLEN_SIGNATURES = {n: (r, a) for n, (r, a, _) in
 # the eighth: include/taiyaki_amd_rnn_varlen_train.h (libtaiyaki_amd_rnn_varlen_train.so)
 VARLEN_TRAIN_SIGNATURES = {n: (r, a) for n, (r, a, _) in
                            parse_prototypes(_blank_comments(open(VARLEN_TRAIN_HEADER).read())).items()}
+
+
+# the twelfth: include/taiyaki_amd_rnn_wide.h (libtaiyaki_amd_rnn_wide.so)
+WIDE_SIGNATURES = {n: (r, a) for n, (r, a, _) in parse_prototypes(_blank_comments(open(WIDE_HEADER).read())).items()}
 
 
 class SeqLabels(ctypes.Structure):
@@ -276,6 +282,12 @@ def varlen_train_lib():
     """The recurrences' training pair with per-column lengths (include/taiyaki_amd_rnn_varlen_train.h).  No fallback: a
     missing library raises."""
     return _load(os.path.join(CSRC, VARLEN_TRAIN_LIBNAME), VARLEN_TRAIN_SIGNATURES)
+
+
+def rnn_wide_lib():
+    """The recurrences at every batch width, as slabs of columns (include/taiyaki_amd_rnn_wide.h).  No fallback: a
+    missing library raises."""
+    return _load(os.path.join(CSRC, WIDE_LIBNAME), WIDE_SIGNATURES)
 
 
 def decode_varlen_lib():

@@ -126,6 +126,25 @@ int gru_backward_varlen_dispatch(const float *whh, const float *y, const float *
                                  int cu_count, float *dgates, float *dq, void *ws, size_t wsb, uint32_t *status,
                                  hipStream_t stream);
 
+// ... and their -DTK_RNN_WIDE build (libtaiyaki_amd_rnn_wide.so; rnn_wide_api.hip defines the C entries): every batch
+// width, as slabs of columns; gates and cell (q) of the forwards may both be NULL
+size_t lstm_wide_slab(size_t N, size_t H, int cu_count);
+size_t lstm_wide_workspace_bytes(size_t N, size_t H, int cu_count);
+int lstm_forward_wide_dispatch(const float *gx, const float *whh, const int32_t *lengths, size_t T, size_t N, size_t H,
+                               int reverse, int cu_count, float *y, float *gates, float *cell, void *ws, size_t wsb,
+                               uint32_t *status, hipStream_t stream);
+int lstm_backward_wide_dispatch(const float *whh, const float *gates, const float *cell, const float *dy,
+                                const int32_t *lengths, size_t T, size_t N, size_t H, int reverse, int cu_count,
+                                float *dgates, void *ws, size_t wsb, uint32_t *status, hipStream_t stream);
+size_t gru_wide_slab(size_t N, size_t H, int cu_count);
+size_t gru_wide_workspace_bytes(size_t N, size_t H, int cu_count);
+int gru_forward_wide_dispatch(const float *gx, const float *whh, const float *bhh, const int32_t *lengths, size_t T,
+                              size_t N, size_t H, int reverse, int cu_count, float *y, float *gates, float *q, void *ws,
+                              size_t wsb, uint32_t *status, hipStream_t stream);
+int gru_backward_wide_dispatch(const float *whh, const float *y, const float *gates, const float *q, const float *dy,
+                               const int32_t *lengths, size_t T, size_t N, size_t H, int reverse, int cu_count,
+                               float *dgates, float *dq, void *ws, size_t wsb, uint32_t *status, hipStream_t stream);
+
 // conv_kernels.hip
 bool conv_small_supported(size_t cin, size_t cout, size_t winlen, size_t stride);
 size_t conv_small_workspace_bytes(size_t T, size_t N, size_t cin, size_t cout, size_t winlen, int cu_count);

@@ -24,7 +24,10 @@
 // in registers and stored right after step s + 1's.  Both drain under the matvec; the granule publish is the last
 // memory operation of a step.  Every sum runs in a fixed order: a launch is bit-reproducible.
 //
-// Three builds of this one source, as for lstm_kernels.hip: the flip-flop library takes the forward and the backward,
+// Columns: `cols.n` of them in tensors of `cols.ld()` per time step, as in lstm_kernels.hip.
+//
+// Four builds of this one source, as for lstm_kernels.hip: -DTK_RNN_WIDE (libtaiyaki_amd_rnn_wide.so) takes the three VL
+// forms on slabs of a batch's columns (`checked`; gru_slab), the flip-flop library takes the forward and the backward,
 // -DTK_RNN_VARLEN (libtaiyaki_amd_rnn_varlen.so) the forward alone in its VL form with nothing saved,
 // -DTK_RNN_VARLEN_TRAIN (libtaiyaki_amd_rnn_varlen_train.so) the saving forward and the backward in their VL form.
 #include "dispatch.h"
@@ -58,10 +61,11 @@ constexpr int bwd_threads_for() { return U == 48 ? 2 * H : gru_threads<H, U>(); 
 // the length); not SAVE: they are not written (the pointers are not read).
 template <int H, int U, int C, bool VL = false, bool SAVE = !VL>
 __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
-    const float *__restrict__ gx, const float *__restrict__ whh, const float *__restrict__ bhh, int T, int N,
+    const float *__restrict__ gx, const float *__restrict__ whh, const float *__restrict__ bhh, int T, Cols cols,
     int reverse, int ngroups, float *__restrict__ y, float *__restrict__ gates, float *__restrict__ qout, u64 *hbuf,
     uint32_t *status, const int32_t *__restrict__ lengths) {
     constexpr int NT = gru_threads<H, U>();
+    const int N = cols.n, LD = cols.ld();               // the launch's columns; the tensors' columns per time step
     constexpr int G = H / U;
     constexpr int KP = NT / U;
     constexpr int KS = H / KP;
@@ -105,7 +109,7 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
     const size_t H3 = 3 * (size_t)H;
     float gq[3] = {0.f, 0.f, 0.f};                    // gx of this step (loaded one step ahead)
     if (valid) {
-        const float *p = gx + ((size_t)(reverse ? T - 1 : 0) * N + n) * H3 + j0 + u;
+        const float *p = gx + ((size_t)(reverse ? T - 1 : 0) * LD + n) * H3 + j0 + u;
 #pragma unroll
         for (int g = 0; g < 3; ++g) gq[g] = p[(size_t)g * H];
     }
@@ -132,7 +136,7 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
                 __syncthreads();                             // hb: written by the cell lanes of step s - 1
             }
             if (valid) {
-                const size_t row = (size_t)(reverse ? t + 1 : t - 1) * N + n;
+                const size_t row = (size_t)(reverse ? t + 1 : t - 1) * LD + n;
                 y[row * H + j0 + u] = held[0];
                 if constexpr (SAVE) {
                     if (gates) {
@@ -146,7 +150,7 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
         }
         float gn[3] = {0.f, 0.f, 0.f};
         if (valid && s + 1 < T) {
-            const float *p = gx + ((size_t)(reverse ? t - 1 : t + 1) * N + n) * H3 + j0 + u;
+            const float *p = gx + ((size_t)(reverse ? t - 1 : t + 1) * LD + n) * H3 + j0 + u;
 #pragma unroll
             for (int g = 0; g < 3; ++g) gn[g] = p[(size_t)g * H];
         }
@@ -220,7 +224,7 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
         for (int g = 0; g < 3; ++g) gq[g] = gn[g];
     }
     if (valid && T > 0) {
-        const size_t row = (size_t)(reverse ? 0 : T - 1) * N + n;
+        const size_t row = (size_t)(reverse ? 0 : T - 1) * LD + n;
         y[row * H + j0 + u] = held[0];
         if constexpr (SAVE) {
             if (gates) {
@@ -247,10 +251,11 @@ __global__ __launch_bounds__((gru_threads<H, U>()), 1) void gru_fwd_kernel(
 template <int H, int U, int C, bool VL = false>
 __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void gru_bwd_kernel(
     const float *__restrict__ whh, const float *__restrict__ y, const float *__restrict__ gates,
-    const float *__restrict__ qin, const float *__restrict__ dy, int T, int N, int reverse, int ngroups,
+    const float *__restrict__ qin, const float *__restrict__ dy, int T, Cols cols, int reverse, int ngroups,
     float *__restrict__ dgates, float *__restrict__ dqout, u64 *pbuf, uint32_t *status,
     const int32_t *__restrict__ lengths) {
     constexpr int NT = bwd_threads_for<H, U>();
+    const int N = cols.n, LD = cols.ld();               // the launch's columns; the tensors' columns per time step
     constexpr int G = H / U;
     constexpr int RP = NT / H;                        // row partitions
     constexpr int R = 3 * U / RP;                     // floats per lane
@@ -294,13 +299,13 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void gru_bwd_kernel(
     float in[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (valid) {
         const int t = reverse ? 0 : T - 1;
-        const size_t row = (size_t)t * N + n;
+        const size_t row = (size_t)t * LD + n;
         in[0] = dy[row * H + j0 + u];
         const float *gp = gates + row * H3 + j0 + u;
 #pragma unroll
         for (int g = 0; g < 3; ++g) in[1 + g] = gp[(size_t)g * H];
         in[4] = qin[row * H + j0 + u];
-        if (T > 1) in[5] = y[((size_t)(reverse ? t + 1 : t - 1) * N + n) * H + j0 + u];
+        if (T > 1) in[5] = y[((size_t)(reverse ? t + 1 : t - 1) * LD + n) * H + j0 + u];
     }
     float held[4] = {0.f, 0.f, 0.f, 0.f};             // dr_pre, dz_pre, dn_pre, dq of the previous step, stored late
     __syncthreads();
@@ -335,7 +340,7 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void gru_bwd_kernel(
                 for (int q = 0; q < RP; ++q) dhr += red[(q * C + cc) * H + u];
             }
             if (valid) {
-                const size_t row = (size_t)(reverse ? t - 1 : t + 1) * N + n;
+                const size_t row = (size_t)(reverse ? t - 1 : t + 1) * LD + n;
                 float *dp = dgates + row * H3 + j0 + u;
 #pragma unroll
                 for (int g = 0; g < 3; ++g) dp[(size_t)g * H] = held[g];
@@ -344,13 +349,13 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void gru_bwd_kernel(
         }
         float nx[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (valid && tt > 0) {
-            const size_t row = (size_t)tp * N + n;
+            const size_t row = (size_t)tp * LD + n;
             nx[0] = dy[row * H + j0 + u];
             const float *gp = gates + row * H3 + j0 + u;
 #pragma unroll
             for (int g = 0; g < 3; ++g) nx[1 + g] = gp[(size_t)g * H];
             nx[4] = qin[row * H + j0 + u];
-            if (tt > 1) nx[5] = y[((size_t)(reverse ? tp + 1 : tp - 1) * N + n) * H + j0 + u];
+            if (tt > 1) nx[5] = y[((size_t)(reverse ? tp + 1 : tp - 1) * LD + n) * H + j0 + u];
         }
         asm volatile("" ::: "memory");                   // the deferred stores and the prefetch stay here
 
@@ -406,7 +411,7 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void gru_bwd_kernel(
         }
     }
     if (valid && T > 0) {
-        const size_t row = (size_t)(reverse ? T - 1 : 0) * N + n;
+        const size_t row = (size_t)(reverse ? T - 1 : 0) * LD + n;
         float *dp = dgates + row * H3 + j0 + u;
 #pragma unroll
         for (int g = 0; g < 3; ++g) dp[(size_t)g * H] = held[g];
@@ -466,11 +471,11 @@ size_t gru_ws_bytes(size_t H, const Plan &p, bool backward) {
 
 template <bool VL, bool SAVE>
 int launch_fwd(const Plan &p, size_t H, hipStream_t st, const float *gx, const float *whh, const float *bhh, int T,
-               int N, int rev, float *y, float *gates, float *q, u64 *ws, uint32_t *status, const int32_t *lengths) {
+               Cols cols, int rev, float *y, float *gates, float *q, u64 *ws, uint32_t *status, const int32_t *lengths) {
 #define TK_GRU_FWD(HH, UU, CC)                                                                                    \
     case HH * 10 + CC:                                                                                            \
         hipLaunchKernelGGL((gru_fwd_kernel<HH, UU, CC, VL, SAVE>), dim3(p.grid), dim3(gru_threads<HH, UU>()), 0, st,    \
-                           gx, whh, bhh, T, N, rev, p.groups, y, gates, q, ws, status, lengths);                  \
+                           gx, whh, bhh, T, cols, rev, p.groups, y, gates, q, ws, status, lengths);               \
         break;
     TK_GRU_SWITCH(TK_GRU_FWD)
 #undef TK_GRU_FWD
@@ -480,12 +485,12 @@ int launch_fwd(const Plan &p, size_t H, hipStream_t st, const float *gx, const f
 #ifndef TK_RNN_VARLEN
 template <bool VL>
 int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const float *y, const float *gates,
-               const float *q, const float *dy, int T, int N, int rev, float *dg, float *dq, u64 *ws,
+               const float *q, const float *dy, int T, Cols cols, int rev, float *dg, float *dq, u64 *ws,
                uint32_t *status, const int32_t *lengths) {
 #define TK_GRU_BWD(HH, UU, CC)                                                                                    \
     case HH * 10 + CC:                                                                                            \
         hipLaunchKernelGGL((gru_bwd_kernel<HH, UU, CC, VL>), dim3(p.grid), dim3(bwd_threads_for<HH, UU>()), 0,    \
-                           st, whh, y, gates, q, dy, T, N, rev, p.groups, dg, dq, ws, status, lengths);           \
+                           st, whh, y, gates, q, dy, T, cols, rev, p.groups, dg, dq, ws, status, lengths);        \
         break;
     TK_GRU_SWITCH(TK_GRU_BWD)
 #undef TK_GRU_BWD
@@ -494,24 +499,46 @@ int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const 
 #endif  // TK_RNN_VARLEN
 #undef TK_GRU_SWITCH
 
+// The slab width of a batch of N columns (rnn_common.h has the rule): the widest batch gru_plan admits at
+// (H, cu_count), or N where one launch admits the batch (H <= 128: always); 0 where the kernels do not run.
+size_t gru_slab(size_t N, size_t H, int cu_count) {
+    Plan p;
+    const size_t S = widest_admitted([&](size_t n) { return gru_plan(n, H, cu_count, &p); });
+    return N == 0 ? 0 : N < S ? N : S;
+}
+
 // What every dispatcher below does around its launch, written once: the pointer and range checks (`pointers_ok`: the
-// entry's own required pointers), the plan, the workspace's size, nothing to do at T == 0, the granules zeroed where
-// there are any, then `launch(plan)`.
+// entry's own required pointers), then for every slab of the batch its plan, the workspace's size, nothing to do at
+// T == 0, the granules zeroed where there are any, then `launch(plan, the slab's first column, its columns)`.  The
+// -DTK_RNN_WIDE build alone cuts a batch: everywhere else the one slab is the batch, and a batch that no launch admits
+// is refused.  The slabs share the workspace and follow each other on `stream`, never side by side (lstm_kernels.hip:
+// checked); the first is the widest and has the largest plan; a launch error returns at once.
 template <class Launch>
 int checked(bool pointers_ok, size_t T, size_t N, size_t H, int cu_count, void *ws, size_t wsb, uint32_t *status,
             hipStream_t stream, bool backward, Launch launch) {
     if (!pointers_ok || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX || N > (size_t)INT32_MAX)
         return TK_ERR_BAD_ARG;
-    Plan p;
-    if (!gru_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    const size_t need = gru_ws_bytes(H, p, backward);
-    if (wsb < (need ? need : 16)) return TK_ERR_WORKSPACE;
-    if (T == 0) return TK_OK;
-    if (need) {
-        int rc = zero_ws(ws, need, stream);
+#ifdef TK_RNN_WIDE
+    const size_t S = gru_slab(N, H, cu_count);
+#else
+    const size_t S = N;
+#endif
+    if (S == 0) return TK_ERR_UNSUPPORTED;
+    for (size_t first = 0; first < N; first += S) {
+        const size_t n = N - first < S ? N - first : S;
+        Plan p;
+        if (!gru_plan(n, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+        const size_t need = gru_ws_bytes(H, p, backward);
+        if (wsb < (need ? need : 16)) return TK_ERR_WORKSPACE;
+        if (T == 0) continue;
+        if (need) {
+            int rc = zero_ws(ws, need, stream);
+            if (rc != TK_OK) return rc;
+        }
+        const int rc = launch(p, first, make_cols(n, N));
         if (rc != TK_OK) return rc;
     }
-    return launch(p);
+    return TK_OK;
 }
 
 // Never 0 where the kernels run (0 means "does not run here"): one granule pair at G = 1, which needs none.
@@ -521,6 +548,38 @@ size_t workspace_bytes(size_t N, size_t H, int cu_count, bool backward) {
     const size_t need = gru_ws_bytes(H, p, backward);
     return need ? need : 16;
 }
+
+// The forward and the backward of every dispatcher below: `checked`, whose launch of a slab takes the tensors, and
+// `lengths`, advanced to the slab's first column.  `saved`: gates and q are required (the plain forward takes NULL for
+// them at run time; not SAVE: they are not read).
+template <bool VL, bool SAVE>
+int forward(bool saved, const float *gx, const float *whh, const float *bhh, const int32_t *lengths, size_t T, size_t N,
+            size_t H, int reverse, int cu_count, float *y, float *gates, float *q, void *ws, size_t wsb,
+            uint32_t *status, hipStream_t stream) {
+    auto launch = [&](const Plan &p, size_t first, Cols cols) {
+        return launch_fwd<VL, SAVE>(p, H, stream, at_column(gx, first, 3 * H), whh, bhh, (int)T, cols, reverse,
+                                    at_column(y, first, H), at_column(gates, first, 3 * H), at_column(q, first, H),
+                                    static_cast<u64 *>(ws), status, at_column(lengths, first, 1));
+    };
+    return checked(gx && whh && bhh && y && (!saved || (gates && q)), T, N, H, cu_count, ws, wsb, status, stream,
+                   false, launch);
+}
+
+#ifndef TK_RNN_VARLEN
+template <bool VL>
+int backward(const float *whh, const float *y, const float *gates, const float *q, const float *dy,
+             const int32_t *lengths, size_t T, size_t N, size_t H, int reverse, int cu_count, float *dgates, float *dq,
+             void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
+    auto launch = [&](const Plan &p, size_t first, Cols cols) {
+        return launch_bwd<VL>(p, H, stream, whh, at_column(y, first, H), at_column(gates, first, 3 * H),
+                              at_column(q, first, H), at_column(dy, first, H), (int)T, cols, reverse,
+                              at_column(dgates, first, 3 * H), at_column(dq, first, H), static_cast<u64 *>(ws), status,
+                              at_column(lengths, first, 1));
+    };
+    return checked(whh && y && gates && q && dy && dgates && dq, T, N, H, cu_count, ws, wsb, status, stream, true,
+                   launch);
+}
+#endif
 
 }  // namespace
 
@@ -532,11 +591,8 @@ size_t gru_varlen_workspace_bytes(size_t N, size_t H, int cu_count) { return wor
 int gru_forward_varlen_dispatch(const float *gx, const float *whh, const float *bhh, const int32_t *lengths, size_t T,
                                 size_t N, size_t H, int reverse, int cu_count, float *y, void *ws, size_t wsb,
                                 uint32_t *status, hipStream_t stream) {
-    auto launch = [&](const Plan &p) {
-        return launch_fwd<true, false>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, nullptr, nullptr,
-                                       static_cast<u64 *>(ws), status, lengths);
-    };
-    return checked(gx && whh && bhh && y, T, N, H, cu_count, ws, wsb, status, stream, false, launch);
+    return forward<true, false>(false, gx, whh, bhh, lengths, T, N, H, reverse, cu_count, y, nullptr, nullptr, ws, wsb,
+                                status, stream);
 }
 #elif defined(TK_RNN_VARLEN_TRAIN)
 // The training pair with per-column lengths (include/taiyaki_amd_rnn_varlen_train.h): the plans, grids and granule
@@ -549,23 +605,44 @@ size_t gru_varlen_train_workspace_bytes(size_t N, size_t H, int cu_count) {
 int gru_forward_varlen_save_dispatch(const float *gx, const float *whh, const float *bhh, const int32_t *lengths,
                                      size_t T, size_t N, size_t H, int reverse, int cu_count, float *y, float *gates,
                                      float *q, void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
-    auto launch = [&](const Plan &p) {
-        return launch_fwd<true, true>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, gates, q,
-                                      static_cast<u64 *>(ws), status, lengths);
-    };
-    return checked(gx && whh && bhh && y && gates && q, T, N, H, cu_count, ws, wsb, status, stream, false, launch);
+    return forward<true, true>(true, gx, whh, bhh, lengths, T, N, H, reverse, cu_count, y, gates, q, ws, wsb, status,
+                               stream);
 }
 
 int gru_backward_varlen_dispatch(const float *whh, const float *y, const float *gates, const float *q,
                                  const float *dy, const int32_t *lengths, size_t T, size_t N, size_t H, int reverse,
                                  int cu_count, float *dgates, float *dq, void *ws, size_t wsb, uint32_t *status,
                                  hipStream_t stream) {
-    auto launch = [&](const Plan &p) {
-        return launch_bwd<true>(p, H, stream, whh, y, gates, q, dy, (int)T, (int)N, reverse, dgates, dq,
-                                static_cast<u64 *>(ws), status, lengths);
-    };
-    return checked(whh && y && gates && q && dy && dgates && dq, T, N, H, cu_count, ws, wsb, status, stream, true,
-                   launch);
+    return backward<true>(whh, y, gates, q, dy, lengths, T, N, H, reverse, cu_count, dgates, dq, ws, wsb, status,
+                          stream);
+}
+#elif defined(TK_RNN_WIDE)
+// Every batch width at the sizes the kernels cover (include/taiyaki_amd_rnn_wide.h): the VL forms, on one slab of
+// gru_slab columns after the other.  A batch that one launch admits is one slab: the call of the training pair with
+// per-column lengths, or of the forward that saves nothing, at the same (N, H, cu_count).
+size_t gru_wide_slab(size_t N, size_t H, int cu_count) { return gru_slab(N, H, cu_count); }
+
+// the training pair's workspace at the widest slab, the first
+size_t gru_wide_workspace_bytes(size_t N, size_t H, int cu_count) {
+    return workspace_bytes(gru_slab(N, H, cu_count), H, cu_count, true);
+}
+
+// gates and q may both be NULL: nothing is saved
+int gru_forward_wide_dispatch(const float *gx, const float *whh, const float *bhh, const int32_t *lengths, size_t T,
+                              size_t N, size_t H, int reverse, int cu_count, float *y, float *gates, float *q, void *ws,
+                              size_t wsb, uint32_t *status, hipStream_t stream) {
+    if (!gates != !q) return TK_ERR_BAD_ARG;
+    return gates ? forward<true, true>(true, gx, whh, bhh, lengths, T, N, H, reverse, cu_count, y, gates, q, ws, wsb,
+                                       status, stream)
+                 : forward<true, false>(false, gx, whh, bhh, lengths, T, N, H, reverse, cu_count, y, nullptr, nullptr,
+                                        ws, wsb, status, stream);
+}
+
+int gru_backward_wide_dispatch(const float *whh, const float *y, const float *gates, const float *q, const float *dy,
+                               const int32_t *lengths, size_t T, size_t N, size_t H, int reverse, int cu_count,
+                               float *dgates, float *dq, void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
+    return backward<true>(whh, y, gates, q, dy, lengths, T, N, H, reverse, cu_count, dgates, dq, ws, wsb, status,
+                          stream);
 }
 #else
 size_t gru_workspace_bytes(size_t N, size_t H, int cu_count) { return workspace_bytes(N, H, cu_count, true); }
@@ -574,22 +651,15 @@ size_t gru_workspace_bytes(size_t N, size_t H, int cu_count) { return workspace_
 int gru_forward_dispatch(const float *gx, const float *whh, const float *bhh, size_t T, size_t N, size_t H,
                          int reverse, int cu_count, float *y, float *gates, float *q, void *ws, size_t wsb,
                          uint32_t *status, hipStream_t stream) {
-    auto launch = [&](const Plan &p) {
-        return launch_fwd<false, true>(p, H, stream, gx, whh, bhh, (int)T, (int)N, reverse, y, gates, q,
-                                       static_cast<u64 *>(ws), status, nullptr);
-    };
-    return checked(gx && whh && bhh && y, T, N, H, cu_count, ws, wsb, status, stream, false, launch);
+    return forward<false, true>(false, gx, whh, bhh, nullptr, T, N, H, reverse, cu_count, y, gates, q, ws, wsb, status,
+                                stream);
 }
 
 int gru_backward_dispatch(const float *whh, const float *y, const float *gates, const float *q, const float *dy,
                           size_t T, size_t N, size_t H, int reverse, int cu_count, float *dgates, float *dq, void *ws,
                           size_t wsb, uint32_t *status, hipStream_t stream) {
-    auto launch = [&](const Plan &p) {
-        return launch_bwd<false>(p, H, stream, whh, y, gates, q, dy, (int)T, (int)N, reverse, dgates, dq,
-                                 static_cast<u64 *>(ws), status, nullptr);
-    };
-    return checked(whh && y && gates && q && dy && dgates && dq, T, N, H, cu_count, ws, wsb, status, stream, true,
-                   launch);
+    return backward<false>(whh, y, gates, q, dy, nullptr, T, N, H, reverse, cu_count, dgates, dq, ws, wsb, status,
+                           stream);
 }
 
 #ifdef TK_LAB

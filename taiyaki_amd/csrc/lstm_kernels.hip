@@ -23,7 +23,13 @@
 // in LDS and the workgroup stores the block as whole rows, 16 bytes per lane (rows_to_global, rnn_common.h): 3 store
 // instructions per workgroup and step at H 256, U 64, C 2 where the cell lanes issued 48.
 //
-// Three builds of this one source.  The flip-flop library takes the training pair: the forward that saves the gates
+// Columns.  A launch works on `cols.n` columns of tensors that hold `cols.ld()` columns per time step (rnn_common.h:
+// Cols).  The two are one number everywhere but in the -DTK_RNN_WIDE build, which runs a batch wider than the admission
+// rule takes as slabs of columns, one admitted launch after the other, in place (`checked`; lstm_slab).
+//
+// Four builds of this one source.  -DTK_RNN_WIDE (libtaiyaki_amd_rnn_wide.so) takes the three VL forms, the saving
+// forward, the forward with nothing saved and the backward, with the tensors' columns per time step as a kernel argument
+// of its own (DESIGN.md "Batches wider than one launch").  The flip-flop library takes the training pair: the forward that saves the gates
 // and c, and the backward.  -DTK_RNN_VARLEN (libtaiyaki_amd_rnn_varlen.so) takes the forward alone in its VL form with
 // nothing saved: per-column lengths, y the only output (DESIGN.md "Variable-length recurrences").
 // -DTK_RNN_VARLEN_TRAIN (libtaiyaki_amd_rnn_varlen_train.so) takes the training pair in its VL form: the saving forward
@@ -60,7 +66,7 @@ constexpr int bwd_threads_for() { return U == 48 ? 2 * H : threads_for<U>(); }
 // they are not written (the pointers are not read); y goes out from the cell lane's register, one step late.
 template <int H, int C, int U, bool VL = false, bool SAVE = !VL>
 __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const float *__restrict__ gx,
-                                                                       const float *__restrict__ whh, int T, int N,
+                                                                       const float *__restrict__ whh, int T, Cols cols,
                                                                        int reverse, int ngroups,
                                                                        float *__restrict__ y,
                                                                        float *__restrict__ gates,
@@ -68,6 +74,7 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
                                                                        uint32_t *status,
                                                                        const int32_t *__restrict__ lengths) {
     constexpr int NT = threads_for<U>();
+    const int N = cols.n, LD = cols.ld();               // the launch's columns; the tensors' columns per time step
     constexpr int G = H / U;
     constexpr int KP = NT / U;
     constexpr int KS = H / KP;
@@ -119,13 +126,13 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
             const int q = tid + i * NT, row = q / U4, v = row / C, nn = n0 + row % C;
             const size_t w = v < 2 ? (size_t)H : H4;
             float *base = v == 0 ? y : v == 1 ? cell : gates + (size_t)(v - 2) * H;
-            rpitch[i] = (size_t)N * w;
+            rpitch[i] = (size_t)LD * w;
             rp[i] = q < 6 * C * U4 && nn < N ? base + (size_t)nn * w + j0 + 4 * (q % U4) : nullptr;
         }
     }
     float gq[4] = {0.f, 0.f, 0.f, 0.f};              // gx of this step (loaded one step ahead)
     if (valid) {
-        const float *p = gx + ((size_t)(reverse ? T - 1 : 0) * N + n) * H4 + j0 + u;
+        const float *p = gx + ((size_t)(reverse ? T - 1 : 0) * LD + n) * H4 + j0 + u;
 #pragma unroll
         for (int g = 0; g < 4; ++g) gq[g] = p[(size_t)g * H];
     }
@@ -149,14 +156,14 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
             if (give_up) return;
             const int tl = reverse ? t + 1 : t - 1;
             if constexpr (!SAVE) {
-                if (valid) y[((size_t)tl * N + n) * H + j0 + u] = held;
+                if (valid) y[((size_t)tl * LD + n) * H + j0 + u] = held;
             } else {
                 rows_to_global<NQ>(stg[(s - 1) & 1], tid, NT, rp, rpitch, (size_t)tl);
             }
         }
         float gn[4] = {0.f, 0.f, 0.f, 0.f};
         if (valid && s + 1 < T) {
-            const float *p = gx + ((size_t)(reverse ? t - 1 : t + 1) * N + n) * H4 + j0 + u;
+            const float *p = gx + ((size_t)(reverse ? t - 1 : t + 1) * LD + n) * H4 + j0 + u;
 #pragma unroll
             for (int g = 0; g < 4; ++g) gn[g] = p[(size_t)g * H];
         }
@@ -229,7 +236,7 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
     if (T > 0) {
         const int tl = reverse ? 0 : T - 1;
         if constexpr (!SAVE) {
-            if (valid) y[((size_t)tl * N + n) * H + j0 + u] = held;
+            if (valid) y[((size_t)tl * LD + n) * H + j0 + u] = held;
         } else {
             __syncthreads();                             // the last step's block: no poll, so no barrier, is behind it
             rows_to_global<NQ>(stg[(T - 1) & 1], tid, NT, rp, rpitch, (size_t)tl);
@@ -254,12 +261,13 @@ template <int H, int C, int U, bool VL = false>
 __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(const float *__restrict__ whh,
                                                                        const float *__restrict__ gates,
                                                                        const float *__restrict__ cell,
-                                                                       const float *__restrict__ dy, int T, int N,
+                                                                       const float *__restrict__ dy, int T, Cols cols,
                                                                        int reverse, int ngroups,
                                                                        float *__restrict__ dgates, u64 *pbuf,
                                                                        uint32_t *status,
                                                                        const int32_t *__restrict__ lengths) {
     constexpr int NT = bwd_threads_for<H, U>();
+    const int N = cols.n, LD = cols.ld();               // the launch's columns; the tensors' columns per time step
     constexpr int G = H / U;
     constexpr bool STRIDED = U == 48;                 // a lane's rows: every RP-th, not R in a run
     constexpr int RP = NT / H;                        // row partitions: lane (k, rp) holds W_hh[rows of rp, k]
@@ -311,11 +319,11 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
     float in[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (valid) {
         const int t = reverse ? 0 : T - 1;
-        const size_t o = ((size_t)t * N + n) * H + j0 + u;
+        const size_t o = ((size_t)t * LD + n) * H + j0 + u;
         in[0] = dy[o];
         in[1] = cell[o];
-        if (T > 1) in[2] = cell[((size_t)(reverse ? t + 1 : t - 1) * N + n) * H + j0 + u];
-        const float *gp = gates + ((size_t)t * N + n) * H4 + j0 + u;
+        if (T > 1) in[2] = cell[((size_t)(reverse ? t + 1 : t - 1) * LD + n) * H + j0 + u];
+        const float *gp = gates + ((size_t)t * LD + n) * H4 + j0 + u;
 #pragma unroll
         for (int g = 0; g < 4; ++g) in[3 + g] = gp[(size_t)g * H];
     }
@@ -347,18 +355,18 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
             }
             if (valid) {
                 const int tl = reverse ? t - 1 : t + 1;
-                float *dp = dgates + ((size_t)tl * N + n) * H4 + j0 + u;
+                float *dp = dgates + ((size_t)tl * LD + n) * H4 + j0 + u;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) dp[(size_t)g * H] = held[g];
             }
         }
         float nx[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (valid && tt > 0) {
-            const size_t o = ((size_t)tp * N + n) * H + j0 + u;
+            const size_t o = ((size_t)tp * LD + n) * H + j0 + u;
             nx[0] = dy[o];
             nx[1] = in[2];
-            if (tt > 1) nx[2] = cell[((size_t)(reverse ? tp + 1 : tp - 1) * N + n) * H + j0 + u];
-            const float *gp = gates + ((size_t)tp * N + n) * H4 + j0 + u;
+            if (tt > 1) nx[2] = cell[((size_t)(reverse ? tp + 1 : tp - 1) * LD + n) * H + j0 + u];
+            const float *gp = gates + ((size_t)tp * LD + n) * H4 + j0 + u;
 #pragma unroll
             for (int g = 0; g < 4; ++g) nx[3 + g] = gp[(size_t)g * H];
         }
@@ -426,7 +434,7 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
     }
     if (valid && T > 0) {
         const int tl = reverse ? T - 1 : 0;
-        float *dp = dgates + ((size_t)tl * N + n) * H4 + j0 + u;
+        float *dp = dgates + ((size_t)tl * LD + n) * H4 + j0 + u;
 #pragma unroll
         for (int g = 0; g < 4; ++g) dp[(size_t)g * H] = held[g];
     }
@@ -508,12 +516,12 @@ bool lstm_plan(size_t N, size_t H, int cu_count, Plan *p) {
     }
 
 template <bool VL, bool SAVE>
-int launch_fwd(const Plan &p, size_t H, hipStream_t st, const float *gx, const float *whh, int T, int N, int rev,
-               float *y, float *gates, float *cell, u64 *ws, uint32_t *status, const int32_t *lengths) {
+int launch_fwd(const Plan &p, size_t H, hipStream_t st, const float *gx, const float *whh, int T, Cols cols,
+               int rev, float *y, float *gates, float *cell, u64 *ws, uint32_t *status, const int32_t *lengths) {
 #define TK_LSTM_FWD(HH, UU, CC)                                                                                  \
     case HH * 100000 + UU * 1000 + CC:                                                                           \
         hipLaunchKernelGGL((lstm_fwd_kernel<HH, CC, UU, VL, SAVE>), dim3(p.grid), dim3(threads_for<UU>()), 0, st, gx,  \
-                           whh, T, N, rev, p.groups, y, gates, cell, ws, status, lengths);                       \
+                           whh, T, cols, rev, p.groups, y, gates, cell, ws, status, lengths);                    \
         break;
     TK_LSTM_SWITCH(TK_LSTM_FWD)
 #undef TK_LSTM_FWD
@@ -523,11 +531,12 @@ int launch_fwd(const Plan &p, size_t H, hipStream_t st, const float *gx, const f
 #ifndef TK_RNN_VARLEN
 template <bool VL>
 int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const float *gates, const float *cell,
-               const float *dy, int T, int N, int rev, float *dg, u64 *ws, uint32_t *status, const int32_t *lengths) {
+               const float *dy, int T, Cols cols, int rev, float *dg, u64 *ws, uint32_t *status,
+               const int32_t *lengths) {
 #define TK_LSTM_BWD(HH, UU, CC)                                                                                   \
     case HH * 100000 + UU * 1000 + CC:                                                                            \
         hipLaunchKernelGGL((lstm_bwd_kernel<HH, CC, UU, VL>), dim3(p.grid), dim3(bwd_threads_for<HH, UU>()), 0,   \
-                           st, whh, gates, cell, dy, T, N, rev, p.groups, dg, ws, status, lengths);               \
+                           st, whh, gates, cell, dy, T, cols, rev, p.groups, dg, ws, status, lengths);            \
         break;
     TK_LSTM_SWITCH(TK_LSTM_BWD)
 #undef TK_LSTM_BWD
@@ -536,22 +545,45 @@ int launch_bwd(const Plan &p, size_t H, hipStream_t st, const float *whh, const 
 #endif  // TK_RNN_VARLEN
 #undef TK_LSTM_SWITCH
 
+// The slab width of a batch of N columns (rnn_common.h has the rule): the widest batch lstm_geometry admits at
+// (H, cu_count), or N where one launch admits the batch; 0 where the kernels do not run.
+size_t lstm_slab(size_t N, size_t H, int cu_count) {
+    int C = 0, groups = 0;
+    const size_t S = widest_admitted([&](size_t n) { return lstm_geometry(n, H, cu_count, &C, &groups); });
+    return N == 0 ? 0 : N < S ? N : S;
+}
+
 // What every dispatcher below does around its launch, written once: the pointer and range checks (`pointers_ok`: the
-// entry's own required pointers), the plan, the workspace's size, nothing to do at T == 0, the granules zeroed, then
-// `launch(plan)`.
+// entry's own required pointers), then for every slab of the batch its plan, the workspace's size, nothing to do at
+// T == 0, the granules zeroed, then `launch(plan, the slab's first column, its columns)`.  The -DTK_RNN_WIDE build alone
+// cuts a batch: everywhere else the one slab is the batch, and a batch that no launch admits is refused.  The slabs
+// share the workspace and follow each other on `stream`: two persistent grids at once could together exceed the CUs
+// and wait on each other for ever.  The first slab is the widest, so it has the largest plan: a later slab cannot fail
+// a check that the first passed, and a launch error returns at once, with no further slab started.
 template <class Launch>
 int checked(bool pointers_ok, size_t T, size_t N, size_t H, int cu_count, void *ws, size_t wsb, uint32_t *status,
             hipStream_t stream, bool backward, Launch launch) {
     if (!pointers_ok || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX || N > (size_t)INT32_MAX)
         return TK_ERR_BAD_ARG;
-    Plan p;
-    if (!lstm_plan(N, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    const size_t need = ws_bytes(H, p.C, p.groups, p.U, backward);
-    if (wsb < need) return TK_ERR_WORKSPACE;
-    if (T == 0) return TK_OK;
-    int rc = zero_ws(ws, need, stream);
-    if (rc != TK_OK) return rc;
-    return launch(p);
+#ifdef TK_RNN_WIDE
+    const size_t S = lstm_slab(N, H, cu_count);
+#else
+    const size_t S = N;
+#endif
+    if (S == 0) return TK_ERR_UNSUPPORTED;
+    for (size_t first = 0; first < N; first += S) {
+        const size_t n = N - first < S ? N - first : S;
+        Plan p;
+        if (!lstm_plan(n, H, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+        const size_t need = ws_bytes(H, p.C, p.groups, p.U, backward);
+        if (wsb < need) return TK_ERR_WORKSPACE;
+        if (T == 0) continue;
+        int rc = zero_ws(ws, need, stream);
+        if (rc != TK_OK) return rc;
+        rc = launch(p, first, make_cols(n, N));
+        if (rc != TK_OK) return rc;
+    }
+    return TK_OK;
 }
 
 // the backward's granule bytes at U = 16 (H = 192, 384: at the launch's U = 48): they bound every plan's, forward and
@@ -562,6 +594,35 @@ size_t train_workspace_bytes(size_t N, size_t H, int cu_count) {
     const int U48 = units48(H);
     return ws_bytes(H, C, groups, U48 ? U48 : 16, true);
 }
+
+// The forward and the backward of every dispatcher below: `checked`, whose launch of a slab takes the tensors, and
+// `lengths`, advanced to the slab's first column.
+template <bool VL, bool SAVE>
+int forward(const float *gx, const float *whh, const int32_t *lengths, size_t T, size_t N, size_t H, int reverse,
+            int cu_count, float *y, float *gates, float *cell, void *ws, size_t wsb, uint32_t *status,
+            hipStream_t stream) {
+    auto launch = [&](const Plan &p, size_t first, Cols cols) {
+        return launch_fwd<VL, SAVE>(p, H, stream, at_column(gx, first, 4 * H), whh, (int)T, cols, reverse,
+                                    at_column(y, first, H), at_column(gates, first, 4 * H), at_column(cell, first, H),
+                                    static_cast<u64 *>(ws), status, at_column(lengths, first, 1));
+    };
+    return checked(gx && whh && y && (!SAVE || (gates && cell)), T, N, H, cu_count, ws, wsb, status, stream, false,
+                   launch);
+}
+
+#ifndef TK_RNN_VARLEN
+template <bool VL>
+int backward(const float *whh, const float *gates, const float *cell, const float *dy, const int32_t *lengths,
+             size_t T, size_t N, size_t H, int reverse, int cu_count, float *dgates, void *ws, size_t wsb,
+             uint32_t *status, hipStream_t stream) {
+    auto launch = [&](const Plan &p, size_t first, Cols cols) {
+        return launch_bwd<VL>(p, H, stream, whh, at_column(gates, first, 4 * H), at_column(cell, first, H),
+                              at_column(dy, first, H), (int)T, cols, reverse, at_column(dgates, first, 4 * H),
+                              static_cast<u64 *>(ws), status, at_column(lengths, first, 1));
+    };
+    return checked(whh && gates && cell && dy && dgates, T, N, H, cu_count, ws, wsb, status, stream, true, launch);
+}
+#endif
 
 }  // namespace
 
@@ -577,11 +638,8 @@ size_t lstm_varlen_workspace_bytes(size_t N, size_t H, int cu_count) {
 int lstm_forward_varlen_dispatch(const float *gx, const float *whh, const int32_t *lengths, size_t T, size_t N,
                                  size_t H, int reverse, int cu_count, float *y, void *ws, size_t wsb,
                                  uint32_t *status, hipStream_t stream) {
-    auto launch = [&](const Plan &p) {
-        return launch_fwd<true, false>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, nullptr, nullptr,
-                                       static_cast<u64 *>(ws), status, lengths);
-    };
-    return checked(gx && whh && y, T, N, H, cu_count, ws, wsb, status, stream, false, launch);
+    return forward<true, false>(gx, whh, lengths, T, N, H, reverse, cu_count, y, nullptr, nullptr, ws, wsb, status,
+                                stream);
 }
 #elif defined(TK_RNN_VARLEN_TRAIN)
 // The training pair with per-column lengths (include/taiyaki_amd_rnn_varlen_train.h): the plans, grids and granule
@@ -594,21 +652,40 @@ size_t lstm_varlen_train_workspace_bytes(size_t N, size_t H, int cu_count) {
 int lstm_forward_varlen_save_dispatch(const float *gx, const float *whh, const int32_t *lengths, size_t T, size_t N,
                                       size_t H, int reverse, int cu_count, float *y, float *gates, float *cell,
                                       void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
-    auto launch = [&](const Plan &p) {
-        return launch_fwd<true, true>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, gates, cell,
-                                      static_cast<u64 *>(ws), status, lengths);
-    };
-    return checked(gx && whh && y && gates && cell, T, N, H, cu_count, ws, wsb, status, stream, false, launch);
+    return forward<true, true>(gx, whh, lengths, T, N, H, reverse, cu_count, y, gates, cell, ws, wsb, status, stream);
 }
 
 int lstm_backward_varlen_dispatch(const float *whh, const float *gates, const float *cell, const float *dy,
                                   const int32_t *lengths, size_t T, size_t N, size_t H, int reverse, int cu_count,
                                   float *dgates, void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
-    auto launch = [&](const Plan &p) {
-        return launch_bwd<true>(p, H, stream, whh, gates, cell, dy, (int)T, (int)N, reverse, dgates,
-                                static_cast<u64 *>(ws), status, lengths);
-    };
-    return checked(whh && gates && cell && dy && dgates, T, N, H, cu_count, ws, wsb, status, stream, true, launch);
+    return backward<true>(whh, gates, cell, dy, lengths, T, N, H, reverse, cu_count, dgates, ws, wsb, status, stream);
+}
+#elif defined(TK_RNN_WIDE)
+// Every batch width at the sizes the kernels cover (include/taiyaki_amd_rnn_wide.h): the VL forms, on one slab of
+// lstm_slab columns after the other.  A batch that one launch admits is one slab: the call of the training pair with
+// per-column lengths, or of the forward that saves nothing, at the same (N, H, cu_count).
+size_t lstm_wide_slab(size_t N, size_t H, int cu_count) { return lstm_slab(N, H, cu_count); }
+
+// the training pair's workspace at the widest slab, the first
+size_t lstm_wide_workspace_bytes(size_t N, size_t H, int cu_count) {
+    return train_workspace_bytes(lstm_slab(N, H, cu_count), H, cu_count);
+}
+
+// gates and cell may both be NULL: nothing is saved
+int lstm_forward_wide_dispatch(const float *gx, const float *whh, const int32_t *lengths, size_t T, size_t N,
+                               size_t H, int reverse, int cu_count, float *y, float *gates, float *cell, void *ws,
+                               size_t wsb, uint32_t *status, hipStream_t stream) {
+    if (!gates != !cell) return TK_ERR_BAD_ARG;
+    return gates ? forward<true, true>(gx, whh, lengths, T, N, H, reverse, cu_count, y, gates, cell, ws, wsb, status,
+                                       stream)
+                 : forward<true, false>(gx, whh, lengths, T, N, H, reverse, cu_count, y, nullptr, nullptr, ws, wsb,
+                                        status, stream);
+}
+
+int lstm_backward_wide_dispatch(const float *whh, const float *gates, const float *cell, const float *dy,
+                                const int32_t *lengths, size_t T, size_t N, size_t H, int reverse, int cu_count,
+                                float *dgates, void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
+    return backward<true>(whh, gates, cell, dy, lengths, T, N, H, reverse, cu_count, dgates, ws, wsb, status, stream);
 }
 #else
 size_t lstm_workspace_bytes(size_t N, size_t H, int cu_count) { return train_workspace_bytes(N, H, cu_count); }
@@ -616,21 +693,13 @@ size_t lstm_workspace_bytes(size_t N, size_t H, int cu_count) { return train_wor
 int lstm_forward_dispatch(const float *gx, const float *whh, size_t T, size_t N, size_t H, int reverse,
                           int cu_count, float *y, float *gates, float *cell, void *ws, size_t wsb,
                           uint32_t *status, hipStream_t stream) {
-    auto launch = [&](const Plan &p) {
-        return launch_fwd<false, true>(p, H, stream, gx, whh, (int)T, (int)N, reverse, y, gates, cell,
-                                       static_cast<u64 *>(ws), status, nullptr);
-    };
-    return checked(gx && whh && y && gates && cell, T, N, H, cu_count, ws, wsb, status, stream, false, launch);
+    return forward<false, true>(gx, whh, nullptr, T, N, H, reverse, cu_count, y, gates, cell, ws, wsb, status, stream);
 }
 
 int lstm_backward_dispatch(const float *whh, const float *gates, const float *cell, const float *dy, size_t T,
                            size_t N, size_t H, int reverse, int cu_count, float *dgates, void *ws, size_t wsb,
                            uint32_t *status, hipStream_t stream) {
-    auto launch = [&](const Plan &p) {
-        return launch_bwd<false>(p, H, stream, whh, gates, cell, dy, (int)T, (int)N, reverse, dgates,
-                                 static_cast<u64 *>(ws), status, nullptr);
-    };
-    return checked(whh && gates && cell && dy && dgates, T, N, H, cu_count, ws, wsb, status, stream, true, launch);
+    return backward<false>(whh, gates, cell, dy, nullptr, T, N, H, reverse, cu_count, dgates, ws, wsb, status, stream);
 }
 
 #ifdef TK_LAB

@@ -19,6 +19,51 @@ namespace {
 
 constexpr uint64_t kSpinTicks = 200000000ull;   // 2 s of s_memrealtime (100 MHz) per wait
 
+// The columns of a launch: n of them, in tensors that hold ld >= n columns per time step (row (t, column) is row
+// t * ld + column of a tensor; the pointers, `lengths` among them, stand at the launch's first column).  ld != n is a
+// window of columns of a wider batch (DESIGN.md "Batches wider than one launch"), which the -DTK_RNN_WIDE build alone
+// launches: there ld is a kernel argument.  In every other build ld is n itself, as a kernel argument this is one int,
+// and the kernels are instruction for instruction what they were when they took n alone.
+struct Cols {
+    int n;
+#ifdef TK_RNN_WIDE
+    int pitch;
+    __host__ __device__ int ld() const { return pitch; }
+#else
+    __host__ __device__ int ld() const { return n; }
+#endif
+};
+
+inline Cols make_cols(size_t n, size_t ld) {
+#ifdef TK_RNN_WIDE
+    return Cols{(int)n, (int)ld};
+#else
+    return Cols{(int)n};
+#endif
+}
+
+// p advanced to column `first` of a tensor with `width` floats per column (lengths: width 1); NULL stays NULL
+template <class P>
+P *at_column(P *p, size_t first, size_t width) {
+    return p ? p + first * width : p;
+}
+
+// The slab rule (DESIGN.md "Batches wider than one launch").  A batch wider than one launch admits runs as slabs of S
+// columns, slab k being columns [k S, min((k + 1) S, N)), one launch after the other on the caller's stream.  S is the
+// widest batch the cell's admission rule admits at (size, cu_count); that rule is monotone in N, so S is found from the
+// rule itself, by bisection, and is never restated.  0: the rule admits no batch; INT32_MAX: it admits every batch.
+template <class Admits>
+size_t widest_admitted(Admits admits) {
+    size_t lo = 1, hi = (size_t)INT32_MAX;
+    if (!admits(lo)) return 0;
+    if (admits(hi)) return hi;
+    while (hi - lo > 1) {                              // admits(lo) && !admits(hi)
+        const size_t mid = lo + (hi - lo) / 2;
+        (admits(mid) ? lo : hi) = mid;
+    }
+    return lo;
+}
+
 typedef unsigned long long u64;
 typedef __attribute__((address_space(1))) u64 gu64;
 typedef __attribute__((address_space(1))) uint32_t gu32;

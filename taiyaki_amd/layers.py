@@ -15,6 +15,8 @@ that feeds them.
 * ``forward_varlen`` runs a ``Serial`` on a batch whose columns have different lengths: every column's rows are what
   the column gives run alone (``Lstm`` / ``GruMod`` ``forward(x, reverse, lengths)`` on the forward-only launches of
   include/taiyaki_amd_rnn_varlen.h; under grad mode on the training pair of include/taiyaki_amd_rnn_varlen_train.h).
+* A batch wider than one launch of a recurrence admits runs as slabs of columns, one admitted launch after the other
+  (include/taiyaki_amd_rnn_wide.h; USE_HIP_RNN_WIDE).
 """
 import numpy as np
 import torch
@@ -330,6 +332,14 @@ TRAIN_VARLEN = False
 # HIP launches of `Lstm` / `GruMod` `forward(x, reverse, lengths)` by kind: "saved" wrote the activations for a backward
 # pass (include/taiyaki_amd_rnn_varlen_train.h), "inference" saved nothing (include/taiyaki_amd_rnn_varlen.h)
 rnn_varlen_calls = {"saved": 0, "inference": 0}
+# True: a batch wider than one launch of a recurrence admits (hip_lstm_workspace_bytes / hip_gru_workspace_bytes or the
+# query with lengths for the call returns 0 for its width alone) runs on the entries of include/taiyaki_amd_rnn_wide.h,
+# as slabs of columns, one admitted launch after the other, wherever `hip_rnn_wide_workspace_bytes` is not 0.
+# False: such a batch runs nn.LSTM / nn.GRU (with lengths: every column alone), as it did before there were slabs
+USE_HIP_RNN_WIDE = True
+# calls of `Lstm` / `GruMod` that went through include/taiyaki_amd_rnn_wide.h by kind, as rnn_varlen_calls counts: "saved"
+# wrote the activations for a backward pass, "inference" saved nothing
+rnn_wide_calls = {"saved": 0, "inference": 0}
 # False: the parameter gradients of LstmRecurrence.backward are two GEMMs and a sum over dG (what they are wherever
 # tk_lstm_weight_grad_workspace_bytes is 0), for comparisons against the fused kernel
 USE_HIP_LSTM_WGRAD = True
@@ -387,25 +397,46 @@ def _hip_lstm_takes(rnn, x):
     return not (rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias or rnn.batch_first or rnn.proj_size)
 
 
-# What a recurrence launches, by (per-column lengths given, activations saved): the library (its accessor in _lib), the
-# forward and the backward entry ("%s": lstm / gru) and the workspace's tag (None: the cell's own).
+def hip_rnn_wide_workspace_bytes(rnn, x):
+    """Workspace of the entries of include/taiyaki_amd_rnn_wide.h for this nn.LSTM or nn.GRU and input: not 0 at every
+    batch width where the HIP recurrence covers the layer and its size (what `hip_lstm_workspace_bytes` /
+    `hip_gru_workspace_bytes` rule out apart from the width, under the same switches), 0 elsewhere and with
+    USE_HIP_RNN_WIDE = False."""
+    lstm = isinstance(rnn, nn.LSTM)
+    if not (USE_HIP_RNN_WIDE and (_hip_lstm_takes(rnn, x) if lstm else _hip_gru_takes(rnn, x))):
+        return 0
+    kind = _lib.VARLEN_DEFINES["TK_RNN_KIND_LSTM" if lstm else "TK_RNN_KIND_GRU"]
+    return _lib.rnn_wide_lib().tk_rnn_wide_workspace_bytes(kind, x.shape[1], rnn.hidden_size, _cu_count(x.device))
+
+
+# What a recurrence launches, by (per-column lengths given, or "wide": a batch cut into slabs; activations saved): the
+# library (its accessor in _lib), the forward and the backward entry ("%s": lstm / gru) and the workspace's tag (None:
+# the cell's own).  The wide entries take the lengths (NULL: none) and all the forward's outputs (NULL: not saved).
 _RNN_LAUNCHES = {
     (False, True): ("lib", "tk_%s_forward_dev", "tk_%s_backward_dev", None),
     (False, False): ("lib", "tk_%s_forward_dev", None, None),       # the GRU alone: NULL for the activations
     (True, True): ("varlen_train_lib", "tk_%s_forward_varlen_save_dev", "tk_%s_backward_varlen_dev",
                    "rnn_varlen_train"),
     (True, False): ("varlen_lib", "tk_%s_forward_varlen_dev", None, "rnn_varlen"),
+    ("wide", True): ("rnn_wide_lib", "tk_%s_forward_wide_dev", "tk_%s_backward_wide_dev", "rnn_wide"),
+    ("wide", False): ("rnn_wide_lib", "tk_%s_forward_wide_dev", None, "rnn_wide"),
 }
 
 
-def _rnn_launch(cell, lens, save, backward, ins, shape, reverse, outs, wsb, dev):
-    """One launch of a recurrence, checked: the entry of _RNN_LAUNCHES on `ins` (the lengths behind them where given),
-    T, N, H, the direction and the CU count, `outs`, then the workspace, the status word and the stream."""
-    libname, fwd, bwd, tag = _RNN_LAUNCHES[lens is not None, bool(save)]
+def _rnn_row(lens, wide):
+    """The first half of a key of _RNN_LAUNCHES."""
+    return "wide" if wide else lens is not None
+
+
+def _rnn_launch(cell, row, lens, save, backward, ins, shape, reverse, outs, wsb, dev):
+    """One launch of a recurrence, checked: the entry of _RNN_LAUNCHES[row, save] on `ins` (the lengths behind them where
+    the entry takes them), T, N, H, the direction and the CU count, `outs`, then the workspace, the status word and the
+    stream."""
+    libname, fwd, bwd, tag = _RNN_LAUNCHES[row, bool(save)]
     name = (bwd if backward else fwd) % cell
     ws = _lib.workspace(wsb, dev, tag or cell)
     status = _lib.status_word(dev)
-    ptrs = [_lib.ptr(t) for t in ins + (() if lens is None else (lens,))]
+    ptrs = [_lib.ptr(t) for t in ins + ((lens,) if row else ())]
     rc = getattr(getattr(_lib, libname)(), name)(*ptrs, *shape, int(reverse), _cu_count(dev),
                                                  *[_lib.ptr(t) for t in outs], _lib.ptr(ws), wsb, _lib.ptr(status),
                                                  _lib.stream_ptr())
@@ -424,25 +455,28 @@ class LstmRecurrence(torch.autograd.Function):
     of include/taiyaki_amd_rnn_varlen.h: nothing but y is allocated or written, and the call cannot be differentiated."""
 
     @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, wsb, lens=None, save=True):
-        if lens is None and not save:
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, wsb, lens=None, save=True, wide=False):
+        if lens is None and not save and not wide:
             raise RuntimeError("the LSTM has no launch without lengths that saves nothing")
         T, N, _ = x.shape
         H = w_hh.shape[1]
         dev = x.device
         x = x.contiguous()
         w_hh = w_hh.contiguous()
-        if lens is not None:
+        if wide:
+            rnn_wide_calls["saved" if save else "inference"] += 1
+        elif lens is not None:
             rnn_varlen_calls["saved" if save else "inference"] += 1
+        row = _rnn_row(lens, wide)
         gx = _rnn_proj(x.view(T * N, -1), w_ih, b_ih + b_hh, False)
         y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
         gates = torch.empty(T, N, 4 * H, dtype=torch.float32, device=dev) if save else None
         cell = torch.empty(T, N, H, dtype=torch.float32, device=dev) if save else None
-        _rnn_launch("lstm", lens, save, False, (gx, w_hh), (T, N, H), reverse, (y, gates, cell) if save else (y,), wsb,
-                    dev)
+        _rnn_launch("lstm", row, lens, save, False, (gx, w_hh), (T, N, H), reverse,
+                    (y, gates, cell) if save or wide else (y,), wsb, dev)
         if save:
             ctx.save_for_backward(x, w_ih, w_hh, y, gates, cell, lens)
-        ctx.reverse, ctx.wsb = reverse, wsb
+        ctx.reverse, ctx.wsb, ctx.row = reverse, wsb, row
         return y
 
     @staticmethod
@@ -452,8 +486,9 @@ class LstmRecurrence(torch.autograd.Function):
         H = w_hh.shape[1]
         dy = dy.contiguous()
         dg = torch.empty_like(gates)
-        _rnn_launch("lstm", lens, True, True, (w_hh, gates, cell, dy), (T, N, H), ctx.reverse, (dg,), ctx.wsb, x.device)
-        return _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None,) * 4
+        _rnn_launch("lstm", ctx.row, lens, True, True, (w_hh, gates, cell, dy), (T, N, H), ctx.reverse, (dg,), ctx.wsb,
+                    x.device)
+        return _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None,) * 5
 
 
 def _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, reverse, need):
@@ -493,7 +528,8 @@ def _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, reverse, need):
 
 class Lstm(_Rnn):
     """layers.py:491-606 (wraps nn.LSTM, bias_hh frozen).  On the GPU the recurrence runs on the HIP kernels
-    (`LstmRecurrence`); nn.LSTM evaluates CPU tensors, sizes the kernels do not cover, and USE_HIP_LSTM = False."""
+    (`LstmRecurrence`), a batch wider than one launch admits as slabs of columns; nn.LSTM evaluates CPU tensors, sizes the
+    kernels do not cover, and USE_HIP_LSTM = False."""
 
     def __init__(self, insize, size):
         super().__init__(nn.LSTM(insize, size))
@@ -506,6 +542,10 @@ class Lstm(_Rnn):
         if wsb:
             return LstmRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
                                         bool(reverse), wsb)
+        wsb = hip_rnn_wide_workspace_bytes(rnn, x) if x.dim() == 3 and x.shape[0] and x.shape[1] else 0
+        if wsb:     # a batch wider than one launch admits: slabs of columns (the activations saved, as above)
+            return LstmRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
+                                        bool(reverse), wsb, None, True, True)
         if reverse:
             return torch.flip(rnn(torch.flip(x, (0,)))[0], (0,))
         return rnn(x)[0]
@@ -576,7 +616,7 @@ class GruRecurrence(torch.autograd.Function):
     over the whole padded tensors."""
 
     @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, wsb, save, lens=None):
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, wsb, save, lens=None, wide=False):
         T, N, _ = x.shape
         H = w_hh.shape[1]
         dev = x.device
@@ -584,19 +624,22 @@ class GruRecurrence(torch.autograd.Function):
         w_hh, b_hh = w_hh.contiguous(), b_hh.contiguous()
         # (grad mode is off inside forward and ctx.needs_input_grad ignores it: the caller decides)
         train = bool(save)
-        if lens is not None:
+        if wide:
+            rnn_wide_calls["saved" if train else "inference"] += 1
+        elif lens is not None:
             rnn_varlen_calls["saved" if train else "inference"] += 1
         if lens is None or train:
             gru_forward_calls["saved" if train else "inference"] += 1
+        row = _rnn_row(lens, wide)
         gx = _rnn_proj(x.view(T * N, -1), w_ih, b_ih, False)
         y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
         gates = torch.empty(T, N, 3 * H, dtype=torch.float32, device=dev) if train else None
         q = torch.empty(T, N, H, dtype=torch.float32, device=dev) if train else None
-        _rnn_launch("gru", lens, train, False, (gx, w_hh, b_hh), (T, N, H), reverse,
-                    (y, gates, q) if train or lens is None else (y,), wsb, dev)
+        _rnn_launch("gru", row, lens, train, False, (gx, w_hh, b_hh), (T, N, H), reverse,
+                    (y, gates, q) if train or lens is None or wide else (y,), wsb, dev)
         if train:
             ctx.save_for_backward(x, w_ih, w_hh, y, gates, q, lens)
-        ctx.reverse, ctx.wsb = reverse, wsb
+        ctx.reverse, ctx.wsb, ctx.row = reverse, wsb, row
         return y
 
     @staticmethod
@@ -607,9 +650,9 @@ class GruRecurrence(torch.autograd.Function):
         dy = dy.contiguous()
         dg = torch.empty_like(gates)
         dq = torch.empty_like(q)
-        _rnn_launch("gru", lens, True, True, (w_hh, y, gates, q, dy), (T, N, H), ctx.reverse, (dg, dq), ctx.wsb,
+        _rnn_launch("gru", ctx.row, lens, True, True, (w_hh, y, gates, q, dy), (T, N, H), ctx.reverse, (dg, dq), ctx.wsb,
                     x.device)
-        return _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None,) * 4
+        return _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None,) * 5
 
 
 def _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, reverse, need):
@@ -661,7 +704,8 @@ def _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, reverse, need):
 
 class GruMod(_Rnn):
     """layers.py:609-725 (wraps nn.GRU, bias_hh frozen).  On the GPU the recurrence runs on the HIP kernels
-    (`GruRecurrence`); nn.GRU evaluates CPU tensors, sizes the kernels do not cover, and USE_HIP_GRU = False."""
+    (`GruRecurrence`), a batch wider than one launch admits as slabs of columns; nn.GRU evaluates CPU tensors, sizes the
+    kernels do not cover, and USE_HIP_GRU = False."""
 
     def __init__(self, insize, size):
         super().__init__(nn.GRU(insize, size))
@@ -675,6 +719,11 @@ class GruMod(_Rnn):
             params = (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)
             save = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
             return GruRecurrence.apply(x, *params, bool(reverse), wsb, save)
+        wsb = hip_rnn_wide_workspace_bytes(rnn, x) if x.dim() == 3 and x.shape[0] and x.shape[1] else 0
+        if wsb:     # a batch wider than one launch admits: slabs of columns
+            params = (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)
+            save = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+            return GruRecurrence.apply(x, *params, bool(reverse), wsb, save, None, True)
         if reverse:
             return torch.flip(rnn(torch.flip(x, (0,)))[0], (0,))
         return rnn(x)[0]
@@ -730,6 +779,9 @@ def _rnn_forward_varlen(layer, x, reverse, lengths):
         wsb = hip_rnn_varlen_train_workspace_bytes(rnn, x)
     else:
         wsb = hip_rnn_varlen_workspace_bytes(rnn, x)
+    wide = bool(T and N) and not wsb
+    if wide:        # a batch wider than one launch admits: slabs of columns
+        wsb = hip_rnn_wide_workspace_bytes(rnn, x)
     if not wsb:
         host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
         assert len(host) == N and (N == 0 or (host.min() >= 0 and host.max() <= T)), "lengths: one per column, 0..T"
@@ -743,8 +795,8 @@ def _rnn_forward_varlen(layer, x, reverse, lengths):
         assert lens.numel() == N, "lengths: one per column"
         args = (x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0, bool(reverse), wsb)
         if isinstance(rnn, nn.LSTM):
-            return LstmRecurrence.apply(*args, lens, train)
-        return GruRecurrence.apply(*args, train, lens)
+            return LstmRecurrence.apply(*args, lens, train, wide)
+        return GruRecurrence.apply(*args, train, lens, wide)
 
 
 class Reverse(nn.Module):

@@ -5,7 +5,8 @@ False: what a size the kernels refuse runs), in turns on one model and one batch
 step (median over --steps per turn).  Both models are built with the trainer's stride, 5: chunk_len 4000 is T = 800.
 --switch NAME flips that switch of `layers` instead (USE_HIP_GRU_WGRAD, USE_HIP_LSTM_WGRAD: the fused weight-gradient
 kernel against the GEMMs, the recurrence on the HIP kernels in both turns); the lists are then `on_ms_per_step` and
-`off_ms_per_step`.
+`off_ms_per_step`.  --switch USE_HIP_RNN_WIDE at a batch wider than one launch of the recurrence admits (say --size 384
+--chunks 341): the slabs of include/taiyaki_amd_rnn_wide.h against nn.LSTM / nn.GRU.
 
     python tools/sizebench.py [--model mLstm_flipflop] [--size 384] [--chunk-len 4000] [--chunks 128] [--pairs 3]
                               [--steps 5] [--warmup 2] [--switch NAME]
@@ -48,7 +49,9 @@ def main():
     probe = torch.zeros(a.chunk_len // stride, a.chunks, a.size, device=dev)
     rnns = [m for m in net.modules() if isinstance(m, layers.GruMod if gru else layers.Lstm)]
     query = layers.hip_gru_workspace_bytes if gru else layers.hip_lstm_workspace_bytes
-    if not (len(rnns) == 5 and all(query(m.rnn, probe) > 0 for m in rnns)):
+    # (a batch wider than one launch admits runs as slabs of columns: layers.USE_HIP_RNN_WIDE, the switch to flip for it)
+    if not (len(rnns) == 5 and all(query(m.rnn, probe) > 0 or layers.hip_rnn_wide_workspace_bytes(m.rnn, probe) > 0
+                                   for m in rnns)):
         raise SystemExit("size %d x %d chunks is not admitted on %d CUs" % (a.size, a.chunks, layers._cu_count(dev)))
     sl = synth.realistic_seqlens(a.chunk_len // stride, a.chunks, 8, a.chunk_len, 9.0)
     sq, _ = synth.sequences(sl, 8)
