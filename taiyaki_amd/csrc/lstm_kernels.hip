@@ -36,6 +36,7 @@
 // and the backward with per-column lengths (DESIGN.md "Training through variable-length batches").
 #include "dispatch.h"
 #include "ff_common.h"
+#include "lstm_bwd_layout.h"
 #include "rnn_common.h"
 
 namespace tk {
@@ -245,6 +246,40 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
 }
 
 #ifndef TK_RNN_VARLEN
+// The value of lane (lane ^ M) of the wave.  M = 1 and 2 are one quad permutation, M = 4 a mirror of the half row and a
+// reversal of the quad (i -> 7 - i -> i ^ 4): DPP operands of the VALU, which the compiler folds into the add that uses
+// them where it can.  They stay off the LDS crossbar, where a ds_bpermute_b32 takes its turn behind the matvec's reads.
+template <int M>
+__device__ __forceinline__ float xor_lane(float v) {
+    static_assert(M == 1 || M == 2 || M == 4, "a partner inside the lane's group of 8");
+    const int x = __float_as_int(v);
+    if constexpr (M == 1) {
+        return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true));      // quad_perm:[1,0,3,2]
+    } else if constexpr (M == 2) {
+        return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true));      // quad_perm:[2,3,0,1]
+    } else {
+        const int y = __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true);              // row_half_mirror
+        return __int_as_float(__builtin_amdgcn_update_dpp(0, y, 0x1B, 0xF, 0xF, true));      // quad_perm:[3,2,1,0]
+    }
+}
+
+// Recursive halving over the lanes rq ^ M, M = M0, 2 M0, ... < RQ (lstm_bwd_layout.h): each round a lane keeps the
+// half of its remaining accumulators that its bit of rq names, and adds its partner's partial sums of that half.
+template <int M, int RQ, int NA>
+__device__ __forceinline__ void halve_rounds(float (&acc)[NA], int rq) {
+    if constexpr (M < RQ) {
+        constexpr int n = NA / (2 * M);
+        const bool up = (rq & M) != 0;
+#pragma unroll
+        for (int a = 0; a < n; ++a) {
+            const float send = up ? acc[a] : acc[a + n];
+            const float keep = up ? acc[a + n] : acc[a];
+            acc[a] = keep + xor_lane<M>(send);
+        }
+        halve_rounds<2 * M, RQ>(acc, rq);
+    }
+}
+
 // Backward.  From the saved gate activations and c, and dy = dL/dy (T, N, H), writes dgates = dL/d(pre-activation)
 // (T, N, 4H) walking the recurrence from its last step.  pbuf: [2][ngroups][G producers][C][H] granules.
 //
@@ -257,6 +292,20 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
 // U = 48 rows i RP + rp, as the GRU backward takes them.  RP divides U, so row i RP + rp is unit (i RP) % U + rp of gate
 // (i RP) / U, a compile-time offset from the lane's first weight: with U and H no powers of two, r / U and r % U of a
 // run-time row keep an address per weight live, and the kernel spills.
+//
+// Block layout (H 256, U 64: lstm_bwd_layout.h has the arithmetic and the order of summation).  In the column layout
+// every lane of a wave reads the same dG row, and a value read from LDS feeds one weight: at C 2 a wave issues 64
+// ds_read_b128 for its 256 v_fmac per step, 64 x 4 LDS-array cycles x 8 waves = 2048 per step and CU against
+// 2 x 256 x 2 = 1024 VALU cycles per SIMD -- the matvec waits for the LDS array (measured: 2192 LDS-array cycles per
+// step and CU, SQ_LDS_IDX_ACTIVE, profiles/r35_lstm_bwd_layout.txt).  Here lane (kb, rq) = (tid / 8, tid % 8) holds
+// the 4 columns k = 4 kb + q of 32 rows, the row pairs p = rq + 8 i: a pair is one read of 2 C floats, the 8 lanes rq
+// read 8 adjacent chunks (the other lanes of the wave the same 8: no conflict), and each value feeds 4 weights: 16
+// ds_read_b128 per wave and step at C 2, 592 LDS-array cycles per step and CU measured.  The 8 partial sums of a
+// (k, c) meet inside the wave by recursive halving over xor 1, 2, 4 (DPP operands of the adds, no LDS), after which a
+// lane holds C H / threads sums of distinct (k, c) and publishes exactly those: no `red`, no third barrier, no strided
+// publish loop.  The order of a sum depends on (H, U) alone, so a column's dgates are the same bits at C 2 and C 4;
+// for that the gather of these instantiations also adds the G producers one by one in producer order at either C
+// (APART below: at C 4 the column layout's two planes each added two producers first).
 template <int H, int C, int U, bool VL = false>
 __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(const float *__restrict__ whh,
                                                                        const float *__restrict__ gates,
@@ -272,15 +321,25 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
     constexpr bool STRIDED = U == 48;                 // a lane's rows: every RP-th, not R in a run
     constexpr int RP = NT / H;                        // row partitions: lane (k, rp) holds W_hh[rows of rp, k]
     constexpr int R = 4 * U / RP;                     // floats per lane
+    constexpr LstmBwdBlock LB(NT, H, U, C);           // the block layout (lstm_bwd_layout.h) ...
+    constexpr bool BLOCK = LB.KQ > 0;                 // ... where the instantiation takes it
+    constexpr int KQ = BLOCK ? LB.KQ : 1, RQ = BLOCK ? LB.RQ : 1, RR = BLOCK ? LB.RR : 1, KEEP = BLOCK ? LB.KEEP : 1;
     constexpr int PAIRS = U * C;                      // (c, u) pairs of the cell update
     constexpr int PL = NT / PAIRS;                    // producer planes of the gather
     constexpr int NP = (G + PL - 1) / PL;
+    // BLOCK: a plane that polls NP > 1 producers leaves them apart in `gath`, and the cell lane adds all G in producer
+    // order, as the launch with one producer per plane does: a column's dh is the same bits whatever C
+    constexpr bool APART = BLOCK && NP > 1;
+    static_assert(!APART || NP * PL == G, "every plane polls NP producers");
     static_assert(RP >= 1 && R >= 1 && PL >= 1 && PL * PAIRS == NT, "every lane polls; one cell lane per pair");
     static_assert(!STRIDED || (RP * H == NT && R * RP == 4 * U && U % RP == 0),
                   "a lane's rows keep their gate index at compile time");
+    static_assert(!BLOCK || (LB.ok() && KQ * RR * NT == 4 * U * H && RQ <= 64 && (RQ & (RQ - 1)) == 0 &&
+                             KEEP * NT == C * H && KQ * RR == R),
+                  "every owned weight in one lane; the RQ partial sums inside one wave; one granule per held sum");
     __shared__ __attribute__((aligned(16))) float dgs[4 * U * C];      // dG_t of the owned rows as [row][c]
-    __shared__ float gath[PL * PAIRS];
-    __shared__ __attribute__((aligned(16))) float red[RP > 1 ? RP * C * H : 1];
+    __shared__ float gath[(APART ? G : PL) * PAIRS];
+    __shared__ __attribute__((aligned(16))) float red[RP > 1 && !BLOCK ? RP * C * H : 1];
     __shared__ int give_up;
 
     int group, member;
@@ -289,8 +348,16 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
     const int j0 = member * U, n0 = group * C;
 
     const int k = tid % H, rp = tid / H;
-    float w[R];
-    if constexpr (STRIDED) {
+    const int kb = tid / RQ, rq = tid % RQ;            // BLOCK: lane (kb, rq)
+    float w[R];                                        // BLOCK: as [q][j], the weight of column KQ kb + q in row(rq, j)
+    if constexpr (BLOCK) {
+#pragma unroll
+        for (int j = 0; j < RR; ++j) {
+            const int r = LB.row(rq, j);
+#pragma unroll
+            for (int q = 0; q < KQ; ++q) w[q * RR + j] = whh[((size_t)(r / U) * H + j0 + (r % U)) * H + KQ * kb + q];
+        }
+    } else if constexpr (STRIDED) {
         const float *wbase = whh + (size_t)(j0 + rp) * H + k;
 #pragma unroll
         for (int i = 0; i < R; ++i) w[i] = wbase[(unsigned)((((i * RP) / U) * H + (i * RP) % U) * H)];
@@ -331,6 +398,9 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
     __syncthreads();
 
     const u64 *mine = pbuf + (size_t)group * G * C * H + cc * H + j0 + u;
+    // BLOCK: the first of the KEEP sums this lane publishes is granule (c, k) = (a0 % C, KQ kb + a0 / C); the others are
+    // the columns c + 1, ... of the same k
+    const int a0 = LB.kept_first(rq), pub = (a0 % C) * H + KQ * kb + a0 / C;
     for (int s = 0; s < T; ++s) {
         const int tt = T - 1 - s;                         // recurrence position
         const int t = reverse ? T - 1 - tt : tt;          // time index
@@ -342,16 +412,21 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
             const int nvalid = plane < G ? (G - plane + PL - 1) / PL : 0;
             const u64 *src = mine + (size_t)((s - 1) & 1) * ngroups * G * C * H;
             if (!sweep<NP>(src, plane * C * H, PL * C * H, G * C * H, (unsigned)s, v, status)) give_up = 1;
-            float sum = 0.f;
+            if constexpr (APART) {
 #pragma unroll
-            for (int q = 0; q < NP; ++q)
-                if (q < nvalid) sum += v[q];
-            gath[plane * PAIRS + pair] = sum;
+                for (int q = 0; q < NP; ++q) gath[(plane + q * PL) * PAIRS + pair] = v[q];
+            } else {
+                float sum = 0.f;
+#pragma unroll
+                for (int q = 0; q < NP; ++q)
+                    if (q < nvalid) sum += v[q];
+                gath[plane * PAIRS + pair] = sum;
+            }
             __syncthreads();
             if (give_up) return;
             if (cell_lane) {
 #pragma unroll
-                for (int p = 0; p < PL; ++p) dhr += gath[p * PAIRS + pair];
+                for (int p = 0; p < (APART ? G : PL); ++p) dhr += gath[p * PAIRS + pair];
             }
             if (valid) {
                 const int tl = reverse ? t - 1 : t + 1;
@@ -406,6 +481,28 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
         __syncthreads();
         if (s + 1 == T) break;                            // the first step has no predecessor to feed
 
+        if constexpr (BLOCK) {
+            u64 *dst = pbuf + (((size_t)(s & 1) * ngroups + group) * G + member) * C * H;
+            float acc[KQ * C];
+#pragma unroll
+            for (int a = 0; a < KQ * C; ++a) acc[a] = 0.f;
+#pragma unroll
+            for (int i = 0; i < RR / 2; ++i) {
+                float d[2 * C];                           // rows 2 p and 2 p + 1 of the pair p = rq + RQ i
+                lds_row<2 * C>(dgs + (rq + RQ * i) * 2 * C, d);
+#pragma unroll
+                for (int e = 0; e < 2; ++e)
+#pragma unroll
+                    for (int q = 0; q < KQ; ++q)
+#pragma unroll
+                        for (int c = 0; c < C; ++c)
+                            acc[q * C + c] = fmaf(w[q * RR + 2 * i + e], d[e * C + c], acc[q * C + c]);
+            }
+            halve_rounds<1, RQ>(acc, rq);
+#pragma unroll
+            for (int v = 0; v < KEEP; ++v) store_granule(dst + pub + v * H, (unsigned)(s + 1), acc[v]);
+            continue;
+        }
         float acc[C];
 #pragma unroll
         for (int c = 0; c < C; ++c) acc[c] = 0.f;
