@@ -37,6 +37,7 @@
 #include "dispatch.h"
 #include "ff_common.h"
 #include "lstm_bwd_layout.h"
+#include "lstm_fwd_layout.h"
 #include "rnn_common.h"
 
 namespace tk {
@@ -50,6 +51,249 @@ constexpr int threads_for() { return U == 48 ? 384 : U <= 32 ? 256 : 512; }
 template <int H, int U>
 constexpr int bwd_threads_for() { return U == 48 ? 2 * H : threads_for<U>(); }
 
+// The value of lane (lane ^ M) of the wave.  M = 1 and 2 are one quad permutation, M = 4 a mirror of the half row and a
+// reversal of the quad (i -> 7 - i -> i ^ 4): DPP operands of the VALU, which the compiler folds into the add that uses
+// them where it can.  They stay off the LDS crossbar, where a ds_bpermute_b32 takes its turn behind the matvec's reads.
+template <int M>
+__device__ __forceinline__ float xor_lane(float v) {
+    static_assert(M == 1 || M == 2 || M == 4, "a partner inside the lane's group of 8");
+    const int x = __float_as_int(v);
+    if constexpr (M == 1) {
+        return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true));      // quad_perm:[1,0,3,2]
+    } else if constexpr (M == 2) {
+        return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true));      // quad_perm:[2,3,0,1]
+    } else {
+        const int y = __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true);              // row_half_mirror
+        return __int_as_float(__builtin_amdgcn_update_dpp(0, y, 0x1B, 0xF, 0xF, true));      // quad_perm:[3,2,1,0]
+    }
+}
+
+// Recursive halving over the lanes rq ^ M, M = M0, 2 M0, ... < RQ (lstm_bwd_layout.h): each round a lane keeps the
+// half of its remaining accumulators that its bit of rq names, and adds its partner's partial sums of that half.
+template <int M, int RQ, int NA>
+__device__ __forceinline__ void halve_rounds(float (&acc)[NA], int rq) {
+    if constexpr (M < RQ) {
+        constexpr int n = NA / (2 * M);
+        const bool up = (rq & M) != 0;
+#pragma unroll
+        for (int a = 0; a < n; ++a) {
+            const float send = up ? acc[a] : acc[a + n];
+            const float keep = up ? acc[a + n] : acc[a];
+            acc[a] = keep + xor_lane<M>(send);
+        }
+        halve_rounds<2 * M, RQ>(acc, rq);
+    }
+}
+
+// The forward at H 256, U 64, C 2 (lstm_fwd_kernel below has the contract, the schedule of a step and the VL and SAVE
+// forms; lstm_fwd_layout.h the arithmetic of this layout and the order of every sum, which is that of the plain body).
+// Written over CK = C / 2 columns per lane; at C 4 (CK 2) it gives the plain body's bits too but measured slower than
+// it (lstm_fwd_layout.h), so only C 2 comes here.  Three things differ from the plain body, all on a step's serial chain:
+//   * h in LDS: two rows of a lane side by side at C 2, so the matvec reads 16 bytes at a time, 16 ds_read_b128 per lane
+//     and step where it issued 16 ds_read2_b64 (8 LDS-array cycles each, against 4);
+//   * the KP = 8 partial sums meet by recursive halving over xor 1, 2, 4, DPP operands of the adds (halve_rounds, as in
+//     the backward), where 12 (C 4: 16) ds_bpermute_b32 queued behind the matvec's reads; a lane is left with the sums
+//     of ONE gate in CK = C / 2 columns;
+//   * every lane adds its own gx to those sums and applies its gate's function, so a wave issues one sigmoidf body and,
+//     for the lanes of gate g, one tanhf body where the cell lanes issued three and one; the lane of gate i takes the
+//     other three activations of its columns from the lanes kp ^ 4 (f), kp ^ 2 (g) and kp ^ 6 (o) by DPP moves and
+//     runs the cell update, the publish and the staging as the plain body's cell lane does.
+template <int H, int C, int U, bool VL, bool SAVE>
+__device__ __forceinline__ void lstm_fwd_lanes_body(const float *__restrict__ gx, const float *__restrict__ whh, int T,
+                                                    Cols cols, int reverse, int ngroups, float *__restrict__ y,
+                                                    float *__restrict__ gates, float *__restrict__ cell, u64 *hbuf,
+                                                    uint32_t *status, const int32_t *__restrict__ lengths) {
+    constexpr int NT = threads_for<U>();
+    const int N = cols.n, LD = cols.ld();               // the launch's columns; the tensors' columns per time step
+    constexpr int G = H / U;
+    constexpr LstmFwdLanes FL(NT, H, U, C);
+    constexpr int KP = FL.KP, KS = FL.KS, PR = FL.PR, CK = FL.CK;
+    constexpr int NG = H * C / NT;
+    static_assert(FL.ok() && KP == 8 && NG * NT == H * C && FL.gate_lane_xor(1) == 4 && FL.gate_lane_xor(2) == 2 &&
+                      FL.gate_lane_xor(3) == 6,
+                  "whole rows in 16-byte reads; the partial sums and the four gates of a column inside 8 lanes of a wave");
+    constexpr int U4 = U / 4;
+    constexpr int NQ = SAVE ? (6 * C * U4 + NT - 1) / NT : 1;        // 16-byte chunks of a staging block per lane
+    static_assert(U % 4 == 0, "a row of the staging block is whole 16-byte chunks");
+    __shared__ __attribute__((aligned(16))) float hs[2][H * C];      // h_{t-1} at FL.hs_index(k, c), by step parity
+    // a step's h, c, i, f, g, o as [value][column][unit], by step parity (as in the plain body)
+    __shared__ __attribute__((aligned(16))) float stg[SAVE ? 2 : 1][SAVE ? 6 * C * U : 4];
+    __shared__ int give_up;
+
+    int group, member;
+    place(G, group, member);
+    const int tid = threadIdx.x;
+    const int j0 = member * U, n0 = group * C;
+    const int u = tid / KP, kp = tid % KP;
+
+    float w[4][KS];
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int i = 0; i < KS; ++i) w[g][i] = whh[((size_t)g * H + j0 + u) * H + FL.k(kp, i)];
+    settle(w);
+
+    const int gate = FL.gate(kp), col = FL.col(kp, 0);  // this lane keeps the sums of `gate` in columns col + v, v < CK
+    const bool cell_lane = gate == 0;
+    const int n = n0 + col;
+    bool fetch[CK], valid[CK];                         // a column of the batch: its gx is loaded; ... and this is its cell lane
+    float cst[CK], held[CK];                           // held: not SAVE, h of the previous step, stored one step late
+    int len[CK];                                       // VL: the steps of this lane's columns
+#pragma unroll
+    for (int v = 0; v < CK; ++v) {
+        fetch[v] = n + v < N;
+        valid[v] = cell_lane && fetch[v];
+        cst[v] = held[v] = 0.f;
+        len[v] = 0;
+        if constexpr (VL) len[v] = !valid[v] ? 0 : lengths ? lengths[n + v] : T;
+    }
+
+    for (int i = tid; i < H * C; i += NT) hs[0][i] = 0.f;
+    if (tid == 0) give_up = 0;
+
+    const size_t H4 = 4 * (size_t)H;
+    // the chunks of the staging block this lane stores: rows (value, column) of y, cell and the gates' four slabs
+    float *rp[NQ];
+    size_t rpitch[NQ];
+    if constexpr (SAVE) {
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            const int q = tid + i * NT, row = q / U4, v = row / C, nn = n0 + row % C;
+            const size_t w = v < 2 ? (size_t)H : H4;
+            float *base = v == 0 ? y : v == 1 ? cell : gates + (size_t)(v - 2) * H;
+            rpitch[i] = (size_t)LD * w;
+            rp[i] = q < 6 * C * U4 && nn < N ? base + (size_t)nn * w + j0 + 4 * (q % U4) : nullptr;
+        }
+    }
+    // gx of this lane's gate in its columns, at time 0 (the next column is H4 floats on)
+    const float *gx0 = gx + (size_t)n * H4 + (size_t)gate * H + j0 + u;
+    float gq[CK];                                      // ... of this step (loaded one step ahead)
+#pragma unroll
+    for (int v = 0; v < CK; ++v) gq[v] = fetch[v] ? gx0[(size_t)(reverse ? T - 1 : 0) * LD * H4 + v * H4] : 0.f;
+    __syncthreads();
+
+    for (int s = 0; s < T; ++s) {
+        const int t = reverse ? T - 1 - s : s;
+        float *hb = hs[s & 1];
+        settle(gq);
+        if (s > 0) {
+            const u64 *src = hbuf + ((size_t)((s - 1) & 1) * ngroups + group) * (H * C);
+            float v[NG];
+            if (!sweep<NG>(src, tid, NT, H * C, (unsigned)s, v, status)) give_up = 1;
+            // granule e = c * H + k.  The 64 lanes of a wave write 64 floats two apart, as the [k][c] image has them: two
+            // lanes per bank of a ds_write_b32's group of 32, which costs that write nothing (its cycles are those of
+            // moving address and data to the LDS)
+#pragma unroll
+            for (int q = 0; q < NG; ++q) {
+                const int e = tid + q * NT;
+                hb[FL.hs_index(e % H, e / H)] = v[q];
+            }
+            __syncthreads();
+            if (give_up) return;
+            const int tl = reverse ? t + 1 : t - 1;
+            if constexpr (!SAVE) {
+#pragma unroll
+                for (int v = 0; v < CK; ++v)
+                    if (valid[v]) y[((size_t)tl * LD + n + v) * H + j0 + u] = held[v];
+            } else {
+                rows_to_global<NQ>(stg[(s - 1) & 1], tid, NT, rp, rpitch, (size_t)tl);
+            }
+        }
+        float gn[CK];
+#pragma unroll
+        for (int v = 0; v < CK; ++v)
+            gn[v] = fetch[v] && s + 1 < T ? gx0[(size_t)(reverse ? t - 1 : t + 1) * LD * H4 + v * H4] : 0.f;
+        asm volatile("" ::: "memory");                   // the deferred stores and the prefetch stay here
+
+        float acc[4 * C];                                // (gate, c) at FL.flat(gate, c): the order the rounds halve
+#pragma unroll
+        for (int a = 0; a < 4 * C; ++a) acc[a] = 0.f;
+        // read j: rows PR j ... PR j + PR - 1 of this lane, one 16-byte read; AHEAD of them in flight in front of the FMAs
+        // that use the first
+        constexpr int NR = KS / PR, AHEAD = 4;
+        float hv[NR][PR * C];
+#pragma unroll
+        for (int j = 0; j < AHEAD; ++j) lds_row<PR * C>(hb + FL.chunk(kp, j), hv[j]);
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            if (j + AHEAD < NR) lds_row<PR * C>(hb + FL.chunk(kp, j + AHEAD), hv[j + AHEAD]);
+            __builtin_amdgcn_sched_barrier(0);           // (left alone, the scheduler sinks the read to its first use)
+#pragma unroll
+            for (int e = 0; e < PR; ++e)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int c = 0; c < C; ++c)
+                        acc[FL.flat(g, c)] = fmaf(w[g][PR * j + e], hv[j][e * C + c], acc[FL.flat(g, c)]);
+        }
+        halve_rounds<1, KP>(acc, kp);                    // acc[v]: `gate` of column col + v, summed over the 8 lanes
+
+        float ig[CK], fg[CK], gg[CK], og[CK];
+#pragma unroll
+        for (int v = 0; v < CK; ++v) {
+            const float x = acc[v] + gq[v];
+            float a;
+            if (gate == 2)
+                a = tanhf(x);
+            else
+                a = sigmoidf(x);
+            ig[v] = a;                                   // (what the cell lane, of gate i, reads)
+            gg[v] = xor_lane<2>(a);
+            fg[v] = xor_lane<4>(a);
+            og[v] = xor_lane<2>(fg[v]);
+        }
+
+        if (cell_lane) {
+            float h[CK];
+#pragma unroll
+            for (int v = 0; v < CK; ++v) {
+                // (the contraction written out, as in the plain body: the builds must not differ in which product the fma takes)
+                cst[v] = fmaf(ig[v], gg[v], fg[v] * cst[v]);
+                h[v] = og[v] * tanhf(cst[v]);
+                if constexpr (VL) {
+                    if (t >= len[v]) {
+                        cst[v] = h[v] = 0.f;
+                        if constexpr (SAVE) ig[v] = fg[v] = gg[v] = og[v] = 0.f;
+                    }
+                }
+            }
+            if (s + 1 < T) {                             // the publish: the step's last operation on global memory
+#pragma unroll
+                for (int v = 0; v < CK; ++v)
+                    store_granule(hbuf + ((size_t)(s & 1) * ngroups + group) * (H * C) + (col + v) * H + j0 + u,
+                                  (unsigned)(s + 1), h[v]);
+            }
+#pragma unroll
+            for (int v = 0; v < CK; ++v) {
+                if constexpr (!SAVE) {
+                    held[v] = h[v];
+                } else {
+                    float *sp = stg[s & 1] + (col + v) * U + u;
+                    sp[0 * C * U] = h[v];
+                    sp[1 * C * U] = cst[v];
+                    sp[2 * C * U] = ig[v];
+                    sp[3 * C * U] = fg[v];
+                    sp[4 * C * U] = gg[v];
+                    sp[5 * C * U] = og[v];
+                }
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < CK; ++v) gq[v] = gn[v];
+    }
+    if (T > 0) {
+        const int tl = reverse ? 0 : T - 1;
+        if constexpr (!SAVE) {
+#pragma unroll
+            for (int v = 0; v < CK; ++v)
+                if (valid[v]) y[((size_t)tl * LD + n + v) * H + j0 + u] = held[v];
+        } else {
+            __syncthreads();                             // the last step's block: no poll, so no barrier, is behind it
+            rows_to_global<NQ>(stg[(T - 1) & 1], tid, NT, rp, rpitch, (size_t)tl);
+        }
+    }
+}
+
 // Forward.  gx (T, N, 4H) = x W_ih^T + b_ih + b_hh.  Writes y = h (T, N, H), the gate activations (T, N, 4H) and
 // c (T, N, H).  Recurrence step s runs time t = s (reverse: T - 1 - s).  hbuf: [2][ngroups][C][H] granules.
 //
@@ -60,6 +304,8 @@ constexpr int bwd_threads_for() { return U == 48 ? 2 * H : threads_for<U>(); }
 // It leaves h, c and the activations in the staging block of the step's parity; behind the next step's barrier (after
 // the loop: one barrier of its own) lane tid stores the 16-byte chunks tid + i NT of that block.  No second barrier
 // per step: a block is written again two steps on, behind the barrier that every wave reaches after its stores.
+// ((256, 64, 2) runs lstm_fwd_lanes_body above: the same lanes, weights, sums and schedule, another h image, reduction
+// and split of the activations.)
 //
 // VL: column n has lengths[n] steps (NULL: T).  A step at t >= lengths[n] leaves h = c = 0, writes y = 0 and
 // publishes h = 0 like any other step: every workgroup runs all T steps, so the hand-off is that of a full batch.
@@ -74,6 +320,10 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
                                                                        float *__restrict__ cell, u64 *hbuf,
                                                                        uint32_t *status,
                                                                        const int32_t *__restrict__ lengths) {
+    if constexpr (lstm_fwd_lanes(H, U, C)) {           // (256, 64, 2): one activation per lane (above); nothing below runs
+        lstm_fwd_lanes_body<H, C, U, VL, SAVE>(gx, whh, T, cols, reverse, ngroups, y, gates, cell, hbuf, status, lengths);
+        return;
+    }
     constexpr int NT = threads_for<U>();
     const int N = cols.n, LD = cols.ld();               // the launch's columns; the tensors' columns per time step
     constexpr int G = H / U;
@@ -246,40 +496,6 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
 }
 
 #ifndef TK_RNN_VARLEN
-// The value of lane (lane ^ M) of the wave.  M = 1 and 2 are one quad permutation, M = 4 a mirror of the half row and a
-// reversal of the quad (i -> 7 - i -> i ^ 4): DPP operands of the VALU, which the compiler folds into the add that uses
-// them where it can.  They stay off the LDS crossbar, where a ds_bpermute_b32 takes its turn behind the matvec's reads.
-template <int M>
-__device__ __forceinline__ float xor_lane(float v) {
-    static_assert(M == 1 || M == 2 || M == 4, "a partner inside the lane's group of 8");
-    const int x = __float_as_int(v);
-    if constexpr (M == 1) {
-        return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true));      // quad_perm:[1,0,3,2]
-    } else if constexpr (M == 2) {
-        return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true));      // quad_perm:[2,3,0,1]
-    } else {
-        const int y = __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true);              // row_half_mirror
-        return __int_as_float(__builtin_amdgcn_update_dpp(0, y, 0x1B, 0xF, 0xF, true));      // quad_perm:[3,2,1,0]
-    }
-}
-
-// Recursive halving over the lanes rq ^ M, M = M0, 2 M0, ... < RQ (lstm_bwd_layout.h): each round a lane keeps the
-// half of its remaining accumulators that its bit of rq names, and adds its partner's partial sums of that half.
-template <int M, int RQ, int NA>
-__device__ __forceinline__ void halve_rounds(float (&acc)[NA], int rq) {
-    if constexpr (M < RQ) {
-        constexpr int n = NA / (2 * M);
-        const bool up = (rq & M) != 0;
-#pragma unroll
-        for (int a = 0; a < n; ++a) {
-            const float send = up ? acc[a] : acc[a + n];
-            const float keep = up ? acc[a + n] : acc[a];
-            acc[a] = keep + xor_lane<M>(send);
-        }
-        halve_rounds<2 * M, RQ>(acc, rq);
-    }
-}
-
 // Backward.  From the saved gate activations and c, and dy = dL/dy (T, N, H), writes dgates = dL/d(pre-activation)
 // (T, N, 4H) walking the recurrence from its last step.  pbuf: [2][ngroups][G producers][C][H] granules.
 //
