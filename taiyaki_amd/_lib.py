@@ -38,6 +38,9 @@ RNN_PROJ_LAB_LIBNAME = "libtaiyaki_amd_rnn_proj_lab.so"     # ... and its lab bu
 CONV_STRIDED_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_conv_strided.h")
 CONV_STRIDED_LIBNAME = "libtaiyaki_amd_conv_strided.so"     # csrc/conv_strided.hip: the 16 -> Cout stride-5 convolution, header and library of its own
 CONV_STRIDED_LAB_LIBNAME = "libtaiyaki_amd_conv_strided_lab.so"     # ... and its lab build (tk_lab_conv_strided_*)
+SQUIGGLE_NET_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_squiggle_net.h")
+SQUIGGLE_NET_LIBNAME = "libtaiyaki_amd_squiggle_net.so"     # csrc/squiggle_net.hip: the squiggle predictor network in one launch per pass, header and library of its own
+SQUIGGLE_NET_LAB_LIBNAME = "libtaiyaki_amd_squiggle_net_lab.so"     # ... and its lab build (tk_lab_squiggle_net_plan)
 
 VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
 VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
@@ -128,6 +131,8 @@ GRU_WGRAD_SIGNATURES, GRU_WGRAD_LAB_SIGNATURES = _read_wgrad_header(GRU_WGRAD_HE
 RNN_PROJ_SIGNATURES, RNN_PROJ_LAB_SIGNATURES = _read_wgrad_header(RNN_PROJ_HEADER)
 # the eleventh: include/taiyaki_amd_conv_strided.h (libtaiyaki_amd_conv_strided.so), and the hooks its lab build adds
 CONV_STRIDED_SIGNATURES, CONV_STRIDED_LAB_SIGNATURES = _read_wgrad_header(CONV_STRIDED_HEADER)
+# the thirteenth: include/taiyaki_amd_squiggle_net.h (libtaiyaki_amd_squiggle_net.so), and the hook its lab build adds
+SQUIGGLE_NET_SIGNATURES, SQUIGGLE_NET_LAB_SIGNATURES = _read_wgrad_header(SQUIGGLE_NET_HEADER)
 
 
 def _read_varlen_header():
@@ -270,6 +275,15 @@ def conv_strided_lib():
         return _load(os.path.join(CSRC, CONV_STRIDED_LAB_LIBNAME),
                      dict(CONV_STRIDED_SIGNATURES, **CONV_STRIDED_LAB_SIGNATURES))
     return _load(os.path.join(CSRC, CONV_STRIDED_LIBNAME), CONV_STRIDED_SIGNATURES)
+
+
+def squiggle_net_lib():
+    """The squiggle predictor network (include/taiyaki_amd_squiggle_net.h): the lab build of that library while the
+    process runs on the lab build (`use_lab`), the release one otherwise.  No fallback: a missing library raises."""
+    if is_lab():
+        return _load(os.path.join(CSRC, SQUIGGLE_NET_LAB_LIBNAME),
+                     dict(SQUIGGLE_NET_SIGNATURES, **SQUIGGLE_NET_LAB_SIGNATURES))
+    return _load(os.path.join(CSRC, SQUIGGLE_NET_LIBNAME), SQUIGGLE_NET_SIGNATURES)
 
 
 def varlen_lib():

@@ -94,6 +94,11 @@ def swish(x):
     return x * torch.sigmoid(x)
 
 
+def linear(x):
+    """activation.linear of the reference: the identity."""
+    return x
+
+
 def _orthonormal_(param):
     """layers.py:37-96 initialises matrix parameters orthonormally."""
     with torch.no_grad():
@@ -816,11 +821,168 @@ class Reverse(nn.Module):
         return torch.flip(self.layer(torch.flip(x, (0,))), (0,))
 
 
+class Residual(nn.Module):
+    """layers.py:156-186: x + layer(x)"""
+
+    def __init__(self, layer):
+        super().__init__()
+        self.layer = layer
+
+    def forward(self, x):
+        return x + self.layer(x)
+
+
 class Serial(nn.Sequential):
     """layers.py:944-982"""
 
     def __init__(self, layers):
         super().__init__(*layers)
+
+
+# False: `SquigglePredictor` runs its layers one by one (the per-layer path), for comparisons against the fused operator
+USE_HIP_SQUIGGLE_NET = True
+# Size 64 at more rows (P x N) than this runs per layer (None: no limit): see SquigglePredictor.  0: measured, the size-64 kernels (one workgroup
+# per CU: 107 KB of LDS) are behind the per-layer path in the forward at every shape tried, 353 against 301 us at 1000 rows
+# and 651 against 401 us at 30 000, and no better than level with it forward + backward (profiles/r37_squiggle_net.txt).
+# The kernels stay built and tested (the tests lift this limit); the model does not take them.
+SQUIGGLE_NET_64_MAX_ROWS = 0
+# calls of the fused operator since the module was loaded (tests and tools read them)
+SQUIGGLE_NET_LAUNCHES = {"forward": 0, "backward": 0}
+
+
+def _pointer_array(tensors):
+    return (_lib._vp * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+class SquiggleNet(torch.autograd.Function):
+    """The squiggle predictor network on the kernels of csrc/squiggle_net.hip (include/taiyaki_amd_squiggle_net.h):
+    the forward is one launch (under no_grad it writes y alone; otherwise also the layers' tanh outputs), the backward
+    one launch and the fixed-order sum of its partial results.  `params`: w_0, b_0, w_1, b_1, ... where the module
+    keeps them."""
+
+    @staticmethod
+    def forward(ctx, x, lens, save, depth, *params):
+        P, N, _ = x.shape
+        size, winlen = params[0].shape[0], params[0].shape[2]
+        dev = x.device
+        L = _lib.squiggle_net_lib()
+        if ctx.needs_input_grad[0] or not save:
+            x = x.detach().contiguous()
+        else:       # (the network's input: a captured step reloads that buffer in place -- see SmallConvolution)
+            x = x.detach().clone(memory_format=torch.contiguous_format)
+        params = [p.detach().contiguous() for p in params]
+        with torch.cuda.device(dev):
+            y = torch.empty(P, N, 3, dtype=torch.float32, device=dev)
+            saved = torch.empty(depth + 1, P, N, size, dtype=torch.float32, device=dev) if save else None
+            if P * N:
+                rc = L.tk_squiggle_net_forward_dev(_lib.ptr(x), _pointer_array(params), _lib.ptr(lens), P, N, size, depth,
+                                                   winlen, _cu_count(dev), _lib.ptr(saved), _lib.ptr(y),
+                                                   _lib.stream_ptr())
+                _lib.check(rc, "tk_squiggle_net_forward_dev")
+                SQUIGGLE_NET_LAUNCHES["forward"] += 1
+        if save:
+            ctx.depth = depth
+            ctx.save_for_backward(x, saved, lens, *params)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, saved, lens, *params = ctx.saved_tensors
+        P, N, _ = x.shape
+        size, winlen, depth = params[0].shape[0], params[0].shape[2], ctx.depth
+        dev = x.device
+        L = _lib.squiggle_net_lib()
+        dy = dy.contiguous()
+        with torch.cuda.device(dev):
+            dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+            grads = [torch.empty_like(p) for p in params]
+            if P * N == 0:
+                return (dx, None, None, None) + tuple(g.zero_() for g in grads)
+            wsb = L.tk_squiggle_net_workspace_bytes(P, N, size, depth, winlen, _cu_count(dev))
+            ws = _lib.workspace(wsb, dev, "squiggle_net")
+            rc = L.tk_squiggle_net_backward_dev(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(saved), _pointer_array(params),
+                                                _lib.ptr(lens), P, N, size, depth, winlen, _cu_count(dev), _lib.ptr(dx),
+                                                _pointer_array(grads), _lib.ptr(ws), wsb, _lib.stream_ptr())
+            _lib.check(rc, "tk_squiggle_net_backward_dev")
+            SQUIGGLE_NET_LAUNCHES["backward"] += 1
+        return (dx, None, None, None) + tuple(grads)
+
+
+class SquigglePredictor(Serial):
+    """The network of bin/train_squiggle.py:86-94 (`models.squiggle_predictor`): a `Serial` of Convolution(3 -> size,
+    tanh), `depth` Residual(Convolution(size -> size, tanh)) and Convolution(size -> 3, linear), every window the same.
+    While its layers are exactly that pattern, the tensors are float32 on the GPU and `tk_squiggle_net_supported` and
+    the workspace size say yes, the whole stack runs as the operator `SquiggleNet` (USE_HIP_SQUIGGLE_NET = False: never;
+    size 64: only up to SQUIGGLE_NET_64_MAX_ROWS rows, which is none as measured); otherwise layer by layer, as any
+    `Serial`.
+
+    `lengths` (one value per column, at most the number of rows; a sequence, an array or a tensor): every layer's
+    output of column n is zero at and beyond lengths[n], so the rows below it are what the column gives run alone."""
+
+    def fused_shape(self):
+        """(size, depth, winlen) if the layers are the pattern the kernels are written for, else None"""
+        layers = list(self)
+        if len(layers) < 3:
+            return None
+        first, last = layers[0], layers[-1]
+        convs = [first] + [r.layer if type(r) is Residual else None for r in layers[1:-1]] + [last]
+        if not all(type(c) is Convolution and c.stride == 1 and c.use_gemm for c in convs):
+            return None
+        size, winlen = first.conv.out_channels, first.winlen
+        want = [(3, size, torch.tanh)] + [(size, size, torch.tanh)] * (len(layers) - 2) + [(size, 3, linear)]
+        for c, (cin, cout, fun) in zip(convs, want):
+            if (c.conv.in_channels, c.conv.out_channels, c.winlen) != (cin, cout, winlen) or c.activation is not fun \
+                    or c.conv.bias is None:
+                return None
+        return size, len(layers) - 2, winlen
+
+    def parameter_list(self):
+        out = []
+        for layer in self:
+            conv = (layer.layer if type(layer) is Residual else layer).conv
+            out += [conv.weight, conv.bias]
+        return out
+
+    def takes_operator(self, x):
+        shape = self.fused_shape() if USE_HIP_SQUIGGLE_NET else None
+        if shape is None or not (x.is_cuda and x.dim() == 3 and x.shape[2] == 3 and x.dtype == torch.float32):
+            return False
+        if not all(p.is_cuda and p.dtype == torch.float32 for p in self.parameter_list()):
+            return False
+        if shape[0] == 64 and SQUIGGLE_NET_64_MAX_ROWS is not None and x.shape[0] * x.shape[1] > SQUIGGLE_NET_64_MAX_ROWS:
+            return False
+        L = _lib.squiggle_net_lib()
+        return bool(L.tk_squiggle_net_supported(*shape)) and (x.shape[0] * x.shape[1] == 0 or bool(
+            L.tk_squiggle_net_workspace_bytes(x.shape[0], x.shape[1], *shape, _cu_count(x.device))))
+
+    def _lengths(self, x, lengths):
+        if lengths is None:
+            return None
+        if torch.is_tensor(lengths) and lengths.is_cuda:     # (device lengths: the kernels clamp them to the rows)
+            lens = lengths
+        else:
+            host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths).astype(np.int64)
+            if host.shape != (x.shape[1],) or (host < 0).any() or (host > x.shape[0]).any():
+                raise ValueError("SquigglePredictor: lengths must be one value in [0, %d] per column (%d columns)"
+                                 % (x.shape[0], x.shape[1]))
+            lens = torch.from_numpy(host)
+        return lens.to(device=x.device, dtype=torch.int32).contiguous()
+
+    def forward(self, x, lengths=None):
+        lens = self._lengths(x, lengths)
+        if self.takes_operator(x):
+            params = self.parameter_list()
+            save = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+            return SquiggleNet.apply(x, lens, save, len(self) - 2, *params)
+        if lens is not None:        # (the input beyond a length counts as the padding it stands for; never in place)
+            keep = torch.arange(x.shape[0], device=x.device)[:, None] < lens[None, :]
+            x = x.masked_fill(~keep[:, :, None], 0)
+        for layer in self:
+            x = layer(x)
+            if lens is not None:
+                x = _zero_beyond(x, lens)
+        return x
 
 
 class GlobalNormFlipFlop(nn.Module):

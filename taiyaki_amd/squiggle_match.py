@@ -219,3 +219,34 @@ class SquiggleMatch(torch.autograd.Function):
 
 
 squiggle_match_loss = SquiggleMatch.apply
+
+
+# ---------------------------------------------------------------------------------------------------
+# bin/predict_squiggle.py: sequences -> predicted squiggles
+# ---------------------------------------------------------------------------------------------------
+def predict_squiggle(model, sequences, alphabet=DEFAULT_ALPHABET):
+    """The model's (`models.squiggle_predictor`) prediction for every sequence of a batch: per sequence its
+    (len, 3) float32 array of level, log-scale and move logit (predict_squiggle.py:38-47, which calls the network
+    one sequence at a time).  Sequences of different lengths go as zero-padded columns with their lengths -- one
+    upload, one call of the network, one download -- and every column's rows are what that sequence gives alone."""
+    embedded = [embed_sequence(seq, alphabet) for seq in sequences]
+    if not embedded:
+        return []
+    lens = np.array([len(e) for e in embedded], dtype=np.int32)
+    x = np.zeros((max(int(lens.max()), 1), len(embedded), 3), dtype=np.float32)
+    for n, e in enumerate(embedded):
+        x[:len(e), n] = e
+    param = next(model.parameters())
+    with torch.no_grad():
+        y = model(torch.from_numpy(x).to(device=param.device, dtype=param.dtype), lengths=lens).cpu().numpy()
+    return [np.ascontiguousarray(y[:m, n], dtype=np.float32) for n, m in enumerate(lens)]
+
+
+def write_predicted_squiggle(fh, sequence, squiggle):
+    """The table of predict_squiggle.py:49-52: a header line, then per position the base, the level, exp(log-scale)
+    and exp(-move logit), the numbers as numpy float32 values print."""
+    if isinstance(sequence, (bytes, bytearray)):
+        sequence = sequence.decode()
+    fh.write('base\tcurrent\tsd\tdwell\n')
+    for base, (mean, logsd, dwell) in zip(sequence, np.asarray(squiggle, dtype=np.float32)):
+        fh.write('{}\t{}\t{}\t{}\n'.format(base, mean, np.exp(logsd), np.exp(-dwell)))
