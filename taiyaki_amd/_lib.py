@@ -52,6 +52,9 @@ WIDE_LIBNAME = "libtaiyaki_amd_rnn_wide.so"     # the same two sources built -DT
 DECODE_VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_decode_varlen.h")
 DECODE_VARLEN_LIBNAME = "libtaiyaki_amd_decode_varlen.so"   # csrc/decode_varlen.hip: the decode operators with per-column lengths, header and library of its own
 
+LOSS_VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_loss_varlen.h")
+LOSS_VARLEN_LIBNAME = "libtaiyaki_amd_loss_varlen.so"       # csrc/crf_band.hip, crf_kernels.hip built -DTK_LOSS_VARLEN: the loss with a time length per column
+
 _vp = ctypes.c_void_p
 _SCALARS = {"size_t": ctypes.c_size_t, "int": ctypes.c_int, "float": ctypes.c_float}
 
@@ -157,6 +160,11 @@ VARLEN_TRAIN_SIGNATURES = {n: (r, a) for n, (r, a, _) in
 
 # the twelfth: include/taiyaki_amd_rnn_wide.h (libtaiyaki_amd_rnn_wide.so)
 WIDE_SIGNATURES = {n: (r, a) for n, (r, a, _) in parse_prototypes(_blank_comments(open(WIDE_HEADER).read())).items()}
+
+
+# the fourteenth: include/taiyaki_amd_loss_varlen.h (libtaiyaki_amd_loss_varlen.so)
+LOSS_VARLEN_SIGNATURES = {n: (r, a) for n, (r, a, _) in
+                          parse_prototypes(_blank_comments(open(LOSS_VARLEN_HEADER).read())).items()}
 
 
 class SeqLabels(ctypes.Structure):
@@ -308,6 +316,12 @@ def decode_varlen_lib():
     """The decode operators with per-column lengths (include/taiyaki_amd_decode_varlen.h).  No fallback: a missing
     library raises."""
     return _load(os.path.join(CSRC, DECODE_VARLEN_LIBNAME), DECODE_VARLEN_SIGNATURES)
+
+
+def loss_varlen_lib():
+    """The flip-flop loss with a time length per column (include/taiyaki_amd_loss_varlen.h): loaded by the first call that
+    brings lengths.  No fallback: a missing library raises."""
+    return _load(os.path.join(CSRC, LOSS_VARLEN_LIBNAME), LOSS_VARLEN_SIGNATURES)
 
 
 def check(rc, what):

@@ -67,6 +67,12 @@ struct BandArgs {
     const float *mcw;           // mod_cat_weights (nbase + nmod)
     long long total_len;
     int nbase;
+#ifdef TK_LOSS_VARLEN
+    // the -DTK_LOSS_VARLEN build (libtaiyaki_amd_loss_varlen.so): a time length per column.  Read n runs on rows
+    // [0, clamp(lengths[n], 0, T)) of its column (crf_log.h: crf_len); every array above stays sized and indexed by T.
+    // Null: every column has T rows -- the operator of the release build.
+    const int32_t *lengths;     // (N) or null
+#endif
 };
 
 // what tk_crf_flipflop_labels_dev / tk_flipflop_loss_fused_labels_dev hand down (include/taiyaki_amd_flipflop.h: tk_seq_labels)
@@ -149,6 +155,10 @@ struct CrfCall {
     float add_scale = 0.f;
     hipEvent_t add_ready = nullptr;     // ... what they hold is ready when this event is; null: now
     const float *mod_col_weights = nullptr;     // cat-mod only (BandArgs::colw)
+#ifdef TK_LOSS_VARLEN
+    const int32_t *lengths = nullptr;           // (N) rows per column (BandArgs::lengths); with add_grad: the add terms take
+                                                // 1 / lengths[n] in place of add_scale
+#endif
 };
 int crf_dispatch(const CrfCall &c);
 size_t crf_workspace_bytes_sharp(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, int want_grad, float sharp);

@@ -376,7 +376,7 @@ __device__ __forceinline__ void band_offset_of(const BandArgs &a, int n, long lo
     *len_out = (int)own;
 }
 
-template <int R, bool MOD, bool FWD, bool GRAD, bool ROWS, bool CW, int BK, bool PRE4 = false>
+template <int R, bool MOD, bool FWD, bool GRAD, bool ROWS, bool CW, int BK, bool PRE4 = false, bool VL = false>
 __device__ __forceinline__ void band_sweep(const BandArgs &a, int n, int ws, int L, int64_t off, float *E, int *Ef, const float *Ezero,
                                            const f4 *Wt, const int wofs = 0) {
     // `n`: the read (scores, labels); `ws`: its slot in the workspace arrays -- n for the batch's launch, the
@@ -385,9 +385,12 @@ __device__ __forceinline__ void band_sweep(const BandArgs &a, int n, int ws, int
     // the wave index is wave-uniform: keep everything derived from it in SGPRs
     // (`wofs`: the workgroup's first wave of THIS sweep -- 0 but in the retry launch, whose two sweeps share a workgroup)
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) - wofs, lane = threadIdx.x & (WAVE - 1);
-    const int N = a.N, T = a.T, S = a.S, W = a.W;
+    // (VL: T = this column's rows -- band, blocks, phases and row counts are those of a call on scores[:T, n:n+1]; the
+    // checkpoint arrays keep the launch's NBL blocks per read)
+    const int N = a.N, T = crf_len<VL>(a, n), S = a.S, W = a.W;
     const int a0 = w * PW;
     const int NB = (T + BK - 1) / BK, NPH = NB + W - 1;
+    const int NBL = VL ? (a.T + BK - 1) / BK : NB;
     const int src = FWD ? w - 1 : w + 1;                        // the chunk our boundary cell comes from
     const Win win = band_window<BK>(w, PW, L, T);
     const Win wsrc = (src >= 0 && src < W) ? band_window<BK>(src, PW, L, T) : Win{1, 0};
@@ -457,9 +460,9 @@ __device__ __forceinline__ void band_sweep(const BandArgs &a, int n, int ws, int
 
     if (FWD && bad_label && a.status) atomicOr(a.status, 8u);
     const unsigned rs4 = 4u * (unsigned)rowstride;
-    float *ckm = GRAD ? (FWD ? a.ckFm : a.ckBm) + (size_t)ws * NB * a.LP + a0 : nullptr;
-    int16_t *ckf = GRAD ? (FWD ? a.ckFf : a.ckBf) + (size_t)ws * NB * a.LP + a0 : nullptr;
-    int *ckb = GRAD ? (FWD ? a.ckFb : a.ckBb) + (size_t)ws * NB * W + w : nullptr;
+    float *ckm = GRAD ? (FWD ? a.ckFm : a.ckBm) + (size_t)ws * NBL * a.LP + a0 : nullptr;
+    int16_t *ckf = GRAD ? (FWD ? a.ckFf : a.ckBf) + (size_t)ws * NBL * a.LP + a0 : nullptr;
+    int *ckb = GRAD ? (FWD ? a.ckFb : a.ckBb) + (size_t)ws * NBL * W + w : nullptr;
     const __amdgpu_buffer_rsrc_t rm_all = __builtin_amdgcn_make_buffer_rsrc(ckm, 0, 0x7fffffff, BUF_WORD3);
     const __amdgpu_buffer_rsrc_t rf_all = __builtin_amdgcn_make_buffer_rsrc(ckf, 0, 0x7fffffff, BUF_WORD3);
     const __amdgpu_buffer_rsrc_t rb_all = __builtin_amdgcn_make_buffer_rsrc(ckb, 0, 0x7fffffff, BUF_WORD3);
@@ -472,7 +475,7 @@ __device__ __forceinline__ void band_sweep(const BandArgs &a, int n, int ws, int
     constexpr int SUBL = WAVE / R;                              // lanes per 64 cells
     const bool sub_lane = ((lane + 1) % SUBL) == 0;
     const int sub_k = (lane + 1) / SUBL;
-    float *bnd = GRAD ? (FWD ? a.bndF : a.bndB) + ((size_t)ws * NB * a.Wp + w * R + (FWD ? sub_k - 1 : R - sub_k)) * BK
+    float *bnd = GRAD ? (FWD ? a.bndF : a.bndB) + ((size_t)ws * NBL * a.Wp + w * R + (FWD ? sub_k - 1 : R - sub_k)) * BK
                       : nullptr;
     // byte offset of the lane's R cells inside a checkpoint row of the chunk
     const unsigned lane_cell4 = 4u * (unsigned)(FWD ? lane * R : PW - (lane + 1) * R);
@@ -838,10 +841,10 @@ __device__ __forceinline__ void band_sweep(const BandArgs &a, int n, int ws, int
 // test_crf_weight_feeds_change_no_bit).  Measured (profiles/r4_feed_modes.txt): the op at the train step's
 // shape 110 us against 125 with helper waves and 134 with neither; -15 .. -22 % at every other shape tried.
 // ===========================================================================
-template <bool MOD, bool FWD, bool CW, int BK>
+template <bool MOD, bool FWD, bool CW, int BK, bool VL = false>
 __device__ __forceinline__ void band_rowmaker(const BandArgs &a, int n, float *Er) {
     const int lane = threadIdx.x & (WAVE - 1);
-    const int N = a.N, T = a.T, S = a.S, W = a.W;
+    const int N = a.N, T = crf_len<VL>(a, n), S = a.S, W = a.W;      // (VL: the column's rows, as in band_sweep -- the same phases)
     const int NB = (T + BK - 1) / BK, NPH = NB + W - 1;
     const size_t rowstride = (size_t)N * S;
     const float *lpn = a.lp + (size_t)n * S;
@@ -969,7 +972,7 @@ __device__ __forceinline__ void band_rank(const BandArgs &a, int ws, int L, int6
 // ===========================================================================
 // WCAP = the most waves a launch of this instantiation may have: the register budget of a lane is
 // 512 / ceil(WCAP / 4) (R = 4 wants more than the 128 that 16 waves leave).
-template <int R, bool MOD, int WCAP, bool ROWS, bool CW, int BK>
+template <int R, bool MOD, int WCAP, bool ROWS, bool CW, int BK, bool VL = false>
 __global__ __launch_bounds__(WCAP *WAVE) void crf_band_sweep_kernel(BandArgs a) {
     extern __shared__ __attribute__((aligned(16))) char band_dyn_lds[];     // ROWS: the exponentiated rows (band_rowmaker)
     constexpr int PW = R * WAVE;
@@ -1007,6 +1010,9 @@ __global__ __launch_bounds__(WCAP *WAVE) void crf_band_sweep_kernel(BandArgs a) 
     } else {
         L = min(a.seqlen[n], (int)(a.seqoff[n + 1] - a.seqoff[n]));            // (offsets are clamped to the label array)
     }
+    if constexpr (VL) {
+        if (crf_len<VL>(a, n) == 0) L = 0;      // a column without rows: an empty read (cost 0; the gradient pass writes its zero rows)
+    }
     // (what is left of build_indices_kernel's outputs: the read's offset, for the launches behind -- the gradient pass
     // and the tail launch take a read's offset and length from seqoff; its label checks ride in the forward sweep's set-up)
     if (a.codes != nullptr && role == 0 && tid == 0) {
@@ -1026,7 +1032,7 @@ __global__ __launch_bounds__(WCAP *WAVE) void crf_band_sweep_kernel(BandArgs a) 
         // c_crf_flipflop.c:269-272: cost 0 for an empty read (the gradient pass does it when
         // there is one); too long for the launch: flagged
         if (!want_grad && role == 0 && tid == 0) {
-            a.cost[n] = (L == 0) ? crf_add_cost(a, n, 0.f) : __builtin_nanf("");
+            a.cost[n] = (L == 0) ? crf_empty_cost<VL>(a, n) : __builtin_nanf("");
             a.gate[n] = 0;
             if (L != 0 && a.status) atomicOr(a.status, 16u);
         }
@@ -1047,20 +1053,20 @@ __global__ __launch_bounds__(WCAP *WAVE) void crf_band_sweep_kernel(BandArgs a) 
         if (w >= W) {
             // the row maker: the workgroup's exponentiated rows, a phase ahead
             if (role == 0)
-                band_rowmaker<MOD, true, CW, BK>(a, n, reinterpret_cast<float *>(band_dyn_lds));
+                band_rowmaker<MOD, true, CW, BK, VL>(a, n, reinterpret_cast<float *>(band_dyn_lds));
             else
-                band_rowmaker<MOD, false, CW, BK>(a, n, reinterpret_cast<float *>(band_dyn_lds));
+                band_rowmaker<MOD, false, CW, BK, VL>(a, n, reinterpret_cast<float *>(band_dyn_lds));
             return;
         }
     }
     if (!want_grad && role == 0)
-        band_sweep<R, MOD, true, false, ROWS, CW, BK, PRE4>(a, n, n, L, off, E, Ef, Ezero, Wt);
+        band_sweep<R, MOD, true, false, ROWS, CW, BK, PRE4, VL>(a, n, n, L, off, E, Ef, Ezero, Wt);
     else if (!want_grad)
-        band_sweep<R, MOD, false, false, ROWS, CW, BK, PRE4>(a, n, n, L, off, E, Ef, Ezero, Wt);
+        band_sweep<R, MOD, false, false, ROWS, CW, BK, PRE4, VL>(a, n, n, L, off, E, Ef, Ezero, Wt);
     else if (role == 0)
-        band_sweep<R, MOD, true, true, ROWS, CW, BK, PRE4>(a, n, n, L, off, E, Ef, Ezero, Wt);
+        band_sweep<R, MOD, true, true, ROWS, CW, BK, PRE4, VL>(a, n, n, L, off, E, Ef, Ezero, Wt);
     else
-        band_sweep<R, MOD, false, true, ROWS, CW, BK, PRE4>(a, n, n, L, off, E, Ef, Ezero, Wt);
+        band_sweep<R, MOD, false, true, ROWS, CW, BK, PRE4, VL>(a, n, n, L, off, E, Ef, Ezero, Wt);
 }
 
 // Inclusive wave prefix sum in six fused DPP adds (the row_bcast steps write only the rows they
@@ -1124,7 +1130,7 @@ __host__ __device__ inline size_t band_post_lds_bytes(bool mod, int bk) {
 // One wave, one time block `jb` of read `n` (workspace slot `ws`: the tail launch's retry, crf_band_tail_kernel); `sP`: the
 // wave's own RG x EPL x 64 floats of LDS.  Returns 0, or why the linear path disowns the read: 1 a sweep score is not
 // finite, 4 the sweeps disagree, 2 a row of this block lost mass (the caller records it).
-template <bool MOD, bool CW, int BK>
+template <bool MOD, bool CW, int BK, bool VL = false>
 __device__ __forceinline__ int band_posterior_block(const BandArgs &a, const int n, const int ws, const int jb, float *sP) {
 #define TK_POST_PREAMBLE const int lane = threadIdx.x & (WAVE - 1); const bool head = jb == 0 && lane == 0;
 #define TK_POST_WS ws
@@ -1143,7 +1149,7 @@ __device__ __forceinline__ int band_posterior_block(const BandArgs &a, const int
 
 // The batch's launch: grid (N, ceil(NB / POST_WAVES)), wave = one time block (BK rows) of read n.
 // (reason codes in gate[n], lab dump: 1 non-finite sweep score, 4 sweeps disagree, 2 a row lost mass)
-template <bool MOD, bool CW, int BK>
+template <bool MOD, bool CW, int BK, bool VL = false>
 __global__ __launch_bounds__(POST_WAVES *WAVE) __attribute__((amdgpu_waves_per_eu(5))) void crf_band_posterior_kernel(BandArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -1192,7 +1198,7 @@ __device__ __forceinline__ int band_first_verdict(const BandRetry &r, int n, dou
     return 0;
 }
 
-template <int R, bool MOD, bool CW>
+template <int R, bool MOD, bool CW, bool VL = false>
 __global__ __launch_bounds__(BAND_MAXW *WAVE) void crf_band_tail_kernel(BandArgs a, BandRetry r, CrfArgs ca) {
     constexpr int BK = 4, PW = R * WAVE, KINDS = MOD ? 3 : 2;
     extern __shared__ __attribute__((aligned(16))) char retry_dyn_lds[];    // the gradient pass's rows: 16 waves x BK x KINDS x 64 floats
@@ -1204,7 +1210,7 @@ __global__ __launch_bounds__(BAND_MAXW *WAVE) void crf_band_tail_kernel(BandArgs
     const int tid = threadIdx.x, lane = tid & (WAVE - 1);
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), nwaves = (int)(blockDim.x >> 6);
     const bool want_grad = a.grad != nullptr;
-    const int T = a.T, NB = (T + BK - 1) / BK;
+    const int T0 = a.T, NB0 = (T0 + BK - 1) / BK;              // (VL: per read below)
     // the common path of a gradient call: the batch's gradient pass disowned nobody -- one word says so
     if (r.anygate != nullptr && *r.anygate == 0) return;
     {
@@ -1216,8 +1222,9 @@ __global__ __launch_bounds__(BAND_MAXW *WAVE) void crf_band_tail_kernel(BandArgs
             const int g = n < a.N ? band_first_verdict(r, n, &score2) : 0;
             if (writer && n < a.N && g == 0 && r.firstF != nullptr && r.gate[n] == 2) {
                 // score = mean of the two sweeps (c_crf_flipflop.c:482-491 does the same), cost = -score / T; the
-                // bias comes back: every one of the T step weights on a path carried 2^-wbias
-                const float cst = crf_add_cost(a, n, (float)(-((score2 + (double)r.first_wbias * (double)T) * 0.6931471805599453) / (double)T) * a.out_scale);
+                // bias comes back: every one of the T step weights on a path carried 2^-wbias  (VL: T = the column's rows)
+                const int T = VL ? crf_len<VL>(a, n) : T0;
+                const float cst = crf_cost_out<VL>(a, n, (float)(-((score2 + (double)r.first_wbias * (double)T) * 0.6931471805599453) / (double)T) * a.out_scale, T);
                 a.cost[n] = cst;
                 if (a.status && !isfinite(cst)) atomicOr(a.status, 1u);
             }
@@ -1236,6 +1243,7 @@ __global__ __launch_bounds__(BAND_MAXW *WAVE) void crf_band_tail_kernel(BandArgs
         if (!mine) continue;
         const int64_t off = a.seqoff[n];
         const int L = min(a.seqlen[n], (int)(a.seqoff[n + 1] - off));
+        const int T = VL ? crf_len<VL>(a, n) : T0, NB = VL ? (T + BK - 1) / BK : NB0;     // (VL: this column's rows and blocks, as in the batch's launch)
         __syncthreads();                                        // (the read before: its verdict is taken, its LDS free)
         if (tid == 0) why_sh = (r.retry && L > 0 && L <= a.W * PW) ? 0 : 16;
         if (r.retry && L > 0 && L <= a.W * PW) {
@@ -1244,14 +1252,14 @@ __global__ __launch_bounds__(BAND_MAXW *WAVE) void crf_band_tail_kernel(BandArgs
             if (2 * a.W <= nwaves) {
                 // both sweeps at once: waves [0, W) forward, [W, 2 W) backward -- the same number of phases, hence of barriers;
                 // the rest of the workgroup keeps them company
-                if (w < a.W) band_sweep<R, MOD, true, true, false, CW, BK>(a, n, ws, L, off, E[0], Ef[0], Ezero, nullptr);
-                else if (w < 2 * a.W) band_sweep<R, MOD, false, true, false, CW, BK>(a, n, ws, L, off, E[1], Ef[1], Ezero, nullptr, a.W);
+                if (w < a.W) band_sweep<R, MOD, true, true, false, CW, BK, false, VL>(a, n, ws, L, off, E[0], Ef[0], Ezero, nullptr);
+                else if (w < 2 * a.W) band_sweep<R, MOD, false, true, false, CW, BK, false, VL>(a, n, ws, L, off, E[1], Ef[1], Ezero, nullptr, a.W);
                 else
                     for (int ph = 0; ph < NB + a.W - 1; ++ph) band_barrier();
             } else {
-                band_sweep<R, MOD, true, true, false, CW, BK>(a, n, ws, L, off, E[0], Ef[0], Ezero, nullptr);
+                band_sweep<R, MOD, true, true, false, CW, BK, false, VL>(a, n, ws, L, off, E[0], Ef[0], Ezero, nullptr);
                 __syncthreads();
-                band_sweep<R, MOD, false, true, false, CW, BK>(a, n, ws, L, off, E[1], Ef[1], Ezero, nullptr);
+                band_sweep<R, MOD, false, true, false, CW, BK, false, VL>(a, n, ws, L, off, E[1], Ef[1], Ezero, nullptr);
             }
             // what the sweeps and the ranking left in the workspace is read by OTHER waves of this workgroup below: release,
             // barrier, acquire (a slot's lines may sit in this CU's vector cache from the read before)
@@ -1262,7 +1270,7 @@ __global__ __launch_bounds__(BAND_MAXW *WAVE) void crf_band_tail_kernel(BandArgs
                 float *sP = reinterpret_cast<float *>(retry_dyn_lds) + (size_t)w * BK * KINDS * WAVE;
                 int why = 0;
                 for (int jb = w; jb < NB && (why & 5) == 0; jb += nwaves)       // (the sweeps' verdict, 1 / 4, is every block's)
-                    why |= band_posterior_block<MOD, CW, BK>(a, n, ws, jb, sP);
+                    why |= band_posterior_block<MOD, CW, BK, VL>(a, n, ws, jb, sP);
                 if (why != 0 && lane == 0) atomicOr(&why_sh, why);
             } else if (tid == 0) {
                 // cost only: both sweeps finite and agreeing, or not the linear path's
@@ -1271,7 +1279,7 @@ __global__ __launch_bounds__(BAND_MAXW *WAVE) void crf_band_tail_kernel(BandArgs
                 else if (!(d > -1e-3 && d < 1e-3)) why_sh = 4;
                 else {
                     const double score2 = 0.5 * (F + B) + (double)a.wbias * (double)T;
-                    const float cst = crf_add_cost(a, n, (float)(-(score2 * 0.6931471805599453) / (double)T) * a.out_scale);
+                    const float cst = crf_cost_out<VL>(a, n, (float)(-(score2 * 0.6931471805599453) / (double)T) * a.out_scale, T);
                     a.cost[n] = cst;
                     if (a.status && !isfinite(cst)) atomicOr(a.status, 1u);
                 }
@@ -1284,7 +1292,7 @@ __global__ __launch_bounds__(BAND_MAXW *WAVE) void crf_band_tail_kernel(BandArgs
             // nobody on the linear path: the log domain, in this workgroup (its cost and gradient rows overwrite whatever
             // the linear attempts left)
             __syncthreads();
-            crf_read<crf_tail_log_R(R), BAND_MAXW, MOD>(ca, n, (int)blockIdx.x);
+            crf_read<crf_tail_log_R(R), BAND_MAXW, MOD, VL>(ca, n, (int)blockIdx.x);
             ++redone;
         }
     }
@@ -1474,7 +1482,7 @@ static int band_launch_sweep(const BandArgs &a, hipStream_t stream) {
     const dim3 grid((want_grad ? 3 : 2) * a.N), block(nw * WAVE);
     auto go = [&](auto cap) {
         constexpr int WCAP = decltype(cap)::value;
-        hipLaunchKernelGGL((crf_band_sweep_kernel<R, MOD, WCAP, ROWS, CW, BK>), grid, block, lds, stream, a);
+        hipLaunchKernelGGL((crf_band_sweep_kernel<R, MOD, WCAP, ROWS, CW, BK, CRF_VL>), grid, block, lds, stream, a);
     };
     if constexpr (R == 4 && BK >= 8) {
         const int cap = crf_band_wave_class(R, BK, nw);
@@ -1503,7 +1511,7 @@ static int band_launch(const BandArgs &a, hipStream_t stream) {
     if (!want_grad || g_band_lab_phase == 1) return 0;
     if (a.before_gradient != nullptr && hipStreamWaitEvent(stream, a.before_gradient, 0) != hipSuccess) return 4;
     const int NB = (a.T + BK - 1) / BK;
-    hipLaunchKernelGGL((crf_band_posterior_kernel<MOD, CW, BK>), dim3(a.N, (NB + POST_WAVES - 1) / POST_WAVES),
+    hipLaunchKernelGGL((crf_band_posterior_kernel<MOD, CW, BK, CRF_VL>), dim3(a.N, (NB + POST_WAVES - 1) / POST_WAVES),
                        dim3(POST_WAVES * WAVE), band_post_lds_bytes(MOD, BK), stream, a);
     return hipGetLastError() == hipSuccess ? 0 : 4;
 }
@@ -1573,8 +1581,8 @@ static int band_tail_launch(const BandArgs &a, const BandRetry &r, const CrfArgs
     const size_t lds_log = crf_lds_bytes(crf_tail_log_R(R), BAND_MAXW, a.S, MOD ? 3 : 2);
     const size_t lds = lds_retry > lds_log ? lds_retry : lds_log;
     if (lds > 150 * 1024) return 2;
-    if (raise_dynamic_lds(reinterpret_cast<const void *>(&crf_band_tail_kernel<R, MOD, CW>), 150 * 1024)) return 4;    // (+ ~1.5 KB static)
-    hipLaunchKernelGGL((crf_band_tail_kernel<R, MOD, CW>), dim3((unsigned)nslots), dim3(BAND_MAXW * WAVE), lds, stream, a, r, ca);
+    if (raise_dynamic_lds(reinterpret_cast<const void *>(&crf_band_tail_kernel<R, MOD, CW, CRF_VL>), 150 * 1024)) return 4;    // (+ ~1.5 KB static)
+    hipLaunchKernelGGL((crf_band_tail_kernel<R, MOD, CW, CRF_VL>), dim3((unsigned)nslots), dim3(BAND_MAXW * WAVE), lds, stream, a, r, ca);
     return hipGetLastError() == hipSuccess ? 0 : 4;
 }
 

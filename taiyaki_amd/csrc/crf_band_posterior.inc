@@ -6,7 +6,7 @@
 // The includer defines:  TK_POST_PREAMBLE (declares lane and whatever TK_POST_HEAD needs), TK_POST_WS (the read's slot in the
 // workspace arrays), TK_POST_HEAD (true in ONE lane per read: it writes the read's cost), TK_POST_LEAVE (nothing more to do),
 // TK_POST_SWEEPS_DISAGREE(why) (the two sweeps are not finite / do not agree: the linear path disowns the read), TK_POST_ROWS_LOST
-// (after the rows are written: `lost` says a row's total is not Z);  and has in scope:  a (BandArgs), n, jb, sP, MOD, CW, BK.
+// (after the rows are written: `lost` says a row's total is not Z);  and has in scope:  a (BandArgs), n, jb, sP, MOD, CW, BK, VL.
     constexpr int R = 1;                                        // 64-cell chunks whatever the sweeps used
     constexpr int PW = R * WAVE;
     constexpr int KINDS = MOD ? 3 : 2;
@@ -14,19 +14,22 @@
     constexpr int RG = (MOD && BK > 8) ? 4 : BK;                // rows evaluated together (cat-mod at 12 steps: three instances per
                                                                 // cell and row -- groups of four keep it under the register cap)
     TK_POST_PREAMBLE
-    const int N = a.N, T = a.T, S = a.S, W = a.Wp;              // W: 64-cell chunks per checkpoint row
+    // (VL: T = this column's rows, NB its blocks; the checkpoint arrays keep the launch's NBL blocks per read, and the
+    // launch has a wave for every one of them: the rows at or beyond T are this pass's to zero)
+    const int N = a.N, T = crf_len<VL>(a, n), S = a.S, W = a.Wp;    // W: 64-cell chunks per checkpoint row
     const int PWS = a.LP / a.W;                                 // cells per SWEEP chunk
     const size_t rowstride = (size_t)N * S;
     const int NB = (T + BK - 1) / BK;
+    const int NBL = VL ? (a.T + BK - 1) / BK : NB;
     const int t0 = jb * BK;
     // WHAT THE WAVE NEEDS BEFORE IT CAN DECIDE ANYTHING, ISSUED TOGETHER (round 4, LABNOTES R4.11): the read's length
     // and offsets, the two sweep scores, the block's score rows, the frame bases of the block's chunks (lane =
     // chunk) -- addresses that depend on nothing but the launch's arguments.  Length -> scores were two round trips
     // one after the other.  (Also issuing the frame columns of all chunks of a short read here -- the mask pass's
     // loads, a third round trip -- costs 32 registers: cat-mod fell from 6 to 5 waves per SIMD and lost 6 us.)
-    const int jbc = min(jb, NB - 1);                            // (waves past the last block leave below)
-    const size_t ckrow = ((size_t)TK_POST_WS * NB + jbc) * a.LP;
-    const size_t ckbase = ((size_t)TK_POST_WS * NB + jbc) * a.W;          // the block's frame bases, one per sweep chunk
+    const int jbc = VL ? max(min(jb, NB - 1), 0) : min(jb, NB - 1);     // (waves past the last block leave below)
+    const size_t ckrow = ((size_t)TK_POST_WS * NBL + jbc) * a.LP;
+    const size_t ckbase = ((size_t)TK_POST_WS * NBL + jbc) * a.W;         // the block's frame bases, one per sweep chunk
     const int pws_sh = 31 - __builtin_clz(PWS);                  // (PWS = 64, 128 or 256 cells)
     const bool coltest = jbc >= 1;
     const unsigned lane4 = 4u * (unsigned)lane;
@@ -41,14 +44,36 @@
     const int col = min(lane, S - 1);
     float raw[BK], er[BK];      // the wave's score rows, one register each (lane = transition id), raw and exponentiated
 #pragma unroll
-    for (int k = 0; k < BK; ++k) raw[k] = lpn[(size_t)min(t0 + k, T - 1) * rowstride + col];
+    for (int k = 0; k < BK; ++k) raw[k] = lpn[(size_t)(VL ? max(min(t0 + k, T - 1), 0) : min(t0 + k, T - 1)) * rowstride + col];
     const int bidx = (min(lane, W - 1) * PW) >> pws_sh;
     const int baseF_l = a.ckFb[ckbase + bidx], baseB_l = a.ckBb[ckbase + bidx];
     const int baseT_l = coltest ? a.ckBb[ckbase_t + bidx] : baseB_l;
     asm volatile("" ::: "memory");
     const int L = min(seqlen_n, (int)(off_next - off));         // (offsets are clamped to the label array)
 
-    if (L == 0 || L > a.LP) {
+    if constexpr (VL) {
+        // the rows of this block at or beyond the column's length: exact zeros, whatever becomes of the read
+        if (lane < S) {
+            for (int t = max(t0, T); t < min(t0 + BK, a.T); ++t) a.grad[(size_t)t * rowstride + (size_t)n * S + lane] = 0.f;
+        }
+    }
+    if constexpr (VL) {
+        const bool empty = L == 0 || T == 0;                    // (a column without rows is an empty read)
+        if (empty || L > a.LP) {
+            if (TK_POST_HEAD) {
+                a.cost[n] = empty ? crf_empty_cost<VL>(a, n) : __builtin_nanf("");
+                if (!empty && a.status) atomicOr(a.status, 16u);
+            }
+            if (lane < S) {
+                const float gs0 = a.grad_scale * (a.grad_scale_vec != nullptr ? a.grad_scale_vec[n] : 1.0f);
+                for (int t = t0; t < min(t0 + BK, T); ++t)
+                    a.grad[(size_t)t * rowstride + (size_t)n * S + lane] =
+                        empty ? crf_empty_grad<VL>(a, (size_t)t, n, lane, gs0) : __builtin_nanf("");
+            }
+            TK_POST_LEAVE;
+        }
+        if (jb >= NB) TK_POST_LEAVE;                            // a block beyond the column's last: its rows are zeroed
+    } else if (L == 0 || L > a.LP) {
         if (TK_POST_HEAD) {
             a.cost[n] = (L == 0) ? crf_add_cost(a, n, 0.f) : __builtin_nanf("");   // c_crf_flipflop.c:269-272, 458-464
             if (L != 0 && a.status) atomicOr(a.status, 16u);
@@ -84,7 +109,7 @@
         // (+ wbias T: the stored sweep scores are in the biased weights, like everything the rows below are
         // scaled by; only the cost takes the bias back)
         const double score2 = 0.5 * (scoreF + scoreB) + (double)a.wbias * (double)T;
-        a.cost[n] = crf_add_cost(a, n, (float)(-(score2 * 0.6931471805599453) / (double)T) * a.out_scale);
+        a.cost[n] = crf_cost_out<VL>(a, n, (float)(-(score2 * 0.6931471805599453) / (double)T) * a.out_scale, T);
     }
     const int Wn = (L + PW - 1) / PW;                           // chunks this read has
     const float c = a.c_can;
@@ -126,8 +151,8 @@
         return p >= 0 && as < L && (notrim || (as <= live_hi && as >= live_lo));
     };
     auto frame_at = [&](const int16_t *ff, const int *fbase, int p) { return fbase[ckbase + (p >> pws_sh)] + (int)ff[ckrow + p]; };
-    const float *bndFn = a.bndF + ((size_t)TK_POST_WS * NB + jb) * W * BK;
-    const float *bndBn = a.bndB + ((size_t)TK_POST_WS * NB + jb) * W * BK;
+    const float *bndFn = a.bndF + ((size_t)TK_POST_WS * NBL + jb) * W * BK;
+    const float *bndBn = a.bndB + ((size_t)TK_POST_WS * NBL + jb) * W * BK;
     // Per-wave buffer descriptors for everything a chunk loads: the chunk is then a SCALAR offset and the lane a
     // constant vector offset -- no 64-bit address arithmetic per load -- and the descriptors' bounds return the
     // 0 that cells past the end of the read take (stay ids at p >= L, move ids at p - 1 < 0 or p >= L - 1).
@@ -508,7 +533,7 @@
 #endif
             // gradient of -score / T  (ctc.pyx:113)
             const float g0 = colacc * (-gsc / (total * (float)T));
-            const float g = adds ? fmaf(addv[k], a.add_scale * gsc, g0) : g0;       // (= crf_add_grad, ff_common.h)
+            const float g = adds ? fmaf(addv[k], (VL ? crf_add_scale<VL>(a, T) : a.add_scale) * gsc, g0) : g0;       // (= crf_add_grad, ff_common.h)
             if (lane < S) a.grad[(size_t)(t0 + k) * rowstride + (size_t)n * S + lane] = g;
         }
     }

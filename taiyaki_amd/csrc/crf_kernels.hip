@@ -27,9 +27,9 @@ namespace tk {
 
 // Workgroup n does read n (TK_CRF_MODE=ckpt, batches the band path does not take).  Behind a band launch the disowned
 // reads are redone by that path's own tail launch (crf_band.hip: crf_band_tail_kernel), which calls crf_read itself.
-template <int R, int W, bool MOD>
+template <int R, int W, bool MOD, bool VL = false>
 __global__ __launch_bounds__(W *WAVE) void crf_kernel(CrfArgs a) {
-    crf_read<R, W, MOD>(a, (int)blockIdx.x, (int)blockIdx.x);
+    crf_read<R, W, MOD, VL>(a, (int)blockIdx.x, (int)blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -304,8 +304,8 @@ template <int R, int W, bool MOD>
 static int crf_launch_one(const CrfArgs &a, hipStream_t stream, size_t nwg) {
     const size_t lds = crf_lds_bytes(R, W, a.S, MOD ? 3 : 2);
     if (lds > 160 * 1024) return 2;
-    if (raise_dynamic_lds(reinterpret_cast<const void *>(&crf_kernel<R, W, MOD>))) return 4;
-    hipLaunchKernelGGL((crf_kernel<R, W, MOD>), dim3((unsigned)nwg), dim3(W * WAVE), lds, stream, a);
+    if (raise_dynamic_lds(reinterpret_cast<const void *>(&crf_kernel<R, W, MOD, CRF_VL>))) return 4;
+    hipLaunchKernelGGL((crf_kernel<R, W, MOD, CRF_VL>), dim3((unsigned)nwg), dim3(W * WAVE), lds, stream, a);
     return hipGetLastError() == hipSuccess ? 0 : 4;
 }
 
@@ -361,6 +361,9 @@ static void crf_fill_args(Args &x, const CrfCall &c, const SeqLabels *ids_from) 
     x.cmo = ids_from != nullptr ? ids_from->can_mods_offsets : nullptr;
     x.mcw = ids_from != nullptr ? ids_from->mod_cat_weights : nullptr;
     x.nbase = ids_from != nullptr ? (int)ids_from->nbase : 0;
+#ifdef TK_LOSS_VARLEN
+    x.lengths = c.lengths;
+#endif
 }
 
 // a band layout placed at `base` -> the sweep and gradient-pass arrays of a launch (a cost-only launch has only the scores)
@@ -448,8 +451,9 @@ static CrfChoice crf_choose(size_t ntrans, size_t nblk, size_t nbatch, size_t ma
     return ch;
 }
 
-#ifdef TK_LAB
-// tk_lab_crf_plan (dispatch.h): the choice above and what the launchers behind it make of it, as numbers
+#if defined(TK_LAB) || defined(TK_LOSS_VARLEN)
+// tk_lab_crf_plan (dispatch.h) and, in the -DTK_LOSS_VARLEN build, tk_crf_varlen_plan: the choice above and what the launchers
+// behind it make of it, as numbers
 bool crf_lab_plan(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, size_t bulk_seqlen, int form, int want_grad,
                   float sharp, size_t workspace_bytes, size_t *out) {
     for (int i = 0; i < 20; ++i) out[i] = 0;

@@ -39,7 +39,74 @@ struct CrfArgs {
     const float *add_cost;      // (N)
     int add_S;
     float add_scale;
+#ifdef TK_LOSS_VARLEN
+    const int32_t *lengths;     // (N) or null: rows per column (crf_band.h: BandArgs::lengths)
+#endif
 };
+
+// A TIME LENGTH PER COLUMN (template parameter VL of kernel A's kernels; the -DTK_LOSS_VARLEN build instantiates VL = true,
+// every other build VL = false, whose code is what it was).  Read n runs on rows [0, T_n) of its column, T_n =
+// clamp(lengths[n], 0, T): its band, its blocks, the bias its scores get back and the 1 / T of its cost and gradient are
+// those of a call on scores[:T_n, n:n+1]; the workspace arrays stay sized and indexed by the launch's T, and the gradient
+// rows [T_n, T) are written as zeros.  A null `lengths` is T rows for everybody.
+#ifdef TK_LOSS_VARLEN
+constexpr bool CRF_VL = true;
+#else
+constexpr bool CRF_VL = false;
+#endif
+template <bool VL, class Args>
+__device__ __forceinline__ bool crf_has_lengths(const Args &a) {
+#ifdef TK_LOSS_VARLEN
+    if constexpr (VL) return a.lengths != nullptr;
+#endif
+    return false;
+}
+template <bool VL, class Args>
+__device__ __forceinline__ int crf_len(const Args &a, int n) {
+#ifdef TK_LOSS_VARLEN
+    if constexpr (VL) {
+        if (a.lengths != nullptr) return min(max(a.lengths[n], 0), a.T);
+    }
+#endif
+    return a.T;
+}
+// the fused loss's add terms (ff_common.h: crf_add_cost / crf_add_grad) with the scale as an argument: add_scale, or with
+// lengths 1 / T_n.  A column with no rows or no labels has cost 0 and gradient 0 under lengths (crf_empty_*).
+template <bool VL, class Args>
+__device__ __forceinline__ float crf_add_scale(const Args &a, int Tn) {
+    return crf_has_lengths<VL>(a) ? 1.0f / (float)max(Tn, 1) : a.add_scale;
+}
+template <class Args>
+__device__ __forceinline__ float crf_add_cost_s(const Args &a, int n, float cst, float scale) {
+    return a.add_cost != nullptr ? cst + scale * a.add_cost[n] : cst;
+}
+template <class Args>
+__device__ __forceinline__ float crf_add_grad_s(const Args &a, size_t t, int n, int lane, float g, float gsc, float scale) {
+    if (a.add_grad != nullptr && lane < a.add_S)
+        g = fmaf(a.add_grad[(t * (size_t)a.N + (size_t)n) * a.add_S + lane], scale * gsc, g);
+    return g;
+}
+// (VL = false: the calls of ff_common.h as they stood, token for token -- the fixed-length kernels' code does not move)
+template <bool VL, class Args>
+__device__ __forceinline__ float crf_cost_out(const Args &a, int n, float cst, int Tn) {
+    if constexpr (VL) return crf_add_cost_s(a, n, cst, crf_add_scale<VL>(a, Tn));
+    else return crf_add_cost(a, n, cst);
+}
+template <bool VL, class Args>
+__device__ __forceinline__ float crf_grad_out(const Args &a, size_t t, int n, int lane, float g, float gsc, int Tn) {
+    if constexpr (VL) return crf_add_grad_s(a, t, n, lane, g, gsc, crf_add_scale<VL>(a, Tn));
+    else return crf_add_grad(a, t, n, lane, g, gsc);
+}
+template <bool VL, class Args>
+__device__ __forceinline__ float crf_empty_cost(const Args &a, int n) {
+    if constexpr (VL) return crf_has_lengths<VL>(a) ? 0.f : crf_add_cost(a, n, 0.f);
+    else return crf_add_cost(a, n, 0.f);
+}
+template <bool VL, class Args>
+__device__ __forceinline__ float crf_empty_grad(const Args &a, size_t t, int n, int lane, float gsc) {
+    if constexpr (VL) return crf_has_lengths<VL>(a) ? 0.f : crf_add_grad(a, t, n, lane, 0.f, gsc);
+    else return crf_add_grad(a, t, n, lane, 0.f, gsc);
+}
 
 __host__ __device__ inline int crf_ck(int R, int W, int kinds) {
     // recompute tile + sorted-posterior tile <= 112 KiB of LDS -- except at (4, 16) cat-mod, where the quotient is 1 and the
@@ -99,14 +166,14 @@ __device__ __forceinline__ double wave_shift_down1(double src, double fill) {
 }
 
 // One read, all three passes.  `ckslot`: which set of checkpoint columns of the workspace this workgroup uses.
-template <int R, int W, bool MOD>
+template <int R, int W, bool MOD, bool VL = false>
 __device__ __forceinline__ void crf_read(const CrfArgs &a, const int n, const int ckslot) {
     using Cfg = CrfCfg<R, W, MOD>;
     constexpr int CK = Cfg::CK, NT = Cfg::NT, MAXK = Cfg::MAXK, LPAD = Cfg::LPAD;
     constexpr int KINDS = Cfg::KINDS, EPL = Cfg::EPL;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & (WAVE - 1);
-    const int T = a.T, N = a.N, S = a.S, SP = S + 2;
+    const int T = crf_len<VL>(a, n), N = a.N, S = a.S, SP = S + 2;       // (VL: this column's rows; a.T sizes the arrays)
     const int L = min(a.seqlen[n], (int)(a.seqoff[n + 1] - a.seqoff[n]));      // (offsets are clamped to the label array)
     const bool want_grad = a.grad != nullptr;
     const float gsc = a.grad_scale * (a.grad_scale_vec != nullptr ? a.grad_scale_vec[n] : 1.0f);
@@ -134,12 +201,18 @@ __device__ __forceinline__ void crf_read(const CrfArgs &a, const int n, const in
     const size_t rowstride = (size_t)N * S;
     const float *lpn = a.lp + (size_t)n * S;
 
-    if (L == 0) {
+    if constexpr (VL) {
+        // the rows beyond the column's length: zeros
+        if (want_grad && lane < S) {
+            for (int t = T + wave; t < a.T; t += W) a.grad[(size_t)t * rowstride + (size_t)n * S + lane] = 0.f;
+        }
+    }
+    if (VL ? (L == 0 || T == 0) : L == 0) {
         // c_crf_flipflop.c:269-272 / 458-464: cost 0, zero gradient rows
-        if (tid == 0) a.cost[n] = crf_add_cost(a, n, 0.f);
+        if (tid == 0) a.cost[n] = crf_empty_cost<VL>(a, n);
         if (want_grad && lane < S) {
             for (int t = wave; t < T; t += W)
-                a.grad[(size_t)t * rowstride + (size_t)n * S + lane] = crf_add_grad(a, (size_t)t, n, lane, 0.f, gsc);
+                a.grad[(size_t)t * rowstride + (size_t)n * S + lane] = crf_empty_grad<VL>(a, (size_t)t, n, lane, gsc);
         }
         return;
     }
@@ -343,8 +416,9 @@ __device__ __forceinline__ void crf_read(const CrfArgs &a, const int n, const in
     };
 
     const int NK = (T + CK - 1) / CK;
-    float *ck_n = a.ckpt + (size_t)ckslot * NK * (R * NT);
-    double *ckoff_n = a.ckoff + (size_t)ckslot * NK;
+    // (VL: the slots of the workspace are the launch's, NK of its T each)
+    float *ck_n = a.ckpt + (size_t)ckslot * (VL ? (a.T + CK - 1) / CK : NK) * (R * NT);
+    double *ckoff_n = a.ckoff + (size_t)ckslot * (VL ? (a.T + CK - 1) / CK : NK);
 
     // ======================= forward sweep ===================================
     double f[R];
@@ -387,7 +461,7 @@ __device__ __forceinline__ void crf_read(const CrfArgs &a, const int n, const in
     const double fwd_score2 = offF + misc[0];
     if (!want_grad) {
         if (tid == 0) {
-            const float cst = crf_add_cost(a, n, (float)(-(fwd_score2 * 0.6931471805599453) / (double)T) * a.out_scale);
+            const float cst = crf_cost_out<VL>(a, n, (float)(-(fwd_score2 * 0.6931471805599453) / (double)T) * a.out_scale, T);
             a.cost[n] = cst;
             if (a.status && !isfinite(cst)) atomicOr(a.status, 1u);
         }
@@ -509,7 +583,7 @@ __device__ __forceinline__ void crf_read(const CrfArgs &a, const int n, const in
                     }
                     wave_lds_fence();
                 }
-                const float g = crf_add_grad(a, (size_t)(t0 + row), n, lane, colval * (-gsc / (total * (float)T)), gsc);
+                const float g = crf_grad_out<VL>(a, (size_t)(t0 + row), n, lane, colval * (-gsc / (total * (float)T)), gsc, T);
                 if (lane < S) {
                     bad |= !isfinite(g);
                     a.grad[(size_t)(t0 + row) * rowstride + (size_t)n * S + lane] = g;
@@ -526,7 +600,7 @@ __device__ __forceinline__ void crf_read(const CrfArgs &a, const int n, const in
     if (tid == 0) {
         const double bwd_score2 = offB + b[0];
         const double score2 = 0.5 * (fwd_score2 + bwd_score2);
-        const float cst = crf_add_cost(a, n, (float)(-(score2 * 0.6931471805599453) / (double)T) * a.out_scale);
+        const float cst = crf_cost_out<VL>(a, n, (float)(-(score2 * 0.6931471805599453) / (double)T) * a.out_scale, T);
         a.cost[n] = cst;
         if (a.status && !isfinite(cst)) atomicOr(a.status, 1u);
     }

@@ -183,6 +183,13 @@ int mod_weights_dispatch(const int64_t *path, const float *mod_weights, size_t n
                          const ModColumns &cols, const int64_t *out_off, float *mods, int32_t *seqlen,
                          uint32_t *status, hipStream_t stream);
 
+// crf_kernels.hip and crf_band.hip built -DTK_LOSS_VARLEN (libtaiyaki_amd_loss_varlen.so; loss_varlen_api.hip defines the C
+// entries): crf_dispatch takes CrfCall::lengths (crf_band.h), and the lab build's plan query is that library's own
+#ifdef TK_LOSS_VARLEN
+bool crf_lab_plan(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, size_t bulk_seqlen, int form, int want_grad,
+                  float sharp, size_t workspace_bytes, size_t *out);
+#endif
+
 #ifdef TK_LAB
 // what the lab hooks below set (crf_band.hip, lstm_kernels.hip, gru_kernels.hip)
 void crf_band_lab_phase(int phase);

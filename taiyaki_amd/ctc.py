@@ -170,8 +170,19 @@ def _max_seqlen(seqlen):
     return int(seqlen.max())
 
 
+def _time_lengths(lengths, outputs, what):
+    """The `lengths` keyword of the losses: None, or one time length per column of `outputs` (T, N, S) -- a host sequence of
+    integers in 0..T or a device int tensor, checked as `decode._column_lengths` checks them, before anything is launched
+    or loaded.  Returns None or an int32 (N) tensor (on the host, or the device tensor as it came)."""
+    if lengths is None:
+        return None
+    from taiyaki_amd import decode
+    return decode._column_lengths(lengths, outputs.shape[0], outputs.shape[1], what)
+
+
 def _run(logprob, seqs, seqlen, sharp_can, sharp_mod, out_scale, ncan, want_grad,
-         mod_cats=None, can_mods_offsets=None, mod_cat_weights=None):
+         mod_cats=None, can_mods_offsets=None, mod_cat_weights=None, lengths=None):
+    lengths = _time_lengths(lengths, logprob, "flip-flop CRF loss")
     _lib.require_gpu(logprob, "flip-flop CRF loss")
     L = _lib.lib()
     lp = logprob.detach().float().contiguous()
@@ -182,7 +193,8 @@ def _run(logprob, seqs, seqlen, sharp_can, sharp_mod, out_scale, ncan, want_grad
         status = _lib.status_word(dev)
         # TK_CATMOD_GENERAL=1 / TK_SEPARATE_INDEX_BUILD=1 (lab / tests): the stand-alone index kernel and the
         # entry point that takes its arrays; default: the index build rides in the operator's first launch
-        separate = _lab_switch("TK_CATMOD_GENERAL") or _lab_switch("TK_SEPARATE_INDEX_BUILD")
+        # (a call with lengths: always the labels entry point -- include/taiyaki_amd_loss_varlen.h has no other)
+        separate = lengths is None and (_lab_switch("TK_CATMOD_GENERAL") or _lab_switch("TK_SEPARATE_INDEX_BUILD"))
         res = _indices(seqs, seqlen, nbase, dev, mod_cats, can_mods_offsets, mod_cat_weights, status, defer=not separate)
         seqlen_d, seqoff, stay, move, mod, fact, keep = res[:7]
         maxlen = _max_seqlen(seqlen)
@@ -200,6 +212,15 @@ def _run(logprob, seqs, seqlen, sharp_can, sharp_mod, out_scale, ncan, want_grad
                 _lib.ptr(grad), _lib.ptr(ws), wsb, _lib.ptr(status), _lib.stream_ptr(),
                 _col_weights(keep, mod))     # (the per-column factors modfact was filled from)
             _lib.check(rc, "tk_crf_flipflop_dev")
+        elif lengths is not None:
+            lens_d = lengths.to(dev)
+            rc = _lib.loss_varlen_lib().tk_crf_flipflop_varlen_labels_dev(
+                _lib.ptr(lp), ntrans, nblk, nbatch, ctypes.byref(res[7]), _lib.ptr(seqlen_d), _lib.ptr(seqoff),
+                _lib.ptr(stay), _lib.ptr(move), _lib.ptr(mod), _lib.ptr(fact), maxlen, ncan,
+                float(sharp_can), float(sharp_mod), float(out_scale), _lib.ptr(cost),
+                _lib.ptr(grad), _lib.ptr(ws), wsb, _lib.ptr(status), _lib.stream_ptr(), _lib.ptr(lens_d))
+            _lib.check(rc, "tk_crf_flipflop_varlen_labels_dev")
+            keep = keep + (lens_d,)
         else:
             rc = L.tk_crf_flipflop_labels_dev(
                 _lib.ptr(lp), ntrans, nblk, nbatch, ctypes.byref(res[7]), _lib.ptr(seqlen_d), _lib.ptr(seqoff),
@@ -321,12 +342,12 @@ class FlipFlopCRF(torch.autograd.Function):
     """taiyaki/ctc/ctc.pyx:116-151"""
 
     @staticmethod
-    def forward(ctx, logprob, seqs, seqlen, sharpfact: float):
+    def forward(ctx, logprob, seqs, seqlen, sharpfact: float, lengths=None):
         ntrans = logprob.shape[2]
         # lp = sharp * logprob; returned cost/sharp; the saved gradient is
         # d(cost/sharp)/d logprob exactly (the two factors cancel, ctc.pyx:119,145)
         cost, grad = _run(logprob, seqs, seqlen, sharpfact, sharpfact, 1.0 / sharpfact,
-                          ntrans, ctx.needs_input_grad[0])
+                          ntrans, ctx.needs_input_grad[0], lengths=lengths)
         if grad is not None:
             ctx.save_for_backward(grad)
         return cost
@@ -334,10 +355,16 @@ class FlipFlopCRF(torch.autograd.Function):
     @staticmethod
     def backward(ctx, output_grads):
         grads, = ctx.saved_tensors
-        return grads * output_grads.unsqueeze(1), None, None, None
+        return grads * output_grads.unsqueeze(1), None, None, None, None
 
 
-crf_flipflop_loss = FlipFlopCRF.apply
+def crf_flipflop_loss(logprob, seqs, seqlen, sharpfact, lengths=None):
+    """ctc.pyx:116-153.  `lengths` (keyword; a host sequence or a device int tensor, one time length 0..T per column):
+    column n's loss and gradient rows [0, lengths[n]) are those of the call on logprob[:lengths[n], n:n+1]; the rows beyond
+    get a gradient of exactly 0 and are never read; a column of length 0 has loss 0.  None: every column has T rows."""
+    if lengths is None:
+        return FlipFlopCRF.apply(logprob, seqs, seqlen, sharpfact)
+    return FlipFlopCRF.apply(logprob, seqs, seqlen, sharpfact, lengths)
 
 
 class CatModFlipFlop(torch.autograd.Function):
@@ -347,12 +374,12 @@ class CatModFlipFlop(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logprob, seqs, seqlen, mod_cats, can_mods_offsets,
-                mod_cat_weights, sharpfact: float):
+                mod_cat_weights, sharpfact: float, lengths=None):
         ntrans = logprob.shape[2]
         n_can_trans = ntrans - n_mod_columns(can_mods_offsets)
         cost, grad = _run(logprob, seqs, seqlen, sharpfact, 1.0, 1.0 / sharpfact,
                           n_can_trans, ctx.needs_input_grad[0], mod_cats,
-                          can_mods_offsets, mod_cat_weights)
+                          can_mods_offsets, mod_cat_weights, lengths=lengths)
         if grad is not None:
             ctx.save_for_backward(grad)
         return cost
@@ -361,17 +388,22 @@ class CatModFlipFlop(torch.autograd.Function):
     def backward(ctx, output_grads):
         grads, = ctx.saved_tensors
         return (grads * output_grads.unsqueeze(1),
-                None, None, None, None, None, None)
+                None, None, None, None, None, None, None)
 
 
-cat_mod_flipflop_loss = CatModFlipFlop.apply
+def cat_mod_flipflop_loss(logprob, seqs, seqlen, mod_cats, can_mods_offsets, mod_cat_weights, sharpfact, lengths=None):
+    """ctc.pyx:258-312; `lengths` as for `crf_flipflop_loss`."""
+    if lengths is None:
+        return CatModFlipFlop.apply(logprob, seqs, seqlen, mod_cats, can_mods_offsets, mod_cat_weights, sharpfact)
+    return CatModFlipFlop.apply(logprob, seqs, seqlen, mod_cats, can_mods_offsets, mod_cat_weights, sharpfact, lengths)
 
 
 # ---------------------------------------------------------------------------------------------
 # fused train-step loss: (A) + (B) / nblk in one operator, one gradient tensor
 # ---------------------------------------------------------------------------------------------
 def _run_fused(outputs, seqs, seqlen, sharpfact, want_grad, grad_scale=1.0, grad_scale_per_read=None,
-               mod_cats=None, can_mods_offsets=None, mod_cat_weights=None):
+               mod_cats=None, can_mods_offsets=None, mod_cat_weights=None, lengths=None):
+    lengths = _time_lengths(lengths, outputs, "flip-flop loss")
     _lib.require_gpu(outputs, "flip-flop loss")
     L = _lib.lib()
     lp = outputs.detach().float().contiguous()
@@ -383,7 +415,7 @@ def _run_fused(outputs, seqs, seqlen, sharpfact, want_grad, grad_scale=1.0, grad
     dev = lp.device
     with torch.cuda.device(dev):
         status = _lib.status_word(dev)
-        separate = _lab_switch("TK_CATMOD_GENERAL") or _lab_switch("TK_SEPARATE_INDEX_BUILD")
+        separate = lengths is None and (_lab_switch("TK_CATMOD_GENERAL") or _lab_switch("TK_SEPARATE_INDEX_BUILD"))
         res = _indices(seqs, seqlen, nbase, dev, mod_cats, can_mods_offsets, mod_cat_weights, status=status,
                        defer=not separate)
         seqlen_d, seqoff, stay, move, mod, fact, keep = res[:7]
@@ -392,9 +424,17 @@ def _run_fused(outputs, seqs, seqlen, sharpfact, want_grad, grad_scale=1.0, grad
         logz = torch.empty(nbatch, dtype=torch.float32, device=dev)
         grad = torch.empty_like(lp)
         wsa = L.tk_crf_flipflop_workspace_bytes_sharp(ntrans, nblk, nbatch, maxlen, 1, float(sharpfact))
-        wsb = L.tk_flipflop_logz_workspace_bytes(nblk, nbatch, nbase)
-        wsx = L.tk_flipflop_loss_fused_aux_bytes(nblk, nbatch, nbase, ntrans)
-        if mod is None and torch.cuda.is_current_stream_capturing() and L.tk_flipflop_loss_overlap(-1) != 2:
+        if lengths is not None:
+            # the log-partition half with lengths (one wave per column) and its compact buffers, then kernel A: one stream
+            V = _lib.loss_varlen_lib()
+            wsb = V.tk_flipflop_loss_varlen_aux_bytes(nblk, nbatch, nbase, ntrans, 1)
+            wsx = V.tk_flipflop_loss_varlen_aux_bytes(nblk, nbatch, nbase, ntrans, 0)
+            if wsb == 0:
+                raise RuntimeError("flip-flop loss with lengths: nbase=%d is not built" % nbase)
+        else:
+            wsb = L.tk_flipflop_logz_workspace_bytes(nblk, nbatch, nbase)
+            wsx = L.tk_flipflop_loss_fused_aux_bytes(nblk, nbatch, nbase, ntrans)
+        if lengths is None and mod is None and torch.cuda.is_current_stream_capturing() and L.tk_flipflop_loss_overlap(-1) != 2:
             wsx = 0         # (a capture replays the one-queue form: no gradient buffer for kernel B in the graph's pool)
         ws_a = _workspace(wsa, dev, "crf")
         ws_b = _workspace(wsb, dev, "logz")
@@ -410,6 +450,16 @@ def _run_fused(outputs, seqs, seqlen, sharpfact, want_grad, grad_scale=1.0, grad
                 _lib.ptr(ws_a), wsa, _lib.ptr(ws_b), wsb, _lib.ptr(ws_x), wsx, _lib.ptr(status), _lib.stream_ptr(),
                 _col_weights(keep, mod))
             _lib.check(rc, "tk_flipflop_loss_fused_dev")
+        elif lengths is not None:
+            lens_d = lengths.to(dev)
+            rc = V.tk_flipflop_loss_fused_varlen_labels_dev(
+                _lib.ptr(lp), nblk, nbatch, ntrans, ctypes.byref(res[7]), _lib.ptr(seqlen_d), _lib.ptr(seqoff),
+                _lib.ptr(stay), _lib.ptr(move), _lib.ptr(mod), _lib.ptr(fact), maxlen, float(sharpfact),
+                float(grad_scale), _lib.ptr(gvec), _lib.ptr(lossvector), _lib.ptr(grad), _lib.ptr(logz),
+                _lib.ptr(ws_a), wsa, _lib.ptr(ws_b), wsb, _lib.ptr(ws_x), wsx, _lib.ptr(status), _lib.stream_ptr(),
+                _lib.ptr(lens_d))
+            _lib.check(rc, "tk_flipflop_loss_fused_varlen_labels_dev")
+            keep = keep + (lens_d,)
         else:
             # (the index build rides in kernel A's first launch: one launch less in the captured step)
             rc = L.tk_flipflop_loss_fused_labels_dev(
@@ -431,10 +481,10 @@ class FlipFlopLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, outputs, seqs, seqlen, sharpfact: float, mod_cats=None, can_mods_offsets=None,
-                mod_cat_weights=None):
+                mod_cat_weights=None, lengths=None):
         lossvector, grad, _ = _run_fused(outputs, seqs, seqlen, sharpfact, ctx.needs_input_grad[0],
                                          mod_cats=mod_cats, can_mods_offsets=can_mods_offsets,
-                                         mod_cat_weights=mod_cat_weights)
+                                         mod_cat_weights=mod_cat_weights, lengths=lengths)
         if grad is not None:
             ctx.save_for_backward(grad)
         return lossvector
@@ -442,10 +492,16 @@ class FlipFlopLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, output_grads):
         grads, = ctx.saved_tensors
-        return grads * output_grads.unsqueeze(1), None, None, None, None, None, None
+        return grads * output_grads.unsqueeze(1), None, None, None, None, None, None, None
 
 
-flipflop_loss = FlipFlopLoss.apply
+def flipflop_loss(outputs, seqs, seqlen, sharpfact, mod_cats=None, can_mods_offsets=None, mod_cat_weights=None,
+                  lengths=None):
+    """`FlipFlopLoss`.  `lengths` (keyword; as for `crf_flipflop_loss`): lossvector[n] = the CRF loss of column n on its
+    own rows + logZ(outputs[:lengths[n], n]) / lengths[n]; 0 for a column without rows or without labels."""
+    if lengths is None:
+        return FlipFlopLoss.apply(outputs, seqs, seqlen, sharpfact, mod_cats, can_mods_offsets, mod_cat_weights)
+    return FlipFlopLoss.apply(outputs, seqs, seqlen, sharpfact, mod_cats, can_mods_offsets, mod_cat_weights, lengths)
 
 
 class FlipFlopMeanLoss(torch.autograd.Function):
@@ -459,11 +515,11 @@ class FlipFlopMeanLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, outputs, seqs, seqlen, sharpfact: float, weights=None, mod_cats=None,
-                can_mods_offsets=None, mod_cat_weights=None):
-        """The last three arguments make it the cat-mod loss (ctc.pyx:258-312 on all columns + logZ
-        of the canonical ones, bin/train_flipflop.py:165-176)."""
+                can_mods_offsets=None, mod_cat_weights=None, lengths=None):
+        """mod_cats, can_mods_offsets and mod_cat_weights make it the cat-mod loss (ctc.pyx:258-312 on all columns +
+        logZ of the canonical ones, bin/train_flipflop.py:165-176); `lengths`: a time length per column."""
         nbatch = outputs.shape[1]
-        mods = dict(mod_cats=mod_cats, can_mods_offsets=can_mods_offsets, mod_cat_weights=mod_cat_weights)
+        mods = dict(mod_cats=mod_cats, can_mods_offsets=can_mods_offsets, mod_cat_weights=mod_cat_weights, lengths=lengths)
         if weights is None:
             lossvector, grad, _ = _run_fused(outputs, seqs, seqlen, sharpfact, ctx.needs_input_grad[0],
                                              grad_scale=1.0 / nbatch, **mods)
@@ -481,8 +537,8 @@ class FlipFlopMeanLoss(torch.autograd.Function):
     def backward(ctx, grad_loss, _grad_lossvector):
         grads, = ctx.saved_tensors
         if getattr(ctx, "tk_unit_grad", False):     # (set by `backward_unit` on THIS node only)
-            return grads, None, None, None, None, None, None, None
-        return grads * grad_loss, None, None, None, None, None, None, None
+            return grads, None, None, None, None, None, None, None, None
+        return grads * grad_loss, None, None, None, None, None, None, None, None
 
 
 def backward_unit(loss, **kwargs):
@@ -505,4 +561,11 @@ def backward_unit(loss, **kwargs):
             node.tk_unit_grad = False
 
 
-flipflop_mean_loss = FlipFlopMeanLoss.apply
+def flipflop_mean_loss(outputs, seqs, seqlen, sharpfact, weights=None, mod_cats=None, can_mods_offsets=None,
+                       mod_cat_weights=None, lengths=None):
+    """`FlipFlopMeanLoss`: (loss, lossvector).  `lengths` (keyword; as for `crf_flipflop_loss`): the lossvector of
+    `flipflop_loss(..., lengths=)`; with `weights` None the loss stays the mean over ALL columns of the batch."""
+    if lengths is None:
+        return FlipFlopMeanLoss.apply(outputs, seqs, seqlen, sharpfact, weights, mod_cats, can_mods_offsets, mod_cat_weights)
+    return FlipFlopMeanLoss.apply(outputs, seqs, seqlen, sharpfact, weights, mod_cats, can_mods_offsets, mod_cat_weights,
+                                  lengths)

@@ -69,9 +69,42 @@ class LogZ(torch.autograd.Function):
         return trans * g[:, None]
 
 
-def flipflop_logpartition(x, _never_use_cupy=False):
-    """layers.py:1875-1890: log-partition function for each batch element, (N,)."""
+class LogZVarlen(torch.autograd.Function):
+    """logZ of every column on its own rows, (N,): the posterior with lengths of include/taiyaki_amd_decode_varlen.h (one
+    wave per column; `decode.flipflop_make_trans(..., lengths=)` is the same launch).  backward = the posterior transition
+    probabilities * g[:, None], rows at or beyond a column's length exactly 0."""
+
+    @staticmethod
+    def forward(ctx, scores, lengths):
+        from taiyaki_amd import decode
+        V, sc, lens, nbase, wsb = decode._varlen_args(scores, lengths, "flipflop_logpartition")
+        T, N, _ = sc.shape
+        with torch.cuda.device(sc.device):
+            trans = torch.empty_like(sc)
+            logz = torch.empty(N, dtype=torch.float32, device=sc.device)
+            ws = _lib.workspace(wsb, sc.device, "decode_varlen")
+            status = _lib.status_word(sc.device)
+            _lib.check(V.tk_flipflop_posterior_varlen_dev(_lib.ptr(sc), _lib.ptr(lens), T, N, nbase, _lib.ptr(trans),
+                                                          _lib.ptr(logz), _lib.ptr(ws), wsb, _lib.ptr(status),
+                                                          _lib.stream_ptr()), "tk_flipflop_posterior_varlen_dev")
+            _lib.finish(status)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(trans)
+        return logz
+
+    @staticmethod
+    def backward(ctx, g):
+        trans, = ctx.saved_tensors
+        return trans * g[:, None], None
+
+
+def flipflop_logpartition(x, _never_use_cupy=False, lengths=None):
+    """layers.py:1875-1890: log-partition function for each batch element, (N,).  `lengths` (a host sequence or a device
+    int tensor, one time length 0..T per column): logZ of x[:lengths[n], n] per column (log nbase at length 0),
+    differentiable, the gradient rows beyond a column's length 0 -- for the loss assembled from its two operators."""
     del _never_use_cupy
+    if lengths is not None:
+        return LogZVarlen.apply(x, lengths)
     return LogZ.apply(x)
 
 
@@ -1109,8 +1142,9 @@ def forward_varlen(model, x, lengths):
     -> (out, out_lengths), where out[:out_lengths[n], n] is what `model(x[:lengths[n], n:n + 1])` gives and every row
     beyond is 0.  out_lengths is a host int64 array (`conv_out_lengths` through every Convolution).  Under grad mode
     (layers.TRAIN_VARLEN = True; a RuntimeError without it) the result is differentiable: the gradient of every parameter, and of x, is the sum over the columns of the gradients
-    of those per-column passes (rows of x beyond a column's length get 0).  The time length per column of the CRF loss
-    is not part of this: the caller masks or slices `out` by `out_lengths`.
+    of those per-column passes (rows of x beyond a column's length get 0).  The loss takes `out_lengths` as its `lengths`
+    keyword (`ctc.flipflop_mean_loss`, `ctc.crf_flipflop_loss`, ...: a time length per column; `train.calculate_loss(...,
+    lengths=)` is the two calls together).
 
     On the GPU the batch goes through every layer once: a Convolution's rows beyond the column's output length are
     zeroed (the next window then sees the zeros its own padding would have supplied), the recurrences take the

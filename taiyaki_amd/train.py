@@ -13,7 +13,7 @@ FUSED_LOSS = os.environ.get("TK_FUSED_LOSS", "1") != "0"
 
 
 def calculate_loss(net, indata, seqs, seqlens, sharpen=1.0, mod_cats=None,
-                   can_mods_offsets=None, mod_cat_weights=None, ignore_empty=False):
+                   can_mods_offsets=None, mod_cat_weights=None, ignore_empty=False, lengths=None):
     """lossvector = (A) crf / cat-mod loss + (B) logZ(outputs[:, :, :ntrans]) / nblk;
     loss = mean (bin/train_flipflop.py:161-182).
 
@@ -21,8 +21,17 @@ def calculate_loss(net, indata, seqs, seqlens, sharpen=1.0, mod_cats=None,
     asked for pass the filters and pad with zero-signal columns of sequence length 0
     (mapped_signal.sample_chunks); the reference trains on the shorter batch.  With the flag the
     mean runs over the columns with a sequence only (on the device, no sync), which is the same
-    loss and the same gradients as the reference's shorter batch."""
-    outputs = net(indata)
+    loss and the same gradients as the reference's shorter batch.
+
+    `lengths` (one sample count 0..T per column of `indata`, zero beyond; needs layers.TRAIN_VARLEN under grad mode): the
+    network runs as `layers.forward_varlen` and the loss takes its `out_lengths` -- column n's loss is the one of
+    `calculate_loss` on `indata[:lengths[n], n:n+1]` with that read's labels (0 for a column without samples), the mean
+    still runs over all columns."""
+    out_lengths = None
+    if lengths is not None:
+        outputs, out_lengths = layers.forward_varlen(net, indata, lengths)
+    else:
+        outputs = net(indata)
     nblk = float(outputs.shape[0])
     ntrans = outputs.shape[2]
     if FUSED_LOSS and outputs.is_cuda:
@@ -33,14 +42,21 @@ def calculate_loss(net, indata, seqs, seqlens, sharpen=1.0, mod_cats=None,
             live = (seqlens.to(outputs.device) > 0).to(torch.float32)
             weights = live / live.sum().clamp(min=1.0)
         return ctc.flipflop_mean_loss(outputs, seqs, seqlens, sharpen, weights, mod_cats, can_mods_offsets,
-                                      mod_cat_weights)
+                                      mod_cat_weights, lengths=out_lengths)
     if mod_cats is not None:
         lossvector = ctc.cat_mod_flipflop_loss(outputs, seqs, seqlens, mod_cats,
-                                               can_mods_offsets, mod_cat_weights, sharpen)
+                                               can_mods_offsets, mod_cat_weights, sharpen, lengths=out_lengths)
         ntrans -= ctc.n_mod_columns(can_mods_offsets)
     else:
-        lossvector = ctc.crf_flipflop_loss(outputs, seqs, seqlens, sharpen)
-    lossvector = lossvector + layers.flipflop_logpartition(outputs[:, :, :ntrans]) / nblk
+        lossvector = ctc.crf_flipflop_loss(outputs, seqs, seqlens, sharpen, lengths=out_lengths)
+    if out_lengths is not None:
+        # logZ_n / T_n on the column's own rows; a column without rows or without labels has loss 0 (as the fused operator)
+        t_n = torch.as_tensor(out_lengths, dtype=lossvector.dtype).to(lossvector.device)
+        used = (t_n > 0) & (seqlens.to(lossvector.device) > 0)
+        logz = layers.flipflop_logpartition(outputs[:, :, :ntrans], lengths=out_lengths)
+        lossvector = lossvector + torch.where(used, logz / t_n.clamp(min=1.0), torch.zeros_like(logz))
+    else:
+        lossvector = lossvector + layers.flipflop_logpartition(outputs[:, :, :ntrans]) / nblk
     if ignore_empty:
         live = (seqlens.to(lossvector.device) > 0).to(lossvector.dtype)
         return (lossvector * live).sum() / live.sum().clamp(min=1.0), lossvector
