@@ -7,7 +7,6 @@ where the kernels depart from the reference (e == 0, e < 0) are asserted against
 
 CPU: the ABI, chunk_read, the numpy restatement of the tail, the packing plan.  GPU: the three kernels, the whole
 call against the chain of existing operators, and packing as a pure regrouping."""
-import ctypes
 import itertools
 import os
 import re
@@ -164,32 +163,9 @@ def test_shim_exposes_the_chunk_helpers():
 # ----------------------------------------------------------------------------------------------------------------------
 # GPU: the kernels at the C ABI.  Every kernel is launched once per check; nothing loops on a failing launch.
 # ----------------------------------------------------------------------------------------------------------------------
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-
-
-def _ok(rc):
-    assert rc == 0, rc
-
-
-def _upload(signals, dev):
-    import torch
-    lens = np.array([len(s) for s in signals], dtype=np.int64)
-    flat = torch.from_numpy(np.concatenate(signals).astype(np.float32)).to(dev)
-    return flat, torch.from_numpy(np.concatenate([[0], np.cumsum(lens)])).to(dev), lens
-
-
-def _med_mad(signals, dev):
-    import torch
-    from taiyaki_amd import _lib
-    flat, off, _ = _upload(signals, dev)
-    med = torch.empty(len(signals), dtype=torch.float32, device=dev)
-    mad, status = torch.empty_like(med), torch.zeros(1, dtype=torch.int32, device=dev)
-    _ok(_lib.basecall_lib().tk_signal_med_mad_dev(_p(flat), _p(off), len(signals), _p(med), _p(mad), _p(status), None))
-    return med.cpu().numpy(), mad.cpu().numpy(), int(status.item())
-
-
-BAD_SIGNAL, CHUNK_PLAN = 128, 256
+# (the launches live in tests/basecall_support.py, which tests/test_basecall_glue_edges.py shares)
+_p, _ok, _med_mad, _gather, _call = bs.dev_ptr, bs.ok, bs.med_mad_dev, bs.gather_dev, bs.call_dev
+BAD_SIGNAL, CHUNK_PLAN = bs.BAD_SIGNAL, bs.CHUNK_PLAN
 
 
 @pytest.mark.gpu
@@ -216,23 +192,6 @@ def test_med_mad_kernel_is_bit_equal_to_the_reference(gpu_device):
         m, d, s = _med_mad([sigs[4], bad, sigs[5]], gpu_device)
         assert s == BAD_SIGNAL and np.isnan(m[1]) and np.isnan(d[1])
         assert m[0] == med[4] and d[2] == mad[5]
-
-
-def _gather(signals, shift, scale, dev, chunk=bs.CHUNK, overlap=bs.OVERLAP):
-    import torch
-    from taiyaki_amd import _lib, basecall
-    L = _lib.basecall_lib()
-    flat, off, lens = _upload(signals, dev)
-    total = int(basecall.chunk_counts(lens, chunk, overlap).sum())
-    chunks = torch.full((chunk, total, 1), 777.0, dtype=torch.float32, device=dev)
-    starts, ends = (torch.zeros(total, dtype=torch.int64, device=dev) for _ in range(2))
-    rco = torch.zeros(len(signals) + 1, dtype=torch.int64, device=dev)
-    ws = torch.empty(L.tk_basecall_gather_workspace_bytes(total), dtype=torch.uint8, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    sh, sc = (torch.from_numpy(np.asarray(v, dtype=np.float32)).to(dev) for v in (shift, scale))
-    _ok(L.tk_basecall_gather_chunks_dev(_p(flat), _p(off), len(signals), int(lens.sum()), _p(sh), _p(sc), chunk, overlap,
-                                        total, _p(chunks), _p(starts), _p(ends), _p(rco), _p(ws), ws.numel(), _p(status), None))
-    return chunks.cpu().numpy(), starts.cpu().numpy(), ends.cpu().numpy(), rco.cpu().numpy(), int(status.item())
 
 
 @pytest.mark.gpu
@@ -274,37 +233,6 @@ def test_gather_kernel_is_bit_equal_to_numpy(gpu_device, params):
     # a read that (a) refused (NaN shift / scale) becomes zeros
     z = _gather([sigs[names.index("len9500")]], [np.nan], [np.nan], gpu_device)
     assert z[4] == 0 and not z[0].any()
-
-
-def _call(path, err, starts, ends, rco, stride, dev, scale=1.0, offset=0.0, room=None, alphabet=b"ACGT"):
-    """tk_basecall_call_dev on per-chunk paths (nrow, nchunks) -> [(seq, qual or None)] per read"""
-    import torch
-    from taiyaki_amd import _lib
-    nread = len(rco) - 1
-    nrow, nch = path.shape
-    if room is None:
-        room = [nrow * int(rco[r + 1] - rco[r]) for r in range(nread)]
-    out_off = np.concatenate([[0], np.cumsum(room)]).astype(np.int64)
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)  # noqa: E731
-    seq = torch.full((max(int(out_off[-1]), 1),), ord("."), dtype=torch.uint8, device=dev)
-    qual = torch.full_like(seq, ord("."))
-    seqlen = torch.full((nread,), -1, dtype=torch.int32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    tensors = [t(path, np.int64), t(err, np.float32) if err is not None else None, t(starts, np.int64), t(ends, np.int64),
-               t(rco, np.int64), t(out_off, np.int64)]
-    _ok(_lib.basecall_lib().tk_basecall_call_dev(
-        _p(tensors[0]), _p(tensors[1]), nrow - 1, nch, _p(tensors[2]), _p(tensors[3]), _p(tensors[4]), None, nread, stride,
-        len(alphabet), alphabet, scale, offset, _p(tensors[5]), _p(seq), _p(qual), _p(seqlen), _p(status), None))
-    seq, qual, seqlen = seq.cpu().numpy(), qual.cpu().numpy(), seqlen.cpu().numpy()
-    assert int(status.item()) == 0
-    res = []
-    for r in range(nread):
-        lo, hi = int(out_off[r]), int(out_off[r]) + int(seqlen[r])
-        assert (seq[hi:int(out_off[r + 1])] == ord(".")).all()          # nothing written past the call
-        res.append((seq[lo:hi].tobytes().decode(), qual[lo:hi].tobytes().decode() if err is not None else None))
-    if err is None:
-        assert (qual == ord(".")).all()                                 # errprobs NULL: qual untouched
-    return res
 
 
 def _tail_case(g, name):
@@ -460,30 +388,10 @@ def test_basecaller_equals_the_chain_of_existing_operators(gpu_device, which):
         assert all(len(batch[i][0]) > 0 for i in (0, 1, 3, 5))      # (the equality above is not one of empty calls)
 
 
-def _columnwise(dev):
-    import torch
-
-    class Columnwise(torch.nn.Module):
-        """A stand-in network whose output column depends on its input column alone, through elementwise and
-        strided-slice operations only (no GEMM): regrouping columns cannot change a bit of its output."""
-
-        def __init__(self):
-            super().__init__()
-            self.w = torch.nn.Parameter(torch.linspace(-2.0, 2.0, 40))
-            self.b = torch.nn.Parameter(torch.cos(torch.arange(40.0)))
-
-        def forward(self, x):                                   # (T, N, 1) -> (ceil(T / 5), N, 40)
-            y = x[::5]
-            z = y * self.w + self.b
-            return 5.0 * torch.tanh(z + 0.25 * torch.sin(3.0 * y * y))
-
-    return Columnwise().to(dev)
-
-
 @pytest.mark.gpu
 def test_packing_is_only_a_regrouping(gpu_device):
     from taiyaki_amd import basecall
-    net = _columnwise(gpu_device)
+    net = bs.columnwise(gpu_device)
     names = list(bs.SIGNALS)
     sigs = [bs.signal(n) for n in names]
     kw = dict(stride=5, chunk_size=bs.CHUNK_BLOCKS, overlap=bs.OVERLAP_BLOCKS, max_concurrent_chunks=16, fastq=True)
