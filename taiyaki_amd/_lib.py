@@ -41,6 +41,9 @@ CONV_STRIDED_LAB_LIBNAME = "libtaiyaki_amd_conv_strided_lab.so"     # ... and it
 SQUIGGLE_NET_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_squiggle_net.h")
 SQUIGGLE_NET_LIBNAME = "libtaiyaki_amd_squiggle_net.so"     # csrc/squiggle_net.hip: the squiggle predictor network in one launch per pass, header and library of its own
 SQUIGGLE_NET_LAB_LIBNAME = "libtaiyaki_amd_squiggle_net_lab.so"     # ... and its lab build (tk_lab_squiggle_net_plan)
+LSTM_LOCAL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_lstm_local.h")
+LSTM_LOCAL_LIBNAME = "libtaiyaki_amd_lstm_local.so"     # csrc/lstm_local.hip: the LSTM recurrence at size 96, one workgroup per column set, header and library of its own
+LSTM_LOCAL_LAB_LIBNAME = "libtaiyaki_amd_lstm_local_lab.so"     # ... and its lab build (tk_lab_lstm_local_cols)
 
 VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
 VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
@@ -136,6 +139,8 @@ RNN_PROJ_SIGNATURES, RNN_PROJ_LAB_SIGNATURES = _read_wgrad_header(RNN_PROJ_HEADE
 CONV_STRIDED_SIGNATURES, CONV_STRIDED_LAB_SIGNATURES = _read_wgrad_header(CONV_STRIDED_HEADER)
 # the thirteenth: include/taiyaki_amd_squiggle_net.h (libtaiyaki_amd_squiggle_net.so), and the hook its lab build adds
 SQUIGGLE_NET_SIGNATURES, SQUIGGLE_NET_LAB_SIGNATURES = _read_wgrad_header(SQUIGGLE_NET_HEADER)
+# the fifteenth: include/taiyaki_amd_lstm_local.h (libtaiyaki_amd_lstm_local.so), and the hook its lab build adds
+LSTM_LOCAL_SIGNATURES, LSTM_LOCAL_LAB_SIGNATURES = _read_wgrad_header(LSTM_LOCAL_HEADER)
 
 
 def _read_varlen_header():
@@ -292,6 +297,16 @@ def squiggle_net_lib():
         return _load(os.path.join(CSRC, SQUIGGLE_NET_LAB_LIBNAME),
                      dict(SQUIGGLE_NET_SIGNATURES, **SQUIGGLE_NET_LAB_SIGNATURES))
     return _load(os.path.join(CSRC, SQUIGGLE_NET_LIBNAME), SQUIGGLE_NET_SIGNATURES)
+
+
+def lstm_local_lib():
+    """The LSTM recurrence at a size one workgroup holds (include/taiyaki_amd_lstm_local.h): the lab build of that
+    library while the process runs on the lab build (`use_lab`), the release one otherwise.  No fallback: a missing
+    library raises."""
+    if is_lab():
+        return _load(os.path.join(CSRC, LSTM_LOCAL_LAB_LIBNAME),
+                     dict(LSTM_LOCAL_SIGNATURES, **LSTM_LOCAL_LAB_SIGNATURES))
+    return _load(os.path.join(CSRC, LSTM_LOCAL_LIBNAME), LSTM_LOCAL_SIGNATURES)
 
 
 def varlen_lib():

@@ -160,6 +160,16 @@ int lstm_wgrad_dispatch(const float *dgates, const float *x, const float *y, siz
                         int reverse, int cu_count, float *dw_ih, float *dw_hh, float *db, void *ws, size_t wsb,
                         hipStream_t stream);
 
+// lstm_local.hip (a library of its own too, include/taiyaki_amd_lstm_local.h: the file defines its C entries itself).
+// One workgroup owns every unit of its columns: no workspace, no status word.  gates and cell may both be NULL
+int lstm_local_supported(size_t H);
+int lstm_local_columns(size_t N, size_t H, int cu_count);
+int lstm_local_forward_dispatch(const float *gx, const float *whh, const int32_t *lengths, size_t T, size_t N, size_t H,
+                                int reverse, int cu_count, float *y, float *gates, float *cell, hipStream_t stream);
+int lstm_local_backward_dispatch(const float *whh, const float *gates, const float *cell, const float *dy,
+                                 const int32_t *lengths, size_t T, size_t N, size_t H, int reverse, int cu_count,
+                                 float *dgates, hipStream_t stream);
+
 // gru_wgrad.hip (a library of its own too, include/taiyaki_amd_gru_wgrad.h; db_hh may be NULL)
 size_t gru_wgrad_workspace_bytes(size_t T, size_t N, size_t H, size_t I, int cu_count);
 int gru_wgrad_dispatch(const float *dgates, const float *dq, const float *x, const float *y, size_t T, size_t N,
@@ -197,6 +207,7 @@ void lstm_lab_cols(int cols);
 void lstm_lab_units(int units);
 bool lstm_lab_geometry(size_t N, size_t H, int cu_count, size_t *out);
 void gru_lab_cols(int cols);
+void lstm_local_lab_cols(int cols);
 bool logz_lab_plan(size_t T, size_t N, size_t nbase, size_t score_bytes, LogzPlan *p);
 int viterbi_lab_waves(size_t N);
 bool crf_lab_plan(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, size_t bulk_seqlen, int form, int want_grad,

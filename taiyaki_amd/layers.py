@@ -9,7 +9,7 @@ that feeds them.
   (BASELINE.json north_star) and only produce the (T, N, S) score tensor.
   ``Lstm`` and ``GruMod`` keep their nn.LSTM / nn.GRU parameters, but on the GPU their
   recurrences run as the persistent HIP kernels of csrc/lstm_kernels.hip
-  (`LstmRecurrence`) and csrc/gru_kernels.hip (`GruRecurrence`), and a narrow
+  (`LstmRecurrence`; size 96: csrc/lstm_local.hip, `LstmLocalRecurrence`) and csrc/gru_kernels.hip (`GruRecurrence`), and a narrow
   ``Convolution`` with swish runs as the fused HIP kernels of csrc/conv_kernels.hip
   (`SmallConvolution`).
 * ``forward_varlen`` runs a ``Serial`` on a batch whose columns have different lengths: every column's rows are what
@@ -564,10 +564,70 @@ def _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, reverse, need):
     return dx, dw_ih, dw_hh, db if need[3] else None, db if need[4] else None
 
 
+# False: an Lstm at a size that only the kernels of include/taiyaki_amd_lstm_local.h cover (96) runs nn.LSTM, with
+# lengths every column alone, as it did before there were such kernels, for comparisons against them
+USE_HIP_LSTM_LOCAL = True
+# launches of `LstmLocalRecurrence` by kind, as rnn_varlen_calls counts: "saved" wrote the activations for a backward
+# pass, "inference" handed the kernel NULL for them
+lstm_local_calls = {"saved": 0, "inference": 0}
+
+
+def hip_lstm_local_takes(rnn, x):
+    """True where the recurrence of include/taiyaki_amd_lstm_local.h runs this nn.LSTM on this input: what
+    `_hip_lstm_takes` admits, at a size one workgroup holds (`tk_lstm_local_supported`), with at least one step and one
+    column.  It needs no workspace, so there is no size to ask for."""
+    return bool(USE_HIP_LSTM_LOCAL and _hip_lstm_takes(rnn, x) and x.shape[0] and x.shape[1]
+                and _lib.lstm_local_lib().tk_lstm_local_supported(rnn.hidden_size))
+
+
+class LstmLocalRecurrence(torch.autograd.Function):
+    """One nn.LSTM layer (h0 = c0 = 0) with its recurrence on the kernels of csrc/lstm_local.hip: one workgroup owns every
+    unit of its columns, so the launches take neither workspace nor status word and admit every batch width.  The
+    projection in front and the gradients behind are `LstmRecurrence`'s (`_rnn_proj`, `_lstm_grads_from_dgates`).
+    `lens` (a device int32 tensor, one entry per column, or None): column n has lens[n] steps; y, the gates, c and dG
+    are 0 at and beyond every length.  `save` False hands NULL for the activations: they are neither allocated nor
+    written, and the call cannot be differentiated."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, lens, save):
+        T, N, _ = x.shape
+        H = w_hh.shape[1]
+        dev = x.device
+        x = x.contiguous()
+        w_hh = w_hh.contiguous()
+        lstm_local_calls["saved" if save else "inference"] += 1
+        gx = _rnn_proj(x.view(T * N, -1), w_ih, b_ih + b_hh, False)
+        y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
+        gates = torch.empty(T, N, 4 * H, dtype=torch.float32, device=dev) if save else None
+        cell = torch.empty(T, N, H, dtype=torch.float32, device=dev) if save else None
+        rc = _lib.lstm_local_lib().tk_lstm_local_forward_dev(
+            _lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(lens), T, N, H, int(reverse), _cu_count(dev), _lib.ptr(y),
+            _lib.ptr(gates), _lib.ptr(cell), _lib.stream_ptr())
+        _lib.check(rc, "tk_lstm_local_forward_dev")
+        if save:
+            ctx.save_for_backward(x, w_ih, w_hh, y, gates, cell, lens)
+        ctx.reverse = reverse
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w_ih, w_hh, y, gates, cell, lens = ctx.saved_tensors
+        T, N, _ = x.shape
+        H = w_hh.shape[1]
+        dev = x.device
+        dy = _aligned(dy)
+        dg = torch.empty_like(gates)
+        rc = _lib.lstm_local_lib().tk_lstm_local_backward_dev(
+            _lib.ptr(w_hh), _lib.ptr(gates), _lib.ptr(cell), _lib.ptr(dy), _lib.ptr(lens), T, N, H, int(ctx.reverse),
+            _cu_count(dev), _lib.ptr(dg), _lib.stream_ptr())
+        _lib.check(rc, "tk_lstm_local_backward_dev")
+        return _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None,) * 3
+
+
 class Lstm(_Rnn):
     """layers.py:491-606 (wraps nn.LSTM, bias_hh frozen).  On the GPU the recurrence runs on the HIP kernels
-    (`LstmRecurrence`), a batch wider than one launch admits as slabs of columns; nn.LSTM evaluates CPU tensors, sizes the
-    kernels do not cover, and USE_HIP_LSTM = False."""
+    (`LstmRecurrence`), a batch wider than one launch admits as slabs of columns, and size 96, which those kernels do not
+    cover, on `LstmLocalRecurrence`; nn.LSTM evaluates CPU tensors, sizes no kernel covers, and USE_HIP_LSTM = False."""
 
     def __init__(self, insize, size):
         super().__init__(nn.LSTM(insize, size))
@@ -584,6 +644,9 @@ class Lstm(_Rnn):
         if wsb:     # a batch wider than one launch admits: slabs of columns (the activations saved, as above)
             return LstmRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
                                         bool(reverse), wsb, None, True, True)
+        if hip_lstm_local_takes(rnn, x):        # a size one workgroup holds: no workspace, any batch width
+            return LstmLocalRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
+                                             bool(reverse), None, _needs_grad(x, self))
         if reverse:
             return torch.flip(rnn(torch.flip(x, (0,)))[0], (0,))
         return rnn(x)[0]
@@ -800,7 +863,8 @@ def _rnn_forward_varlen(layer, x, reverse, lengths):
     tensors, `LstmRecurrence` / `GruRecurrence` with the lengths: under grad mode with something that requires a
     gradient they save the activations (x must be finite in the padding: the parameter gradients are sums over the
     whole padded tensors); otherwise it is one launch of tk_lstm_forward_varlen_dev / tk_gru_forward_varlen_dev, which
-    saves nothing.  Every column alone at its own length otherwise (differentiable like any other call of the layer).
+    saves nothing.  An LSTM at a size one workgroup holds (96) makes the launch of `LstmLocalRecurrence` with the lengths
+    instead.  Every column alone at its own length otherwise (differentiable like any other call of the layer).
     Under grad mode the call needs
     layers.TRAIN_VARLEN = True; without it it raises, as it did before there was a backward with lengths."""
     rnn = layer.rnn
@@ -820,6 +884,12 @@ def _rnn_forward_varlen(layer, x, reverse, lengths):
     wide = bool(T and N) and not wsb
     if wide:        # a batch wider than one launch admits: slabs of columns
         wsb = hip_rnn_wide_workspace_bytes(rnn, x)
+    if not wsb and isinstance(rnn, nn.LSTM) and hip_lstm_local_takes(rnn, x):
+        with torch.cuda.device(x.device):
+            lens = torch.as_tensor(lengths).to(device=x.device, dtype=torch.int32).reshape(-1).clamp(0, T).contiguous()
+            assert lens.numel() == N, "lengths: one per column"
+            return LstmLocalRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
+                                             bool(reverse), lens, train)
     if not wsb:
         host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
         assert len(host) == N and (N == 0 or (host.min() >= 0 and host.max() <= T)), "lengths: one per column, 0..T"
