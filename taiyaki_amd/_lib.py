@@ -44,6 +44,8 @@ SQUIGGLE_NET_LAB_LIBNAME = "libtaiyaki_amd_squiggle_net_lab.so"     # ... and it
 LSTM_LOCAL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_lstm_local.h")
 LSTM_LOCAL_LIBNAME = "libtaiyaki_amd_lstm_local.so"     # csrc/lstm_local.hip: the LSTM recurrence at size 96, one workgroup per column set, header and library of its own
 LSTM_LOCAL_LAB_LIBNAME = "libtaiyaki_amd_lstm_local_lab.so"     # ... and its lab build (tk_lab_lstm_local_cols)
+ALIGN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_align.h")
+ALIGN_LIBNAME = "libtaiyaki_amd_align.so"       # csrc/align_kernels.hip: edit-distance alignment of batches of pairs, header and library of its own
 
 VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
 VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
@@ -170,6 +172,16 @@ WIDE_SIGNATURES = {n: (r, a) for n, (r, a, _) in parse_prototypes(_blank_comment
 # the fourteenth: include/taiyaki_amd_loss_varlen.h (libtaiyaki_amd_loss_varlen.so)
 LOSS_VARLEN_SIGNATURES = {n: (r, a) for n, (r, a, _) in
                           parse_prototypes(_blank_comments(open(LOSS_VARLEN_HEADER).read())).items()}
+
+
+def _read_align_header():
+    raw = open(ALIGN_HEADER).read()
+    sigs = {n: (r, a) for n, (r, a, _) in parse_prototypes(_blank_comments(raw)).items()}
+    return sigs, {k: int(v) for k, v in re.findall(r"(?m)^#define (TK_ALIGN_\w+) (\d+)", raw)}
+
+
+# the sixteenth: include/taiyaki_amd_align.h (libtaiyaki_amd_align.so), and its limits
+ALIGN_SIGNATURES, ALIGN_DEFINES = _read_align_header()
 
 
 class SeqLabels(ctypes.Structure):
@@ -307,6 +319,12 @@ def lstm_local_lib():
         return _load(os.path.join(CSRC, LSTM_LOCAL_LAB_LIBNAME),
                      dict(LSTM_LOCAL_SIGNATURES, **LSTM_LOCAL_LAB_SIGNATURES))
     return _load(os.path.join(CSRC, LSTM_LOCAL_LIBNAME), LSTM_LOCAL_SIGNATURES)
+
+
+def align_lib():
+    """The alignment kernels behind taiyaki_amd.accuracy (include/taiyaki_amd_align.h).  No fallback: a missing library
+    raises."""
+    return _load(os.path.join(CSRC, ALIGN_LIBNAME), ALIGN_SIGNATURES)
 
 
 def varlen_lib():

@@ -63,6 +63,29 @@ def calculate_loss(net, indata, seqs, seqlens, sharpen=1.0, mod_cats=None,
     return lossvector.mean(), lossvector
 
 
+def validation_accuracy(net, batch):
+    """How good the network's calls are on one batch: the Viterbi call of every column aligned against that column's
+    labels (taiyaki_amd.accuracy.call_accuracy), under `no_grad`, nothing read back.
+
+    `batch`: what `Trainer.step` takes -- indata, seqs, seqlens, and where it has them lengths and the cat-mod keys (a
+    cat-mod model's calls are those of its canonical transition scores).  Returns (mean, accuracy): the mean over the
+    columns that have labels (seqlens > 0; 0 if none has) and the per-column vector, both on the device."""
+    from taiyaki_amd import accuracy
+    with torch.no_grad():
+        out_lengths = None
+        if batch.get("lengths") is not None:
+            outputs, out_lengths = layers.forward_varlen(net, batch["indata"], batch["lengths"])
+        else:
+            outputs = net(batch["indata"])
+        ntrans = outputs.shape[2]
+        if batch.get("mod_cats") is not None:
+            ntrans -= ctc.n_mod_columns(batch["can_mods_offsets"])
+        acc = accuracy.call_accuracy(outputs[:, :, :ntrans], batch["seqs"], batch["seqlens"], out_lengths)
+        live = torch.as_tensor(batch["seqlens"]).to(acc.device) > 0
+        mean = torch.where(live, acc, torch.zeros_like(acc)).sum() / live.sum().clamp(min=1).to(acc.dtype)
+    return mean, acc
+
+
 class GateWatch:
     """Says so when the loss is losing time.  The CRF's linear-domain path hands a read it cannot
     represent (scores far outside the network's 5 tanh range, sharpening beyond 3.5, violent cat-mod
