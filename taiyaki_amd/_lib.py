@@ -46,6 +46,8 @@ LSTM_LOCAL_LIBNAME = "libtaiyaki_amd_lstm_local.so"     # csrc/lstm_local.hip: t
 LSTM_LOCAL_LAB_LIBNAME = "libtaiyaki_amd_lstm_local_lab.so"     # ... and its lab build (tk_lab_lstm_local_cols)
 ALIGN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_align.h")
 ALIGN_LIBNAME = "libtaiyaki_amd_align.so"       # csrc/align_kernels.hip: edit-distance alignment of batches of pairs, header and library of its own
+CONV_SIGNAL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_conv_signal.h")
+CONV_SIGNAL_LIBNAME = "libtaiyaki_amd_conv_signal.so"       # csrc/conv_signal.hip: the 1 -> Cout convolution on the raw signal (tanh), header and library of its own
 
 VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
 VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
@@ -182,6 +184,11 @@ def _read_align_header():
 
 # the sixteenth: include/taiyaki_amd_align.h (libtaiyaki_amd_align.so), and its limits
 ALIGN_SIGNATURES, ALIGN_DEFINES = _read_align_header()
+
+
+# the seventeenth: include/taiyaki_amd_conv_signal.h (libtaiyaki_amd_conv_signal.so)
+CONV_SIGNAL_SIGNATURES = {n: (r, a) for n, (r, a, _) in
+                          parse_prototypes(_blank_comments(open(CONV_SIGNAL_HEADER).read())).items()}
 
 
 class SeqLabels(ctypes.Structure):
@@ -325,6 +332,12 @@ def align_lib():
     """The alignment kernels behind taiyaki_amd.accuracy (include/taiyaki_amd_align.h).  No fallback: a missing library
     raises."""
     return _load(os.path.join(CSRC, ALIGN_LIBNAME), ALIGN_SIGNATURES)
+
+
+def conv_signal_lib():
+    """The mGru models' first layer, 1 -> Cout channels on the raw signal (include/taiyaki_amd_conv_signal.h).  No
+    fallback: a missing library raises."""
+    return _load(os.path.join(CSRC, CONV_SIGNAL_LIBNAME), CONV_SIGNAL_SIGNATURES)
 
 
 def varlen_lib():

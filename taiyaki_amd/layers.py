@@ -11,7 +11,8 @@ that feeds them.
   recurrences run as the persistent HIP kernels of csrc/lstm_kernels.hip
   (`LstmRecurrence`; size 96: csrc/lstm_local.hip, `LstmLocalRecurrence`) and csrc/gru_kernels.hip (`GruRecurrence`), and a narrow
   ``Convolution`` with swish runs as the fused HIP kernels of csrc/conv_kernels.hip
-  (`SmallConvolution`).
+  (`SmallConvolution`); the mGru models' first layer (1 -> size channels on the raw signal, tanh) as those of
+  csrc/conv_signal.hip (`SignalConvolution`).
 * ``forward_varlen`` runs a ``Serial`` on a batch whose columns have different lengths: every column's rows are what
   the column gives run alone (``Lstm`` / ``GruMod`` ``forward(x, reverse, lengths)`` on the forward-only launches of
   include/taiyaki_amd_rnn_varlen.h; under grad mode on the training pair of include/taiyaki_amd_rnn_varlen_train.h).
@@ -277,6 +278,78 @@ class StridedConvolution(torch.autograd.Function):
         return dx, dw, db, None
 
 
+# False: the mGru models' first layer (1 -> Cout channels, window 19, tanh) runs unfold + GEMM (exactly as with
+# USE_HIP_CONV = False), for comparisons against the kernels of include/taiyaki_amd_conv_signal.h
+USE_HIP_CONV_SIGNAL = True
+# HIP launches of `SignalConvolution` by pass
+conv_signal_calls = {"forward": 0, "backward": 0}
+
+
+def _stream_ptr(dev):
+    """The device's current stream as the C ABI takes it, without building a `torch.cuda.Stream` (`_lib.stream_ptr`
+    costs the host as much as the rest of a `SignalConvolution` call)."""
+    return _lib._vp(torch._C._cuda_getCurrentRawStream(dev.index))
+
+
+class SignalConvolution(torch.autograd.Function):
+    """tanh(conv1d(x) + b) of the mGru models' first layer (1 -> Cout channels on the raw signal, window 19, stride
+    1 ... 8; the shapes tk_conv_signal_supported names) on the kernels of csrc/conv_signal.hip.  Forward: one launch
+    writes y.  Backward: dz = dy (1 - y^2) in registers, dW and db as one launch of partial results and their sum in a
+    fixed order; no dx (the layer takes this path only where its input needs no gradient).  `save` (the caller under
+    grad mode): y and a copy of x are saved; False: nothing is."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, save, stride):
+        T, N, _ = x.shape
+        cout = weight.shape[0]
+        dev = x.device
+        ctx.stride = stride
+        weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+        if save:
+            # the network's input: a captured train step reloads that buffer in place before every replay, which
+            # autograd refuses for a saved tensor -- keep a copy (made inside the captured graph; 4 bytes a sample)
+            x = x.detach().clone(memory_format=torch.contiguous_format)
+        else:
+            x = x.detach().contiguous()
+        with torch.cuda.device(dev):
+            y = torch.empty(-(-T // stride), N, cout, dtype=torch.float32, device=dev)
+            if T * N:
+                rc = _lib.conv_signal_lib().tk_conv_signal_forward_dev(
+                    _lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), T, N, cout, stride, _cu_count(dev), _lib.ptr(y),
+                    _stream_ptr(dev))
+                _lib.check(rc, "tk_conv_signal_forward_dev")
+                conv_signal_calls["forward"] += 1
+        if save:
+            ctx.save_for_backward(x, y)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, y = ctx.saved_tensors
+        T, N, _ = x.shape
+        cout, stride = y.shape[2], ctx.stride
+        dev = x.device
+        L = _lib.conv_signal_lib()
+        dy = _aligned(dy)
+        with torch.cuda.device(dev):
+            dw = torch.empty(cout, 1, 19, dtype=torch.float32, device=dev)
+            db = torch.empty(cout, dtype=torch.float32, device=dev)
+            if T * N == 0:
+                return None, dw.zero_(), db.zero_(), None, None
+            wsb = L.tk_conv_signal_workspace_bytes(T, N, cout, stride, _cu_count(dev))
+            # the partial results (16 MB at most on 256 CUs): a block of the caching allocator, which orders its reuse
+            # on the stream and belongs to the graph's pool under capture -- the call is short enough on the GPU for
+            # the host's side of it to show (tools/convbench.py --signal)
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+            rc = L.tk_conv_signal_backward_dev(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(y), T, N, cout, stride,
+                                               _cu_count(dev), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), wsb,
+                                               _stream_ptr(dev))
+        _lib.check(rc, "tk_conv_signal_backward_dev")
+        conv_signal_calls["backward"] += 1
+        return None, dw, db, None, None
+
+
 class Convolution(nn.Module):
     """layers.py:744-850: TBF in/out, pad (winlen//2, (winlen-1)//2), then activation.
 
@@ -296,6 +369,11 @@ class Convolution(nn.Module):
     The wide layer behind them (16 -> 192, 256 or 384 channels, window 19, stride 5, swish) runs as `StridedConvolution` where
     `tk_conv_strided_supported` names the shape (USE_HIP_CONV or USE_HIP_CONV_STRIDED = False: never): its GEMMs
     read x through the window's address map, so the 124 MB window matrix of the unfold path is never written.
+
+    The mGru models' first layer (1 -> 32 ... 384 channels on the raw signal, window 19, stride 1 ... 8, tanh) runs as
+    `SignalConvolution` where `tk_conv_signal_supported` names the shape and the input needs no gradient (USE_HIP_CONV
+    or USE_HIP_CONV_SIGNAL = False: never): plain FMAs over a row's 19 taps in a fixed order, so a row has the same
+    bits in any batch, and a weight gradient without a window matrix, a pre-activation tensor or atomics.
     """
 
     def __init__(self, insize, size, winlen, stride=1, fun=torch.tanh, use_gemm=True):
@@ -324,6 +402,18 @@ class Convolution(nn.Module):
         return bool(L.tk_conv_strided_supported(w.shape[1], w.shape[0], self.winlen, self.stride)
                     and L.tk_conv_strided_workspace_bytes(x.shape[0], x.shape[1], w.shape[0], _cu_count(x.device)))
 
+    def _hip_signal(self, x):
+        w = self.conv.weight
+        if not (USE_HIP_CONV and USE_HIP_CONV_SIGNAL and self.activation is torch.tanh and x.is_cuda and x.dim() == 3
+                and x.shape[2] == 1 and x.dtype == torch.float32 and w.is_cuda and w.dtype == torch.float32
+                and self.conv.bias.is_cuda and self.conv.bias.dtype == torch.float32
+                and not (torch.is_grad_enabled() and x.requires_grad)):
+            return False
+        L = _lib.conv_signal_lib()
+        return bool(L.tk_conv_signal_supported(w.shape[1], w.shape[0], self.winlen, self.stride)
+                    and L.tk_conv_signal_workspace_bytes(x.shape[0], x.shape[1], w.shape[0], self.stride,
+                                                         _cu_count(x.device)))
+
     def forward(self, x):
         if not self.use_gemm:
             out = self.activation(self.conv(self.pad(x.permute(1, 2, 0))))
@@ -334,6 +424,10 @@ class Convolution(nn.Module):
             w, b = self.conv.weight, self.conv.bias
             save = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or b.requires_grad)
             return StridedConvolution.apply(x, w, b, save)
+        if self._hip_signal(x):
+            w, b = self.conv.weight, self.conv.bias
+            save = torch.is_grad_enabled() and (w.requires_grad or b.requires_grad)
+            return SignalConvolution.apply(x, w, b, save, self.stride)
         # x: (T, N, C) -> pad time -> windows (Tout, N, C, winlen) -> GEMM with (C*winlen, size)
         xp = nn.functional.pad(x, (0, 0, 0, 0, self.winlen // 2, (self.winlen - 1) // 2))
         win = xp.unfold(0, self.winlen, self.stride)            # (Tout, N, C, winlen) view

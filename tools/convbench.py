@@ -5,8 +5,11 @@ warm-up.  The HIP operator and the unfold + GEMM path (layers.USE_HIP_CONV = Fal
 line each (median and min over --steps, and the achieved GB/s against the compulsory bytes: forward reads x and
 writes y, backward reads dy and x and writes dx where the layer has an input gradient -- conv 1 has none).  Then conv 3
 (16 -> 256, window 19, stride 5; csrc/conv_strided.hip) against its unfold + GEMM path, in alternating turns (`conv3`).
+--signal: only the mGru models' first layer (1 -> Cout on the raw signal, window 19, tanh; csrc/conv_signal.hip) against
+its unfold + GEMM path, in alternating turns, at every TxN:stride:cout[:fwd] of --signal-shapes (`signal`).
 
     python tools/convbench.py [--steps 30] [--warmup 5] [--shapes 4000x128 8000x64] [--turns 5] [--calls 20]
+    python tools/convbench.py --signal [--signal-shapes 2000x64:2:96 60000x8:4:96:fwd] [--turns 5] [--calls 20]
 """
 import argparse
 import json
@@ -43,11 +46,22 @@ def main():
     ap.add_argument("--turns", type=int, default=5, help="conv 3: alternating turns of the kernels and the GEMM path")
     ap.add_argument("--calls", type=int, default=20, help="conv 3: calls per turn")
     ap.add_argument("--cout", type=int, nargs="*", default=[256], help="conv 3: output channels (the models' size)")
+    ap.add_argument("--signal", action="store_true", help="time the signal convolution (1 -> Cout, tanh) only")
+    ap.add_argument("--signal-shapes", nargs="*", default=["2000x64:2:96", "4000x128:5:256", "4000x128:5:384",
+                                                            "60000x8:4:96:fwd"],
+                    help="signal: TxN:stride:cout, `:fwd` for the forward alone (whole reads)")
+    ap.add_argument("--host-warmup", type=int, default=1000, help="signal: eager calls per path before the first turn")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("convbench needs a GPU")
     dev = torch.device("cuda:0")
     torch.backends.cuda.preferred_blas_library("cublas")        # rocBLAS, as bench.py runs the GEMM path
+    if a.signal:
+        for spec in a.signal_shapes:
+            shape, stride, cout, *rest = spec.split(":")
+            T, N = (int(v) for v in shape.split("x"))
+            signal(T, N, int(stride), int(cout), rest == ["fwd"], a, dev)
+        return
     for shape in a.shapes:
         T, N = (int(v) for v in shape.split("x"))
         for name, cin, cout, want_dx in (("conv1", 1, 4, False), ("conv2", 4, 16, True)):
@@ -116,6 +130,76 @@ def conv3(T, N, cout, a, dev):
     print(json.dumps({"layer": "conv3", "T": T, "N": N, "cout": cout, "hip_below_gemm_every_turn": {
         "fwd": max(f for f, _ in res[True]) < min(f for f, _ in res[False]),
         "bwd": max(b for _, b in res[True]) < min(b for _, b in res[False])}}))
+
+
+def signal(T, N, stride, cout, fwd_only, a, dev):
+    """The mGru models' first layer (1 -> cout, window 19, tanh; csrc/conv_signal.hip): the kernels and the unfold + GEMM
+    path (layers.USE_HIP_CONV_SIGNAL = False) in alternating turns, the median of --calls calls per turn: the forward
+    under no_grad, as a basecaller runs it, the grad-mode forward + backward of a training step called eagerly (the
+    larger of the host's and the device's time), and the same step (whole reads: the forward) replayed from a hipGraph
+    (the device's time alone).  The last line says whether the kernels were below the GEMM path in every turn."""
+    torch.manual_seed(1)
+    conv = layers.Convolution(1, cout, 19, stride=stride).to(dev)
+    x = torch.randn(T, N, 1, device=dev)
+    tout = -(-T // stride)
+    dy = torch.randn(tout, N, cout, device=dev)
+    tag = {"layer": "signal", "T": T, "N": N, "stride": stride, "cout": cout}
+    if not conv._hip_signal(x):
+        print(json.dumps(dict(tag, kernels="not admitted at this size")))
+        return
+
+    def fwd():
+        with torch.no_grad():
+            conv(x)
+
+    def both():
+        conv(x).backward(dy)
+
+    def step():
+        return torch.autograd.grad(conv(x), [conv.conv.weight, conv.conv.bias], dy)
+
+    def captured(fn):       # one hipGraph of the call, as a captured train step holds it: replays cost the host nothing
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            fn()
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            keep = fn()
+        return g, keep
+
+    graphs = {}
+    for hip in (True, False):
+        layers.USE_HIP_CONV_SIGNAL = hip
+        graphs[hip] = captured(fwd if fwd_only else step)
+        # the eager calls are bound by the host at these sizes, and the host (the autograd thread, the allocator's
+        # pools, its clocks) takes a few hundred calls to settle: both paths get them before the first turn
+        for _ in range(a.host_warmup):
+            fwd() if fwd_only else both()
+        torch.cuda.synchronize()
+    res = {True: [], False: []}
+    for turn in range(a.turns):
+        for hip in (True, False):
+            layers.USE_HIP_CONV_SIGNAL = hip
+            f_med, f_min = timed(fwd, a.calls, a.warmup)
+            fb_med, fb_min = (f_med, f_min) if fwd_only else timed(both, a.calls, a.warmup)
+            g_med, g_min = timed(graphs[hip][0].replay, a.calls, a.warmup)
+            res[hip].append((f_med, fb_med, g_med))
+            line = dict(tag, turn=turn, path="hip" if hip else "gemm", fwd_us=round(1e3 * f_med, 1),
+                        fwd_min_us=round(1e3 * f_min, 1), y_MB=round(4 * tout * N * cout / 1e6, 1))
+            if not fwd_only:
+                line.update(fwd_bwd_us=round(1e3 * fb_med, 1), fwd_bwd_min_us=round(1e3 * fb_min, 1))
+            line.update({"graph_%s_us" % ("fwd" if fwd_only else "fwd_bwd"): round(1e3 * g_med, 1),
+                         "graph_min_us": round(1e3 * g_min, 1)})
+            print(json.dumps(line))
+            conv.zero_grad(set_to_none=True)
+    layers.USE_HIP_CONV_SIGNAL = True
+    below = {"fwd": max(r[0] for r in res[True]) < min(r[0] for r in res[False])}
+    if not fwd_only:
+        below["fwd_bwd"] = max(r[1] for r in res[True]) < min(r[1] for r in res[False])
+    below["graph"] = max(r[2] for r in res[True]) < min(r[2] for r in res[False])
+    print(json.dumps(dict(tag, hip_below_gemm_every_turn=below)))
 
 
 if __name__ == "__main__":
