@@ -7,13 +7,16 @@
 //
 // Two launches.  proj_prep_kernel writes the three bf16 parts of B (nout x k; for the input gradient B[n][k] =
 // w_ih[k][n]) into the workspace as [column tile][k block][part][32 columns][lane][16 bytes]: exactly the bytes, in
-// their order, that a workgroup copies into LDS for one k block, zeros beyond nout.  proj_kernel: a workgroup of four
-// waves owns a PJ_RT x PJ_NT = 128 x 128 output tile (each wave 64 x 64: 2 x 2 accumulators of 32 x 32, twice) and
-// walks k in blocks of PJ_KB = 16, one MFMA step.  Per block every thread loads two float4 of `a` and three 16-byte
-// pieces of the B images; after the block's MFMAs it splits the float4s of the NEXT block, writes 8 bytes into each of
-// the three images of `a` and copies the B pieces into the other LDS buffer; the block after that is already on its
-// way from memory (two register sets).  One barrier per block.  With 52 KB of LDS and at most 256 registers two
-// workgroups share a CU: two waves per SIMD, so one's split, loads and final stores run beside the other's MFMAs.
+// their order, of the MFMA operand fragments of one k block (a fragment = 64 lanes x 16 bytes), zeros beyond nout.
+// proj_kernel: a workgroup of four waves owns a PJ_RT x PJ_NT = 128 x 128 output tile (each wave 64 x 64: 2 x 2
+// accumulators of 32 x 32, twice) and walks k in blocks of PJ_KB = 16, one MFMA step.  Per block every thread loads
+// two float4 of `a`; after the block's MFMAs it splits the float4s of the NEXT block and writes 8 bytes into each of
+// the three images of `a` in the other LDS buffer; the block after that is already on its way from memory (two
+// register sets).  The weights do not pass through LDS: each wave loads its six B fragments of the next block from
+// the workspace (L2) straight into the registers the MFMAs read, one coalesced 1 KB load each, one block ahead (two
+// register sets); the prep launch precedes this one on the stream, so they are plain loads.  One barrier per block.
+// With 27 KB of LDS and at most 256 registers two workgroups share a CU: two waves per SIMD, so one's split, loads and
+// final stores run beside the other's MFMAs.
 // LDS images: a fragment (32 rows x 16 k) is 64 lanes x 16 bytes, lane = row + 32 (k / 8), read as one ds_read_b128 per
 // lane, linear in the lane (conflict-free).  In the images of `a` the two halves of a fragment are 576 bytes apart: the
 // 16 lanes of one ds_write_b64 group (4 rows x 4 float4) then cover a whole 128-byte bank row once.
@@ -38,9 +41,6 @@ constexpr int PJ_A_PART = (PJ_RT / 32) * PJ_A_MB;   // and of one part
 constexpr int PJ_A_PASSES = PJ_RT * (PJ_KB / 4) / PJ_THREADS;   // float4s of `a` per thread and block
 constexpr int PJ_B_PART = (PJ_NT / 32) * 1024;      // images of B: one part of one block,
 constexpr int PJ_B_BLOCK = 3 * PJ_B_PART;           // one block
-constexpr int PJ_B_COPIES = PJ_B_BLOCK / 16 / PJ_THREADS;       // 16-byte pieces per thread
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-static_assert(PJ_B_COPIES * 16 * PJ_THREADS == PJ_B_BLOCK, "the B block is copied in whole passes");
 static_assert(PJ_A_PASSES * PJ_THREADS == PJ_RT * (PJ_KB / 4), "the block of `a` is staged in whole passes");
 
 // The gradient form (k > nout: a long k walked by few workgroups) was measured slower than rocBLAS at 15 and 1600 rows
@@ -114,7 +114,6 @@ struct ProjArgs {
 template <bool WIDE>
 __global__ __launch_bounds__(PJ_THREADS, 2) void proj_kernel(const ProjArgs p) {
     __shared__ __attribute__((aligned(16))) unsigned char imga[2][3 * PJ_A_PART];   // [buffer][part]
-    __shared__ __attribute__((aligned(16))) unsigned char imgb[2][PJ_B_BLOCK];
 
     const float *asrc = p.a;
     const int M = p.M, K = p.K, nkb = p.nkb;
@@ -129,10 +128,10 @@ __global__ __launch_bounds__(PJ_THREADS, 2) void proj_kernel(const ProjArgs p) {
     const int q = tid & 3, r = tid >> 2;
     const int awoff = (r >> 5) * PJ_A_MB + (q >> 1) * PJ_A_HALF + (r & 31) * 16 + 8 * (q & 1);
     const int m_first = mt * PJ_RT + r;
-    const u32x4 *bsrc = reinterpret_cast<const u32x4 *>(p.bimg + (size_t)nt * nkb * PJ_B_BLOCK) + tid;
-    // operand fragments
+    // operand fragments: those of `a` from LDS, those of B from the workspace, where fragment (32-column block, part) of
+    // a block is 64 lanes x 16 consecutive bytes
     const int aroff = wmb * PJ_A_MB + lhalf * PJ_A_HALF + l31 * 16;
-    const int broff = (wnb * 64 + lane) * 16;
+    const unsigned char *bsrc = p.bimg + (size_t)nt * nkb * PJ_B_BLOCK + (wnb * 64 + lane) * 16;
 
     f32x16 acc[WG_ACC_SETS][2][2];
 #pragma unroll
@@ -144,14 +143,16 @@ __global__ __launch_bounds__(PJ_THREADS, 2) void proj_kernel(const ProjArgs p) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[s][i][j][e] = 0.f;
 
-    // two blocks are in flight from memory: block kb + 2 is requested before the MFMAs of block kb, block kb + 1 is
-    // split and written to the other LDS buffer after them
+    // two blocks of `a` are in flight from memory: block kb + 2 is requested before the MFMAs of block kb, block kb + 1
+    // is split and written to the other LDS buffer after them.  The wave's six fragments of B (2 column blocks x 3
+    // parts) of block kb + 1 are requested before the MFMAs of block kb as well, into the register set the MFMAs of
+    // block kb - 1 read
     float4 ra[2][PJ_A_PASSES];
     bool oka[2][PJ_A_PASSES];
-    u32x4 rb[2][PJ_B_COPIES];
+    bf16x8 fb[2][2][3];
 
-    // a block past the end is fetched as zeros of `a` (element 0 where the loads are unguarded) against the last block
-    // of B again; it is staged but never multiplied
+    // a block past the end is fetched as zeros of `a` (element 0 where the loads are unguarded) and staged but never
+    // multiplied; of B the last block is fetched again (the workspace ends with it) and never multiplied either
     auto fetch = [&](int kb, int set) {
         const int k = kb * PJ_KB + 4 * q;
         const bool kok = kb < nkb;
@@ -164,9 +165,14 @@ __global__ __launch_bounds__(PJ_THREADS, 2) void proj_kernel(const ProjArgs p) {
             else
                 ra[set][j] = load4<false>(asrc, K, m, oka[set][j], k);
         }
-        const int kbb = kok ? kb : nkb - 1;
+    };
+    auto fetchb = [&](int kb, int set) {
+        const unsigned char *at = bsrc + (size_t)(kb < nkb ? kb : nkb - 1) * PJ_B_BLOCK;
 #pragma unroll
-        for (int c = 0; c < PJ_B_COPIES; ++c) rb[set][c] = bsrc[(size_t)kbb * (PJ_B_BLOCK / 16) + c * PJ_THREADS];
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int t = 0; t < 3; ++t)
+                fb[set][i][t] = *reinterpret_cast<const bf16x8 *>(at + t * PJ_B_PART + i * 1024);
     };
     auto stash = [&](int set, int buf) {
 #pragma unroll
@@ -181,11 +187,20 @@ __global__ __launch_bounds__(PJ_THREADS, 2) void proj_kernel(const ProjArgs p) {
             *reinterpret_cast<uint2 *>(at + PJ_A_PART) = p2;
             *reinterpret_cast<uint2 *>(at + 2 * PJ_A_PART) = p3;
         }
-#pragma unroll
-        for (int c = 0; c < PJ_B_COPIES; ++c) reinterpret_cast<u32x4 *>(imgb[buf])[tid + c * PJ_THREADS] = rb[set][c];
     };
 
+    // the bias is loaded ahead of the loop, whose waits cover it.  Loaded in the epilogue, inside a branch, it left a
+    // pending load at every join of the guarded stores, and a wait for it waits for the stores issued so far as well
+    // (one counter for both): each store then waited for the one before it to reach L2
+    float bias[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int n = nt * PJ_NT + (wnb + j) * 32 + l31;
+        bias[j] = (p.bias && n < p.N) ? p.bias[n] : 0.f;
+    }
+
     fetch(0, 0);
+    fetchb(0, 0);
     fetch(1, 1);
     stash(0, 0);
     __syncthreads();
@@ -195,14 +210,13 @@ __global__ __launch_bounds__(PJ_THREADS, 2) void proj_kernel(const ProjArgs p) {
             const int kb = kb2 + cur;
             if (kb >= nkb) break;
             fetch(kb + 2, cur);
-            bf16x8 fa[2][3], fb[2][3];
+            fetchb(kb + 1, cur ^ 1);
+            bf16x8 fa[2][3];
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int t = 0; t < 3; ++t) {
+                for (int t = 0; t < 3; ++t)
                     fa[i][t] = *reinterpret_cast<const bf16x8 *>(&imga[cur][t * PJ_A_PART + i * PJ_A_MB + aroff]);
-                    fb[i][t] = *reinterpret_cast<const bf16x8 *>(&imgb[cur][t * PJ_B_PART + i * 1024 + broff]);
-                }
             // a1 b1, then the corrections, the smallest first
             constexpr int PA[6] = {0, 2, 0, 1, 1, 0}, PB[6] = {0, 0, 2, 1, 0, 1};
 #pragma unroll
@@ -212,7 +226,7 @@ __global__ __launch_bounds__(PJ_THREADS, 2) void proj_kernel(const ProjArgs p) {
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
-                        acc[set][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][PA[t]], fb[j][PB[t]],
+                        acc[set][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][PA[t]], fb[cur][j][PB[t]],
                                                                                   acc[set][i][j], 0, 0, 0);
             }
             stash(cur ^ 1, cur ^ 1);    // (its last readers passed the barrier of block kb - 1)
@@ -225,7 +239,7 @@ __global__ __launch_bounds__(PJ_THREADS, 2) void proj_kernel(const ProjArgs p) {
     for (int j = 0; j < 2; ++j) {
         const int n = nt * PJ_NT + (wnb + j) * 32 + l31;
         const bool nok = n < p.N;
-        const float b = (p.bias && nok) ? p.bias[n] : 0.f;
+        const float b = bias[j];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
