@@ -22,6 +22,12 @@
 // cut again, inside its workgroup, into partial results of their own: no accumulation chain is longer than that.
 // blockIdx = column tile * rstride + (row tile * runs + run) with rstride a multiple of 8: the workgroups that
 // read the same rows of A sit on one XCD and share its L2.
+// The tall form (TALL; wgrad_tall says when): a workgroup owns the two row tiles 2p and 2p + 1, 256 x 128 (each wave
+// 64 x 64: 2 x 2 accumulators, twice), over the first or the second half of a run's partial results.  The x / y block is
+// split, written and read as fragments once for both row tiles, and a wave issues 24 MFMAs between two barriers, not 12.
+// A partial result is the same sums of the same fragments in the same order as in the square form: the same bits.
+// blockIdx = column tile * rstride + ((tile pair * runs + run) * 2 + half): same grid, same padding of rstride, and
+// with runs a multiple of 4 the workgroups of one (run, half) share blockIdx % 8.
 //
 // A cell:
 //   GATES        M = GATES H
@@ -157,29 +163,40 @@ __device__ __forceinline__ bf16x8 frag(const unsigned char *at) {
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-template <class Cell, int LOADS>
+template <class Cell, int LOADS, bool TALL = false>
 __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const typename Cell::Args a) {
-    __shared__ __attribute__((aligned(16))) unsigned char img[2][2][3][WG_IMAGE];    // [buffer][A, x / y][part]
-    __shared__ __attribute__((aligned(16))) float colsum[WG_THREADS / 32][WG_TILE];
+    constexpr int RT = TALL ? 2 : 1;                        // row tiles of a workgroup
+    constexpr int WACR = TALL ? 2 : WG_THREADS / 128;       // waves across its 128 columns
+    constexpr int NJ = WG_TILE / 32 / WACR;                 // 32-column accumulators per wave across (two down)
+    static_assert(!TALL || LOADS == WG_FAST, "the tall form stages whole tiles");
+    __shared__ __attribute__((aligned(16))) unsigned char img[2][RT + 1][3][WG_IMAGE];   // [buffer][A's row tiles, x / y][part]
+    __shared__ __attribute__((aligned(16))) float colsum[WG_THREADS / 32][RT * WG_TILE];
 
     const int tnx = blockIdx.x / a.rstride, q = blockIdx.x % a.rstride;
     if (q >= a.tiles_m * a.splits) return;      // (the padding of rstride)
-    const int run = q % a.splits, tmx = q / a.splits;
+    // square: q = row tile * runs + run, every part of the run.  Tall: q = (tile pair * runs + run) * 2 + half, the
+    // first or the second nsub / 2 parts of the run
+    const int qr = TALL ? q >> 1 : q;
+    const int run = qr % a.splits, tmx = RT * (qr / a.splits);
+    const int sub_begin = TALL ? (q & 1) * (a.nsub / 2) : 0, sub_end = TALL ? sub_begin + a.nsub / 2 : a.nsub;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lhalf = lane >> 5;
-    const int wm = (wave / (WG_THREADS / 128)) * 64, wn = (wave % (WG_THREADS / 128)) * 32 * WG_NJ;
+    // tall: the wave's 64 rows lie in A's image wm / 128, from its column wm % 128 on
+    const int wm = (wave / WACR) * 64, wn = (wave % WACR) * 32 * NJ;
+    const int wmi = TALL ? wm & (WG_TILE - 1) : wm;
     const int c4 = (tid & 31) * 4, r0 = tid >> 5;       // staging: this thread's four columns and first row of a block
     // ... and where they go in an image: chunk c4 / 8 of row r0, swizzled; rows r0 and r0 + 8 swizzle alike
     const int woff = 256 * r0 + 16 * (((tid & 31) >> 1) ^ ((r0 & 3) << 2)) + 8 * (tid & 1);
     // the transposed read: lane 4 tq + tp of each 16 gives the address of row tq, columns 4 tp ... + 3 of its block of
     // 4 rows x 16 columns; the wave's four blocks are columns 0-15 / 16-31 of rows 8 lhalf ... + 3
     const int tq = (lane >> 2) & 3, tp = lane & 3;
-    int aoff[2], boff[WG_NJ];
+    int aoff[2], boff[NJ];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int row = 256 * (8 * lhalf + tq) + 8 * (tp & 1), chunk = 4 * i + 2 * ((lane >> 4) & 1) + (tp >> 1);
-        aoff[i] = row + 16 * ((wm / 8 + chunk) ^ (tq << 2));
-        if (i < WG_NJ) boff[i] = row + 16 * ((wn / 8 + chunk) ^ (tq << 2));
+        aoff[i] = row + 16 * ((wmi / 8 + chunk) ^ (tq << 2));
+        if constexpr (TALL) aoff[i] += (wm / WG_TILE) * 3 * WG_IMAGE;
+        if (i < NJ) boff[i] = row + 16 * ((wn / 8 + chunk) ^ (tq << 2));
     }
 
     const bool is_x = tnx < a.tiles_x;
@@ -191,7 +208,8 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const typename Cell::
     const int W = a.I + a.H;
     const bool sum_cols = tnx == 0 || (Cell::SEAM && tnx == a.tiles_x);
     const int acol = tmx * WG_TILE + c4, bcol = bcol0 + c4;
-    // where this thread's float4 of A comes from
+    // where this thread's float4 of A comes from (tall: the second row tile's 128 columns on; with whole tiles 2H is a
+    // multiple of 256, so both lie on one side of the seam)
     const float *asrc = a.dg;
     int ald = a.M, acolx = acol;
     if constexpr (Cell::SEAM) {
@@ -209,24 +227,26 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const typename Cell::
     const int run_begin = run * a.run_rows;
     const int run_end = min(run_begin + a.run_rows, a.K);
 
-    for (int sub = 0; sub < a.nsub; ++sub) {
+    for (int sub = sub_begin; sub < sub_end; ++sub) {
         const int k0 = run_begin + sub * a.sub_rows;
         const int k1 = min(k0 + a.sub_rows, run_end);
         const int nkb = k1 > k0 ? (k1 - k0 + WG_KB - 1) / WG_KB : 0;
 
-        f32x16 acc[WG_ACC_SETS][2][WG_NJ];
+        f32x16 acc[WG_ACC_SETS][2][NJ];
 #pragma unroll
         for (int s = 0; s < WG_ACC_SETS; ++s)
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < WG_NJ; ++j)
+                for (int j = 0; j < NJ; ++j)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[s][i][j][r] = 0.f;
-        float4 dbacc = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 dbacc[RT];
+#pragma unroll
+        for (int t = 0; t < RT; ++t) dbacc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
         // two blocks are in flight from memory: block kb + 2 is requested before the MFMAs of block kb, block kb + 1
         // is split and written to LDS after them
-        float4 ra[2][WG_SPASS], rb[2][WG_SPASS];
+        float4 ra[2][WG_SPASS][RT], rb[2][WG_SPASS];
         bool oka[2][WG_SPASS], okb[2][WG_SPASS];
 
         auto fetch = [&](int kb, int set) {
@@ -235,19 +255,29 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const typename Cell::
                 const int k = k0 + kb * WG_KB + r0 + WG_SROWS * j;
                 const int kk = k + shift;
                 oka[set][j] = k < k1 && acok, okb[set][j] = k < k1 && kk >= 0 && kk < a.K && bcok;
-                ra[set][j] = load4<LOADS != WG_GUARDED>(asrc, ald, k, oka[set][j], acl);
+                // (the second row tile's load written out: as a loop over the row tiles the guarded form's branches
+                // compiled to three more scalar instructions than they had)
+                ra[set][j][0] = load4<LOADS != WG_GUARDED>(asrc, ald, k, oka[set][j], acl);
+                if constexpr (TALL) ra[set][j][1] = load4<true>(asrc, ald, k, oka[set][j], acl + WG_TILE);
                 rb[set][j] = load4<LOADS != WG_GUARDED>(bsrc, bld, kk, okb[set][j], bcl);
             }
         };
         auto stash = [&](int set, int buf) {
 #pragma unroll
             for (int j = 0; j < WG_SPASS; ++j) {
-                float4 va = ra[set][j], vb = rb[set][j];
-                if (!oka[set][j]) va = make_float4(0.f, 0.f, 0.f, 0.f);
+                float4 va[RT], vb = rb[set][j];
+#pragma unroll
+                for (int t = 0; t < RT; ++t) {
+                    va[t] = ra[set][j][t];
+                    if (!oka[set][j]) va[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
                 if (!okb[set][j]) vb = make_float4(0.f, 0.f, 0.f, 0.f);
-                stage4(&img[buf][0][0][woff + 256 * WG_SROWS * j], va);
-                stage4(&img[buf][1][0][woff + 256 * WG_SROWS * j], vb);
-                dbacc.x += va.x, dbacc.y += va.y, dbacc.z += va.z, dbacc.w += va.w;     // (used where sum_cols)
+#pragma unroll
+                for (int t = 0; t < RT; ++t) stage4(&img[buf][t][0][woff + 256 * WG_SROWS * j], va[t]);
+                stage4(&img[buf][RT][0][woff + 256 * WG_SROWS * j], vb);
+#pragma unroll
+                for (int t = 0; t < RT; ++t)    // (used where sum_cols)
+                    dbacc[t].x += va[t].x, dbacc[t].y += va[t].y, dbacc[t].z += va[t].z, dbacc[t].w += va[t].w;
             }
         };
 
@@ -262,13 +292,13 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const typename Cell::
             for (int cur = 0; cur < 2; ++cur) {     // block kb is in LDS buffer kb & 1 and came through register set kb & 1
                 const int kb = kb2 + cur;
                 fetch(kb + 2, cur);
-                bf16x8 fa[2][3], fb[WG_NJ][3];
+                bf16x8 fa[2][3], fb[NJ][3];
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int p = 0; p < 3; ++p) {
-                        fa[i][p] = frag(&img[cur][0][p][aoff[i]]);
-                        if (i < WG_NJ) fb[i][p] = frag(&img[cur][1][p][boff[i]]);
+                        fa[i][p] = frag(&img[cur][0][0][p * WG_IMAGE + aoff[i]]);
+                        if (i < NJ) fb[i][p] = frag(&img[cur][RT][p][boff[i]]);
                     }
                 // a1 b1, then the corrections, the smallest first
                 constexpr int PA[6] = {0, 2, 0, 1, 1, 0}, PB[6] = {0, 0, 2, 1, 0, 1};
@@ -278,7 +308,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const typename Cell::
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
-                        for (int j = 0; j < WG_NJ; ++j)
+                        for (int j = 0; j < NJ; ++j)
                             acc[s][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][PA[t]], fb[j][PB[t]],
                                                                                     acc[s][i][j], 0, 0, 0);
                 }
@@ -289,22 +319,27 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const typename Cell::
 
         // this partial result: C[m][n] of accumulator register r sits at row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31
         float *slab = a.ws + (size_t)(run * a.nsub + sub) * a.slab_floats;
+        // tall: the stores' addresses are worked out here, after the blocks; left to the compiler they are hoisted out
+        // of the loop over the parts and, with 128 accumulators, 38 registers of them spill around the block loop
+        int wme = wm, wne = wn;
+        if constexpr (TALL) asm volatile("" : "+v"(wme), "+v"(wne));
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < WG_NJ; ++j) {
-                const int n = wn + 32 * j + l31;
+            for (int j = 0; j < NJ; ++j) {
+                const int n = wne + 32 * j + l31;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int m = tmx * WG_TILE + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
+                    const int m = tmx * WG_TILE + wme + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
                     const float v = WG_ACC_SETS == 2 ? acc[0][i][j][r] + acc[WG_ACC_SETS - 1][i][j][r] : acc[0][i][j][r];
                     if (m < a.M && bcol0 + n < bld) slab[(size_t)m * W + out_col0 + n] = v;
                 }
             }
         if (sum_cols) {
-            *reinterpret_cast<float4 *>(&colsum[r0][c4]) = dbacc;
+#pragma unroll
+            for (int t = 0; t < RT; ++t) *reinterpret_cast<float4 *>(&colsum[r0][c4 + WG_TILE * t]) = dbacc[t];
             __syncthreads();
-            if (tid < WG_TILE) {
+            if (tid < RT * WG_TILE) {
                 float v = colsum[0][tid];
 #pragma unroll
                 for (int r = 1; r < WG_THREADS / 32; ++r) v += colsum[r][tid];
@@ -362,6 +397,11 @@ int wgrad_loads(bool aligned, size_t H, size_t I) {
     return WG_GUARDED;
 }
 
+// Which form a call with those loads and that plan takes.  Tall: a workgroup owns two row tiles, 2p and 2p + 1, over
+// half of a run's partial results, where a square one owns one tile over all of them; every partial result is made of
+// the same sums in the same order either way.  It wants whole tiles, row tiles in pairs and the parts of a run in halves.
+inline bool wgrad_tall(int loads, const WgradPlan &p) { return loads == WG_FAST && p.tiles_m % 2 == 0 && p.nsub % 2 == 0; }
+
 // The two launches.  `a` comes with its operand pointers set (the caller has refused NULLs); `aligned`: they are all
 // 16-byte aligned.
 template <class Cell>
@@ -379,7 +419,10 @@ int wgrad_launch(typename Cell::Args a, bool aligned, size_t T, size_t N, size_t
     constexpr int EDGE = Cell::VEC4_EDGE ? WG_VEC4 : WG_GUARDED;
     switch (wgrad_loads<Cell>(aligned, H, I)) {
     case WG_FAST:
-        hipLaunchKernelGGL((wgrad_kernel<Cell, WG_FAST>), dim3(p.grid), dim3(WG_THREADS), 0, stream, a);
+        if (wgrad_tall(WG_FAST, p))
+            hipLaunchKernelGGL((wgrad_kernel<Cell, WG_FAST, true>), dim3(p.grid), dim3(WG_THREADS), 0, stream, a);
+        else
+            hipLaunchKernelGGL((wgrad_kernel<Cell, WG_FAST>), dim3(p.grid), dim3(WG_THREADS), 0, stream, a);
         break;
     case WG_VEC4:
         hipLaunchKernelGGL((wgrad_kernel<Cell, EDGE>), dim3(p.grid), dim3(WG_THREADS), 0, stream, a);
