@@ -48,6 +48,9 @@ ALIGN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_alig
 ALIGN_LIBNAME = "libtaiyaki_amd_align.so"       # csrc/align_kernels.hip: edit-distance alignment of batches of pairs, header and library of its own
 CONV_SIGNAL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_conv_signal.h")
 CONV_SIGNAL_LIBNAME = "libtaiyaki_amd_conv_signal.so"       # csrc/conv_signal.hip: the 1 -> Cout convolution on the raw signal (tanh), header and library of its own
+OUT_LAYER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_out_layer.h")
+OUT_LAYER_LIBNAME = "libtaiyaki_amd_out_layer.so"       # csrc/out_layer.hip: the models' output layer (plain and cat-mod), header and library of its own
+OUT_LAYER_LAB_LIBNAME = "libtaiyaki_amd_out_layer_lab.so"       # ... and its lab build (tk_lab_out_layer_plan)
 
 VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
 VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
@@ -189,6 +192,10 @@ ALIGN_SIGNATURES, ALIGN_DEFINES = _read_align_header()
 # the seventeenth: include/taiyaki_amd_conv_signal.h (libtaiyaki_amd_conv_signal.so)
 CONV_SIGNAL_SIGNATURES = {n: (r, a) for n, (r, a, _) in
                           parse_prototypes(_blank_comments(open(CONV_SIGNAL_HEADER).read())).items()}
+
+
+# the eighteenth: include/taiyaki_amd_out_layer.h (libtaiyaki_amd_out_layer.so), and the hook its lab build adds
+OUT_LAYER_SIGNATURES, OUT_LAYER_LAB_SIGNATURES = _read_wgrad_header(OUT_LAYER_HEADER)
 
 
 class SeqLabels(ctypes.Structure):
@@ -338,6 +345,16 @@ def conv_signal_lib():
     """The mGru models' first layer, 1 -> Cout channels on the raw signal (include/taiyaki_amd_conv_signal.h).  No
     fallback: a missing library raises."""
     return _load(os.path.join(CSRC, CONV_SIGNAL_LIBNAME), CONV_SIGNAL_SIGNATURES)
+
+
+def out_layer_lib():
+    """The models' output layer, plain and cat-mod (include/taiyaki_amd_out_layer.h): the lab build of that library
+    while the process runs on the lab build (`use_lab`), the release one otherwise.  No fallback: a missing library
+    raises."""
+    if is_lab():
+        return _load(os.path.join(CSRC, OUT_LAYER_LAB_LIBNAME),
+                     dict(OUT_LAYER_SIGNATURES, **OUT_LAYER_LAB_SIGNATURES))
+    return _load(os.path.join(CSRC, OUT_LAYER_LIBNAME), OUT_LAYER_SIGNATURES)
 
 
 def varlen_lib():

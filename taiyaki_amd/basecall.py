@@ -171,8 +171,11 @@ class Basecaller:
     `call_mods` is wanted; `call` gives what it gives without it.  `batch_short`: the reads shorter than a chunk go
     through the network and the decode operators as zero-padded columns of shared tensors (`layers.forward_varlen`, the
     operators of include/taiyaki_amd_decode_varlen.h), up to max_concurrent_chunks of them at a time, instead of one by
-    one; the model must be one `forward_varlen` has a rule for (TypeError otherwise).  A read's call may differ from the
-    one it gets alone where the network's GEMMs round differently at another column count."""
+    one; the model must be one `forward_varlen` has a rule for (TypeError otherwise).  The output layer's scores do
+    not depend on the batch (include/taiyaki_amd_out_layer.h), nor do those of the layers in front of it in the mGru
+    models (tests/test_out_layer.py); a read's call may still differ from the one it gets alone where the network keeps
+    a library GEMM that rounds differently at another column count: the strided convolution at sizes outside 192, 256
+    and 384."""
 
     def __init__(self, model, stride=None, chunk_size=1000, overlap=100, max_concurrent_chunks=128, alphabet="ACGT",
                  posterior=True, temperature=1.0, fastq=False, qscore_scale=1.0, qscore_offset=0.0, reverse=False,

@@ -19,6 +19,8 @@ that feeds them.
 * A batch wider than one launch of a recurrence admits runs as slabs of columns, one admitted launch after the other
   (include/taiyaki_amd_rnn_wide.h; USE_HIP_RNN_WIDE).
 """
+import ctypes
+
 import numpy as np
 import torch
 from torch import nn
@@ -1182,6 +1184,111 @@ class SquigglePredictor(Serial):
         return x
 
 
+# False: the output layers run nn.Linear and the element-wise operators behind it, exactly as before the kernels of
+# include/taiyaki_amd_out_layer.h, for comparisons against them
+USE_HIP_OUT_LAYER = True
+# Under no_grad the kernels take every supported shape: a row's scores then never depend on the rest of its batch.
+# Under grad mode they take a layer from this many rows (T N) on, None: never -- where forward + backward was measured
+# no slower than the library path (tools/outlayerbench.py, profiles/r44_out_layer.txt).  The cat-mod layer: 1.9 to 4.9 x
+# faster at every shape measured (1600 to 102400 rows, three runs).  The plain layer: ahead or level at 1600 and 12800
+# rows in most runs, but at 102400 rows 1.2 to 1.35 x slower at sizes 96 and 384 and between level and 1.3 x slower at
+# 256; no number of rows from which it is ahead was found, so it keeps the library path under grad mode.
+OUT_LAYER_GRAD_MIN_ROWS = 0
+OUT_LAYER_PLAIN_GRAD_MIN_ROWS = None
+# HIP launches of `OutLayer` by pass
+out_layer_calls = {"forward": 0, "backward": 0}
+
+
+def out_layer_tables(ntrans, can_nmods):
+    """The cat-mod epilogue as include/taiyaki_amd_out_layer.h takes it: for every output column the linear column it
+    reads (`src`) and -1 for 5 tanh or the base whose log_softmax group it belongs to (`group`).  The single canonical
+    column `ntrans` opens every base's group, followed by that base's modifications."""
+    src, group = list(range(ntrans)), [-1] * ntrans
+    curr = 0
+    for k, n in enumerate(can_nmods):
+        src += [ntrans] + [ntrans + curr + 1 + i for i in range(int(n))]
+        group += [k] * (1 + int(n))
+        curr += int(n)
+    return src, group
+
+
+def _int_array(values):
+    return (ctypes.c_int * len(values))(*values)
+
+
+def hip_out_layer_takes(layer, x):
+    """Whether `layer` (a GlobalNormFlipFlop or a GlobalNormFlipFlopCatMod) runs `x` on the kernels of
+    include/taiyaki_amd_out_layer.h: the switch, a float32 CUDA tensor (T, N, I), a supported shape, and under grad
+    mode at least OUT_LAYER_GRAD_MIN_ROWS (the plain layer: OUT_LAYER_PLAIN_GRAD_MIN_ROWS) rows."""
+    w = layer.linear.weight
+    if not (USE_HIP_OUT_LAYER and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32 and w.is_cuda
+            and w.dtype == torch.float32 and x.shape[2] == w.shape[1]):
+        return False
+    rows = x.shape[0] * x.shape[1]
+    if rows == 0:
+        return False
+    if _needs_grad(x, layer):
+        least = OUT_LAYER_GRAD_MIN_ROWS if isinstance(layer, GlobalNormFlipFlopCatMod) else OUT_LAYER_PLAIN_GRAD_MIN_ROWS
+        if least is None or rows < least:
+            return False
+    L = _lib.out_layer_lib()
+    nout = layer.nout if isinstance(layer, GlobalNormFlipFlopCatMod) else layer.size
+    return bool(L.tk_out_layer_supported(w.shape[1], w.shape[0], nout)
+                and L.tk_out_layer_workspace_bytes(rows, w.shape[1], w.shape[0], _cu_count(x.device)))
+
+
+class OutLayer(torch.autograd.Function):
+    """An output layer on the kernels of csrc/out_layer.hip.  Forward: one launch writes the weights' bf16 parts, one
+    GEMM writes y finished (bias, scale tanh and the log_softmax groups in its epilogue; no pre-activation tensor).
+    Backward: dz from dy and y alone, dx as a GEMM over it, dW and db as one launch over runs of rows and the
+    fixed-order sum of its partial results.  y, x and w are saved and nothing else; `tables` is None (the plain layer)
+    or the (src, group) int arrays of the cat-mod epilogue."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, scale, nout, tables):
+        T, N, I = x.shape
+        dev = x.device
+        L = _lib.out_layer_lib()
+        x = x.detach().contiguous()
+        weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+        src, group = tables if tables is not None else (None, None)
+        ctx.scale, ctx.tables = scale, tables
+        with torch.cuda.device(dev):
+            y = torch.empty(T, N, nout, dtype=torch.float32, device=dev)
+            wsb = L.tk_out_layer_workspace_bytes(T * N, I, weight.shape[0], _cu_count(dev))
+            ws = _lib.workspace(wsb, dev, "out_layer")
+            rc = L.tk_out_layer_forward_dev(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), src, group, T * N, I,
+                                            weight.shape[0], nout, scale, _cu_count(dev), _lib.ptr(y), _lib.ptr(ws),
+                                            wsb, _stream_ptr(dev))
+        _lib.check(rc, "tk_out_layer_forward_dev")
+        out_layer_calls["forward"] += 1
+        ctx.save_for_backward(y, x, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        y, x, weight = ctx.saved_tensors
+        T, N, I = x.shape
+        nlin, nout = weight.shape[0], y.shape[2]
+        dev = x.device
+        L = _lib.out_layer_lib()
+        dy = dy.contiguous()
+        src, group = ctx.tables if ctx.tables is not None else (None, None)
+        with torch.cuda.device(dev):
+            dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+            dw = torch.empty_like(weight)
+            db = torch.empty(nlin, dtype=torch.float32, device=dev)
+            wsb = L.tk_out_layer_workspace_bytes(T * N, I, nlin, _cu_count(dev))
+            ws = _lib.workspace(wsb, dev, "out_layer")
+            rc = L.tk_out_layer_backward_dev(_lib.ptr(dy), _lib.ptr(y), _lib.ptr(x), _lib.ptr(weight), src, group,
+                                             T * N, I, nlin, nout, ctx.scale, _cu_count(dev), _lib.ptr(dx),
+                                             _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), wsb, _stream_ptr(dev))
+        _lib.check(rc, "tk_out_layer_backward_dev")
+        out_layer_calls["backward"] += 1
+        return dx, dw, db, None, None, None
+
+
 class GlobalNormFlipFlop(nn.Module):
     """layers.py:1316-1411: scale * tanh(x W + b); NO normalisation inside the layer."""
 
@@ -1195,6 +1302,8 @@ class GlobalNormFlipFlop(nn.Module):
         _truncated_normal_(self.linear.bias, 0.5)
 
     def forward(self, x):
+        if hip_out_layer_takes(self, x):
+            return OutLayer.apply(x, self.linear.weight, self.linear.bias, float(self.scale), self.size, None)
         return self.scale * torch.tanh(self.linear(x))
 
 
@@ -1226,12 +1335,17 @@ class GlobalNormFlipFlopCatMod(nn.Module):
         self.linear = nn.Linear(insize, self.size)
         _orthonormal_(self.linear.weight)
         _truncated_normal_(self.linear.bias, 0.5)
+        # the same epilogue as the kernels take it (host arrays: they travel in the launch's arguments)
+        self.out_src, self.out_group = out_layer_tables(self.ntrans_states, self.can_nmods)
 
     @property
     def nout(self):
         return self.ntrans_states + self.ncan_base + self.nmod_base
 
     def forward(self, x):
+        if hip_out_layer_takes(self, x):
+            return OutLayer.apply(x, self.linear.weight, self.linear.bias, 5.0, self.nout,
+                                  (_int_array(self.out_src), _int_array(self.out_group)))
         y = self.linear(x)
         trans = 5.0 * torch.tanh(y[:, :, :self.ntrans_states])
         cat = y[:, :, self.ntrans_states:]
