@@ -51,6 +51,9 @@ CONV_SIGNAL_LIBNAME = "libtaiyaki_amd_conv_signal.so"       # csrc/conv_signal.h
 OUT_LAYER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_out_layer.h")
 OUT_LAYER_LIBNAME = "libtaiyaki_amd_out_layer.so"       # csrc/out_layer.hip: the models' output layer (plain and cat-mod), header and library of its own
 OUT_LAYER_LAB_LIBNAME = "libtaiyaki_amd_out_layer_lab.so"       # ... and its lab build (tk_lab_out_layer_plan)
+CONV_WINDOW_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_conv_window.h")
+CONV_WINDOW_LIBNAME = "libtaiyaki_amd_conv_window.so"       # csrc/conv_strided.hip built -DTK_CONV_WINDOW: the 16 -> Cout convolution at the fast and RNA shapes, header and library of its own
+CONV_WINDOW_LAB_LIBNAME = "libtaiyaki_amd_conv_window_lab.so"       # ... and its lab build (tk_lab_conv_window_*)
 
 VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
 VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
@@ -196,6 +199,8 @@ CONV_SIGNAL_SIGNATURES = {n: (r, a) for n, (r, a, _) in
 
 # the eighteenth: include/taiyaki_amd_out_layer.h (libtaiyaki_amd_out_layer.so), and the hook its lab build adds
 OUT_LAYER_SIGNATURES, OUT_LAYER_LAB_SIGNATURES = _read_wgrad_header(OUT_LAYER_HEADER)
+# the nineteenth: include/taiyaki_amd_conv_window.h (libtaiyaki_amd_conv_window.so), and the hooks its lab build adds
+CONV_WINDOW_SIGNATURES, CONV_WINDOW_LAB_SIGNATURES = _read_wgrad_header(CONV_WINDOW_HEADER)
 
 
 class SeqLabels(ctypes.Structure):
@@ -355,6 +360,16 @@ def out_layer_lib():
         return _load(os.path.join(CSRC, OUT_LAYER_LAB_LIBNAME),
                      dict(OUT_LAYER_SIGNATURES, **OUT_LAYER_LAB_SIGNATURES))
     return _load(os.path.join(CSRC, OUT_LAYER_LIBNAME), OUT_LAYER_SIGNATURES)
+
+
+def conv_window_lib():
+    """The 16 -> Cout convolution at the fast and the RNA models' shapes (include/taiyaki_amd_conv_window.h): the lab
+    build of that library while the process runs on the lab build (`use_lab`), the release one otherwise.  No fallback:
+    a missing library raises."""
+    if is_lab():
+        return _load(os.path.join(CSRC, CONV_WINDOW_LAB_LIBNAME),
+                     dict(CONV_WINDOW_SIGNATURES, **CONV_WINDOW_LAB_SIGNATURES))
+    return _load(os.path.join(CSRC, CONV_WINDOW_LIBNAME), CONV_WINDOW_SIGNATURES)
 
 
 def varlen_lib():

@@ -18,17 +18,51 @@
 // dW, db (cs_wgrad_kernel): dW'[o][k'] = sum over rows of dz[row][o] window[row][k'], split-K over runs of rows, chains
 // cut at WG_CHAIN, the first tile column adds up dz's columns (db); cs_reduce_kernel adds the partial results in their
 // order and writes dW[o][c][j].  2 x 3 tiles of 128 x 128 (the last 48 wide): cu_count / 6 runs.
+//
+// The window, the stride and what follows from them are a template argument of every kernel (CsGeo); the text above is
+// the geometry (19, 5), the one this library instantiates.  Compiled a second time with -DTK_CONV_WINDOW the same
+// source is libtaiyaki_amd_conv_window.so (include/taiyaki_amd_conv_window.h): the entry points take the window and
+// the stride as arguments, the geometries (31, 10) and (31, 12) are instantiated beside (19, 5), and Cout 96 and 128
+// are admitted.  There input time S u + r lies in the windows u + d, d = -1 ... 2 as well, at tap r - S d + h: a dx row
+// has 16 S = 160 or 192 outputs (two column tiles), a window 496 columns (dW: 4 tiles, the last 112 wide; 31 k blocks in
+// the forward), and Cout 96 is one tile with 96 of its 128 columns (dW: rows) used.
 #include "wgrad_common.h"
 
+#ifdef TK_CONV_WINDOW
+#include "../../include/taiyaki_amd_conv_window.h"
+#else
 #include "../../include/taiyaki_amd_conv_strided.h"
+#endif
 
 namespace tk {
 namespace {
 
-constexpr int CS_CIN = 16, CS_WIN = 19, CS_STRIDE = 5, CS_HALO = 9;
-constexpr int CS_K = CS_CIN * CS_WIN;          // 304
-constexpr int CS_DXN = CS_STRIDE * CS_CIN;     // 80 outputs per row of the gather GEMM
+constexpr int CS_CIN = 16;
 constexpr int CS_DXD = 4;                      // windows per input time: d = -1 ... 2
+
+// a geometry: window 19, stride 5 has K = 304 and 80 outputs per row of the gather GEMM
+template <int WIN_, int STRIDE_>
+struct CsGeo {
+    static constexpr int WIN = WIN_, STRIDE = STRIDE_, HALO = WIN_ / 2;
+    static constexpr int K = CS_CIN * WIN_;            // columns of a window
+    static constexpr int DXN = STRIDE_ * CS_CIN;       // outputs per row of the gather GEMM
+    static_assert(WIN_ % 2 == 1, "the window is centred on its time");
+    static_assert(DXN <= K, "an index into x is below rows x K (cs_plan's bound)");
+    // input time S u + r, r < S, lies in no window before u - 1 (tap r + 2 S + h is past the last) or after u + 2
+    // (tap r - 3 S + h is negative)
+    static_assert(2 * STRIDE_ + HALO >= WIN_ && STRIDE_ - 1 - 3 * STRIDE_ + HALO < 0, "d = -1 ... 2 are all the windows");
+};
+
+// f(geometry) for the geometry (win, stride), where this library has it
+template <class F>
+bool cs_geometry(size_t win, size_t stride, F f) {
+    if (win == 19 && stride == 5) return f(CsGeo<19, 5>()), true;
+#ifdef TK_CONV_WINDOW
+    if (win == 31 && stride == 10) return f(CsGeo<31, 10>()), true;
+    if (win == 31 && stride == 12) return f(CsGeo<31, 12>()), true;
+#endif
+    return false;
+}
 
 // the projection geometry (rnn_proj.hip)
 constexpr int PJ_RT = 128, PJ_NT = 128, PJ_KB = 16, PJ_THREADS = 256;
@@ -48,7 +82,7 @@ enum { CS_FWD = 0, CS_DX = 1 };
 
 struct CsPlan {
     size_t rows;
-    int tout;
+    int tout, win, stride;
     // forward and dx GEMMs
     int tiles_m, f_tiles_n, f_nkb, f_grid, d_tiles_n, d_nkb, d_grid;
     // weight gradient
@@ -57,27 +91,37 @@ struct CsPlan {
     size_t off_dx, off_slabs, bytes;
 };
 
-bool cs_cout_ok(size_t cout) { return cout == 192 || cout == 256 || cout == 384; }
+bool cs_cout_ok(size_t cout) {
+#ifdef TK_CONV_WINDOW
+    if (cout == 96 || cout == 128) return true;
+#endif
+    return cout == 192 || cout == 256 || cout == 384;
+}
 
-bool cs_plan(size_t T, size_t N, size_t cout, int cu_count, CsPlan *p) {
-    if (T == 0 || N == 0 || cu_count <= 0 || !cs_cout_ok(cout)) return false;
+bool cs_supported(size_t cin, size_t cout, size_t win, size_t stride) {
+    return cin == CS_CIN && cs_cout_ok(cout) && cs_geometry(win, stride, [](auto) {});
+}
+
+bool cs_plan(size_t T, size_t N, size_t cout, size_t win, size_t stride, int cu_count, CsPlan *p) {
+    if (T == 0 || N == 0 || cu_count <= 0 || !cs_supported(CS_CIN, cout, win, stride)) return false;
     if (T > (size_t(1) << 31) || N > (size_t(1) << 31)) return false;
-    const size_t tout = ceil_div(T, CS_STRIDE);
-    // the kernels index in int: the widest row is a window (304 floats) or a row of z, dz (Cout floats)
-    const size_t width = cout > (size_t)CS_K ? cout : (size_t)CS_K;
+    const size_t tout = ceil_div(T, stride), K = CS_CIN * win, dxn = CS_CIN * stride;
+    // the kernels index in int: the widest row is a window (304 floats at window 19) or a row of z, dz (Cout floats);
+    // a row of x's S input times is narrower than its window
+    const size_t width = cout > K ? cout : K;
     if (tout > ((size_t(1) << 31) - 1) / width / N) return false;
     const size_t rows = tout * N;
     if (rows * width >= (size_t(1) << 31)) return false;
-    p->rows = rows, p->tout = (int)tout;
+    p->rows = rows, p->tout = (int)tout, p->win = (int)win, p->stride = (int)stride;
     const size_t tm = ceil_div(rows, PJ_RT);
     p->tiles_m = (int)tm;
-    p->f_tiles_n = (int)ceil_div(cout, PJ_NT), p->f_nkb = CS_WIN;
-    p->d_tiles_n = (int)ceil_div(CS_DXN, PJ_NT), p->d_nkb = (int)(CS_DXD * cout / PJ_KB);
+    p->f_tiles_n = (int)ceil_div(cout, PJ_NT), p->f_nkb = (int)win;
+    p->d_tiles_n = (int)ceil_div(dxn, PJ_NT), p->d_nkb = (int)(CS_DXD * cout / PJ_KB);
     if (ceil_div(tm, 8) * 8 * p->f_tiles_n >= (size_t(1) << 31)) return false;
     p->f_grid = (int)(ceil_div(tm, 8) * 8 * p->f_tiles_n);
     p->d_grid = (int)(ceil_div(tm, 8) * 8 * p->d_tiles_n);
     // the weight gradient: wgrad_plan's rule
-    const size_t wm = ceil_div(cout, WG_TILE), wn = ceil_div(CS_K, WG_TILE);
+    const size_t wm = ceil_div(cout, WG_TILE), wn = ceil_div(K, WG_TILE);
     size_t G = g_lab_splits > 0 ? (size_t)g_lab_splits : (size_t)cu_count / (wm * wn);
     if (G < 1) G = 1;
     const size_t run = ceil_div(ceil_div(rows, G), WG_KB) * WG_KB;
@@ -88,7 +132,7 @@ bool cs_plan(size_t T, size_t N, size_t cout, int cu_count, CsPlan *p) {
     if (rstride * wn >= (size_t(1) << 31)) return false;
     p->w_tiles_m = (int)wm, p->w_tiles_n = (int)wn, p->splits = (int)G, p->nsub = (int)nsub;
     p->run_rows = (int)run, p->sub_rows = (int)sub, p->rstride = (int)rstride, p->w_grid = (int)(rstride * wn);
-    p->slab_floats = (cout * CS_K + cout + 3) / 4 * 4;
+    p->slab_floats = (cout * K + cout + 3) / 4 * 4;
     p->slabs = G * nsub;
     p->off_dx = (size_t)p->f_tiles_n * p->f_nkb * PJ_B_BLOCK;
     p->off_slabs = p->off_dx + (size_t)p->d_tiles_n * p->d_nkb * PJ_B_BLOCK;
@@ -96,15 +140,17 @@ bool cs_plan(size_t T, size_t N, size_t cout, int cu_count, CsPlan *p) {
     return true;
 }
 
-// B (nout x k) of one of the two GEMMs from w (Cout, 16, 19), as proj_prep_kernel lays it out
+// B (nout x k) of one of the two GEMMs from w (Cout, 16, WIN), as proj_prep_kernel lays it out
+template <class G>
 __device__ __forceinline__ float cs_b(const float *w, int mode, int cout, int n, int k) {
-    if (mode == CS_FWD) return n < cout ? w[(size_t)n * CS_K + (k & 15) * CS_WIN + (k >> 4)] : 0.f;
-    if (n >= CS_DXN) return 0.f;
+    if (mode == CS_FWD) return n < cout ? w[(size_t)n * G::K + (k & 15) * G::WIN + (k >> 4)] : 0.f;
+    if (n >= G::DXN) return 0.f;
     const int r = n >> 4, c = n & 15, d = k / cout - 1, o = k % cout;
-    const int j = r - CS_STRIDE * d + CS_HALO;
-    return j >= 0 && j < CS_WIN ? w[(size_t)o * CS_K + c * CS_WIN + j] : 0.f;
+    const int j = r - G::STRIDE * d + G::HALO;
+    return j >= 0 && j < G::WIN ? w[(size_t)o * G::K + c * G::WIN + j] : 0.f;
 }
 
+template <class G>
 __global__ __launch_bounds__(256) void cs_prep_kernel(const float *w, unsigned char *img, int mode, int cout, int nkb,
                                                       unsigned pieces) {
     const unsigned idx = blockIdx.x * 256u + threadIdx.x;
@@ -114,7 +160,7 @@ __global__ __launch_bounds__(256) void cs_prep_kernel(const float *w, unsigned c
     const int k0 = (blk % nkb) * PJ_KB + 8 * (lane >> 5);
     float v[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = cs_b(w, mode, cout, n, k0 + e);
+    for (int e = 0; e < 8; ++e) v[e] = cs_b<G>(w, mode, cout, n, k0 + e);
     uint4 p1, p2, p3;
     split2(v[0], v[1], p1.x, p2.x, p3.x);
     split2(v[2], v[3], p1.y, p2.y, p3.y);
@@ -136,7 +182,7 @@ struct CsGemmArgs {
 };
 
 // proj_kernel (rnn_proj.hip) with `a` read through the map of MODE; every load of `a` is one float4
-template <int MODE>
+template <class G, int MODE>
 __global__ __launch_bounds__(PJ_THREADS, 2) void cs_gemm_kernel(const CsGemmArgs p) {
     __shared__ __attribute__((aligned(16))) unsigned char imga[2][3 * PJ_A_PART];   // [buffer][part]
     __shared__ __attribute__((aligned(16))) unsigned char imgb[2][PJ_B_BLOCK];
@@ -157,7 +203,7 @@ __global__ __launch_bounds__(PJ_THREADS, 2) void cs_gemm_kernel(const CsGemmArgs
     const int aroff = wmb * PJ_A_MB + lhalf * PJ_A_HALF + l31 * 16;
     const int broff = (wnb * 64 + lane) * 16;
 
-    // the map of this thread's rows.  CS_FWD: the row's first input time 5 t - 9 and its column; CS_DX: the row itself
+    // the map of this thread's rows.  CS_FWD: the row's first input time S t - h and its column; CS_DX: the row itself
     int rowa[PJ_A_PASSES], rown[PJ_A_PASSES];
     bool mok[PJ_A_PASSES];
 #pragma unroll
@@ -166,7 +212,7 @@ __global__ __launch_bounds__(PJ_THREADS, 2) void cs_gemm_kernel(const CsGemmArgs
         mok[j] = m < M;
         if (MODE == CS_FWD) {
             const int t = m / N;
-            rowa[j] = CS_STRIDE * t - CS_HALO, rown[j] = m - t * N;
+            rowa[j] = G::STRIDE * t - G::HALO, rown[j] = m - t * N;
         } else {
             rowa[j] = m, rown[j] = 0;
         }
@@ -267,7 +313,7 @@ __global__ __launch_bounds__(PJ_THREADS, 2) void cs_gemm_kernel(const CsGemmArgs
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int n = nt * PJ_NT + (wnb + j) * 32 + l31;
-        const bool nok = n < (MODE == CS_FWD ? p.cout : CS_DXN);
+        const bool nok = n < (MODE == CS_FWD ? p.cout : G::DXN);
         const float b = (MODE == CS_FWD && nok) ? p.bias[n] : 0.f;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -283,7 +329,7 @@ __global__ __launch_bounds__(PJ_THREADS, 2) void cs_gemm_kernel(const CsGemmArgs
                     p.out2[at] = z / (1.f + __expf(-z));
                 } else {
                     const int u = m / N, col = m - u * N;
-                    const int time = CS_STRIDE * u + (n >> 4);
+                    const int time = G::STRIDE * u + (n >> 4);
                     if (time < p.T) p.out[((size_t)time * N + col) * CS_CIN + (n & 15)] = v;
                 }
             }
@@ -312,6 +358,7 @@ struct CsWgradArgs {
 
 // wgrad_kernel (wgrad_common.h) with its second operand, the windows in k' = 16 j + c order, read from x through the
 // window map: this thread's four columns are four channels of one tap.  Every load is one float4.
+template <class G>
 __global__ __launch_bounds__(WG_THREADS) void cs_wgrad_kernel(const CsWgradArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char img[2][2][3][WG_IMAGE];    // [buffer][dz, windows][part]
     __shared__ __attribute__((aligned(16))) float colsum[WG_THREADS / 32][WG_TILE];
@@ -336,7 +383,7 @@ __global__ __launch_bounds__(WG_THREADS) void cs_wgrad_kernel(const CsWgradArgs 
     const int bcol0 = tnx * WG_TILE;
     const bool sum_cols = tnx == 0;
     const int acol = tmx * WG_TILE + c4, bcol = bcol0 + c4;
-    const bool acok = acol < a.M, bcok = bcol < CS_K;
+    const bool acok = acol < a.M, bcok = bcol < G::K;
     const int acl = acok ? acol : 0;
     const int tap = bcol >> 4, chan = bcol & 15;    // this thread's float4 of a window
 
@@ -367,7 +414,7 @@ __global__ __launch_bounds__(WG_THREADS) void cs_wgrad_kernel(const CsWgradArgs 
                 const int k = k0 + kb * WG_KB + r0 + WG_SROWS * j;
                 const bool kok = k < k1;
                 const int t = k / a.N, n = k - t * a.N;
-                const int time = CS_STRIDE * t - CS_HALO + tap;
+                const int time = G::STRIDE * t - G::HALO + tap;
                 oka[set][j] = kok && acok;
                 okb[set][j] = kok && bcok && time >= 0 && time < a.T;
                 ra[set][j] = load4<true>(a.dz, a.M, k, oka[set][j], acl);
@@ -420,7 +467,7 @@ __global__ __launch_bounds__(WG_THREADS) void cs_wgrad_kernel(const CsWgradArgs 
             }
         }
 
-        // this partial result: [M][304] in k' order | [M]
+        // this partial result: [M][K] in k' order | [M]
         float *slab = a.ws + (size_t)(run * a.nsub + sub) * a.slab_floats;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -431,7 +478,7 @@ __global__ __launch_bounds__(WG_THREADS) void cs_wgrad_kernel(const CsWgradArgs 
                 for (int r = 0; r < 16; ++r) {
                     const int m = tmx * WG_TILE + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
                     const float v = WG_ACC_SETS == 2 ? acc[0][i][j][r] + acc[WG_ACC_SETS - 1][i][j][r] : acc[0][i][j][r];
-                    if (m < a.M && n < CS_K) slab[(size_t)m * CS_K + n] = v;
+                    if (m < a.M && n < G::K) slab[(size_t)m * G::K + n] = v;
                 }
             }
         if (sum_cols) {
@@ -442,17 +489,18 @@ __global__ __launch_bounds__(WG_THREADS) void cs_wgrad_kernel(const CsWgradArgs 
 #pragma unroll
                 for (int r = 1; r < WG_THREADS / 32; ++r) v += colsum[r][tid];
                 const int m = tmx * WG_TILE + tid;
-                if (m < a.M) slab[(size_t)a.M * CS_K + m] = v;
+                if (m < a.M) slab[(size_t)a.M * G::K + m] = v;
             }
         }
     }
 }
 
-// dw (Cout, 16, 19) | db = the partial results added in their order
+// dw (Cout, 16, WIN) | db = the partial results added in their order
+template <class G>
 __global__ __launch_bounds__(256) void cs_reduce_kernel(const float *ws, size_t slab_floats, int slabs, int M, float *dw,
                                                         float *db) {
     const unsigned idx = blockIdx.x * 256u + threadIdx.x;
-    const unsigned MW = (unsigned)M * CS_K;
+    const unsigned MW = (unsigned)M * G::K;
     if (idx >= MW + M) return;
     float v = ws[idx];
 #pragma unroll 4
@@ -461,49 +509,30 @@ __global__ __launch_bounds__(256) void cs_reduce_kernel(const float *ws, size_t 
         db[idx - MW] = v;
         return;
     }
-    const unsigned m = idx / CS_K, k = idx % CS_K;
-    dw[(size_t)m * CS_K + (k & 15) * CS_WIN + (k >> 4)] = v;
+    const unsigned m = idx / G::K, k = idx % G::K;
+    dw[(size_t)m * G::K + (k & 15) * G::WIN + (k >> 4)] = v;
 }
 
+template <class G>
 int cs_launch_gemm(int mode, const CsPlan &p, const float *w, CsGemmArgs g, unsigned char *img, hipStream_t stream) {
     const int tiles_n = mode == CS_FWD ? p.f_tiles_n : p.d_tiles_n, nkb = mode == CS_FWD ? p.f_nkb : p.d_nkb;
     const unsigned pieces = (unsigned)(tiles_n * nkb) * (PJ_B_PART / 16);
-    hipLaunchKernelGGL(cs_prep_kernel, dim3((pieces + 255) / 256), dim3(256), 0, stream, w, img, mode, g.cout, nkb,
+    hipLaunchKernelGGL(cs_prep_kernel<G>, dim3((pieces + 255) / 256), dim3(256), 0, stream, w, img, mode, g.cout, nkb,
                        pieces);
     if (hipGetLastError() != hipSuccess) return TK_ERR_LAUNCH;
     g.bimg = img, g.tiles_m = p.tiles_m, g.tiles_n = tiles_n, g.nkb = nkb;
     if (mode == CS_FWD)
-        hipLaunchKernelGGL(cs_gemm_kernel<CS_FWD>, dim3(p.f_grid), dim3(PJ_THREADS), 0, stream, g);
+        hipLaunchKernelGGL((cs_gemm_kernel<G, CS_FWD>), dim3(p.f_grid), dim3(PJ_THREADS), 0, stream, g);
     else
-        hipLaunchKernelGGL(cs_gemm_kernel<CS_DX>, dim3(p.d_grid), dim3(PJ_THREADS), 0, stream, g);
+        hipLaunchKernelGGL((cs_gemm_kernel<G, CS_DX>), dim3(p.d_grid), dim3(PJ_THREADS), 0, stream, g);
     return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
 
-}  // namespace
-
-int conv_strided_forward(const float *x, const float *w, const float *b, size_t T, size_t N, size_t cout, int cu_count,
-                         float *z, float *y, void *ws, size_t wsb, hipStream_t stream) {
-    if (!x || !w || !b || !y || !ws) return TK_ERR_BAD_ARG;
-    if (!aligned16(x) || !aligned16(y) || !aligned16(z) || !aligned16(ws)) return TK_ERR_BAD_ARG;
-    CsPlan p;
-    if (!cs_plan(T, N, cout, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    if (wsb < p.bytes) return TK_ERR_WORKSPACE;
-    CsGemmArgs g = {};
-    g.a = x, g.bias = b, g.out = z, g.out2 = y;
-    g.M = (int)p.rows, g.N = (int)N, g.T = (int)T, g.cout = (int)cout;
-    return cs_launch_gemm(CS_FWD, p, w, g, static_cast<unsigned char *>(ws), stream);
-}
-
-int conv_strided_backward(const float *dy, const float *x, const float *z, const float *w, size_t T, size_t N,
-                          size_t cout, int cu_count, float *dz, float *dx, float *dw, float *db, void *ws, size_t wsb,
-                          hipStream_t stream) {
-    if (!dy || !x || !z || !w || !dz || !dw || !db || !ws) return TK_ERR_BAD_ARG;
-    if (!aligned16(dy) || !aligned16(x) || !aligned16(z) || !aligned16(dz) || !aligned16(dx) || !aligned16(ws))
-        return TK_ERR_BAD_ARG;
-    CsPlan p;
-    if (!cs_plan(T, N, cout, cu_count, &p)) return TK_ERR_UNSUPPORTED;
-    if (wsb < p.bytes) return TK_ERR_WORKSPACE;
-    unsigned char *base = static_cast<unsigned char *>(ws);
+// the backward's launches at one geometry
+template <class G>
+int cs_launch_backward(const CsPlan &p, const float *dy, const float *x, const float *z, const float *w, size_t T,
+                       size_t N, size_t cout, float *dz, float *dx, float *dw, float *db, unsigned char *base,
+                       hipStream_t stream) {
     const unsigned quads = (unsigned)(p.rows * cout / 4);
     hipLaunchKernelGGL(cs_dz_kernel, dim3((quads + 255) / 256), dim3(256), 0, stream,
                        reinterpret_cast<const float4 *>(dy), reinterpret_cast<const float4 *>(z),
@@ -513,7 +542,7 @@ int conv_strided_backward(const float *dy, const float *x, const float *z, const
         CsGemmArgs g = {};
         g.a = dz, g.out = dx;
         g.M = (int)p.rows, g.N = (int)N, g.T = (int)T, g.cout = (int)cout;
-        const int rc = cs_launch_gemm(CS_DX, p, w, g, base + p.off_dx, stream);
+        const int rc = cs_launch_gemm<G>(CS_DX, p, w, g, base + p.off_dx, stream);
         if (rc != TK_OK) return rc;
     }
     CsWgradArgs a;
@@ -521,47 +550,55 @@ int conv_strided_backward(const float *dy, const float *x, const float *z, const
     a.K = (int)p.rows, a.N = (int)N, a.T = (int)T, a.M = (int)cout;
     a.tiles_m = p.w_tiles_m, a.splits = p.splits, a.nsub = p.nsub, a.run_rows = p.run_rows, a.sub_rows = p.sub_rows;
     a.rstride = p.rstride, a.slab_floats = p.slab_floats;
-    hipLaunchKernelGGL(cs_wgrad_kernel, dim3(p.w_grid), dim3(WG_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(cs_wgrad_kernel<G>, dim3(p.w_grid), dim3(WG_THREADS), 0, stream, a);
     if (hipGetLastError() != hipSuccess) return TK_ERR_LAUNCH;
-    const unsigned total = (unsigned)(cout * CS_K + cout);
-    hipLaunchKernelGGL(cs_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, stream,
+    const unsigned total = (unsigned)(cout * G::K + cout);
+    hipLaunchKernelGGL(cs_reduce_kernel<G>, dim3((total + 255) / 256), dim3(256), 0, stream,
                        static_cast<const float *>(a.ws), p.slab_floats, (int)p.slabs, (int)cout, dw, db);
     return hipGetLastError() == hipSuccess ? TK_OK : TK_ERR_LAUNCH;
 }
 
-}  // namespace tk
+}  // namespace
 
-extern "C" {
-
-int tk_conv_strided_supported(size_t cin, size_t cout, size_t winlen, size_t stride) {
-    return cin == tk::CS_CIN && winlen == tk::CS_WIN && stride == tk::CS_STRIDE && tk::cs_cout_ok(cout);
+int conv_strided_forward(const float *x, const float *w, const float *b, size_t T, size_t N, size_t cout, size_t win,
+                         size_t stride, int cu_count, float *z, float *y, void *ws, size_t wsb, hipStream_t stream) {
+    if (!x || !w || !b || !y || !ws) return TK_ERR_BAD_ARG;
+    if (!aligned16(x) || !aligned16(y) || !aligned16(z) || !aligned16(ws)) return TK_ERR_BAD_ARG;
+    CsPlan p;
+    if (!cs_plan(T, N, cout, win, stride, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+    if (wsb < p.bytes) return TK_ERR_WORKSPACE;
+    CsGemmArgs g = {};
+    g.a = x, g.bias = b, g.out = z, g.out2 = y;
+    g.M = (int)p.rows, g.N = (int)N, g.T = (int)T, g.cout = (int)cout;
+    int rc = TK_ERR_UNSUPPORTED;
+    cs_geometry(win, stride, [&](auto geo) {
+        rc = cs_launch_gemm<decltype(geo)>(CS_FWD, p, w, g, static_cast<unsigned char *>(ws), stream);
+    });
+    return rc;
 }
 
-size_t tk_conv_strided_workspace_bytes(size_t T, size_t N, size_t cout, int cu_count) {
-    tk::CsPlan p;
-    return tk::cs_plan(T, N, cout, cu_count, &p) ? p.bytes : 0;
-}
-
-int tk_conv_strided_forward_dev(const float *x, const float *w, const float *b, size_t T, size_t N, size_t cout,
-                                int cu_count, float *z, float *y, void *workspace, size_t workspace_bytes,
-                                void *stream) {
-    return tk::conv_strided_forward(x, w, b, T, N, cout, cu_count, z, y, workspace, workspace_bytes,
-                                    static_cast<hipStream_t>(stream));
-}
-
-int tk_conv_strided_backward_dev(const float *dy, const float *x, const float *z, const float *w, size_t T, size_t N,
-                                 size_t cout, int cu_count, float *dz, float *dx, float *dw, float *db,
-                                 void *workspace, size_t workspace_bytes, void *stream) {
-    return tk::conv_strided_backward(dy, x, z, w, T, N, cout, cu_count, dz, dx, dw, db, workspace, workspace_bytes,
-                                     static_cast<hipStream_t>(stream));
+int conv_strided_backward(const float *dy, const float *x, const float *z, const float *w, size_t T, size_t N,
+                          size_t cout, size_t win, size_t stride, int cu_count, float *dz, float *dx, float *dw,
+                          float *db, void *ws, size_t wsb, hipStream_t stream) {
+    if (!dy || !x || !z || !w || !dz || !dw || !db || !ws) return TK_ERR_BAD_ARG;
+    if (!aligned16(dy) || !aligned16(x) || !aligned16(z) || !aligned16(dz) || !aligned16(dx) || !aligned16(ws))
+        return TK_ERR_BAD_ARG;
+    CsPlan p;
+    if (!cs_plan(T, N, cout, win, stride, cu_count, &p)) return TK_ERR_UNSUPPORTED;
+    if (wsb < p.bytes) return TK_ERR_WORKSPACE;
+    int rc = TK_ERR_UNSUPPORTED;
+    cs_geometry(win, stride, [&](auto geo) {
+        rc = cs_launch_backward<decltype(geo)>(p, dy, x, z, w, T, N, cout, dz, dx, dw, db,
+                                               static_cast<unsigned char *>(ws), stream);
+    });
+    return rc;
 }
 
 #ifdef TK_LAB
-void tk_lab_conv_strided_set_splits(int splits) { tk::g_lab_splits = splits; }
-
-int tk_lab_conv_strided_plan(size_t T, size_t N, size_t cout, int cu_count, size_t *out) {
-    tk::CsPlan p;
-    if (!tk::cs_plan(T, N, cout, cu_count, &p)) return 0;
+// the lab hook's view of the plan
+int cs_lab_plan(size_t T, size_t N, size_t cout, size_t win, size_t stride, int cu_count, size_t *out) {
+    CsPlan p;
+    if (!cs_plan(T, N, cout, win, stride, cu_count, &p)) return 0;
     const size_t v[12] = {(size_t)p.tiles_m, (size_t)p.f_tiles_n, (size_t)p.f_nkb, (size_t)p.f_grid,
                           (size_t)p.d_tiles_n, (size_t)p.d_nkb, (size_t)p.splits, (size_t)p.nsub,
                           (size_t)p.run_rows, (size_t)p.sub_rows, (size_t)p.w_grid, p.bytes};
@@ -569,5 +606,77 @@ int tk_lab_conv_strided_plan(size_t T, size_t N, size_t cout, int cu_count, size
     return 1;
 }
 #endif
+
+}  // namespace tk
+
+extern "C" {
+
+#ifndef TK_CONV_WINDOW
+
+int tk_conv_strided_supported(size_t cin, size_t cout, size_t winlen, size_t stride) {
+    return tk::cs_supported(cin, cout, winlen, stride);
+}
+
+size_t tk_conv_strided_workspace_bytes(size_t T, size_t N, size_t cout, int cu_count) {
+    tk::CsPlan p;
+    return tk::cs_plan(T, N, cout, 19, 5, cu_count, &p) ? p.bytes : 0;
+}
+
+int tk_conv_strided_forward_dev(const float *x, const float *w, const float *b, size_t T, size_t N, size_t cout,
+                                int cu_count, float *z, float *y, void *workspace, size_t workspace_bytes,
+                                void *stream) {
+    return tk::conv_strided_forward(x, w, b, T, N, cout, 19, 5, cu_count, z, y, workspace, workspace_bytes,
+                                    static_cast<hipStream_t>(stream));
+}
+
+int tk_conv_strided_backward_dev(const float *dy, const float *x, const float *z, const float *w, size_t T, size_t N,
+                                 size_t cout, int cu_count, float *dz, float *dx, float *dw, float *db,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+    return tk::conv_strided_backward(dy, x, z, w, T, N, cout, 19, 5, cu_count, dz, dx, dw, db, workspace,
+                                     workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+#ifdef TK_LAB
+void tk_lab_conv_strided_set_splits(int splits) { tk::g_lab_splits = splits; }
+
+int tk_lab_conv_strided_plan(size_t T, size_t N, size_t cout, int cu_count, size_t *out) {
+    return tk::cs_lab_plan(T, N, cout, 19, 5, cu_count, out);
+}
+#endif
+
+#else   // TK_CONV_WINDOW: include/taiyaki_amd_conv_window.h
+
+int tk_conv_window_supported(size_t cin, size_t cout, size_t winlen, size_t stride) {
+    return tk::cs_supported(cin, cout, winlen, stride);
+}
+
+size_t tk_conv_window_workspace_bytes(size_t T, size_t N, size_t cout, size_t winlen, size_t stride, int cu_count) {
+    tk::CsPlan p;
+    return tk::cs_plan(T, N, cout, winlen, stride, cu_count, &p) ? p.bytes : 0;
+}
+
+int tk_conv_window_forward_dev(const float *x, const float *w, const float *b, size_t T, size_t N, size_t cout,
+                               size_t winlen, size_t stride, int cu_count, float *z, float *y, void *workspace,
+                               size_t workspace_bytes, void *stream) {
+    return tk::conv_strided_forward(x, w, b, T, N, cout, winlen, stride, cu_count, z, y, workspace, workspace_bytes,
+                                    static_cast<hipStream_t>(stream));
+}
+
+int tk_conv_window_backward_dev(const float *dy, const float *x, const float *z, const float *w, size_t T, size_t N,
+                                size_t cout, size_t winlen, size_t stride, int cu_count, float *dz, float *dx, float *dw,
+                                float *db, void *workspace, size_t workspace_bytes, void *stream) {
+    return tk::conv_strided_backward(dy, x, z, w, T, N, cout, winlen, stride, cu_count, dz, dx, dw, db, workspace,
+                                     workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+#ifdef TK_LAB
+void tk_lab_conv_window_set_splits(int splits) { tk::g_lab_splits = splits; }
+
+int tk_lab_conv_window_plan(size_t T, size_t N, size_t cout, size_t winlen, size_t stride, int cu_count, size_t *out) {
+    return tk::cs_lab_plan(T, N, cout, winlen, stride, cu_count, out);
+}
+#endif
+
+#endif  // TK_CONV_WINDOW
 
 }  // extern "C"

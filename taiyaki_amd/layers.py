@@ -280,6 +280,84 @@ class StridedConvolution(torch.autograd.Function):
         return dx, dw, db, None
 
 
+# False: the 16 -> Cout layer at the shapes `StridedConvolution` does not take (the fast and the RNA models') runs unfold
+# + GEMM (exactly as with USE_HIP_CONV or USE_HIP_CONV_STRIDED = False), for comparisons against the kernels of
+# include/taiyaki_amd_conv_window.h
+USE_HIP_CONV_WINDOW = True
+# HIP launches of `WindowConvolution` by pass
+conv_window_calls = {"forward": 0, "backward": 0}
+# The (size, winlen, stride) that take those kernels in grad mode: the configurations whose forward + backward was
+# measured not behind the unfold + GEMM path at the trainer's shapes (tools/convbench.py --window;
+# profiles/r45_conv_window.txt).  Under no_grad every shape tk_conv_window_supported names takes them: there a read's
+# scores being a function of the read and the weights alone is the point, as for the output layer.
+CONV_WINDOW_GRAD_SHAPES = frozenset(
+    [(size, 19, 5) for size in (96, 128)]
+    + [(size, 31, stride) for size in (96, 128, 192, 256, 384) for stride in (10, 12)])
+# The workspace handed to those calls, as _CONV_STRIDED_WORKSPACE_BYTES: one size for every shape whose weight gradient
+# has one partial result per run (at most 8192 rows per run); a larger need regrows the cached buffer
+_CONV_WINDOW_WORKSPACE_BYTES = 24 << 20
+
+
+class WindowConvolution(torch.autograd.Function):
+    """swish(conv1d(x) + b) of the mLstm models' third layer at the fast and the RNA models' shapes (16 -> Cout channels,
+    window 19 or 31, stride 5, 10 or 12; the shapes tk_conv_window_supported names) on the kernels of
+    csrc/conv_strided.hip as libtaiyaki_amd_conv_window.so builds them.  The contract of `StridedConvolution`: one GEMM
+    whose rows are read straight from x writes z and y (`save` False, the caller under no_grad: y alone); the backward
+    writes dz in one element-wise launch, dx (when wanted) as a gather GEMM over dz, dW and db as one split-K launch and
+    the fixed-order sum of its partial results.  x and z are saved; no window matrix exists, forward or backward."""
+
+    @staticmethod
+    def _workspace(L, T, N, cout, winlen, stride, dev):
+        wsb = max(L.tk_conv_window_workspace_bytes(T, N, cout, winlen, stride, _cu_count(dev)),
+                  _CONV_WINDOW_WORKSPACE_BYTES)
+        return _lib.workspace(wsb, dev, "conv_window"), wsb
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, save, stride):
+        T, N, _ = x.shape
+        cout, _, winlen = weight.shape
+        dev = x.device
+        ctx.stride = stride
+        L = _lib.conv_window_lib()
+        x = _aligned(x.detach())
+        weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+        with torch.cuda.device(dev):
+            y = torch.empty(-(-T // stride), N, cout, dtype=torch.float32, device=dev)
+            z = torch.empty_like(y) if save else None
+            ws, wsb = WindowConvolution._workspace(L, T, N, cout, winlen, stride, dev)
+            rc = L.tk_conv_window_forward_dev(_lib.ptr(x), _lib.ptr(weight), _lib.ptr(bias), T, N, cout, winlen, stride,
+                                              _cu_count(dev), _lib.ptr(z), _lib.ptr(y), _lib.ptr(ws), wsb,
+                                              _lib.stream_ptr())
+        _lib.check(rc, "tk_conv_window_forward_dev")
+        conv_window_calls["forward"] += 1
+        if save:
+            ctx.save_for_backward(x, z, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, z, weight = ctx.saved_tensors
+        T, N, _ = x.shape
+        cout, _, winlen = weight.shape
+        stride = ctx.stride
+        dev = x.device
+        L = _lib.conv_window_lib()
+        dy = _aligned(dy)
+        with torch.cuda.device(dev):
+            dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+            dw = torch.empty_like(weight)
+            db = torch.empty(cout, dtype=torch.float32, device=dev)
+            dz = torch.empty_like(z)
+            ws, wsb = WindowConvolution._workspace(L, T, N, cout, winlen, stride, dev)
+            rc = L.tk_conv_window_backward_dev(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(z), _lib.ptr(weight), T, N, cout,
+                                               winlen, stride, _cu_count(dev), _lib.ptr(dz), _lib.ptr(dx), _lib.ptr(dw),
+                                               _lib.ptr(db), _lib.ptr(ws), wsb, _lib.stream_ptr())
+        _lib.check(rc, "tk_conv_window_backward_dev")
+        conv_window_calls["backward"] += 1
+        return dx, dw, db, None, None
+
+
 # False: the mGru models' first layer (1 -> Cout channels, window 19, tanh) runs unfold + GEMM (exactly as with
 # USE_HIP_CONV = False), for comparisons against the kernels of include/taiyaki_amd_conv_signal.h
 USE_HIP_CONV_SIGNAL = True
@@ -371,6 +449,10 @@ class Convolution(nn.Module):
     The wide layer behind them (16 -> 192, 256 or 384 channels, window 19, stride 5, swish) runs as `StridedConvolution` where
     `tk_conv_strided_supported` names the shape (USE_HIP_CONV or USE_HIP_CONV_STRIDED = False: never): its GEMMs
     read x through the window's address map, so the 124 MB window matrix of the unfold path is never written.
+    The same layer at the fast and the RNA models' shapes (window 19 or 31, stride 5, 10 or 12, 96 channels or more)
+    runs as `WindowConvolution` where `tk_conv_window_supported` names the shape (any of USE_HIP_CONV,
+    USE_HIP_CONV_STRIDED, USE_HIP_CONV_WINDOW = False: never): under no_grad always, in grad mode for the
+    configurations of CONV_WINDOW_GRAD_SHAPES.  Sizes below 96 and other windows or strides run unfold + GEMM.
 
     The mGru models' first layer (1 -> 32 ... 384 channels on the raw signal, window 19, stride 1 ... 8, tanh) runs as
     `SignalConvolution` where `tk_conv_signal_supported` names the shape and the input needs no gradient (USE_HIP_CONV
@@ -404,6 +486,18 @@ class Convolution(nn.Module):
         return bool(L.tk_conv_strided_supported(w.shape[1], w.shape[0], self.winlen, self.stride)
                     and L.tk_conv_strided_workspace_bytes(x.shape[0], x.shape[1], w.shape[0], _cu_count(x.device)))
 
+    def _hip_window(self, x):
+        w = self.conv.weight
+        if not (USE_HIP_CONV and USE_HIP_CONV_STRIDED and USE_HIP_CONV_WINDOW and self.activation is swish and x.is_cuda
+                and x.dim() == 3 and x.dtype == torch.float32 and w.is_cuda and w.dtype == torch.float32):
+            return False
+        if torch.is_grad_enabled() and (w.shape[0], self.winlen, self.stride) not in CONV_WINDOW_GRAD_SHAPES:
+            return False
+        L = _lib.conv_window_lib()
+        return bool(L.tk_conv_window_supported(w.shape[1], w.shape[0], self.winlen, self.stride)
+                    and L.tk_conv_window_workspace_bytes(x.shape[0], x.shape[1], w.shape[0], self.winlen, self.stride,
+                                                         _cu_count(x.device)))
+
     def _hip_signal(self, x):
         w = self.conv.weight
         if not (USE_HIP_CONV and USE_HIP_CONV_SIGNAL and self.activation is torch.tanh and x.is_cuda and x.dim() == 3
@@ -426,6 +520,10 @@ class Convolution(nn.Module):
             w, b = self.conv.weight, self.conv.bias
             save = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or b.requires_grad)
             return StridedConvolution.apply(x, w, b, save)
+        if self._hip_window(x):
+            w, b = self.conv.weight, self.conv.bias
+            save = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or b.requires_grad)
+            return WindowConvolution.apply(x, w, b, save, self.stride)
         if self._hip_signal(x):
             w, b = self.conv.weight, self.conv.bias
             save = torch.is_grad_enabled() and (w.requires_grad or b.requires_grad)

@@ -7,9 +7,13 @@ writes y, backward reads dy and x and writes dx where the layer has an input gra
 (16 -> 256, window 19, stride 5; csrc/conv_strided.hip) against its unfold + GEMM path, in alternating turns (`conv3`).
 --signal: only the mGru models' first layer (1 -> Cout on the raw signal, window 19, tanh; csrc/conv_signal.hip) against
 its unfold + GEMM path, in alternating turns, at every TxN:stride:cout[:fwd] of --signal-shapes (`signal`).
+--window: only conv 3 at the fast and the RNA models' shapes (16 -> Cout, window 19 or 31, stride 5, 10 or 12;
+csrc/conv_strided.hip built -DTK_CONV_WINDOW) against its unfold + GEMM path, in alternating turns, at every
+TxN:cout:winlen:stride of --window-shapes (`window`).
 
     python tools/convbench.py [--steps 30] [--warmup 5] [--shapes 4000x128 8000x64] [--turns 5] [--calls 20]
     python tools/convbench.py --signal [--signal-shapes 2000x64:2:96 60000x8:4:96:fwd] [--turns 5] [--calls 20]
+    python tools/convbench.py --window [--window-shapes 4000x128:96:19:5 20000x128:256:31:10] [--turns 5] [--calls 20]
 """
 import argparse
 import json
@@ -50,12 +54,24 @@ def main():
     ap.add_argument("--signal-shapes", nargs="*", default=["2000x64:2:96", "4000x128:5:256", "4000x128:5:384",
                                                             "60000x8:4:96:fwd"],
                     help="signal: TxN:stride:cout, `:fwd` for the forward alone (whole reads)")
+    ap.add_argument("--window", action="store_true",
+                    help="time conv 3 at the fast and the RNA models' shapes (libtaiyaki_amd_conv_window.so) only")
+    ap.add_argument("--window-shapes", nargs="*",
+                    default=["4000x128:96:19:5", "2000x256:96:19:5", "20000x128:256:31:10", "10000x256:256:31:10",
+                             "20000x128:96:31:12", "10000x256:96:31:12"],
+                    help="window: TxN:cout:winlen:stride (the trainer's shapes: DNA fast, RNA, RNA fast)")
     ap.add_argument("--host-warmup", type=int, default=1000, help="signal: eager calls per path before the first turn")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("convbench needs a GPU")
     dev = torch.device("cuda:0")
     torch.backends.cuda.preferred_blas_library("cublas")        # rocBLAS, as bench.py runs the GEMM path
+    if a.window:
+        for spec in a.window_shapes:
+            shape, cout, winlen, stride = spec.split(":")
+            T, N = (int(v) for v in shape.split("x"))
+            window(T, N, int(cout), int(winlen), int(stride), a, dev)
+        return
     if a.signal:
         for spec in a.signal_shapes:
             shape, stride, cout, *rest = spec.split(":")
@@ -130,6 +146,49 @@ def conv3(T, N, cout, a, dev):
     print(json.dumps({"layer": "conv3", "T": T, "N": N, "cout": cout, "hip_below_gemm_every_turn": {
         "fwd": max(f for f, _ in res[True]) < min(f for f, _ in res[False]),
         "bwd": max(b for _, b in res[True]) < min(b for _, b in res[False])}}))
+
+
+def window(T, N, cout, winlen, stride, a, dev):
+    """The third layer at the fast and the RNA models' shapes (16 -> cout, window 19 or 31, stride 5, 10 or 12;
+    libtaiyaki_amd_conv_window.so): the kernels and the unfold + GEMM path (layers.USE_HIP_CONV_WINDOW = False) in
+    alternating turns, as `conv3` runs them, the forward in grad mode with the configuration in
+    layers.CONV_WINDOW_GRAD_SHAPES whatever that table holds.  The last line says in how many turns the kernels' forward
+    + backward was not behind the GEMM path's: the majority puts a configuration into the table."""
+    torch.manual_seed(1)
+    conv = layers.Convolution(16, cout, winlen, stride=stride, fun=layers.swish).to(dev)
+    x = torch.randn(T, N, 16, device=dev).requires_grad_(True)
+    dy = torch.randn(-(-T // stride), N, cout, device=dev)
+    tag = {"layer": "window", "T": T, "N": N, "cout": cout, "winlen": winlen, "stride": stride}
+    table = layers.CONV_WINDOW_GRAD_SHAPES
+    layers.CONV_WINDOW_GRAD_SHAPES = table | {(cout, winlen, stride)}
+    try:
+        if conv._hip_strided(x) or not conv._hip_window(x):
+            print(json.dumps(dict(tag, kernels="not this library's shape")))
+            return
+        res = {True: [], False: []}
+        for turn in range(a.turns):
+            for hip in (True, False):
+                layers.USE_HIP_CONV_WINDOW = hip
+                calls = dict(layers.conv_window_calls)
+                y = conv(x)
+                f_med, f_min = timed(lambda: conv(x), a.calls, a.warmup)
+                b_med, b_min = timed(lambda: y.backward(dy, retain_graph=True), a.calls, a.warmup)
+                assert (layers.conv_window_calls != calls) == hip
+                res[hip].append((f_med, b_med))
+                print(json.dumps(dict(tag, turn=turn, path="hip" if hip else "gemm", fwd_us=round(1e3 * f_med, 1),
+                                      fwd_min_us=round(1e3 * f_min, 1), bwd_us=round(1e3 * b_med, 1),
+                                      bwd_min_us=round(1e3 * b_min, 1), fwd_bwd_us=round(1e3 * (f_med + b_med), 1))))
+                del y
+                conv.zero_grad(set_to_none=True)
+                x.grad = None
+        not_behind = sum(fh + bh <= fg + bg for (fh, bh), (fg, bg) in zip(res[True], res[False]))
+        print(json.dumps(dict(tag, turns=a.turns, hip_fwd_bwd_not_behind_gemm_turns=not_behind,
+                              hip_fwd_bwd_us=round(1e3 * float(np.median([f + b for f, b in res[True]])), 1),
+                              gemm_fwd_bwd_us=round(1e3 * float(np.median([f + b for f, b in res[False]])), 1),
+                              grad_mode=bool(2 * not_behind > a.turns))))
+    finally:
+        layers.USE_HIP_CONV_WINDOW = True
+        layers.CONV_WINDOW_GRAD_SHAPES = table
 
 
 def signal(T, N, stride, cout, fwd_only, a, dev):
