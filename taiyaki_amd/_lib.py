@@ -54,6 +54,8 @@ OUT_LAYER_LAB_LIBNAME = "libtaiyaki_amd_out_layer_lab.so"       # ... and its la
 CONV_WINDOW_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_conv_window.h")
 CONV_WINDOW_LIBNAME = "libtaiyaki_amd_conv_window.so"       # csrc/conv_strided.hip built -DTK_CONV_WINDOW: the 16 -> Cout convolution at the fast and RNA shapes, header and library of its own
 CONV_WINDOW_LAB_LIBNAME = "libtaiyaki_amd_conv_window_lab.so"       # ... and its lab build (tk_lab_conv_window_*)
+CHUNKS_SEQLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_chunks_seqlen.h")
+CHUNKS_SEQLEN_LIBNAME = "libtaiyaki_amd_chunks_seqlen.so"       # csrc/chunk_seqlen.hip: chunks of a fixed number of bases (the squiggle trainer's batches), header and library of its own
 
 VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
 VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
@@ -201,6 +203,9 @@ CONV_SIGNAL_SIGNATURES = {n: (r, a) for n, (r, a, _) in
 OUT_LAYER_SIGNATURES, OUT_LAYER_LAB_SIGNATURES = _read_wgrad_header(OUT_LAYER_HEADER)
 # the nineteenth: include/taiyaki_amd_conv_window.h (libtaiyaki_amd_conv_window.so), and the hooks its lab build adds
 CONV_WINDOW_SIGNATURES, CONV_WINDOW_LAB_SIGNATURES = _read_wgrad_header(CONV_WINDOW_HEADER)
+# the twentieth: include/taiyaki_amd_chunks_seqlen.h (libtaiyaki_amd_chunks_seqlen.so)
+CHUNKS_SEQLEN_SIGNATURES = {n: (r, a) for n, (r, a, _) in
+                            parse_prototypes(_blank_comments(open(CHUNKS_SEQLEN_HEADER).read())).items()}
 
 
 class SeqLabels(ctypes.Structure):
@@ -370,6 +375,12 @@ def conv_window_lib():
         return _load(os.path.join(CSRC, CONV_WINDOW_LAB_LIBNAME),
                      dict(CONV_WINDOW_SIGNATURES, **CONV_WINDOW_LAB_SIGNATURES))
     return _load(os.path.join(CSRC, CONV_WINDOW_LIBNAME), CONV_WINDOW_SIGNATURES)
+
+
+def chunks_seqlen_lib():
+    """Chunks of a fixed number of bases and the squiggle trainer's batch of them (include/taiyaki_amd_chunks_seqlen.h).
+    No fallback: a missing library raises."""
+    return _load(os.path.join(CSRC, CHUNKS_SEQLEN_LIBNAME), CHUNKS_SEQLEN_SIGNATURES)
 
 
 def varlen_lib():

@@ -184,6 +184,41 @@ class Trainer:
             self.arena.flat.clamp_(min=-self.grad_clip, max=self.grad_clip)
 
 
+class SquiggleTrainer:
+    """The train step of bin/train_squiggle.py:165-171, 216-224, 255 around the squiggle predictor
+    (`models.squiggle_predictor`) and the squiggle-match loss: AdamW and the LambdaLR decay
+    lr_max * lr_decay / (i + lr_decay).  The defaults are the reference's (bin/train_squiggle.py:28-60,
+    common_cmdargs.py).  Unlike the reference's, the loss value stays on the device: the step itself does not
+    wait for the GPU."""
+
+    def __init__(self, net, lr_max=1e-4, betas=(0.9, 0.999), weight_decay=0.0, eps=1e-6, lr_decay=5000,
+                 back_prob=1e-15):
+        self.net = net
+        self.back_prob = back_prob
+        params = list(net.parameters())
+        self.opt = torch.optim.AdamW(params, lr=lr_max, betas=betas, weight_decay=weight_decay, eps=eps,
+                                     capturable=params[0].is_cuda)      # no host sync in step()
+        self.lr_scheduler = torch.optim.lr_scheduler.LambdaLR(self.opt, lambda i: lr_decay / (i + lr_decay))
+
+    @staticmethod
+    def loss(net, seq_embed, signal, siglens, back_prob):
+        """bin/train_squiggle.py:218-221: the batch's cost per sample."""
+        from taiyaki_amd.squiggle_match import squiggle_match_loss
+        return squiggle_match_loss(net(seq_embed), signal, siglens, back_prob).sum() / siglens.sum()
+
+    def step(self, batch):
+        """`batch`: a `mapped_signal.SquiggleChunkBatch` (trained on through its `trimmed()`: the batch may be
+        short, and the squiggle match refuses a chunk without samples; that is one small copy to the host)
+        or a (seq_embed, signal, siglens) triple of device tensors.  Returns the loss value, on the device."""
+        seq_embed, signal, siglens = batch.trimmed() if hasattr(batch, "trimmed") else batch
+        self.opt.zero_grad()
+        fval = self.loss(self.net, seq_embed, signal, siglens, self.back_prob)
+        fval.backward()
+        self.opt.step()
+        self.lr_scheduler.step()
+        return fval.detach()
+
+
 # Other threads of the process (the NCCL/RCCL watchdog polls events) must not invalidate a
 # capture in progress: capture errors are scoped to the capturing thread.
 _CAPTURE = dict(capture_error_mode="thread_local")
