@@ -56,6 +56,8 @@ CONV_WINDOW_LIBNAME = "libtaiyaki_amd_conv_window.so"       # csrc/conv_strided.
 CONV_WINDOW_LAB_LIBNAME = "libtaiyaki_amd_conv_window_lab.so"       # ... and its lab build (tk_lab_conv_window_*)
 CHUNKS_SEQLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_chunks_seqlen.h")
 CHUNKS_SEQLEN_LIBNAME = "libtaiyaki_amd_chunks_seqlen.so"       # csrc/chunk_seqlen.hip: chunks of a fixed number of bases (the squiggle trainer's batches), header and library of its own
+OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_optim.h")
+OPTIM_LIBNAME = "libtaiyaki_amd_optim.so"       # csrc/optim.hip: the optimiser step (scale, maxima, clamp, norm cap, AdamW, zero fill), header and library of its own
 
 VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_rnn_varlen.h")
 VARLEN_LIBNAME = "libtaiyaki_amd_rnn_varlen.so"     # csrc/lstm_kernels.hip, gru_kernels.hip built -DTK_RNN_VARLEN: header and library of its own
@@ -206,6 +208,16 @@ CONV_WINDOW_SIGNATURES, CONV_WINDOW_LAB_SIGNATURES = _read_wgrad_header(CONV_WIN
 # the twentieth: include/taiyaki_amd_chunks_seqlen.h (libtaiyaki_amd_chunks_seqlen.so)
 CHUNKS_SEQLEN_SIGNATURES = {n: (r, a) for n, (r, a, _) in
                             parse_prototypes(_blank_comments(open(CHUNKS_SEQLEN_HEADER).read())).items()}
+
+
+def _read_optim_header():
+    raw = open(OPTIM_HEADER).read()
+    sigs = {n: (r, a) for n, (r, a, _) in parse_prototypes(_blank_comments(raw)).items()}
+    return sigs, {k: int(v) for k, v in re.findall(r"(?m)^#define (TK_OPTIM_\w+) (\d+)", raw)}
+
+
+# the twenty-first: include/taiyaki_amd_optim.h (libtaiyaki_amd_optim.so), its tile length and the words of its hyper block
+OPTIM_SIGNATURES, OPTIM_DEFINES = _read_optim_header()
 
 
 class SeqLabels(ctypes.Structure):
@@ -381,6 +393,12 @@ def chunks_seqlen_lib():
     """Chunks of a fixed number of bases and the squiggle trainer's batch of them (include/taiyaki_amd_chunks_seqlen.h).
     No fallback: a missing library raises."""
     return _load(os.path.join(CSRC, CHUNKS_SEQLEN_LIBNAME), CHUNKS_SEQLEN_SIGNATURES)
+
+
+def optim_lib():
+    """The optimiser step over the flat gradient arena (include/taiyaki_amd_optim.h).  No fallback: a missing library
+    raises."""
+    return _load(os.path.join(CSRC, OPTIM_LIBNAME), OPTIM_SIGNATURES)
 
 
 def varlen_lib():

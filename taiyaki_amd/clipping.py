@@ -113,6 +113,28 @@ class RollingMAD:
         return out
 
 
+class RollingQuantile:
+    """The value exceeded by `upper_quantile` of the last `window` values (the interface of taiyaki/maths.py:104-136, which
+    bin/train_abinitio.py:193-222 feeds the gradient's L2 norm to cap the next step's): `update(x)` takes x in and
+    returns `np.quantile(window, 1 - upper_quantile)`, or `default_to` while fewer than `min_data` values are held."""
+
+    def __init__(self, upper_quantile, window=100, min_data=1, default_to=None):
+        self.upper_quantile = upper_quantile
+        self.window = window
+        self.min_data = min_data
+        self.default_to = default_to
+        self._ring = np.zeros(window, dtype=np.float64)
+        self._seen = 0
+
+    def update(self, x):
+        self._ring[self._seen % self.window] = x
+        self._seen += 1
+        held = min(self._seen, self.window)
+        if held < self.min_data:
+            return self.default_to
+        return np.quantile(self._ring[:held], 1.0 - self.upper_quantile)
+
+
 class DeviceClipper:
     """Maxima + clip-by-value over a `parallel.FlatGradArena`, thresholds from a RollingMAD.
 

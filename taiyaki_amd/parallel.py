@@ -374,18 +374,20 @@ class FlatGradArena:
             _trace("whole arena")
             self._work.append(self._all_reduce(self.flat))
 
-    def finish(self, scale=1.0):
-        """Wait for the slices, apply 1 / world (x `scale`: 1 / number of accumulated sub-batches)."""
+    def finish(self, scale=1.0, defer=False):
+        """Wait for the slices, apply 1 / world (x `scale`: 1 / number of accumulated sub-batches).  `defer`: only wait,
+        and return the factor for a caller that folds it into its own pass over the arena (optim.FlatAdamW.step)."""
         _trace("finish: %d pending" % len(self._work))
         if self._work:
             for w in self._work:
                 w.wait()
             self._work = []
             scale = scale / self.world
-        if scale != 1.0:
+        if scale != 1.0 and not defer:
             self.flat.mul_(scale)
         for b, c in zip(self._buckets, getattr(self, "_bucket_size", [])):
             b[2], b[3] = c, False
+        return scale
 
 
 def broadcast_parameters(module, src=0, collective=None):

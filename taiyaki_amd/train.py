@@ -10,6 +10,10 @@ from taiyaki_amd import ctc, layers
 # the fused (A) + (B) / nblk operator, plain CRF and cat-mod (TK_FUSED_LOSS=0: the two reference
 # operators and autograd's add, as bin/train_flipflop.py:165-176 calls them)
 FUSED_LOSS = os.environ.get("TK_FUSED_LOSS", "1") != "0"
+# the optimiser step as this project's kernels (optim.FlatAdamW: scale, maxima, clamp, norm cap, AdamW and the zero fill in
+# two launches) for trainers on the GPU; `Trainer(hip_optim=...)` overrides it.  Off: torch.optim.AdamW behind arena.finish
+# and DeviceClipper, exactly as before.
+USE_HIP_OPTIM = os.environ.get("TK_HIP_OPTIM", "0") == "1"
 
 
 def calculate_loss(net, indata, seqs, seqlens, sharpen=1.0, mod_cats=None,
@@ -132,21 +136,42 @@ class Trainer:
     Defaults follow bin/_bin_argparse.py:16-193 (AdamW lr 4e-3, wd 0.01, eps 1e-6)."""
 
     def __init__(self, net, arena, lr=4e-3, weight_decay=0.01, eps=1e-6, grad_clip=None,
-                 clip_num_mads=None, clip_window=1000):
+                 clip_num_mads=None, clip_window=1000, hip_optim=None, grad_norm_cap_fraction=None):
         """`clip_num_mads` (reference default 0, `--gradient_clip_num_mads`; None = off) turns on
         the reference's adaptive clipping: per-parameter gradient maxima every step, clamp at
         median + num_mads * MAD of the last `clip_window` maxima once that many were seen
         (bin/train_flipflop.py:201-212, 575-578) -- on the device, see clipping.DeviceClipper.
-        `grad_clip` is a fixed clip-by-value bound."""
+        `grad_clip` is a fixed clip-by-value bound.
+        `hip_optim` (None: the module's USE_HIP_OPTIM): on, and the arena on the GPU, the optimiser is an
+        `optim.FlatAdamW` -- the 1 / (world x sub-batches) factor, the adaptive clipping, AdamW and the zero fill of the
+        next step's arena are its launch pair (the fixed `grad_clip` keeps its `clamp_` in front of it, behind a `mul_`
+        by that factor: the maxima of a trainer that sets both are then taken after the fixed clamp).  On the CPU it is
+        ignored.
+        `grad_norm_cap_fraction` (bin/train_abinitio.py's `--gradient_cap_fraction`; needs the HIP optimiser): the
+        gradient's L2 norm is capped at the value that this fraction of the last 100 steps' norms exceeded
+        (`optim.NormCap`)."""
         self.net = net
         self.arena = arena
         self.clipper = None
         if clip_num_mads is not None and arena.flat.is_cuda:
             from taiyaki_amd import clipping
             self.clipper = clipping.DeviceClipper(arena, clip_num_mads, clip_window)
-        self.opt = torch.optim.AdamW(arena.params, lr=lr, weight_decay=weight_decay, eps=eps,
-                                     betas=(0.9, 0.999),
-                                     capturable=arena.flat.is_cuda)  # no host sync in step()
+        self.hip_optim = bool(USE_HIP_OPTIM if hip_optim is None else hip_optim) and arena.flat.is_cuda
+        self.norm_cap = None
+        self._arena_zeroed = False          # the last thing that wrote the arena was an update that zeroed it
+        if self.hip_optim:
+            from taiyaki_amd import optim
+            self.opt = optim.FlatAdamW(arena, lr=lr, weight_decay=weight_decay, eps=eps, betas=(0.9, 0.999),
+                                       clipper=self.clipper)
+            if grad_norm_cap_fraction is not None:
+                self.norm_cap = optim.NormCap(self.opt, grad_norm_cap_fraction)
+        else:
+            if grad_norm_cap_fraction is not None:
+                raise ValueError("grad_norm_cap_fraction: the norm cap is part of the HIP optimiser step "
+                                 "(hip_optim=True, arena on the GPU)")
+            self.opt = torch.optim.AdamW(arena.params, lr=lr, weight_decay=weight_decay, eps=eps,
+                                         betas=(0.9, 0.999),
+                                         capturable=arena.flat.is_cuda)  # no host sync in step()
         self.grad_clip = grad_clip
         self.gate_watch = GateWatch()
 
@@ -157,7 +182,9 @@ class Trainer:
         the sub-batch losses (:195).  The reference's DDP reduces after every sub-batch's backward;
         here only the last backward issues the (hook-overlapped) all-reduce -- the same average."""
         subs = batch if isinstance(batch, (list, tuple)) else [batch]
-        self.arena.zero()
+        if not (self.hip_optim and self._arena_zeroed):
+            self.arena.zero()
+        self._arena_zeroed = False          # true again only when this step's update has run to its end
         hooks = self.arena.hooks_enabled
         total = None
         for k, sub in enumerate(subs):
@@ -167,11 +194,51 @@ class Trainer:
             total = loss.detach() if total is None else total + loss.detach()
         self.arena.hooks_enabled = hooks
         self.arena.allreduce_async()
-        self.arena.finish(scale=1.0 / len(subs))
-        self.clip()
-        self.opt.step()
+        self.update(nsubs=len(subs))
         self.gate_watch.note(sum(int(sub["seqlens"].numel()) for sub in subs))
         return loss if len(subs) == 1 else total / len(subs)
+
+    def update(self, nsubs=1, launch=None):
+        """The tail of a step, behind `arena.allreduce_async()`: wait for the all-reduce, average, clip, optimiser.
+        `launch`: what to call in place of `self.opt.step()` (the hybrid trainers' own optimiser, or the replay of its
+        captured step)."""
+        if not self.hip_optim:
+            self.arena.finish(scale=1.0 / nsubs)
+            self.clip()
+            (launch or self.opt.step)()
+            return
+        scale = self.arena.finish(scale=1.0 / nsubs, defer=True)
+        if self.grad_clip is not None:
+            if scale != 1.0:
+                self.arena.flat.mul_(scale)
+                scale = 1.0
+            self.arena.flat.clamp_(min=-self.grad_clip, max=self.grad_clip)
+        eager = not torch.cuda.is_current_stream_capturing()    # whole-step capture: no host traffic inside
+        if eager:
+            self.collect()
+        if launch is None:
+            self.opt.step(grad_scale=scale)
+        else:
+            self.opt.set_grad_scale(scale)
+            launch()
+        if eager:
+            self.copy_async()
+        self._arena_zeroed = True
+
+    def collect(self):
+        """HIP optimiser, the host side in front of an update: the previous step's maxima and norm become this step's
+        thresholds and cap."""
+        if self.clipper is not None:
+            self.clipper.collect()
+        if self.norm_cap is not None:
+            self.norm_cap.collect()
+
+    def copy_async(self):
+        """... and behind it: this step's maxima and norm start their way to the host."""
+        if self.clipper is not None:
+            self.clipper.copy_maxima_async()
+        if self.norm_cap is not None:
+            self.norm_cap.copy_norm_async()
 
     def clip(self):
         """Gradient maxima / clipping between the all-reduce and the optimiser step."""
@@ -313,13 +380,27 @@ class GraphedTrainer:
         captured clamp kernel sees them), and this step's maxima start their way to the host."""
         clipper = self.trainer.clipper
         self.load(batch)
-        if clipper is not None:
+        if self.trainer.hip_optim:
+            self.trainer.collect()
+        elif clipper is not None:
             clipper.collect()
         self.graph.replay()
-        if clipper is not None:
+        if self.trainer.hip_optim:
+            self.trainer.copy_async()
+        elif clipper is not None:
             clipper.copy_maxima_async()
         self.trainer.gate_watch.note(batch["seqlens"].numel())
         return self.loss
+
+
+def _set_momentum(opt, beta1):
+    """beta1 of the next replay (the reference's OneCycleLR cycles it with `--min_momentum`, bin/train_flipflop.py:417-429).
+    Only the HIP optimiser reads it from the device: torch's capturable AdamW takes `betas` as host floats, so a replay
+    keeps the beta1 of its capture."""
+    if not hasattr(opt, "set_momentum"):
+        raise RuntimeError("set_momentum: the captured torch.optim.AdamW keeps the beta1 of its capture; build the "
+                           "trainer with hip_optim=True (train.USE_HIP_OPTIM)")
+    opt.set_momentum(beta1)
 
 
 def _aliased_adamw(trainer):
@@ -329,7 +410,10 @@ def _aliased_adamw(trainer):
     parameters (same storage, own version counters) -- the replayed forward and the eager backward of
     one step always see the same, current weights.  The learning rate lives in a DEVICE scalar
     (capturable AdamW reads it at replay time): `_set_lr` between replays is what a per-iteration
-    schedule needs.  Returns (aliases, optimiser)."""
+    schedule needs.  Returns (aliases, optimiser).  A trainer on the HIP optimiser needs no aliases: `optim.FlatAdamW`
+    writes the parameters through raw pointers (the same contract) and is captured as it is."""
+    if trainer.hip_optim:
+        return None, trainer.opt
     arena = trainer.arena
     alias = []
     for p in arena.params:
@@ -346,6 +430,9 @@ def _aliased_adamw(trainer):
 
 
 def _set_lr(opt, lr):
+    if hasattr(opt, "set_lr"):          # optim.FlatAdamW: a fill of its hyper block
+        opt.set_lr(lr)
+        return
     for g in opt.param_groups:
         if torch.is_tensor(g["lr"]):
             g["lr"].fill_(float(lr))
@@ -375,13 +462,16 @@ class HybridGraphTrainer(GraphedTrainer):
         scalar, so a new value is one tiny fill between replays."""
         _set_lr(self.opt, lr)
 
+    def set_momentum(self, beta1):
+        """... and beta1 likewise (HIP optimiser only)."""
+        _set_momentum(self.opt, beta1)
+
     def _eager_step(self):
         tr = self.trainer
         tr.arena.zero()
         loss, _ = calculate_loss(tr.net, **self.static)
         ctc.backward_unit(loss)
         tr.arena.allreduce_async()
-        tr.arena.finish()
         self._clip_and_step()
 
     def capture(self, warmup=3):
@@ -405,17 +495,24 @@ class HybridGraphTrainer(GraphedTrainer):
         torch.cuda.synchronize()
         self.opt_graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.opt_graph, **_CAPTURE):
-            self.opt.step()
+            self._opt_step()
         torch.cuda.synchronize()
 
-    def _clip_and_step(self):
-        self.trainer.clip()
-        self.opt.step()
+    def _opt_step(self):
+        """What the optimiser graph captures (the HIP optimiser at the factor its hyper block holds: `Trainer.update`
+        fills a new one in before a replay)."""
+        if self.trainer.hip_optim:
+            self.opt.step(grad_scale=self.opt.grad_scale)
+        else:
+            self.opt.step()
+
+    def _clip_and_step(self, launch=None):
+        """finish (the all-reduce's waits and factor), clip, optimiser: eager, or `launch` for the optimiser"""
+        self.trainer.update(launch=launch or self._opt_step)
 
     def _tail_eager(self):
         ctc.backward_unit(self.loss, retain_graph=True)
         self.trainer.arena.allreduce_async()
-        self.trainer.arena.finish()
         self._clip_and_step()
 
     def step(self, batch):
@@ -423,9 +520,8 @@ class HybridGraphTrainer(GraphedTrainer):
         self.graph.replay()
         ctc.backward_unit(self.loss, retain_graph=True)
         self.trainer.arena.allreduce_async()
-        self.trainer.arena.finish()
-        self.trainer.clip()         # eager: two tiny launches + an async copy of the maxima
-        self.opt_graph.replay()
+        # (torch's optimiser: the clip is eager, two tiny launches + an async copy of the maxima)
+        self._clip_and_step(self.opt_graph.replay)
         self.trainer.gate_watch.note(batch["seqlens"].numel())
         return self.loss
 
@@ -458,6 +554,11 @@ class GraphCacheTrainer:
 
     def set_lr(self, lr):
         _set_lr(self.opt, lr)
+
+    def set_momentum(self, beta1):
+        _set_momentum(self.opt, beta1)
+
+    _opt_step = HybridGraphTrainer._opt_step
 
     @staticmethod
     def key_of(batch):
@@ -507,16 +608,14 @@ class GraphCacheTrainer:
         one.graph.replay()
         ctc.backward_unit(one.loss, retain_graph=True)
         self.trainer.arena.allreduce_async()
-        self.trainer.arena.finish()
-        self.trainer.clip()
         if self.opt_graph is not None:
-            self.opt_graph.replay()
+            self.trainer.update(launch=self.opt_graph.replay)
         else:
-            self.opt.step()             # the first step creates the optimiser state eagerly ...
+            self.trainer.update(launch=self._opt_step)      # the first step creates the optimiser state eagerly ...
             torch.cuda.synchronize()
             self.opt_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.opt_graph, **_CAPTURE):
-                self.opt.step()         # ... (capture records, it does not run) replayed from the second on
+                self._opt_step()        # ... (capture records, it does not run) replayed from the second on
             torch.cuda.synchronize()
         self.nsteps += 1
         self.trainer.gate_watch.note(batch["seqlens"].numel())
