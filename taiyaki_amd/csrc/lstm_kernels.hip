@@ -22,6 +22,11 @@
 // forward's cell lanes are kp < C of every KP lanes, 32-byte pieces of a row per store, so they stage the six values
 // in LDS and the workgroup stores the block as whole rows, 16 bytes per lane (rows_to_global, rnn_common.h): 3 store
 // instructions per workgroup and step at H 256, U 64, C 2 where the cell lanes issued 48.
+// What a step computes without the hand-off stands in front of its poll, where the wave would only wait (the forward at
+// H 256, U 64, C 2 and every backward): the addresses, as running pointers advanced once per step, and in the backward
+// tanh(c_t) and the factors of the gate derivatives; behind the barrier stand the memory instructions alone and what
+// needs the gathered values.  give_up is read behind the barrier by every wave and tested once, in front of the
+// publish: no wait for it stands on the chain (DESIGN.md "Step schedule" has the argument for the path it guards).
 //
 // Columns.  A launch works on `cols.n` columns of tensors that hold `cols.ld()` columns per time step (rnn_common.h:
 // Cols).  The two are one number everywhere but in the -DTK_RNN_WIDE build, which runs a batch wider than the admission
@@ -98,6 +103,9 @@ __device__ __forceinline__ void halve_rounds(float (&acc)[NA], int rq) {
 //     for the lanes of gate g, one tanhf body where the cell lanes issued three and one; the lane of gate i takes the
 //     other three activations of its columns from the lanes kp ^ 4 (f), kp ^ 2 (g) and kp ^ 6 (o) by DPP moves and
 //     runs the cell update, the publish and the staging as the plain body's cell lane does.
+// And the step's schedule keeps off the chain what does not depend on the hand-off (the file's header): running pointers
+// advanced in front of the poll, give_up and the staged rows read behind the matvec's leading reads, the rows stored
+// behind the first group of FMAs, give_up tested once in front of the cell update.
 template <int H, int C, int U, bool VL, bool SAVE>
 __device__ __forceinline__ void lstm_fwd_lanes_body(const float *__restrict__ gx, const float *__restrict__ whh, int T,
                                                     Cols cols, int reverse, int ngroups, float *__restrict__ y,
@@ -152,30 +160,68 @@ __device__ __forceinline__ void lstm_fwd_lanes_body(const float *__restrict__ gx
     if (tid == 0) give_up = 0;
 
     const size_t H4 = 4 * (size_t)H;
+    // Running pointers, each advanced by one recurrence step at the top of every step, in front of the poll, so that
+    // behind the barrier stand the loads and stores alone.  With t(s) the time index of step s, in step s they stand at
+    // t(s + 1) (gxp: the prefetch) and at t(s - 1) (rp, yp: the outputs held back); one is read only where that is a
+    // time index of the tensor (s + 1 < T; s > 0).
+    const ptrdiff_t dir = reverse ? -1 : 1, t0 = reverse ? T - 1 : 0;
     // the chunks of the staging block this lane stores: rows (value, column) of y, cell and the gates' four slabs
-    float *rp[NQ];
-    size_t rpitch[NQ];
+    gfloat *rp[NQ];
+    ptrdiff_t rstep[NQ];
+    bool rok[NQ];                                      // a chunk of the block and of a column of the batch
     if constexpr (SAVE) {
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
             const int q = tid + i * NT, row = q / U4, v = row / C, nn = n0 + row % C;
             const size_t w = v < 2 ? (size_t)H : H4;
             float *base = v == 0 ? y : v == 1 ? cell : gates + (size_t)(v - 2) * H;
-            rpitch[i] = (size_t)LD * w;
-            rp[i] = q < 6 * C * U4 && nn < N ? base + (size_t)nn * w + j0 + 4 * (q % U4) : nullptr;
+            rstep[i] = dir * (ptrdiff_t)((size_t)LD * w);
+            rok[i] = q < 6 * C * U4 && nn < N;
+            rp[i] = (gfloat *)base + (size_t)nn * w + j0 + 4 * (q % U4) + (t0 - 2 * dir) * (ptrdiff_t)((size_t)LD * w);
         }
     }
+    const float4 *stg4 = reinterpret_cast<const float4 *>(&stg[0][0]);       // the two blocks as 16-byte chunks
+    // not SAVE: y of this lane's columns
+    gfloat *yp = (gfloat *)y + ((t0 - 2 * dir) * LD + n) * (ptrdiff_t)H + j0 + u;
+    const ptrdiff_t ystep = dir * (ptrdiff_t)LD * H;
     // gx of this lane's gate in its columns, at time 0 (the next column is H4 floats on)
     const float *gx0 = gx + (size_t)n * H4 + (size_t)gate * H + j0 + u;
+    const ptrdiff_t gstep = dir * (ptrdiff_t)((size_t)LD * H4);
+    gcfloat *gxp = (gcfloat *)gx0 + t0 * (ptrdiff_t)((size_t)LD * H4);
     float gq[CK];                                      // ... of this step (loaded one step ahead)
 #pragma unroll
-    for (int v = 0; v < CK; ++v) gq[v] = fetch[v] ? gx0[(size_t)(reverse ? T - 1 : 0) * LD * H4 + v * H4] : 0.f;
+    for (int v = 0; v < CK; ++v) gq[v] = fetch[v] ? gxp[v * H4] : 0.f;
+    // the granule this lane publishes, by step parity
+    u64 *const pub0 = hbuf + (size_t)group * (H * C) + col * H + j0 + u;
+    const size_t pubpitch = (size_t)ngroups * (H * C);
     __syncthreads();
 
     for (int s = 0; s < T; ++s) {
         const int t = reverse ? T - 1 - s : s;
         float *hb = hs[s & 1];
         settle(gq);
+        gxp += gstep;
+        settle_ptr(gxp);
+        if constexpr (SAVE) {
+#pragma unroll
+            for (int i = 0; i < NQ; ++i) {
+                rp[i] += rstep[i];
+                settle_ptr(rp[i]);
+            }
+        } else {
+            yp += ystep;
+            settle_ptr(yp);
+        }
+        gu64 *pub = (gu64 *)pub0 + (s & 1) * pubpitch;
+        settle_ptr(pub);
+        int blk[NQ];                                     // SAVE: this lane's chunks of the step before's block (none: chunk 0)
+        if constexpr (SAVE) {
+#pragma unroll
+            for (int i = 0; i < NQ; ++i) {
+                blk[i] = rok[i] ? ((s - 1) & 1) * (6 * C * U4) + tid + i * NT : 0;
+                asm volatile("" : "+v"(blk[i]));
+            }
+        }
         if (s > 0) {
             const u64 *src = hbuf + ((size_t)((s - 1) & 1) * ngroups + group) * (H * C);
             float v[NG];
@@ -189,21 +235,16 @@ __device__ __forceinline__ void lstm_fwd_lanes_body(const float *__restrict__ gx
                 hb[FL.hs_index(e % H, e / H)] = v[q];
             }
             __syncthreads();
-            if (give_up) return;
-            const int tl = reverse ? t + 1 : t - 1;
-            if constexpr (!SAVE) {
+            if constexpr (!SAVE) {                       // (from a register: nothing to wait for)
 #pragma unroll
                 for (int v = 0; v < CK; ++v)
-                    if (valid[v]) y[((size_t)tl * LD + n + v) * H + j0 + u] = held[v];
-            } else {
-                rows_to_global<NQ>(stg[(s - 1) & 1], tid, NT, rp, rpitch, (size_t)tl);
+                    if (valid[v]) yp[v * H] = held[v];
             }
         }
         float gn[CK];
 #pragma unroll
-        for (int v = 0; v < CK; ++v)
-            gn[v] = fetch[v] && s + 1 < T ? gx0[(size_t)(reverse ? t - 1 : t + 1) * LD * H4 + v * H4] : 0.f;
-        asm volatile("" ::: "memory");                   // the deferred stores and the prefetch stay here
+        for (int v = 0; v < CK; ++v) gn[v] = fetch[v] && s + 1 < T ? gxp[v * H4] : 0.f;
+        asm volatile("" ::: "memory");                   // the prefetch stays here
 
         float acc[4 * C];                                // (gate, c) at FL.flat(gate, c): the order the rounds halve
 #pragma unroll
@@ -214,6 +255,17 @@ __device__ __forceinline__ void lstm_fwd_lanes_body(const float *__restrict__ gx
         float hv[NR][PR * C];
 #pragma unroll
         for (int j = 0; j < AHEAD; ++j) lds_row<PR * C>(hb + FL.chunk(kp, j), hv[j]);
+        // Behind them, so that no wait for either stands in front of the first FMA: give_up, read by every wave behind
+        // the same barrier and tested once, in front of the cell update (a workgroup that has given up runs the matvec
+        // out on an h it does not know, and neither publishes nor stages); and this lane's chunks of the step before's
+        // block, which leave behind the first group of FMAs (LDS answers in order: they have come when read 1 has).
+        // Both reads stand in step 0 as well, which has no poll: give_up is 0 there, and the chunks are not stored.
+        const int gu = give_up;
+        float4 out[NQ];
+        if constexpr (SAVE) {
+#pragma unroll
+            for (int i = 0; i < NQ; ++i) out[i] = stg4[blk[i]];
+        }
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
             if (j + AHEAD < NR) lds_row<PR * C>(hb + FL.chunk(kp, j + AHEAD), hv[j + AHEAD]);
@@ -225,8 +277,21 @@ __device__ __forceinline__ void lstm_fwd_lanes_body(const float *__restrict__ gx
 #pragma unroll
                     for (int c = 0; c < C; ++c)
                         acc[FL.flat(g, c)] = fmaf(w[g][PR * j + e], hv[j][e * C + c], acc[FL.flat(g, c)]);
+            if constexpr (SAVE) {
+                if (j == 0) {                            // behind the step's poll, in front of its cell update
+#pragma unroll
+                    for (int i = 0; i < NQ; ++i) {
+                        // (a chunk made to wait for the sums as they stand: left alone, the FMAs above sink below its store)
+#pragma unroll
+                        for (int a = 0; a < 4 * C; ++a) asm volatile("" : "+v"(out[i].x) : "v"(acc[a]));
+                        if (rok[i] && s > 0) *(grow_chunk *)rp[i] = row_chunk{out[i].x, out[i].y, out[i].z, out[i].w};
+                    }
+                    asm volatile("" ::: "memory");       // the deferred stores stay here
+                }
+            }
         }
         halve_rounds<1, KP>(acc, kp);                    // acc[v]: `gate` of column col + v, summed over the 8 lanes
+        if (gu) return;
 
         float ig[CK], fg[CK], gg[CK], og[CK];
 #pragma unroll
@@ -259,9 +324,7 @@ __device__ __forceinline__ void lstm_fwd_lanes_body(const float *__restrict__ gx
             }
             if (s + 1 < T) {                             // the publish: the step's last operation on global memory
 #pragma unroll
-                for (int v = 0; v < CK; ++v)
-                    store_granule(hbuf + ((size_t)(s & 1) * ngroups + group) * (H * C) + (col + v) * H + j0 + u,
-                                  (unsigned)(s + 1), h[v]);
+                for (int v = 0; v < CK; ++v) store_granule((u64 *)(pub + v * H), (unsigned)(s + 1), h[v]);
             }
 #pragma unroll
             for (int v = 0; v < CK; ++v) {
@@ -281,15 +344,19 @@ __device__ __forceinline__ void lstm_fwd_lanes_body(const float *__restrict__ gx
 #pragma unroll
         for (int v = 0; v < CK; ++v) gq[v] = gn[v];
     }
-    if (T > 0) {
-        const int tl = reverse ? 0 : T - 1;
+    if (T > 0) {                                         // the last step's outputs: one step on from where the pointers stand
         if constexpr (!SAVE) {
 #pragma unroll
             for (int v = 0; v < CK; ++v)
-                if (valid[v]) y[((size_t)tl * LD + n + v) * H + j0 + u] = held[v];
+                if (valid[v]) yp[ystep + v * H] = held[v];
         } else {
             __syncthreads();                             // the last step's block: no poll, so no barrier, is behind it
-            rows_to_global<NQ>(stg[(T - 1) & 1], tid, NT, rp, rpitch, (size_t)tl);
+#pragma unroll
+            for (int i = 0; i < NQ; ++i) {
+                if (!rok[i]) continue;
+                const float4 o = stg4[((T - 1) & 1) * (6 * C * U4) + tid + i * NT];
+                *(grow_chunk *)(rp[i] + rstep[i]) = row_chunk{o.x, o.y, o.z, o.w};
+            }
         }
     }
 }
@@ -304,8 +371,8 @@ __device__ __forceinline__ void lstm_fwd_lanes_body(const float *__restrict__ gx
 // It leaves h, c and the activations in the staging block of the step's parity; behind the next step's barrier (after
 // the loop: one barrier of its own) lane tid stores the 16-byte chunks tid + i NT of that block.  No second barrier
 // per step: a block is written again two steps on, behind the barrier that every wave reaches after its stores.
-// ((256, 64, 2) runs lstm_fwd_lanes_body above: the same lanes, weights, sums and schedule, another h image, reduction
-// and split of the activations.)
+// ((256, 64, 2) runs lstm_fwd_lanes_body above: the same lanes, weights and sums, another h image, reduction and split
+// of the activations, and the deferred stores and give_up's test further down the step.)
 //
 // VL: column n has lengths[n] steps (NULL: T).  A step at t >= lengths[n] leaves h = c = 0, writes y = 0 and
 // publishes h = 0 like any other step: every workgroup runs all T steps, so the hand-off is that of a full batch.
@@ -611,6 +678,15 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
         for (int g = 0; g < 4; ++g) in[3 + g] = gp[(size_t)g * H];
     }
     float held[4] = {0.f, 0.f, 0.f, 0.f};             // dG of the previous step, stored one step late
+    // Running pointers, each advanced by one recurrence step at the top of every step, in front of the poll, so that
+    // behind the gather's barrier stand the loads and stores alone.  With t(s) the time index of step s, in step s they
+    // stand at: dyp, gp: dy and the gates of t(s + 1); cnp: c of t(s + 2); dgp: dgates of t(s - 1).  A pointer is read
+    // only where its time index is one of the tensor's (valid lanes; the guards on tt below; s > 0).
+    const ptrdiff_t step1 = (reverse ? 1 : -1) * (ptrdiff_t)LD * H, step4 = 4 * step1;
+    const ptrdiff_t row0 = ((ptrdiff_t)(reverse ? 0 : T - 1) * LD + n) * H;      // row (t(0), n) of a (T, N, H) tensor
+    gcfloat *dyp = (gcfloat *)dy + row0 + j0 + u, *cnp = (gcfloat *)cell + row0 + step1 + j0 + u;
+    gcfloat *gp = (gcfloat *)gates + 4 * row0 + j0 + u;
+    gfloat *dgp = (gfloat *)dgates + 4 * row0 - 2 * step4 + j0 + u;
     __syncthreads();
 
     const u64 *mine = pbuf + (size_t)group * G * C * H + cc * H + j0 + u;
@@ -622,7 +698,32 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
         const int t = reverse ? T - 1 - tt : tt;          // time index
         const int tp = reverse ? t + 1 : t - 1;           // time index of the recurrence's previous step
         settle(in);
+        // What the cell update takes from in[] alone, computed here, where the wave would otherwise only wait for the
+        // poll: tanh(c_t) and the factors of the gate derivatives, each the operation the update always was (fac[0] one
+        // fma; fac[3] a product, then a difference).  Pinned in front of the poll like the loads.
+        float fac[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (cell_lane) {
+#pragma clang fp contract(off)
+            const float tc = tanhf(in[1]);
+            fac[0] = fmaf(-tc, tc, 1.f);
+            fac[1] = 1.f - in[3];
+            fac[2] = 1.f - in[4];
+            const float g2 = in[5] * in[5];
+            fac[3] = 1.f - g2;
+            fac[4] = 1.f - in[6];
+            fac[5] = tc;
+        }
+        settle(fac);
+        dyp += step1;
+        cnp += step1;
+        gp += step4;
+        dgp += step4;
+        settle_ptr(dyp);
+        settle_ptr(cnp);
+        settle_ptr(gp);
+        settle_ptr(dgp);
         float dhr = 0.f;
+        int gu = 0;                                       // give_up as read behind the gather's barrier
         if (s > 0) {
             float v[NP];
             const int nvalid = plane < G ? (G - plane + PL - 1) / PL : 0;
@@ -639,32 +740,31 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
                 gath[plane * PAIRS + pair] = sum;
             }
             __syncthreads();
-            if (give_up) return;
+            // read here, by every wave behind the same barrier, and tested once, behind the dgs barrier: no wait for it
+            // stands on the chain, and a workgroup that has given up runs the step out (on a dh it does not know, into
+            // registers and LDS only: the stores below are the step before's) but does not publish
+            gu = give_up;
             if (cell_lane) {
 #pragma unroll
                 for (int p = 0; p < (APART ? G : PL); ++p) dhr += gath[p * PAIRS + pair];
             }
             if (valid) {
-                const int tl = reverse ? t - 1 : t + 1;
-                float *dp = dgates + ((size_t)tl * LD + n) * H4 + j0 + u;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) dp[(size_t)g * H] = held[g];
+                for (int g = 0; g < 4; ++g) dgp[(size_t)g * H] = held[g];
             }
         }
         float nx[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (valid && tt > 0) {
-            const size_t o = ((size_t)tp * LD + n) * H + j0 + u;
-            nx[0] = dy[o];
+            nx[0] = *dyp;
             nx[1] = in[2];
-            if (tt > 1) nx[2] = cell[((size_t)(reverse ? tp + 1 : tp - 1) * LD + n) * H + j0 + u];
-            const float *gp = gates + ((size_t)tp * LD + n) * H4 + j0 + u;
+            if (tt > 1) nx[2] = *cnp;
 #pragma unroll
             for (int g = 0; g < 4; ++g) nx[3 + g] = gp[(size_t)g * H];
         }
         asm volatile("" ::: "memory");                   // the deferred stores and the prefetch stay here
 
         if (cell_lane) {
-            const float ct = in[1];
+#pragma clang fp contract(off)
             float cp = in[2];
             if constexpr (VL) {
                 if (tp >= len) cp = 0.f;                  // (reverse: the column's first step starts from c = 0)
@@ -672,12 +772,13 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
             const float ig = in[3], gg = in[5], og = in[6];
             float fg = in[4];
             const float dh = in[0] + dhr;
-            const float tc = tanhf(ct);
-            float dc = dh * og * (1.f - tc * tc) + dc_next * f_next;
-            float di = dc * gg * ig * (1.f - ig);
-            float df = dc * cp * fg * (1.f - fg);
-            float dg = dc * ig * (1.f - gg * gg);
-            float dout = dh * tc * og * (1.f - og);
+            const float tc = fac[5];
+            // (the one contraction written out: dc_next f_next is the product the fma takes, as it always was)
+            float dc = fmaf(dc_next, f_next, dh * og * fac[0]);
+            float di = dc * gg * ig * fac[1];
+            float df = dc * cp * fg * fac[2];
+            float dg = dc * ig * fac[3];
+            float dout = dh * tc * og * fac[4];
             if constexpr (VL) {
                 if (t >= len) dc = fg = di = df = dg = dout = 0.f;
             }
@@ -694,8 +795,11 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
         }
 #pragma unroll
         for (int q = 0; q < 7; ++q) in[q] = nx[q];
+        // every wave holds the same gu; in front of the barrier the waves without cell lanes test it while they would
+        // wait for the others (and in front of the last step's stores: the dG of a step that gave up is not one)
+        if (gu) return;
         __syncthreads();
-        if (s + 1 == T) break;                            // the first step has no predecessor to feed
+        if (s + 1 == T) break;                           // the first step has no predecessor to feed
 
         if constexpr (BLOCK) {
             u64 *dst = pbuf + (((size_t)(s & 1) * ngroups + group) * G + member) * C * H;

@@ -126,6 +126,18 @@ __device__ __forceinline__ void settle(float (&v)[M][K]) {
     for (int i = 0; i < M; ++i) settle(v[i]);
 }
 
+// A running pointer of the step schedule, advanced at the top of a step: pinned as advanced there, in front of the poll
+// (left alone, the compiler sinks the addition to the pointer's first use, behind the barrier).  Typed as a pointer to
+// global memory: behind the pin the compiler no longer sees where the pointer came from, and a plain one would be read
+// through flat instructions.
+typedef __attribute__((address_space(1))) float gfloat;
+typedef __attribute__((address_space(1))) const float gcfloat;
+
+template <class P>
+__device__ __forceinline__ void settle_ptr(P *&p) {        // P: gfloat, gcfloat, gu64
+    asm volatile("" : "+v"(p));
+}
+
 __device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
 
 // C consecutive floats of LDS (16-byte aligned where C is a multiple of 4)
@@ -157,6 +169,7 @@ __device__ __forceinline__ void lds_row(const float *p, float (&v)[C]) {
 // dst[i] is where chunk i goes at time 0 (NULL: a chunk past the block or of a column past N, not stored), pitch[i]
 // its tensor's floats per time step.  One dwordx4 per chunk; the tensors need no more than a float's alignment.
 typedef float row_chunk __attribute__((ext_vector_type(4), aligned(4)));
+typedef __attribute__((address_space(1))) row_chunk grow_chunk;          // ... through a running pointer (settle_ptr)
 
 template <int NQ>
 __device__ __forceinline__ void rows_to_global(const float *blk, int tid, int nt, float *const (&dst)[NQ],
