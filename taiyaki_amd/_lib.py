@@ -44,6 +44,9 @@ SQUIGGLE_NET_LAB_LIBNAME = "libtaiyaki_amd_squiggle_net_lab.so"     # ... and it
 LSTM_LOCAL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_lstm_local.h")
 LSTM_LOCAL_LIBNAME = "libtaiyaki_amd_lstm_local.so"     # csrc/lstm_local.hip: the LSTM recurrence at size 96, one workgroup per column set, header and library of its own
 LSTM_LOCAL_LAB_LIBNAME = "libtaiyaki_amd_lstm_local_lab.so"     # ... and its lab build (tk_lab_lstm_local_cols)
+LSTM_LARGE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_lstm_large.h")
+LSTM_LARGE_LIBNAME = "libtaiyaki_amd_lstm_large.so"     # csrc/lstm_kernels.hip built -DTK_LSTM_LARGE: the LSTM recurrence at size 512, header and library of its own
+LSTM_LARGE_LAB_LIBNAME = "libtaiyaki_amd_lstm_large_lab.so"     # ... and its lab build (tk_lab_lstm_large_cols, tk_lab_lstm_large_geometry)
 ALIGN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_align.h")
 ALIGN_LIBNAME = "libtaiyaki_amd_align.so"       # csrc/align_kernels.hip: edit-distance alignment of batches of pairs, header and library of its own
 CONV_SIGNAL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_conv_signal.h")
@@ -218,6 +221,8 @@ def _read_optim_header():
 
 # the twenty-first: include/taiyaki_amd_optim.h (libtaiyaki_amd_optim.so), its tile length and the words of its hyper block
 OPTIM_SIGNATURES, OPTIM_DEFINES = _read_optim_header()
+# the twenty-second: include/taiyaki_amd_lstm_large.h (libtaiyaki_amd_lstm_large.so), and the hooks its lab build adds
+LSTM_LARGE_SIGNATURES, LSTM_LARGE_LAB_SIGNATURES = _read_wgrad_header(LSTM_LARGE_HEADER)
 
 
 class SeqLabels(ctypes.Structure):
@@ -355,6 +360,15 @@ def lstm_local_lib():
         return _load(os.path.join(CSRC, LSTM_LOCAL_LAB_LIBNAME),
                      dict(LSTM_LOCAL_SIGNATURES, **LSTM_LOCAL_LAB_SIGNATURES))
     return _load(os.path.join(CSRC, LSTM_LOCAL_LIBNAME), LSTM_LOCAL_SIGNATURES)
+
+
+def lstm_large_lib():
+    """The LSTM recurrence at hidden size 512 (include/taiyaki_amd_lstm_large.h): the lab build of that library while
+    the process runs on the lab build (`use_lab`), the release one otherwise.  No fallback: a missing library raises."""
+    if is_lab():
+        return _load(os.path.join(CSRC, LSTM_LARGE_LAB_LIBNAME),
+                     dict(LSTM_LARGE_SIGNATURES, **LSTM_LARGE_LAB_SIGNATURES))
+    return _load(os.path.join(CSRC, LSTM_LARGE_LIBNAME), LSTM_LARGE_SIGNATURES)
 
 
 def align_lib():

@@ -136,6 +136,18 @@ int lstm_forward_wide_dispatch(const float *gx, const float *whh, const int32_t 
 int lstm_backward_wide_dispatch(const float *whh, const float *gates, const float *cell, const float *dy,
                                 const int32_t *lengths, size_t T, size_t N, size_t H, int reverse, int cu_count,
                                 float *dgates, void *ws, size_t wsb, uint32_t *status, hipStream_t stream);
+
+// ... and lstm_kernels.hip's -DTK_LSTM_LARGE build (libtaiyaki_amd_lstm_large.so; lstm_large_api.hip defines the C
+// entries): hidden size 512 at every batch width, as slabs of columns; gates and cell of the forward may both be NULL
+int lstm_large_supported(size_t H);
+size_t lstm_large_slab(size_t N, size_t H, int cu_count);
+size_t lstm_large_workspace_bytes(size_t N, size_t H, int cu_count);
+int lstm_forward_large_dispatch(const float *gx, const float *whh, const int32_t *lengths, size_t T, size_t N, size_t H,
+                                int reverse, int cu_count, float *y, float *gates, float *cell, void *ws, size_t wsb,
+                                uint32_t *status, hipStream_t stream);
+int lstm_backward_large_dispatch(const float *whh, const float *gates, const float *cell, const float *dy,
+                                 const int32_t *lengths, size_t T, size_t N, size_t H, int reverse, int cu_count,
+                                 float *dgates, void *ws, size_t wsb, uint32_t *status, hipStream_t stream);
 size_t gru_wide_slab(size_t N, size_t H, int cu_count);
 size_t gru_wide_workspace_bytes(size_t N, size_t H, int cu_count);
 int gru_forward_wide_dispatch(const float *gx, const float *whh, const float *bhh, const int32_t *lengths, size_t T,
@@ -208,6 +220,8 @@ void lstm_lab_units(int units);
 bool lstm_lab_geometry(size_t N, size_t H, int cu_count, size_t *out);
 void gru_lab_cols(int cols);
 void lstm_local_lab_cols(int cols);
+void lstm_large_lab_cols(int cols);
+bool lstm_large_lab_geometry(size_t N, size_t H, int cu_count, size_t *out);
 bool logz_lab_plan(size_t T, size_t N, size_t nbase, size_t score_bytes, LogzPlan *p);
 int viterbi_lab_waves(size_t N);
 bool crf_lab_plan(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, size_t bulk_seqlen, int form, int want_grad,

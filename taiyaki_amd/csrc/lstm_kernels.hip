@@ -39,6 +39,10 @@
 // nothing saved: per-column lengths, y the only output (DESIGN.md "Variable-length recurrences").
 // -DTK_RNN_VARLEN_TRAIN (libtaiyaki_amd_rnn_varlen_train.so) takes the training pair in its VL form: the saving forward
 // and the backward with per-column lengths (DESIGN.md "Training through variable-length batches").
+// A fifth, -DTK_LSTM_LARGE (libtaiyaki_amd_lstm_large.so), is hidden size 512 and nothing else: the three VL forms at
+// (512, 32, 4) and (512, 32, 8), 512 lanes per workgroup, with a geometry of its own and the slabs of the -DTK_RNN_WIDE
+// build (DESIGN.md "LSTM at size 512").  What it needs stands under its #ifdef or is a template argument that no other
+// build instantiates: the other builds' objects do not change with it.
 #include "dispatch.h"
 #include "ff_common.h"
 #include "lstm_bwd_layout.h"
@@ -52,9 +56,14 @@ namespace {
 // forward's lanes (u, kp) at KP = 8, 192 floats per lane at H = 384
 template <int U>
 constexpr int threads_for() { return U == 48 ? 384 : U <= 32 ? 256 : 512; }
-// ... of the backward: two lanes per column of W_hh at U = 48, 96 floats per lane at either size
+// ... of the forward at (H, U): H = 512 (-DTK_LSTM_LARGE alone instantiates it) takes 512 lanes at U = 32, lanes (u, kp)
+// at KP = 16, so that a lane holds the 128 floats of (256, 64) and not 256
 template <int H, int U>
-constexpr int bwd_threads_for() { return U == 48 ? 2 * H : threads_for<U>(); }
+constexpr int fwd_threads_for() { return H == 512 ? 512 : threads_for<U>(); }
+// ... of the backward: two lanes per column of W_hh at U = 48, 96 floats per lane at either size; H = 512: one lane per
+// column (RP 1), 4 U = 128 floats per lane
+template <int H, int U>
+constexpr int bwd_threads_for() { return U == 48 ? 2 * H : fwd_threads_for<H, U>(); }
 
 // The value of lane (lane ^ M) of the wave.  M = 1 and 2 are one quad permutation, M = 4 a mirror of the half row and a
 // reversal of the quad (i -> 7 - i -> i ^ 4): DPP operands of the VALU, which the compiler folds into the add that uses
@@ -379,7 +388,7 @@ __device__ __forceinline__ void lstm_fwd_lanes_body(const float *__restrict__ gx
 // SAVE: gates and cell are written, through the staging block (with VL: 0 on a step at or beyond the length).  Not SAVE:
 // they are not written (the pointers are not read); y goes out from the cell lane's register, one step late.
 template <int H, int C, int U, bool VL = false, bool SAVE = !VL>
-__global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const float *__restrict__ gx,
+__global__ __launch_bounds__((fwd_threads_for<H, U>()), 1) void lstm_fwd_kernel(const float *__restrict__ gx,
                                                                        const float *__restrict__ whh, int T, Cols cols,
                                                                        int reverse, int ngroups,
                                                                        float *__restrict__ y,
@@ -391,7 +400,7 @@ __global__ __launch_bounds__(threads_for<U>(), 1) void lstm_fwd_kernel(const flo
         lstm_fwd_lanes_body<H, C, U, VL, SAVE>(gx, whh, T, cols, reverse, ngroups, y, gates, cell, hbuf, status, lengths);
         return;
     }
-    constexpr int NT = threads_for<U>();
+    constexpr int NT = fwd_threads_for<H, U>();
     const int N = cols.n, LD = cols.ld();               // the launch's columns; the tensors' columns per time step
     constexpr int G = H / U;
     constexpr int KP = NT / U;
@@ -871,6 +880,26 @@ int units48(size_t H) { return H == 192 || H == 384 ? 48 : 0; }
 // workgroups with 4 columns where they fit, else, at H = 192 only, with 8 (at H = 384 the forward at 8 columns does not
 // fit its registers); this is the launch itself.  Every kernel waits on the other members of its group, so a grid
 // larger than the CU count is never admitted.
+#ifdef TK_LSTM_LARGE
+// -DTK_LSTM_LARGE (libtaiyaki_amd_lstm_large.so): H = 512 alone.  Groups of 512 / 32 = 16 workgroups with 4 columns
+// where they fit one workgroup per CU, else with 8; this is the launch itself, as at H = 192 and 384.
+constexpr int kLargeUnits = 32;
+
+bool lstm_geometry(size_t N, size_t H, int cu_count, int *C_out, int *groups_out) {
+    if (H != 512 || N == 0 || cu_count <= 0) return false;
+    const size_t G = H / kLargeUnits;
+    for (int C = 4; C <= 8; C *= 2) {
+        if (g_lab_cols != 0 && C != g_lab_cols) continue;
+        const size_t groups = (N + C - 1) / C;
+        if (groups * G <= (size_t)cu_count) {
+            *C_out = C;
+            *groups_out = (int)groups;
+            return true;
+        }
+    }
+    return false;
+}
+#else
 bool lstm_geometry(size_t N, size_t H, int cu_count, int *C_out, int *groups_out) {
     const int U48 = units48(H);
     if (!(U48 || H == 16 || H == 32 || H == 64 || H == 128 || H == 256) || N == 0 || cu_count <= 0) return false;
@@ -887,6 +916,7 @@ bool lstm_geometry(size_t N, size_t H, int cu_count, int *C_out, int *groups_out
     }
     return false;
 }
+#endif  // TK_LSTM_LARGE
 
 size_t ws_bytes(size_t H, int C, int groups, int U, bool backward) {
     return 2 * (size_t)groups * (backward ? H / U : 1) * C * H * sizeof(u64);
@@ -905,6 +935,10 @@ struct Plan {
 bool lstm_plan(size_t N, size_t H, int cu_count, Plan *p) {
     int C16 = 0, groups16 = 0;
     if (!lstm_geometry(N, H, cu_count, &C16, &groups16)) return false;
+#ifdef TK_LSTM_LARGE
+    *p = Plan{kLargeUnits, C16, groups16, (unsigned)(groups16 * (H / kLargeUnits))};
+    return true;
+#endif
     if (const int U48 = units48(H)) {
         *p = Plan{U48, C16, groups16, (unsigned)(groups16 * (H / U48))};
         return true;
@@ -920,8 +954,15 @@ bool lstm_plan(size_t N, size_t H, int cu_count, Plan *p) {
 }
 
 // (H, U, C) -> one instantiation: U = 16 takes 8 or 16 columns, U = 32 4 or 8, U = 64 2 or 4; U <= H; U = 48 takes 4,
-// and 8 at H = 192
+// and 8 at H = 192.  -DTK_LSTM_LARGE: (512, 32, 4) and (512, 32, 8) and no other
+#ifdef TK_LSTM_LARGE
 #define TK_LSTM_SWITCH(LAUNCH)                                                                                    \
+    switch ((int)H * 100000 + p.U * 1000 + p.C) {                                                                 \
+        LAUNCH(512, 32, 4) LAUNCH(512, 32, 8)                                                                     \
+        default: return TK_ERR_UNSUPPORTED;                                                                       \
+    }
+#else
+#define TK_LSTM_SWITCH(LAUNCH)                                                                                   \
     switch ((int)H * 100000 + p.U * 1000 + p.C) {                                                                 \
         LAUNCH(16, 16, 8) LAUNCH(16, 16, 16) LAUNCH(32, 16, 8) LAUNCH(32, 16, 16) LAUNCH(64, 16, 8)                \
         LAUNCH(64, 16, 16) LAUNCH(128, 16, 8) LAUNCH(128, 16, 16) LAUNCH(256, 16, 8) LAUNCH(256, 16, 16)          \
@@ -931,14 +972,15 @@ bool lstm_plan(size_t N, size_t H, int cu_count, Plan *p) {
         LAUNCH(256, 64, 4) LAUNCH(192, 48, 4) LAUNCH(192, 48, 8) LAUNCH(384, 48, 4)                               \
         default: return TK_ERR_UNSUPPORTED;                                                                       \
     }
+#endif
 
 template <bool VL, bool SAVE>
 int launch_fwd(const Plan &p, size_t H, hipStream_t st, const float *gx, const float *whh, int T, Cols cols,
                int rev, float *y, float *gates, float *cell, u64 *ws, uint32_t *status, const int32_t *lengths) {
 #define TK_LSTM_FWD(HH, UU, CC)                                                                                  \
     case HH * 100000 + UU * 1000 + CC:                                                                           \
-        hipLaunchKernelGGL((lstm_fwd_kernel<HH, CC, UU, VL, SAVE>), dim3(p.grid), dim3(threads_for<UU>()), 0, st, gx,  \
-                           whh, T, cols, rev, p.groups, y, gates, cell, ws, status, lengths);                    \
+        hipLaunchKernelGGL((lstm_fwd_kernel<HH, CC, UU, VL, SAVE>), dim3(p.grid), dim3(fwd_threads_for<HH, UU>()), 0,  \
+                           st, gx, whh, T, cols, rev, p.groups, y, gates, cell, ws, status, lengths);            \
         break;
     TK_LSTM_SWITCH(TK_LSTM_FWD)
 #undef TK_LSTM_FWD
@@ -972,8 +1014,8 @@ size_t lstm_slab(size_t N, size_t H, int cu_count) {
 
 // What every dispatcher below does around its launch, written once: the pointer and range checks (`pointers_ok`: the
 // entry's own required pointers), then for every slab of the batch its plan, the workspace's size, nothing to do at
-// T == 0, the granules zeroed, then `launch(plan, the slab's first column, its columns)`.  The -DTK_RNN_WIDE build alone
-// cuts a batch: everywhere else the one slab is the batch, and a batch that no launch admits is refused.  The slabs
+// T == 0, the granules zeroed, then `launch(plan, the slab's first column, its columns)`.  The -DTK_RNN_WIDE and
+// -DTK_LSTM_LARGE builds alone cut a batch: everywhere else the one slab is the batch, and a batch that no launch admits is refused.  The slabs
 // share the workspace and follow each other on `stream`: two persistent grids at once could together exceed the CUs
 // and wait on each other for ever.  The first slab is the widest, so it has the largest plan: a later slab cannot fail
 // a check that the first passed, and a launch error returns at once, with no further slab started.
@@ -982,7 +1024,7 @@ int checked(bool pointers_ok, size_t T, size_t N, size_t H, int cu_count, void *
             hipStream_t stream, bool backward, Launch launch) {
     if (!pointers_ok || !ws || !status || !aligned16(ws) || T > (size_t)INT32_MAX || N > (size_t)INT32_MAX)
         return TK_ERR_BAD_ARG;
-#ifdef TK_RNN_WIDE
+#ifdef TK_RNN_SLABS
     const size_t S = lstm_slab(N, H, cu_count);
 #else
     const size_t S = N;
@@ -1008,6 +1050,9 @@ int checked(bool pointers_ok, size_t T, size_t N, size_t H, int cu_count, void *
 size_t train_workspace_bytes(size_t N, size_t H, int cu_count) {
     int C = 0, groups = 0;
     if (!lstm_geometry(N, H, cu_count, &C, &groups)) return 0;
+#ifdef TK_LSTM_LARGE
+    return ws_bytes(H, C, groups, kLargeUnits, true);
+#endif
     const int U48 = units48(H);
     return ws_bytes(H, C, groups, U48 ? U48 : 16, true);
 }
@@ -1077,6 +1122,49 @@ int lstm_backward_varlen_dispatch(const float *whh, const float *gates, const fl
                                   float *dgates, void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
     return backward<true>(whh, gates, cell, dy, lengths, T, N, H, reverse, cu_count, dgates, ws, wsb, status, stream);
 }
+#elif defined(TK_LSTM_LARGE)
+// Hidden size 512 (include/taiyaki_amd_lstm_large.h): the VL forms at every batch width, on one slab of lstm_slab
+// columns after the other, as the -DTK_RNN_WIDE build runs the sizes it covers.
+int lstm_large_supported(size_t H) { return H == 512; }
+
+size_t lstm_large_slab(size_t N, size_t H, int cu_count) { return lstm_slab(N, H, cu_count); }
+
+// the training pair's workspace at the widest slab, the first
+size_t lstm_large_workspace_bytes(size_t N, size_t H, int cu_count) {
+    return train_workspace_bytes(lstm_slab(N, H, cu_count), H, cu_count);
+}
+
+// gates and cell may both be NULL: nothing is saved
+int lstm_forward_large_dispatch(const float *gx, const float *whh, const int32_t *lengths, size_t T, size_t N,
+                                size_t H, int reverse, int cu_count, float *y, float *gates, float *cell, void *ws,
+                                size_t wsb, uint32_t *status, hipStream_t stream) {
+    if (!gates != !cell) return TK_ERR_BAD_ARG;
+    return gates ? forward<true, true>(gx, whh, lengths, T, N, H, reverse, cu_count, y, gates, cell, ws, wsb, status,
+                                       stream)
+                 : forward<true, false>(gx, whh, lengths, T, N, H, reverse, cu_count, y, nullptr, nullptr, ws, wsb,
+                                        status, stream);
+}
+
+int lstm_backward_large_dispatch(const float *whh, const float *gates, const float *cell, const float *dy,
+                                 const int32_t *lengths, size_t T, size_t N, size_t H, int reverse, int cu_count,
+                                 float *dgates, void *ws, size_t wsb, uint32_t *status, hipStream_t stream) {
+    return backward<true>(whh, gates, cell, dy, lengths, T, N, H, reverse, cu_count, dgates, ws, wsb, status, stream);
+}
+
+#ifdef TK_LAB
+void lstm_large_lab_cols(int cols) { g_lab_cols = cols; }
+
+// the eight numbers of lstm_lab_geometry (the admission geometry is the launch's own)
+bool lstm_large_lab_geometry(size_t N, size_t H, int cu_count, size_t *out) {
+    int C = 0, groups = 0;
+    Plan p;
+    if (!lstm_geometry(N, H, cu_count, &C, &groups) || !lstm_plan(N, H, cu_count, &p)) return false;
+    const size_t v[8] = {(size_t)C, (size_t)groups, (size_t)p.U, (size_t)p.C, (size_t)p.groups, p.grid,
+                         ws_bytes(H, p.C, p.groups, p.U, false), ws_bytes(H, p.C, p.groups, p.U, true)};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return true;
+}
+#endif
 #elif defined(TK_RNN_WIDE)
 // Every batch width at the sizes the kernels cover (include/taiyaki_amd_rnn_wide.h): the VL forms, on one slab of
 // lstm_slab columns after the other.  A batch that one launch admits is one slab: the call of the training pair with

@@ -21,12 +21,17 @@ constexpr uint64_t kSpinTicks = 200000000ull;   // 2 s of s_memrealtime (100 MHz
 
 // The columns of a launch: n of them, in tensors that hold ld >= n columns per time step (row (t, column) is row
 // t * ld + column of a tensor; the pointers, `lengths` among them, stand at the launch's first column).  ld != n is a
-// window of columns of a wider batch (DESIGN.md "Batches wider than one launch"), which the -DTK_RNN_WIDE build alone
-// launches: there ld is a kernel argument.  In every other build ld is n itself, as a kernel argument this is one int,
-// and the kernels are instruction for instruction what they were when they took n alone.
+// window of columns of a wider batch (DESIGN.md "Batches wider than one launch"), which the -DTK_RNN_WIDE build and the
+// -DTK_LSTM_LARGE build of lstm_kernels.hip alone launch (TK_RNN_SLABS): there ld is a kernel argument.  In every other
+// build ld is n itself, as a kernel argument this is one int, and the kernels are instruction for instruction what they
+// were when they took n alone.
+#if defined(TK_RNN_WIDE) || defined(TK_LSTM_LARGE)
+#define TK_RNN_SLABS 1
+#endif
+
 struct Cols {
     int n;
-#ifdef TK_RNN_WIDE
+#ifdef TK_RNN_SLABS
     int pitch;
     __host__ __device__ int ld() const { return pitch; }
 #else
@@ -35,7 +40,7 @@ struct Cols {
 };
 
 inline Cols make_cols(size_t n, size_t ld) {
-#ifdef TK_RNN_WIDE
+#ifdef TK_RNN_SLABS
     return Cols{(int)n, (int)ld};
 #else
     return Cols{(int)n};

@@ -9,7 +9,8 @@ that feeds them.
   (BASELINE.json north_star) and only produce the (T, N, S) score tensor.
   ``Lstm`` and ``GruMod`` keep their nn.LSTM / nn.GRU parameters, but on the GPU their
   recurrences run as the persistent HIP kernels of csrc/lstm_kernels.hip
-  (`LstmRecurrence`; size 96: csrc/lstm_local.hip, `LstmLocalRecurrence`) and csrc/gru_kernels.hip (`GruRecurrence`), and a narrow
+  (`LstmRecurrence`; size 96: csrc/lstm_local.hip, `LstmLocalRecurrence`; size 512: the same kernels from
+  libtaiyaki_amd_lstm_large.so, include/taiyaki_amd_lstm_large.h, USE_HIP_LSTM_LARGE) and csrc/gru_kernels.hip (`GruRecurrence`), and a narrow
   ``Convolution`` with swish runs as the fused HIP kernels of csrc/conv_kernels.hip
   (`SmallConvolution`); the mGru models' first layer (1 -> size channels on the raw signal, tanh) as those of
   csrc/conv_signal.hip (`SignalConvolution`).
@@ -622,6 +623,28 @@ def hip_lstm_workspace_bytes(rnn, x):
     return _lib.lib().tk_lstm_workspace_bytes(x.shape[1], rnn.hidden_size, _cu_count(x.device))
 
 
+# True: an Lstm at hidden size 512, which the other recurrence libraries do not cover, runs on the entries of
+# include/taiyaki_amd_lstm_large.h (every batch width, with or without lengths) wherever
+# `hip_lstm_large_workspace_bytes` is not 0.  False: it runs nn.LSTM (with lengths: every column alone), as it did
+# before there were such kernels, for comparisons against them
+USE_HIP_LSTM_LARGE = True
+# calls of `Lstm` that went through include/taiyaki_amd_lstm_large.h by kind, as rnn_varlen_calls counts: "saved" wrote
+# the activations for a backward pass, "inference" handed the kernel NULL for them
+lstm_large_calls = {"saved": 0, "inference": 0}
+
+
+def hip_lstm_large_workspace_bytes(rnn, x):
+    """Workspace of the entries of include/taiyaki_amd_lstm_large.h for this nn.LSTM and input: not 0 at every batch
+    width where `_hip_lstm_takes` admits the layer and the library supports its size (512), 0 elsewhere: other sizes,
+    empty tensors, what `_hip_lstm_takes` refuses, and USE_HIP_LSTM_LARGE = False."""
+    if not (USE_HIP_LSTM_LARGE and isinstance(rnn, nn.LSTM) and _hip_lstm_takes(rnn, x) and x.shape[0] and x.shape[1]):
+        return 0
+    L = _lib.lstm_large_lib()
+    if not L.tk_lstm_large_supported(rnn.hidden_size):
+        return 0
+    return L.tk_lstm_large_workspace_bytes(x.shape[1], rnn.hidden_size, _cu_count(x.device))
+
+
 def _hip_lstm_takes(rnn, x):
     if not (USE_HIP_LSTM and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
             and rnn.weight_hh_l0.is_cuda and rnn.weight_hh_l0.dtype == torch.float32):
@@ -652,12 +675,15 @@ _RNN_LAUNCHES = {
     (True, False): ("varlen_lib", "tk_%s_forward_varlen_dev", None, "rnn_varlen"),
     ("wide", True): ("rnn_wide_lib", "tk_%s_forward_wide_dev", "tk_%s_backward_wide_dev", "rnn_wide"),
     ("wide", False): ("rnn_wide_lib", "tk_%s_forward_wide_dev", None, "rnn_wide"),
+    # hidden size 512 (include/taiyaki_amd_lstm_large.h): one pair of entries, the arguments of the wide ones
+    ("large", True): ("lstm_large_lib", "tk_%s_large_forward_dev", "tk_%s_large_backward_dev", "lstm_large"),
+    ("large", False): ("lstm_large_lib", "tk_%s_large_forward_dev", None, "lstm_large"),
 }
 
 
 def _rnn_row(lens, wide):
-    """The first half of a key of _RNN_LAUNCHES."""
-    return "wide" if wide else lens is not None
+    """The first half of a key of _RNN_LAUNCHES (`wide`: False, True or "large")."""
+    return wide if isinstance(wide, str) else "wide" if wide else lens is not None
 
 
 def _rnn_launch(cell, row, lens, save, backward, ins, shape, reverse, outs, wsb, dev):
@@ -684,7 +710,9 @@ class LstmRecurrence(torch.autograd.Function):
     `lens` (a device int32 tensor, one entry per column): column n has lens[n] steps, and the launches are those of
     include/taiyaki_amd_rnn_varlen_train.h.  y, the gates, c and dG are 0 at and beyond every length, so the input and
     parameter gradients are the same sums over the whole padded tensors.  `save` False (only with `lens`) is the launch
-    of include/taiyaki_amd_rnn_varlen.h: nothing but y is allocated or written, and the call cannot be differentiated."""
+    of include/taiyaki_amd_rnn_varlen.h: nothing but y is allocated or written, and the call cannot be differentiated.
+    `wide` True: the entries of include/taiyaki_amd_rnn_wide.h; "large": those of include/taiyaki_amd_lstm_large.h (size
+    512).  Both take `lens` or None and `save` either way, and cut a batch wider than one launch into slabs themselves."""
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, wsb, lens=None, save=True, wide=False):
@@ -695,7 +723,9 @@ class LstmRecurrence(torch.autograd.Function):
         dev = x.device
         x = x.contiguous()
         w_hh = w_hh.contiguous()
-        if wide:
+        if wide == "large":
+            lstm_large_calls["saved" if save else "inference"] += 1
+        elif wide:
             rnn_wide_calls["saved" if save else "inference"] += 1
         elif lens is not None:
             rnn_varlen_calls["saved" if save else "inference"] += 1
@@ -820,8 +850,8 @@ class LstmLocalRecurrence(torch.autograd.Function):
 
 class Lstm(_Rnn):
     """layers.py:491-606 (wraps nn.LSTM, bias_hh frozen).  On the GPU the recurrence runs on the HIP kernels
-    (`LstmRecurrence`), a batch wider than one launch admits as slabs of columns, and size 96, which those kernels do not
-    cover, on `LstmLocalRecurrence`; nn.LSTM evaluates CPU tensors, sizes no kernel covers, and USE_HIP_LSTM = False."""
+    (`LstmRecurrence`), a batch wider than one launch admits as slabs of columns, size 96, which those kernels do not
+    cover, on `LstmLocalRecurrence`, and size 512 on the entries of include/taiyaki_amd_lstm_large.h; nn.LSTM evaluates CPU tensors, sizes no kernel covers, and USE_HIP_LSTM = False."""
 
     def __init__(self, insize, size):
         super().__init__(nn.LSTM(insize, size))
@@ -841,6 +871,10 @@ class Lstm(_Rnn):
         if hip_lstm_local_takes(rnn, x):        # a size one workgroup holds: no workspace, any batch width
             return LstmLocalRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
                                              bool(reverse), None, _needs_grad(x, self))
+        wsb = hip_lstm_large_workspace_bytes(rnn, x)
+        if wsb:     # size 512: a library of its own, any batch width; nothing saved where nothing needs a gradient
+            return LstmRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
+                                        bool(reverse), wsb, None, _needs_grad(x, self), "large")
         if reverse:
             return torch.flip(rnn(torch.flip(x, (0,)))[0], (0,))
         return rnn(x)[0]
@@ -1084,6 +1118,9 @@ def _rnn_forward_varlen(layer, x, reverse, lengths):
             assert lens.numel() == N, "lengths: one per column"
             return LstmLocalRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
                                              bool(reverse), lens, train)
+    if not wsb and isinstance(rnn, nn.LSTM):        # size 512: the entries of include/taiyaki_amd_lstm_large.h
+        wsb = hip_lstm_large_workspace_bytes(rnn, x)
+        wide = "large" if wsb else wide
     if not wsb:
         host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
         assert len(host) == N and (N == 0 or (host.min() >= 0 and host.max() <= T)), "lengths: one per column, 0..T"
@@ -1501,7 +1538,7 @@ def _varlen_batched(plan, x, lens):
         h = _zero_beyond(h, lens_dev)
     for layer, rnn_layer, rev in plan:
         if rnn_layer is not None:
-            if not hip_rnn_varlen_workspace_bytes(rnn_layer.rnn, h):
+            if not (hip_rnn_varlen_workspace_bytes(rnn_layer.rnn, h) or hip_lstm_large_workspace_bytes(rnn_layer.rnn, h)):
                 return None
             h = rnn_layer(h, reverse=rev, lengths=lens_dev)
             continue
