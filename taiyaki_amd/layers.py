@@ -9,8 +9,10 @@ that feeds them.
   (BASELINE.json north_star) and only produce the (T, N, S) score tensor.
   ``Lstm`` and ``GruMod`` keep their nn.LSTM / nn.GRU parameters, but on the GPU their
   recurrences run as the persistent HIP kernels of csrc/lstm_kernels.hip
-  (`LstmRecurrence`; size 96: csrc/lstm_local.hip, `LstmLocalRecurrence`; size 512: the same kernels from
-  libtaiyaki_amd_lstm_large.so, include/taiyaki_amd_lstm_large.h, USE_HIP_LSTM_LARGE) and csrc/gru_kernels.hip (`GruRecurrence`), and a narrow
+  (`LstmRecurrence`; size 96: csrc/lstm_local.hip; size 512: the same kernels from
+  libtaiyaki_amd_lstm_large.so, include/taiyaki_amd_lstm_large.h, USE_HIP_LSTM_LARGE) and csrc/gru_kernels.hip (`GruRecurrence`):
+  one Function per cell, on the launch of the first library that admits the call, in the order that `_rnn_route`
+  states.  A narrow
   ``Convolution`` with swish runs as the fused HIP kernels of csrc/conv_kernels.hip
   (`SmallConvolution`); the mGru models' first layer (1 -> size channels on the raw signal, tanh) as those of
   csrc/conv_signal.hip (`SignalConvolution`).
@@ -552,7 +554,17 @@ class _Rnn(nn.Module):
             else:
                 _truncated_normal_(param, 0.5)
 
-    def forward(self, x):
+    def forward(self, x, reverse=False, lengths=None):
+        if lengths is not None:
+            return _rnn_forward_varlen(self, x, reverse, lengths)
+        route = _rnn_route(self, x, False, False)
+        if route:
+            # The LSTM has no launch without lengths that saves nothing, so its main row saves whatever the grad mode,
+            # and its slabs of columns do as that row does; every other row saves only where something needs a gradient
+            save = (isinstance(self.rnn, nn.LSTM) and route[0] in (False, "wide")) or _needs_grad(x, self)
+            return _rnn_apply(self, x, reverse, *route, None, save)
+        if reverse:
+            return torch.flip(self.rnn(torch.flip(x, (0,)))[0], (0,))
         return self.rnn(x)[0]
 
 
@@ -645,6 +657,22 @@ def hip_lstm_large_workspace_bytes(rnn, x):
     return L.tk_lstm_large_workspace_bytes(x.shape[1], rnn.hidden_size, _cu_count(x.device))
 
 
+# False: an Lstm at a size that only the kernels of include/taiyaki_amd_lstm_local.h cover (96) runs nn.LSTM, with
+# lengths every column alone, as it did before there were such kernels, for comparisons against them
+USE_HIP_LSTM_LOCAL = True
+# calls of `Lstm` that went through include/taiyaki_amd_lstm_local.h by kind, as rnn_varlen_calls counts: "saved" wrote
+# the activations for a backward pass, "inference" handed the kernel NULL for them
+lstm_local_calls = {"saved": 0, "inference": 0}
+
+
+def hip_lstm_local_takes(rnn, x):
+    """True where the recurrence of include/taiyaki_amd_lstm_local.h runs this nn.LSTM on this input: what
+    `_hip_lstm_takes` admits, at a size one workgroup holds (`tk_lstm_local_supported`), with at least one step and one
+    column.  It needs no workspace, so there is no size to ask for."""
+    return bool(USE_HIP_LSTM_LOCAL and _hip_lstm_takes(rnn, x) and x.shape[0] and x.shape[1]
+                and _lib.lstm_local_lib().tk_lstm_local_supported(rnn.hidden_size))
+
+
 def _hip_lstm_takes(rnn, x):
     if not (USE_HIP_LSTM and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
             and rnn.weight_hh_l0.is_cuda and rnn.weight_hh_l0.dtype == torch.float32):
@@ -664,7 +692,8 @@ def hip_rnn_wide_workspace_bytes(rnn, x):
     return _lib.rnn_wide_lib().tk_rnn_wide_workspace_bytes(kind, x.shape[1], rnn.hidden_size, _cu_count(x.device))
 
 
-# What a recurrence launches, by (per-column lengths given, or "wide": a batch cut into slabs; activations saved): the
+# What a recurrence launches, by (row: per-column lengths given, or "wide": a batch cut into slabs, or a size with a
+# library of its own; activations saved), the row being what `_rnn_route` chooses: the
 # library (its accessor in _lib), the forward and the backward entry ("%s": lstm / gru) and the workspace's tag (None:
 # the cell's own).  The wide entries take the lengths (NULL: none) and all the forward's outputs (NULL: not saved).
 _RNN_LAUNCHES = {
@@ -678,28 +707,71 @@ _RNN_LAUNCHES = {
     # hidden size 512 (include/taiyaki_amd_lstm_large.h): one pair of entries, the arguments of the wide ones
     ("large", True): ("lstm_large_lib", "tk_%s_large_forward_dev", "tk_%s_large_backward_dev", "lstm_large"),
     ("large", False): ("lstm_large_lib", "tk_%s_large_forward_dev", None, "lstm_large"),
+    # hidden size 96 (include/taiyaki_amd_lstm_local.h): the arguments of the wide entries less the workspace, its size
+    # and the status word (_RNN_BARE_ROWS), so the tag is never read
+    ("local", True): ("lstm_local_lib", "tk_%s_local_forward_dev", "tk_%s_local_backward_dev", None),
+    ("local", False): ("lstm_local_lib", "tk_%s_local_forward_dev", None, None),
 }
+# The rows whose entries take neither workspace, workspace size nor status word (csrc/lstm_local.hip: one workgroup owns
+# every unit of its columns)
+_RNN_BARE_ROWS = frozenset({"local"})
+# The counter a call on a row moves, by "saved" / "inference"; the main row has none (the GRU: gru_forward_calls)
+_RNN_CALLS = {True: rnn_varlen_calls, "wide": rnn_wide_calls, "local": lstm_local_calls, "large": lstm_large_calls}
 
 
-def _rnn_row(lens, wide):
-    """The first half of a key of _RNN_LAUNCHES (`wide`: False, True or "large")."""
-    return wide if isinstance(wide, str) else "wide" if wide else lens is not None
+def _rnn_route(layer, x, lengths_given, save):
+    """Which launch runs the recurrence of `layer` (an `Lstm` or a `GruMod`) on x: (row of _RNN_LAUNCHES, workspace
+    bytes) of the first candidate that admits the call, None where none does (nn.LSTM / nn.GRU; with lengths every
+    column alone).  The order, for both cells, with and without lengths:
+      1. the main library (`hip_lstm_workspace_bytes` / `hip_gru_workspace_bytes`, row False); with lengths the library
+         with lengths in its place (row True): the training pair where `save`, the inference launch otherwise, neither
+         asked on a tensor without steps or columns.  `save` is read for nothing else;
+      2. slabs of columns ("wide"), not asked on a tensor without steps or columns;
+      3. the LSTM alone: size 96 ("local"), which has no workspace (0 bytes), then
+      4. size 512 ("large").
+    Every query is looked up when it is asked and none is asked behind the first that admits, so a call costs the host
+    no more than the queries in front of its row."""
+    rnn = layer.rnn
+    lstm = isinstance(rnn, nn.LSTM)
+    full = x.dim() == 3 and x.shape[0] and x.shape[1]
+    if not lengths_given:
+        first = (False, hip_lstm_workspace_bytes if lstm else hip_gru_workspace_bytes, True)
+    else:
+        first = (True, hip_rnn_varlen_train_workspace_bytes if save else hip_rnn_varlen_workspace_bytes, full)
+    for row, query, asked in (first, ("wide", hip_rnn_wide_workspace_bytes, full),
+                              ("local", hip_lstm_local_takes, lstm), ("large", hip_lstm_large_workspace_bytes, lstm)):
+        wsb = asked and query(rnn, x)
+        if wsb:
+            return row, 0 if row in _RNN_BARE_ROWS else wsb
+    return None
+
+
+def _rnn_apply(layer, x, reverse, row, wsb, lens, save):
+    """The recurrence of `layer` on x through the launch that `_rnn_route` chose: the one place that spells the
+    arguments of `LstmRecurrence` / `GruRecurrence`."""
+    rnn = layer.rnn
+    function = LstmRecurrence if isinstance(rnn, nn.LSTM) else GruRecurrence
+    return function.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0, bool(reverse), row, wsb,
+                          lens, save)
 
 
 def _rnn_launch(cell, row, lens, save, backward, ins, shape, reverse, outs, wsb, dev):
     """One launch of a recurrence, checked: the entry of _RNN_LAUNCHES[row, save] on `ins` (the lengths behind them where
-    the entry takes them), T, N, H, the direction and the CU count, `outs`, then the workspace, the status word and the
-    stream."""
+    the entry takes them), T, N, H, the direction and the CU count, `outs`, then the workspace, its size and the status
+    word (all three or, on a row of _RNN_BARE_ROWS, none) and the stream."""
     libname, fwd, bwd, tag = _RNN_LAUNCHES[row, bool(save)]
     name = (bwd if backward else fwd) % cell
-    ws = _lib.workspace(wsb, dev, tag or cell)
-    status = _lib.status_word(dev)
+    checked = ()
+    if row not in _RNN_BARE_ROWS:
+        ws = _lib.workspace(wsb, dev, tag or cell)
+        status = _lib.status_word(dev)
+        checked = (_lib.ptr(ws), wsb, _lib.ptr(status))
     ptrs = [_lib.ptr(t) for t in ins + ((lens,) if row else ())]
     rc = getattr(getattr(_lib, libname)(), name)(*ptrs, *shape, int(reverse), _cu_count(dev),
-                                                 *[_lib.ptr(t) for t in outs], _lib.ptr(ws), wsb, _lib.ptr(status),
-                                                 _lib.stream_ptr())
+                                                 *[_lib.ptr(t) for t in outs], *checked, _lib.stream_ptr())
     _lib.check(rc, name)
-    _lib.finish(status)
+    if checked:
+        _lib.finish(status)
 
 
 class LstmRecurrence(torch.autograd.Function):
@@ -707,35 +779,33 @@ class LstmRecurrence(torch.autograd.Function):
     b_hh as one GEMM, then tk_lstm_forward_dev.  Backward: tk_lstm_backward_dev gives dG (the gates'
     pre-activation gradient, T x N x 4H), the parameter and input gradients are GEMMs / a sum over it.
     `reverse` runs the recurrence from the last time step (layers.Reverse) on tensors in time order.
-    `lens` (a device int32 tensor, one entry per column): column n has lens[n] steps, and the launches are those of
-    include/taiyaki_amd_rnn_varlen_train.h.  y, the gates, c and dG are 0 at and beyond every length, so the input and
-    parameter gradients are the same sums over the whole padded tensors.  `save` False (only with `lens`) is the launch
-    of include/taiyaki_amd_rnn_varlen.h: nothing but y is allocated or written, and the call cannot be differentiated.
-    `wide` True: the entries of include/taiyaki_amd_rnn_wide.h; "large": those of include/taiyaki_amd_lstm_large.h (size
-    512).  Both take `lens` or None and `save` either way, and cut a batch wider than one launch into slabs themselves."""
+    `row` and `wsb` are what `_rnn_route` chose, the first library in its order that admits the call (a key of
+    _RNN_LAUNCHES with `save`).  False: the entries above.  True, with `lens` (a device int32 tensor, one entry per
+    column; column n has lens[n] steps): the launches of include/taiyaki_amd_rnn_varlen_train.h; y, the gates, c and dG
+    are 0 at and beyond every length, so the input and parameter gradients are the same sums over the whole padded
+    tensors; `save` False is the launch of include/taiyaki_amd_rnn_varlen.h: nothing but y is allocated or written, and
+    the call cannot be differentiated.  "wide": the entries of include/taiyaki_amd_rnn_wide.h; "large": those of
+    include/taiyaki_amd_lstm_large.h (size 512); "local": those of include/taiyaki_amd_lstm_local.h (size 96).  These
+    three take `lens` or None and `save` either way (not `save`: NULL for the activations, which are neither allocated
+    nor written), and admit every batch width."""
 
     @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, wsb, lens=None, save=True, wide=False):
-        if lens is None and not save and not wide:
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, row, wsb, lens, save):
+        if row is False and not save:
             raise RuntimeError("the LSTM has no launch without lengths that saves nothing")
         T, N, _ = x.shape
         H = w_hh.shape[1]
         dev = x.device
         x = x.contiguous()
         w_hh = w_hh.contiguous()
-        if wide == "large":
-            lstm_large_calls["saved" if save else "inference"] += 1
-        elif wide:
-            rnn_wide_calls["saved" if save else "inference"] += 1
-        elif lens is not None:
-            rnn_varlen_calls["saved" if save else "inference"] += 1
-        row = _rnn_row(lens, wide)
+        if row in _RNN_CALLS:
+            _RNN_CALLS[row]["saved" if save else "inference"] += 1
         gx = _rnn_proj(x.view(T * N, -1), w_ih, b_ih + b_hh, False)
         y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
         gates = torch.empty(T, N, 4 * H, dtype=torch.float32, device=dev) if save else None
         cell = torch.empty(T, N, H, dtype=torch.float32, device=dev) if save else None
         _rnn_launch("lstm", row, lens, save, False, (gx, w_hh), (T, N, H), reverse,
-                    (y, gates, cell) if save or wide else (y,), wsb, dev)
+                    (y,) if row is True and not save else (y, gates, cell), wsb, dev)
         if save:
             ctx.save_for_backward(x, w_ih, w_hh, y, gates, cell, lens)
         ctx.reverse, ctx.wsb, ctx.row = reverse, wsb, row
@@ -746,7 +816,8 @@ class LstmRecurrence(torch.autograd.Function):
         x, w_ih, w_hh, y, gates, cell, lens = ctx.saved_tensors
         T, N, I = x.shape
         H = w_hh.shape[1]
-        dy = dy.contiguous()
+        # (the size-96 entries refuse a pointer that is not 16-byte aligned, and dy is the one tensor not allocated here)
+        dy = _aligned(dy) if ctx.row == "local" else dy.contiguous()
         dg = torch.empty_like(gates)
         _rnn_launch("lstm", ctx.row, lens, True, True, (w_hh, gates, cell, dy), (T, N, H), ctx.reverse, (dg,), ctx.wsb,
                     x.device)
@@ -788,96 +859,13 @@ def _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, reverse, need):
     return dx, dw_ih, dw_hh, db if need[3] else None, db if need[4] else None
 
 
-# False: an Lstm at a size that only the kernels of include/taiyaki_amd_lstm_local.h cover (96) runs nn.LSTM, with
-# lengths every column alone, as it did before there were such kernels, for comparisons against them
-USE_HIP_LSTM_LOCAL = True
-# launches of `LstmLocalRecurrence` by kind, as rnn_varlen_calls counts: "saved" wrote the activations for a backward
-# pass, "inference" handed the kernel NULL for them
-lstm_local_calls = {"saved": 0, "inference": 0}
-
-
-def hip_lstm_local_takes(rnn, x):
-    """True where the recurrence of include/taiyaki_amd_lstm_local.h runs this nn.LSTM on this input: what
-    `_hip_lstm_takes` admits, at a size one workgroup holds (`tk_lstm_local_supported`), with at least one step and one
-    column.  It needs no workspace, so there is no size to ask for."""
-    return bool(USE_HIP_LSTM_LOCAL and _hip_lstm_takes(rnn, x) and x.shape[0] and x.shape[1]
-                and _lib.lstm_local_lib().tk_lstm_local_supported(rnn.hidden_size))
-
-
-class LstmLocalRecurrence(torch.autograd.Function):
-    """One nn.LSTM layer (h0 = c0 = 0) with its recurrence on the kernels of csrc/lstm_local.hip: one workgroup owns every
-    unit of its columns, so the launches take neither workspace nor status word and admit every batch width.  The
-    projection in front and the gradients behind are `LstmRecurrence`'s (`_rnn_proj`, `_lstm_grads_from_dgates`).
-    `lens` (a device int32 tensor, one entry per column, or None): column n has lens[n] steps; y, the gates, c and dG
-    are 0 at and beyond every length.  `save` False hands NULL for the activations: they are neither allocated nor
-    written, and the call cannot be differentiated."""
-
-    @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, lens, save):
-        T, N, _ = x.shape
-        H = w_hh.shape[1]
-        dev = x.device
-        x = x.contiguous()
-        w_hh = w_hh.contiguous()
-        lstm_local_calls["saved" if save else "inference"] += 1
-        gx = _rnn_proj(x.view(T * N, -1), w_ih, b_ih + b_hh, False)
-        y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
-        gates = torch.empty(T, N, 4 * H, dtype=torch.float32, device=dev) if save else None
-        cell = torch.empty(T, N, H, dtype=torch.float32, device=dev) if save else None
-        rc = _lib.lstm_local_lib().tk_lstm_local_forward_dev(
-            _lib.ptr(gx), _lib.ptr(w_hh), _lib.ptr(lens), T, N, H, int(reverse), _cu_count(dev), _lib.ptr(y),
-            _lib.ptr(gates), _lib.ptr(cell), _lib.stream_ptr())
-        _lib.check(rc, "tk_lstm_local_forward_dev")
-        if save:
-            ctx.save_for_backward(x, w_ih, w_hh, y, gates, cell, lens)
-        ctx.reverse = reverse
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w_ih, w_hh, y, gates, cell, lens = ctx.saved_tensors
-        T, N, _ = x.shape
-        H = w_hh.shape[1]
-        dev = x.device
-        dy = _aligned(dy)
-        dg = torch.empty_like(gates)
-        rc = _lib.lstm_local_lib().tk_lstm_local_backward_dev(
-            _lib.ptr(w_hh), _lib.ptr(gates), _lib.ptr(cell), _lib.ptr(dy), _lib.ptr(lens), T, N, H, int(ctx.reverse),
-            _cu_count(dev), _lib.ptr(dg), _lib.stream_ptr())
-        _lib.check(rc, "tk_lstm_local_backward_dev")
-        return _lstm_grads_from_dgates(dg, x, w_ih, w_hh, y, ctx.reverse, ctx.needs_input_grad) + (None,) * 3
-
-
 class Lstm(_Rnn):
     """layers.py:491-606 (wraps nn.LSTM, bias_hh frozen).  On the GPU the recurrence runs on the HIP kernels
-    (`LstmRecurrence`), a batch wider than one launch admits as slabs of columns, size 96, which those kernels do not
-    cover, on `LstmLocalRecurrence`, and size 512 on the entries of include/taiyaki_amd_lstm_large.h; nn.LSTM evaluates CPU tensors, sizes no kernel covers, and USE_HIP_LSTM = False."""
+    (`LstmRecurrence`) of the first library that `_rnn_route` finds to admit the call; nn.LSTM evaluates CPU tensors,
+    sizes no kernel covers, and USE_HIP_LSTM = False."""
 
     def __init__(self, insize, size):
         super().__init__(nn.LSTM(insize, size))
-
-    def forward(self, x, reverse=False, lengths=None):
-        if lengths is not None:
-            return _rnn_forward_varlen(self, x, reverse, lengths)
-        rnn = self.rnn
-        wsb = hip_lstm_workspace_bytes(rnn, x)
-        if wsb:
-            return LstmRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
-                                        bool(reverse), wsb)
-        wsb = hip_rnn_wide_workspace_bytes(rnn, x) if x.dim() == 3 and x.shape[0] and x.shape[1] else 0
-        if wsb:     # a batch wider than one launch admits: slabs of columns (the activations saved, as above)
-            return LstmRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
-                                        bool(reverse), wsb, None, True, True)
-        if hip_lstm_local_takes(rnn, x):        # a size one workgroup holds: no workspace, any batch width
-            return LstmLocalRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
-                                             bool(reverse), None, _needs_grad(x, self))
-        wsb = hip_lstm_large_workspace_bytes(rnn, x)
-        if wsb:     # size 512: a library of its own, any batch width; nothing saved where nothing needs a gradient
-            return LstmRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
-                                        bool(reverse), wsb, None, _needs_grad(x, self), "large")
-        if reverse:
-            return torch.flip(rnn(torch.flip(x, (0,)))[0], (0,))
-        return rnn(x)[0]
 
 
 # False: every GruMod runs nn.GRU (MIOpen on the GPU), for comparisons against the HIP recurrence
@@ -942,10 +930,10 @@ class GruRecurrence(torch.autograd.Function):
     `lens` (a device int32 tensor, one entry per column): column n has lens[n] steps, and the launches are those of
     include/taiyaki_amd_rnn_varlen_train.h (`save`) or include/taiyaki_amd_rnn_varlen.h (not `save`).  y, the
     activations, q, dG and dq are 0 at and beyond every length, so the input and parameter gradients are the same sums
-    over the whole padded tensors."""
+    over the whole padded tensors.  `row` and `wsb` are what `_rnn_route` chose, as for `LstmRecurrence`."""
 
     @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, wsb, save, lens=None, wide=False):
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, row, wsb, lens, save):
         T, N, _ = x.shape
         H = w_hh.shape[1]
         dev = x.device
@@ -953,19 +941,16 @@ class GruRecurrence(torch.autograd.Function):
         w_hh, b_hh = w_hh.contiguous(), b_hh.contiguous()
         # (grad mode is off inside forward and ctx.needs_input_grad ignores it: the caller decides)
         train = bool(save)
-        if wide:
-            rnn_wide_calls["saved" if train else "inference"] += 1
-        elif lens is not None:
-            rnn_varlen_calls["saved" if train else "inference"] += 1
+        if row in _RNN_CALLS:
+            _RNN_CALLS[row]["saved" if train else "inference"] += 1
         if lens is None or train:
             gru_forward_calls["saved" if train else "inference"] += 1
-        row = _rnn_row(lens, wide)
         gx = _rnn_proj(x.view(T * N, -1), w_ih, b_ih, False)
         y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
         gates = torch.empty(T, N, 3 * H, dtype=torch.float32, device=dev) if train else None
         q = torch.empty(T, N, H, dtype=torch.float32, device=dev) if train else None
         _rnn_launch("gru", row, lens, train, False, (gx, w_hh, b_hh), (T, N, H), reverse,
-                    (y, gates, q) if train or lens is None or wide else (y,), wsb, dev)
+                    (y,) if row is True and not train else (y, gates, q), wsb, dev)
         if train:
             ctx.save_for_backward(x, w_ih, w_hh, y, gates, q, lens)
         ctx.reverse, ctx.wsb, ctx.row = reverse, wsb, row
@@ -1033,29 +1018,11 @@ def _gru_grads_from_dgates(dg, dq, x, w_ih, w_hh, y, reverse, need):
 
 class GruMod(_Rnn):
     """layers.py:609-725 (wraps nn.GRU, bias_hh frozen).  On the GPU the recurrence runs on the HIP kernels
-    (`GruRecurrence`), a batch wider than one launch admits as slabs of columns; nn.GRU evaluates CPU tensors, sizes the
-    kernels do not cover, and USE_HIP_GRU = False."""
+    (`GruRecurrence`) of the first library that `_rnn_route` finds to admit the call; nn.GRU evaluates CPU tensors, sizes
+    the kernels do not cover, and USE_HIP_GRU = False."""
 
     def __init__(self, insize, size):
         super().__init__(nn.GRU(insize, size))
-
-    def forward(self, x, reverse=False, lengths=None):
-        if lengths is not None:
-            return _rnn_forward_varlen(self, x, reverse, lengths)
-        rnn = self.rnn
-        wsb = hip_gru_workspace_bytes(rnn, x)
-        if wsb:
-            params = (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)
-            save = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-            return GruRecurrence.apply(x, *params, bool(reverse), wsb, save)
-        wsb = hip_rnn_wide_workspace_bytes(rnn, x) if x.dim() == 3 and x.shape[0] and x.shape[1] else 0
-        if wsb:     # a batch wider than one launch admits: slabs of columns
-            params = (rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0)
-            save = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
-            return GruRecurrence.apply(x, *params, bool(reverse), wsb, save, None, True)
-        if reverse:
-            return torch.flip(rnn(torch.flip(x, (0,)))[0], (0,))
-        return rnn(x)[0]
 
 
 def _rnn_varlen_workspace_bytes(rnn, x, train):
@@ -1091,40 +1058,21 @@ def _rnn_forward_varlen(layer, x, reverse, lengths):
     tensors, `LstmRecurrence` / `GruRecurrence` with the lengths: under grad mode with something that requires a
     gradient they save the activations (x must be finite in the padding: the parameter gradients are sums over the
     whole padded tensors); otherwise it is one launch of tk_lstm_forward_varlen_dev / tk_gru_forward_varlen_dev, which
-    saves nothing.  An LSTM at a size one workgroup holds (96) makes the launch of `LstmLocalRecurrence` with the lengths
-    instead.  Every column alone at its own length otherwise (differentiable like any other call of the layer).
+    saves nothing.  The libraries behind those two in the order of `_rnn_route` take the lengths as well.  Every column
+    alone at its own length otherwise (differentiable like any other call of the layer).
     Under grad mode the call needs
     layers.TRAIN_VARLEN = True; without it it raises, as it did before there was a backward with lengths."""
-    rnn = layer.rnn
     T, N, _ = x.shape
-    H = rnn.hidden_size
     train = _needs_grad(x, layer)
     if train and not TRAIN_VARLEN:
         raise RuntimeError("%s.forward with lengths is inference only unless layers.TRAIN_VARLEN is set: call it under "
                            "torch.no_grad(), or set layers.TRAIN_VARLEN = True to train through variable-length "
                            "batches" % type(layer).__name__)
-    if not (T and N):
-        wsb = 0
-    elif train:
-        wsb = hip_rnn_varlen_train_workspace_bytes(rnn, x)
-    else:
-        wsb = hip_rnn_varlen_workspace_bytes(rnn, x)
-    wide = bool(T and N) and not wsb
-    if wide:        # a batch wider than one launch admits: slabs of columns
-        wsb = hip_rnn_wide_workspace_bytes(rnn, x)
-    if not wsb and isinstance(rnn, nn.LSTM) and hip_lstm_local_takes(rnn, x):
-        with torch.cuda.device(x.device):
-            lens = torch.as_tensor(lengths).to(device=x.device, dtype=torch.int32).reshape(-1).clamp(0, T).contiguous()
-            assert lens.numel() == N, "lengths: one per column"
-            return LstmLocalRecurrence.apply(x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0,
-                                             bool(reverse), lens, train)
-    if not wsb and isinstance(rnn, nn.LSTM):        # size 512: the entries of include/taiyaki_amd_lstm_large.h
-        wsb = hip_lstm_large_workspace_bytes(rnn, x)
-        wide = "large" if wsb else wide
-    if not wsb:
+    route = _rnn_route(layer, x, True, train)
+    if not route:
         host = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths, dtype=np.int64).reshape(-1)
         assert len(host) == N and (N == 0 or (host.min() >= 0 and host.max() <= T)), "lengths: one per column, 0..T"
-        y = x.new_zeros(T, N, H)
+        y = x.new_zeros(T, N, layer.rnn.hidden_size)
         for n, ln in enumerate(host):
             if ln:
                 y[:ln, n:n + 1] = layer(x[:ln, n:n + 1], reverse=reverse)
@@ -1132,10 +1080,7 @@ def _rnn_forward_varlen(layer, x, reverse, lengths):
     with torch.cuda.device(x.device):
         lens = torch.as_tensor(lengths).to(device=x.device, dtype=torch.int32).reshape(-1).clamp(0, T).contiguous()
         assert lens.numel() == N, "lengths: one per column"
-        args = (x, rnn.weight_ih_l0, rnn.weight_hh_l0, rnn.bias_ih_l0, rnn.bias_hh_l0, bool(reverse), wsb)
-        if isinstance(rnn, nn.LSTM):
-            return LstmRecurrence.apply(*args, lens, train, wide)
-        return GruRecurrence.apply(*args, train, lens, wide)
+        return _rnn_apply(layer, x, reverse, *route, lens, train)
 
 
 class Reverse(nn.Module):

@@ -1,5 +1,5 @@
 """The LSTM recurrence at hidden size 512 (include/taiyaki_amd_lstm_large.h; csrc/lstm_kernels.hip built -DTK_LSTM_LARGE;
-layers.LstmRecurrence with wide = "large").
+layers.LstmRecurrence with row = "large").
 
 An instantiation is (512, 32, C), named by the library's own plan (tk_lab_lstm_large_geometry) and never only by shape:
 C = 4 at N = 7 * 4 + 1 = 29 (eight groups, the last ragged), C = 8 at one column more than C = 4 admits (65 on 256 CUs).

@@ -1,5 +1,5 @@
-"""The LSTM recurrence at hidden size 96 (include/taiyaki_amd_lstm_local.h, csrc/lstm_local.hip, layers.LstmLocalRecurrence):
-one workgroup owns every unit of its columns.  Against nn.LSTM in float64 by the rule of tests/test_lstm_hip.py, and bit
+"""The LSTM recurrence at hidden size 96 (include/taiyaki_amd_lstm_local.h, csrc/lstm_local.hip, layers.LstmRecurrence on
+the "local" rows of layers._RNN_LAUNCHES): one workgroup owns every unit of its columns.  Against nn.LSTM in float64 by the rule of tests/test_lstm_hip.py, and bit
 for bit across batch widths, columns per workgroup and per-column lengths."""
 import copy
 import ctypes
