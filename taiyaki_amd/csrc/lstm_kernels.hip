@@ -99,6 +99,30 @@ __device__ __forceinline__ void halve_rounds(float (&acc)[NA], int rq) {
     }
 }
 
+// Two floats in one aligned 64-bit register pair, and the matvec's fused multiply-add on both halves at once.  At C 2 the
+// two batch columns of a group are the halves: acc(c0, c1) += w * d(c0, c1), one v_pk_fma_f32 where two v_fma_f32 stood.
+// Each half rounds as fmaf does and no sum changes its operands or their order, so every bit stays.  The weight is one
+// half of a pair of two consecutive weights, broadcast to both halves of the product by the instruction's op_sel bits:
+// pk_fma_lo takes w[0], pk_fma_hi w[1].  Written as asm, one statement per instruction, because a splat of the weight
+// (__builtin_elementwise_fma) costs a register pair per weight, which 128 weights per lane do not have; not volatile, so
+// the compiler schedules them and places the waits for the LDS reads as for plain FMAs.  The backward's block path at C 2
+// takes it (0.09 us per step); the forward at (256, 64, 2) gave the same bits 0.48 us per step slower and keeps its plain
+// FMAs (DESIGN.md "Packed-FMA matvec", profiles/r50_lstm_packed.txt).
+typedef float pair2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void pk_fma_lo(pair2 &acc, pair2 w, pair2 h) {
+    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(acc) : "v"(w), "v"(h));
+}
+__device__ __forceinline__ void pk_fma_hi(pair2 &acc, pair2 w, pair2 h) {
+    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(w), "v"(h));
+}
+// (as settle, rnn_common.h: the pairs formed once, in front of the step loop, and kept as pairs)
+template <int M>
+__device__ __forceinline__ void settle_pairs(pair2 (&v)[M]) {
+#pragma unroll
+    for (int i = 0; i < M; ++i) asm volatile("" : "+v"(v[i]));
+}
+
 // The forward at H 256, U 64, C 2 (lstm_fwd_kernel below has the contract, the schedule of a step and the VL and SAVE
 // forms; lstm_fwd_layout.h the arithmetic of this layout and the order of every sum, which is that of the plain body).
 // Written over CK = C / 2 columns per lane; at C 4 (CK 2) it gives the plain body's bits too but measured slower than
@@ -661,6 +685,16 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
         }
     }
     settle(w);
+    // PACKED (BLOCK at C 2): the matvec as packed FMAs over the two columns (pk_fma_lo above).  wq[q RR / 2 + i] =
+    // {w[q RR + 2 i], w[q RR + 2 i + 1]}, column KQ kb + q of the row pair i, one register pair for the whole launch; w is
+    // not read behind this
+    constexpr bool PACKED = BLOCK && C == 2;
+    pair2 wq[PACKED ? R / 2 : 1];
+    if constexpr (PACKED) {
+#pragma unroll
+        for (int m = 0; m < R / 2; ++m) wq[m] = pair2{w[2 * m], w[2 * m + 1]};
+        settle_pairs(wq);
+    }
 
     const bool cell_lane = tid < PAIRS;
     const int pair = tid % PAIRS, plane = tid / PAIRS;
@@ -815,17 +849,34 @@ __global__ __launch_bounds__((bwd_threads_for<H, U>()), 1) void lstm_bwd_kernel(
             float acc[KQ * C];
 #pragma unroll
             for (int a = 0; a < KQ * C; ++a) acc[a] = 0.f;
+            pair2 accp[KQ];                               // PACKED: one per column k of the lane, the halves the two batch columns
+#pragma unroll
+            for (int q = 0; q < KQ; ++q) accp[q] = pair2{0.f, 0.f};
 #pragma unroll
             for (int i = 0; i < RR / 2; ++i) {
                 float d[2 * C];                           // rows 2 p and 2 p + 1 of the pair p = rq + RQ i
                 lds_row<2 * C>(dgs + (rq + RQ * i) * 2 * C, d);
+                if constexpr (PACKED) {
+                    const pair2 d0 = {d[0], d[1]}, d1 = {d[2], d[3]};        // the read's two aligned halves: a row each
 #pragma unroll
-                for (int e = 0; e < 2; ++e)
+                    for (int q = 0; q < KQ; ++q) pk_fma_lo(accp[q], wq[q * RR / 2 + i], d0);
 #pragma unroll
-                    for (int q = 0; q < KQ; ++q)
+                    for (int q = 0; q < KQ; ++q) pk_fma_hi(accp[q], wq[q * RR / 2 + i], d1);
+                } else {
 #pragma unroll
-                        for (int c = 0; c < C; ++c)
-                            acc[q * C + c] = fmaf(w[q * RR + 2 * i + e], d[e * C + c], acc[q * C + c]);
+                    for (int e = 0; e < 2; ++e)
+#pragma unroll
+                        for (int q = 0; q < KQ; ++q)
+#pragma unroll
+                            for (int c = 0; c < C; ++c)
+                                acc[q * C + c] = fmaf(w[q * RR + 2 * i + e], d[e * C + c], acc[q * C + c]);
+                }
+            }
+            if constexpr (PACKED) {
+#pragma unroll
+                for (int q = 0; q < KQ; ++q)
+#pragma unroll
+                    for (int c = 0; c < C; ++c) acc[q * C + c] = accp[q][c];
             }
             halve_rounds<1, RQ>(acc, rq);
 #pragma unroll
