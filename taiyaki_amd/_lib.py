@@ -74,6 +74,8 @@ DECODE_VARLEN_LIBNAME = "libtaiyaki_amd_decode_varlen.so"   # csrc/decode_varlen
 
 LOSS_VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_loss_varlen.h")
 LOSS_VARLEN_LIBNAME = "libtaiyaki_amd_loss_varlen.so"       # csrc/crf_band.hip, crf_kernels.hip built -DTK_LOSS_VARLEN: the loss with a time length per column
+LOGZ_VARLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_logz_varlen.h")
+LOGZ_VARLEN_LIBNAME = "libtaiyaki_amd_logz_varlen.so"       # csrc/logz_kernels.hip built -DTK_LOGZ_VARLEN: the log-partition with a time length per column on the transfer-matrix kernels
 
 _vp = ctypes.c_void_p
 _SCALARS = {"size_t": ctypes.c_size_t, "int": ctypes.c_int, "float": ctypes.c_float}
@@ -223,6 +225,9 @@ def _read_optim_header():
 OPTIM_SIGNATURES, OPTIM_DEFINES = _read_optim_header()
 # the twenty-second: include/taiyaki_amd_lstm_large.h (libtaiyaki_amd_lstm_large.so), and the hooks its lab build adds
 LSTM_LARGE_SIGNATURES, LSTM_LARGE_LAB_SIGNATURES = _read_wgrad_header(LSTM_LARGE_HEADER)
+# the twenty-third: include/taiyaki_amd_logz_varlen.h (libtaiyaki_amd_logz_varlen.so)
+LOGZ_VARLEN_SIGNATURES = {n: (r, a) for n, (r, a, _) in
+                          parse_prototypes(_blank_comments(open(LOGZ_VARLEN_HEADER).read())).items()}
 
 
 class SeqLabels(ctypes.Structure):
@@ -443,6 +448,13 @@ def loss_varlen_lib():
     """The flip-flop loss with a time length per column (include/taiyaki_amd_loss_varlen.h): loaded by the first call that
     brings lengths.  No fallback: a missing library raises."""
     return _load(os.path.join(CSRC, LOSS_VARLEN_LIBNAME), LOSS_VARLEN_SIGNATURES)
+
+
+def logz_varlen_lib():
+    """The log-partition with a time length per column on the transfer-matrix kernels, and the fused loss on it
+    (include/taiyaki_amd_logz_varlen.h): loaded by the first call that brings lengths with layers.USE_HIP_LOGZ_VARLEN on.
+    No fallback: a missing library raises."""
+    return _load(os.path.join(CSRC, LOGZ_VARLEN_LIBNAME), LOGZ_VARLEN_SIGNATURES)
 
 
 def check(rc, what):

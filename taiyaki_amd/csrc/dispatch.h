@@ -212,6 +212,15 @@ bool crf_lab_plan(size_t ntrans, size_t nblk, size_t nbatch, size_t max_seqlen, 
                   float sharp, size_t workspace_bytes, size_t *out);
 #endif
 
+// logz_kernels.hip built -DTK_LOGZ_VARLEN (libtaiyaki_amd_logz_varlen.so; logz_varlen_api.hip defines the C entries): the
+// log-partition with a length per column (LogzWs::lengths, the kernels' VL = true instantiations); `supported`: whether
+// the launcher takes the shape (false: too many chunks for the middle kernel's LDS image)
+#ifdef TK_LOGZ_VARLEN
+bool logz_varlen_supported(size_t T, size_t N, size_t nbase);
+int logz_varlen_dispatch(const float *scores, const int32_t *lengths, size_t T, size_t N, size_t nbase, float *logz,
+                         float *grad, void *workspace, size_t workspace_bytes, uint32_t *status, hipStream_t stream);
+#endif
+
 #ifdef TK_LAB
 // what the lab hooks below set (crf_band.hip, lstm_kernels.hip, gru_kernels.hip)
 void crf_band_lab_phase(int phase);

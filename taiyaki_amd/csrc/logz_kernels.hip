@@ -194,7 +194,49 @@ struct LogzWs {
     // reads in the whole tensor: the row stride.  (A launch may cover a sub-range of the reads --
     // every pointer then starts at its first read -- see logz_launch.)
     int nstride;
+#ifdef TK_LOGZ_VARLEN
+    // rows per column, (N) or null (libtaiyaki_amd_logz_varlen.so): column n has T_n = clamp(lengths[n], 0, T) rows
+    const int32_t *lengths;
+#endif
 };
+
+// The kernels' VL parameter: a length per column.  The -DTK_LOGZ_VARLEN build instantiates VL = true alone, every other
+// build VL = false alone (their instruction streams are what they were before there was the parameter).
+#ifdef TK_LOGZ_VARLEN
+constexpr bool LOGZ_VL = true;
+#else
+constexpr bool LOGZ_VL = false;
+#endif
+
+// T_n of the lane's column n (a lane past the batch: 0 rows), and the maximum over the wave's 64 columns as a scalar:
+// what a wave loads up to, and beyond which it has nothing to do
+template <bool VL>
+__device__ __forceinline__ int logz_len(const LogzWs &ws, int n, int N, int T) {
+#ifdef TK_LOGZ_VARLEN
+    if constexpr (VL) {
+        if (n >= N) return 0;
+        return ws.lengths != nullptr ? min(max(ws.lengths[n], 0), T) : T;
+    }
+#endif
+    return T;
+}
+__device__ __forceinline__ int wave_max_len(int x) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) x = max(x, __shfl_xor(x, m, WAVE));
+    return __builtin_amdgcn_readfirstlane(x);
+}
+// the row a wave stops at: `end`, or with lengths the longest of its columns where that comes first
+template <bool VL>
+__device__ __forceinline__ int logz_rows_end(int end, int Tn) {
+    if constexpr (VL) return min(end, wave_max_len(Tn));
+    else return end;
+}
+// word k of the image of a chunk without rows: unit matrix, exponents 0, M = 0
+template <int NB>
+__device__ __forceinline__ float xmat_identity_word(int k) {
+    constexpr int NS = 2 * NB;
+    return (k < NS * NS && k / NS == k % NS) ? 1.f : 0.f;
+}
 
 // per-wave LDS buffer of K3 in f4 units: the row-set transpose buffer, which
 // doubles as storage for the wave's K3_ROWS forward vectors
@@ -229,7 +271,12 @@ __host__ __device__ constexpr bool k3_chain_in_buf() {
 typedef __attribute__((address_space(3))) void tk_lds_void;
 typedef const __attribute__((address_space(1))) void tk_global_void;
 
-template <int NB, int CH, int RING, bool NT>
+// VL: a lane folds row t into its matrix only where t < T_n -- a select that keeps the old matrix, never a masked weight,
+// so nothing beyond a column's length reaches it; inside its length a lane's steps and renormalisations are the ones
+// above.  The wave stops loading at the longest of its 64 columns, and a chunk at or beyond that loads nothing and
+// writes the identity image -- which is also what a lane whose own column ended before the chunk writes, so a column's
+// matrices do not depend on its neighbours' lengths.
+template <int NB, int CH, int RING, bool NT, bool VL = false>
 __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_kernel(
     const float *__restrict__ scores, int T, int N, int C, int Npad, LogzWs ws) {
     using F = FF<NB>;
@@ -245,9 +292,25 @@ __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_kernel(
     f4 *buf = reinterpret_cast<f4 *>(img);
     const int n0 = blockIdx.x * WAVE;
     const int nvalid = min(WAVE, N - n0) * F::PIECES;
-    const int t0 = c * CH, t1 = min(T, t0 + CH);
+    const int Tn = logz_len<VL>(ws, n0 + lane, N, T);
+    const int t0 = c * CH, t1 = logz_rows_end<VL>(min(T, t0 + CH), Tn);
     const size_t rowstride = (size_t)ws.nstride * F::S;
     const float *base = scores + (size_t)n0 * F::S;
+    if constexpr (VL) {
+        if (t1 <= t0) {                         // wave-uniform: every column of the wave ended before this chunk
+            f4 *dst = ws.Pc + ((size_t)n0 * C + c) * X::NF4;
+#pragma unroll
+            for (int k = 0; k < X::NF4; ++k) {      // (the layout of the store at the end of the kernel)
+                const int p = lane + k * WAVE;
+                const int r = p / X::NF4, q = p - r * X::NF4;
+                f4 o;
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) o[kk] = xmat_identity_word<NB>(4 * q + kk);
+                dst[(size_t)r * C * X::NF4 + q] = o;
+            }
+            return;
+        }
+    }
 
     // The running product is kept as PAIRS OF ROWS (Pp[ip][j] = rows 2ip, 2ip+1 at column
     // j): both rows of a pair take the same step, so every multiply-add is one
@@ -271,7 +334,8 @@ __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_kernel(
                 float mx = A[ip][0][h];
 #pragma unroll
                 for (int j = 1; j < NS; ++j) mx = fmaxf(mx, A[ip][j][h]);
-                shrunk |= mx < 0x1p-60f;
+                if constexpr (VL) shrunk |= mx < 0x1p-60f && Tn > t0;      // (a lane beyond its length takes no part)
+                else shrunk |= mx < 0x1p-60f;
                 if (mx > 0.f) {
                     const int ex = __builtin_amdgcn_frexp_expf(mx);
 #pragma unroll
@@ -307,6 +371,16 @@ __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_kernel(
 #pragma unroll
             for (int ip = 0; ip < NP; ++ip)
                 B[ip][NB + b] = __builtin_elementwise_fma(A[ip][b], f2{wf, wf}, A[ip][NB + b] * f2{wst, wst});
+        }
+    };
+    // (VL) B = the step's result where row t is the lane's own, A as it was elsewhere
+    auto keep = [&](const f2 (&A)[NP][NS], f2 (&B)[NP][NS], int t) {
+        if constexpr (VL) {
+            const bool on = t < Tn;
+#pragma unroll
+            for (int ip = 0; ip < NP; ++ip)
+#pragma unroll
+                for (int j = 0; j < NS; ++j) B[ip][j] = f2{on ? B[ip][j][0] : A[ip][j][0], on ? B[ip][j][1] : A[ip][j][1]};
         }
     };
     pM = 0.0;
@@ -349,11 +423,13 @@ __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_kernel(
         for (int t = t0; t < t1; t += 2) {
             landed(t);
             take(r0, slot);
-            pM += (double)r0.exp_normalise();           // every piece of the slot is in registers now
+            if constexpr (VL) { const float mx = r0.exp_normalise(); pM = t < Tn ? pM + (double)mx : pM; }
+            else pM += (double)r0.exp_normalise();            // every piece of the slot is in registers now
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (t + RING < t1) issue(slot, t + RING);
             slot = (slot + 1 == RING) ? 0 : slot + 1;
             step(Pp, Pq, r0);
+            keep(Pp, Pq, t);
             if (t == t0) TK_STAMP(9);
             if (t + 1 >= t1) {              // odd tail: the product sits in the other set
 #pragma unroll
@@ -364,11 +440,13 @@ __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_kernel(
             }
             landed(t + 1);
             take(r1, slot);
-            pM += (double)r1.exp_normalise();
+            if constexpr (VL) { const float mx = r1.exp_normalise(); pM = t + 1 < Tn ? pM + (double)mx : pM; }
+            else pM += (double)r1.exp_normalise();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (t + 1 + RING < t1) issue(slot, t + 1 + RING);
             slot = (slot + 1 == RING) ? 0 : slot + 1;
             step(Pq, Pp, r1);
+            keep(Pq, Pp, t + 1);
             if (((t - t0) & 3) == 2) renorm(Pp);
             if (t == t0 + 8) TK_STAMP(10);
         }
@@ -385,8 +463,10 @@ __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_kernel(
         for (int t = t0; t < t1; t += 2) {
             fetch(r1, t + 1);
             r0.to_rows(buf, lane);
-            pM += (double)r0.exp_normalise();
+            if constexpr (VL) { const float mx = r0.exp_normalise(); pM = t < Tn ? pM + (double)mx : pM; }
+            else pM += (double)r0.exp_normalise();
             step(Pp, Pq, r0);
+            keep(Pp, Pq, t);
             if (t == t0) TK_STAMP(9);
             if (t + 1 >= t1) {              // odd tail: the product sits in the other set
 #pragma unroll
@@ -397,8 +477,10 @@ __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_kernel(
             }
             fetch(r0, t + 2);
             r1.to_rows(buf, lane);
-            pM += (double)r1.exp_normalise();
+            if constexpr (VL) { const float mx = r1.exp_normalise(); pM = t + 1 < Tn ? pM + (double)mx : pM; }
+            else pM += (double)r1.exp_normalise();
             step(Pq, Pp, r1);
+            keep(Pq, Pp, t + 1);
             if (((t - t0) & 3) == 2) renorm(Pp);
             if (t == t0 + 8) TK_STAMP(10);
         }
@@ -422,17 +504,23 @@ __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_kernel(
         for (int t = t0; t < t1; ++t) {
             r.issue(rowptr(t), nvalid, lane);
             r.to_rows(buf, lane);
-            P.M += (double)r.exp_normalise();
+            if constexpr (VL) { const float mx = r.exp_normalise(); P.M = t < Tn ? P.M + (double)mx : P.M; }
+            else P.M += (double)r.exp_normalise();
 #pragma unroll
             for (int i = 0; i < NS; ++i) {
                 float out[NS];
                 ff_fwd_step<NB>(P.m[i], r, out);
 #pragma unroll
-                for (int j = 0; j < NS; ++j) P.m[i][j] = out[j];
+                for (int j = 0; j < NS; ++j) {
+                    if constexpr (VL) P.m[i][j] = t < Tn ? out[j] : P.m[i][j];
+                    else P.m[i][j] = out[j];
+                }
             }
-            P.renorm();
+            P.renorm();         // (VL: idempotent on a matrix that took no step)
         }
     }
+    if constexpr (VL)
+        if (Tn <= t0) P.set_identity();         // this lane's column ended before the chunk: the identity image
     // Pc is READ-major ([read][chunk][NF4] float4): the middle kernel streams one
     // read's matrices as a single contiguous run (a [chunk][q][read] layout put
     // all of a read's pieces 16*Npad bytes apart = on ONE L2 channel).  The wave turns
@@ -468,7 +556,10 @@ __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_kernel(
 // small tensor has no other way to put more than C * ncols waves on the chip.
 // grid = (ncols, C), block = 256 = one chunk.
 // ---------------------------------------------------------------------------
-template <int NB, int CH>
+// VL: the four partial folds are predicated as the one-wave form's steps are (a lane beyond its length keeps its partial
+// matrix; a wave loads up to the longest of the 64 columns); a block at or beyond that maximum loads nothing and
+// writes the identity image, which is also what a lane whose own column ended before the chunk writes.
+template <int NB, int CH, bool VL = false>
 __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_coop_kernel(
     const float *__restrict__ scores, int T, int N, int C, int Npad, LogzWs ws) {
     using F = FF<NB>;
@@ -480,9 +571,25 @@ __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_coop_kernel(
     const int n0 = blockIdx.x * WAVE;
     const int nvalid = min(WAVE, N - n0) * F::PIECES;
     constexpr int K1_ROWS = CH / K1_WAVES;
-    const int t0 = c * CH + wave * K1_ROWS, t1 = min(T, t0 + K1_ROWS);
+    const int Tn = logz_len<VL>(ws, n0 + lane, N, T);
+    const int Tmax = VL ? wave_max_len(Tn) : T;         // (the four waves hold the same 64 columns: block-uniform)
+    const int t0 = c * CH + wave * K1_ROWS, t1 = min(min(T, Tmax), t0 + K1_ROWS);
     const size_t rowstride = (size_t)ws.nstride * F::S;
     const float *base = scores + (size_t)n0 * F::S;
+    if constexpr (VL) {
+        if (Tmax <= c * CH) {                           // before any barrier, all four waves
+            f4 *dst = ws.Pc + ((size_t)n0 * C + c) * X::NF4;
+            for (int p = threadIdx.x; p < WAVE * X::NF4; p += K1_WAVES * WAVE) {
+                const int r = p / X::NF4, q = p - r * X::NF4;
+                f4 o;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) o[k] = xmat_identity_word<NB>(4 * q + k);
+                dst[(size_t)r * C * X::NF4 + q] = o;
+            }
+            return;
+        }
+    }
+    const bool dead = VL && Tn <= c * CH;               // this lane's column ended before the chunk
 
     X P;
     P.set_identity();
@@ -494,15 +601,18 @@ __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_coop_kernel(
         auto rowptr = [&](int t) { return base + (size_t)min(t, t1 - 1) * rowstride; };
         auto consume = [&](RowSet<NB> &cur, int t) {
             cur.to_rows(buf, lane);
-            P.M += (double)cur.exp_normalise();
+            const float mx = cur.exp_normalise();
+            if (!VL || t < Tn) {        // (VL: a lane beyond its length keeps its partial matrix, untouched)
+                P.M += (double)mx;
 #pragma unroll
-            for (int i = 0; i < F::NS; ++i) {
-                float out[F::NS];
-                ff_fwd_step<NB>(P.m[i], cur, out);
+                for (int i = 0; i < F::NS; ++i) {
+                    float out[F::NS];
+                    ff_fwd_step<NB>(P.m[i], cur, out);
 #pragma unroll
-                for (int j = 0; j < F::NS; ++j) P.m[i][j] = out[j];
+                    for (int j = 0; j < F::NS; ++j) P.m[i][j] = out[j];
+                }
+                P.renorm();         // every step: this form serves small problems, the cost is noise
             }
-            P.renorm();         // every step: this form serves small problems, the cost is noise
         };
         auto fetch = [&](RowSet<NB> &r, int t) {
             if (TK_K1_NT_LOAD) r.issue_nt(rowptr(t), nvalid, lane);
@@ -554,9 +664,15 @@ __global__ __launch_bounds__(K1_WAVES *WAVE, 2) void logz_transfer_coop_kernel(
             rexp[q] = (zero_row || !(mx > 0.f)) ? ZERO_ROW_EXP : (int)eacc;
 #pragma unroll
             for (int k = 0; k < F::NS; ++k) rows[q][k] = v[k];
+            if (dead) {                 // the identity image: unit matrix, exponents 0
+                rexp[q] = 0;
+#pragma unroll
+                for (int k = 0; k < F::NS; ++k) rows[q][k] = (k == r) ? 1.f : 0.f;
+            }
         }
     }
     if (wave == 0) msum += P.M;         // M of P0 (each wave added P1..P3 once)
+    if (dead) msum = 0.0;
     __syncthreads();                    // all reads of `mats` done
     // assemble the chunk matrix in LDS in OUTPUT order: float4 number r * NF4 + q is piece q
     // of read r, so the store below is a linear, conflict-free ds_read_b128 (a [word][read]
@@ -973,11 +1089,16 @@ __global__ __launch_bounds__(K2_WAVES *WAVE, 8) void logz_middle_kernel(int N, i
 // between the waves through LDS; posteriors overwrite the rows in place and
 // are streamed out through the same coalescing transpose.
 // ---------------------------------------------------------------------------
-template <int NB, int CH, bool ACC = false>
+// VL: row j of a wave is LIVE in a lane where tw + j < T_n.  The two chains and the posterior take a step only in live
+// lanes (selects: a NaN beyond a length reaches nothing), a row that is not live is stored as exactly 0 and sets no
+// status bit.  A block whose chunk lies at or beyond the longest of its 64 columns loads nothing -- neither scores nor
+// its chain heads --, stores zeros for its rows and leaves.
+template <int NB, int CH, bool ACC = false, bool VL = false>
 __global__ __launch_bounds__(K3_WAVES *WAVE, (CH / K3_WAVES <= 2 ? 4 : 2)) void logz_posterior_kernel(
     const float *__restrict__ scores, float *__restrict__ grad, int T, int N, int Npad,
     LogzWs ws, uint32_t *__restrict__ status, int nt_load) {
     // ACC: add acc_scale * posterior to the gradient kernel A left in `grad` (fused loss)
+    static_assert(!(VL && ACC), "the accumulating form has no lengths");
     using F = FF<NB>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wave = threadIdx.x >> 6, lane = lane_id();
@@ -1015,6 +1136,23 @@ __global__ __launch_bounds__(K3_WAVES *WAVE, (CH / K3_WAVES <= 2 ? 4 : 2)) void 
     const float acc_g = ACC ? ws.acc_scale * ws.grad_scale *
                                   (ws.grad_scale_vec != nullptr ? ws.grad_scale_vec[min((int)n, N - 1)] : 1.0f)
                             : 1.0f;
+    const int Tn = logz_len<VL>(ws, n0 + lane, N, T);
+    const int Tld = VL ? min(T, wave_max_len(Tn)) : T;  // rows anyone in the block reads (the eight waves hold the same columns)
+    if constexpr (VL) {
+        if (Tld <= c * CH) {                            // block-uniform, before any barrier
+            RowSet<NB> z;
+#pragma unroll
+            for (int q = 0; q < F::PIECES; ++q) z.v[q] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < K3_ROWS; ++j)
+                if (tw + j < T) {
+                    if (TK_K3_NT_STORE) z.store_nt(grad + (size_t)n0 * F::S + (size_t)(tw + j) * rowstride, nvalid, lane);
+                    else z.store(grad + (size_t)n0 * F::S + (size_t)(tw + j) * rowstride, nvalid, lane);
+                }
+            return;
+        }
+    }
+    auto live = [&](int j) { return !VL || tw + j < Tn; };
 
     // 1. rows -> registers (weights w = exp(s - rowmax))
     RowSet<NB> w[K3_ROWS];
@@ -1023,8 +1161,8 @@ __global__ __launch_bounds__(K3_WAVES *WAVE, (CH / K3_WAVES <= 2 ? 4 : 2)) void 
         // last use of the scores.  Tensors that fit the 256 MB Infinity Cache are read with
         // plain loads (part of this second read then hits L2 / MALL: 105 -> 100 us at
         // T=4000 N=256); bigger ones stream past the caches (non-temporal)
-        if (nt_load) w[j].issue_nt(base + (size_t)min(tw + j, T - 1) * rowstride, nvalid, lane);
-        else w[j].issue(base + (size_t)min(tw + j, T - 1) * rowstride, nvalid, lane);
+        if (nt_load) w[j].issue_nt(base + (size_t)min(tw + j, Tld - 1) * rowstride, nvalid, lane);
+        else w[j].issue(base + (size_t)min(tw + j, Tld - 1) * rowstride, nvalid, lane);
     // chain heads (wave 0: forward vector entering the chunk, last wave: backward
     // vector leaving it), loaded while the rows are in flight
     float head[F::NS];
@@ -1056,6 +1194,10 @@ __global__ __launch_bounds__(K3_WAVES *WAVE, (CH / K3_WAVES <= 2 ? 4 : 2)) void 
                 if (tw + j < T) {
                     float out[F::NS];
                     ff_fwd_step<NB>(f, w[j], out);
+                    if constexpr (VL) {     // (the select first: the old vector is dead before the normalisation)
+#pragma unroll
+                        for (int k = 0; k < F::NS; ++k) out[k] = live(j) ? out[k] : f[k];
+                    }
                     (void)pow2_normalise(out);
 #pragma unroll
                     for (int k = 0; k < F::NS; ++k) f[k] = out[k];
@@ -1075,6 +1217,10 @@ __global__ __launch_bounds__(K3_WAVES *WAVE, (CH / K3_WAVES <= 2 ? 4 : 2)) void 
                 if (tw + j < T) {
                     float out[F::NS];
                     ff_bwd_step<NB>(b, w[j], out);
+                    if constexpr (VL) {     // (a vector that took no step is rescaled by an exact power of two at most)
+#pragma unroll
+                        for (int k = 0; k < F::NS; ++k) out[k] = live(j) ? out[k] : b[k];
+                    }
                     (void)pow2_normalise(out);
 #pragma unroll
                     for (int k = 0; k < F::NS; ++k) b[k] = out[k];
@@ -1091,6 +1237,16 @@ __global__ __launch_bounds__(K3_WAVES *WAVE, (CH / K3_WAVES <= 2 ? 4 : 2)) void 
     //    (cupy flipflop.py:280-291 + softmax at 351-354)
     float b[F::NS];
     bool bad = false;
+    // a row's sum: each product rounded, then added.  The fixed-length build gets that from its packed multiplies; the
+    // build with lengths has none (Makefile) and would contract the add into an FMA -- other bits at full lengths
+    auto add_to = [](float &sum, float g) {
+        if constexpr (VL) {
+#pragma clang fp contract(off)
+            sum = sum + g;
+        } else {
+            sum += g;
+        }
+    };
 #pragma unroll
     for (int k = 0; k < F::NS; ++k) b[k] = bexit[k];
 #pragma unroll
@@ -1098,6 +1254,10 @@ __global__ __launch_bounds__(K3_WAVES *WAVE, (CH / K3_WAVES <= 2 ? 4 : 2)) void 
         if (tw + j < T) {
             float bn[F::NS], fv[F::NS];
             ff_bwd_step<NB>(b, w[j], bn);
+            if constexpr (VL) {             // (as in the chain above)
+#pragma unroll
+                for (int k = 0; k < F::NS; ++k) bn[k] = live(j) ? bn[k] : b[k];
+            }
             (void)pow2_normalise(bn);
 #pragma unroll
             for (int k = 0; k < F::NS; ++k) fv[k] = fvb[(j * F::NS + k) * WAVE + lane];
@@ -1108,19 +1268,19 @@ __global__ __launch_bounds__(K3_WAVES *WAVE, (CH / K3_WAVES <= 2 ? 4 : 2)) void 
                 for (int from = 0; from < F::NS; ++from) {
                     const float g = fv[from] * w[j].get(to * F::NS + from) * b[to];
                     w[j].set(to * F::NS + from, g);
-                    sum += g;
+                    add_to(sum, g);
                 }
             }
 #pragma unroll
             for (int from = 0; from < F::NS; ++from) {
                 const float g = fv[from] * w[j].get(F::FLOP0 + from) * b[NB + (from % NB)];
                 w[j].set(F::FLOP0 + from, g);
-                sum += g;
+                add_to(sum, g);
             }
             const float inv = (ACC ? acc_g : 1.0f) / sum;
-            bad |= !isfinite(inv);
+            bad |= live(j) && !isfinite(inv);
 #pragma unroll
-            for (int i = 0; i < F::S; ++i) w[j].set(i, w[j].get(i) * inv);
+            for (int i = 0; i < F::S; ++i) w[j].set(i, live(j) ? w[j].get(i) * inv : 0.f);
 #pragma unroll
             for (int k = 0; k < F::NS; ++k) b[k] = bn[k];
         }
@@ -1236,25 +1396,25 @@ static int logz_launch_ch(const float *scores, size_t T, size_t N, float *logz, 
         const size_t bufwords = 4 * (size_t)WAVE * F::PIECES, imgwords = 4 * (size_t)XMat<NB>::NF4 * WAVE;
         const size_t lds = K1_WAVES * (imgwords > bufwords ? imgwords : bufwords) * sizeof(float);
         // (the ring form's LDS image can exceed the plain one's: raise for every form, whatever `lds` is)
-        if (raise_dynamic_lds(reinterpret_cast<const void *>(&logz_transfer_kernel<NB, CH, 0, false>)) ||
-            raise_dynamic_lds(reinterpret_cast<const void *>(&logz_transfer_kernel<NB, CH, 0, true>)) ||
-            raise_dynamic_lds(reinterpret_cast<const void *>(&logz_transfer_kernel<NB, CH, K1_RING, false>)) ||
-            raise_dynamic_lds(reinterpret_cast<const void *>(&logz_transfer_coop_kernel<NB, CH>)))
+        if (raise_dynamic_lds(reinterpret_cast<const void *>(&logz_transfer_kernel<NB, CH, 0, false, LOGZ_VL>)) ||
+            raise_dynamic_lds(reinterpret_cast<const void *>(&logz_transfer_kernel<NB, CH, 0, true, LOGZ_VL>)) ||
+            raise_dynamic_lds(reinterpret_cast<const void *>(&logz_transfer_kernel<NB, CH, K1_RING, false, LOGZ_VL>)) ||
+            raise_dynamic_lds(reinterpret_cast<const void *>(&logz_transfer_coop_kernel<NB, CH, LOGZ_VL>)))
             return 4;
         const int form = logz_transfer_form(nchunks_all, (size_t)ncols * C, (size_t)T * ws.nstride * F::S * sizeof(float));
         const dim3 grid(ncols, (C + K1_WAVES - 1) / K1_WAVES);
         if (form == LOGZ_RING) {
             const size_t ringlds = K1_WAVES * (size_t)K1_RING * WAVE * F::PIECES * sizeof(f4);
-            hipLaunchKernelGGL((logz_transfer_kernel<NB, CH, K1_RING, false>), grid, dim3(K1_WAVES * WAVE),
+            hipLaunchKernelGGL((logz_transfer_kernel<NB, CH, K1_RING, false, LOGZ_VL>), grid, dim3(K1_WAVES * WAVE),
                                ringlds > lds ? ringlds : lds, stream, scores, (int)T, (int)N, C, Npad, ws);
         } else if (form == LOGZ_STREAM)
-            hipLaunchKernelGGL((logz_transfer_kernel<NB, CH, 0, true>), grid, dim3(K1_WAVES * WAVE), lds, stream,
+            hipLaunchKernelGGL((logz_transfer_kernel<NB, CH, 0, true, LOGZ_VL>), grid, dim3(K1_WAVES * WAVE), lds, stream,
                                scores, (int)T, (int)N, C, Npad, ws);
         else if (form == LOGZ_PLAIN)
-            hipLaunchKernelGGL((logz_transfer_kernel<NB, CH, 0, false>), grid, dim3(K1_WAVES * WAVE), lds, stream,
+            hipLaunchKernelGGL((logz_transfer_kernel<NB, CH, 0, false, LOGZ_VL>), grid, dim3(K1_WAVES * WAVE), lds, stream,
                                scores, (int)T, (int)N, C, Npad, ws);
         else
-            hipLaunchKernelGGL((logz_transfer_coop_kernel<NB, CH>), dim3(ncols, C), dim3(K1_WAVES * WAVE),
+            hipLaunchKernelGGL((logz_transfer_coop_kernel<NB, CH, LOGZ_VL>), dim3(ncols, C), dim3(K1_WAVES * WAVE),
                                lds, stream, scores, (int)T, (int)N, C, Npad, ws);
     }
     if (phases & PH_MIDDLE) {
@@ -1275,16 +1435,18 @@ static int logz_launch_ch(const float *scores, size_t T, size_t N, float *logz, 
         constexpr bool chain_in_buf = k3_chain_in_buf<NB, CH>();
         const size_t lds = K3_WAVES * (size_t)k3_buf_f4<NB, CH>() * sizeof(f4) +
                            (chain_in_buf ? 0 : 2 * F::NS * WAVE * sizeof(float));
-        if (raise_dynamic_lds(reinterpret_cast<const void *>(&logz_posterior_kernel<NB, CH, false>)) ||
-            raise_dynamic_lds(reinterpret_cast<const void *>(&logz_posterior_kernel<NB, CH, true>)))
-            return 4;
+        if (raise_dynamic_lds(reinterpret_cast<const void *>(&logz_posterior_kernel<NB, CH, false, LOGZ_VL>))) return 4;
         const int nt_load = (size_t)T * ws.nstride * F::S * sizeof(float) > ((size_t)200 << 20);
-        if (ws.loss_acc != nullptr)
-            hipLaunchKernelGGL((logz_posterior_kernel<NB, CH, true>), grid, block, lds, stream, scores, grad,
-                               (int)T, (int)N, Npad, ws, status, nt_load);
-        else
-            hipLaunchKernelGGL((logz_posterior_kernel<NB, CH, false>), grid, block, lds, stream, scores, grad,
-                               (int)T, (int)N, Npad, ws, status, nt_load);
+        if constexpr (!LOGZ_VL) {           // (the accumulating form has no lengths: logz_dispatch refuses the call)
+            if (raise_dynamic_lds(reinterpret_cast<const void *>(&logz_posterior_kernel<NB, CH, true, false>))) return 4;
+            if (ws.loss_acc != nullptr) {
+                hipLaunchKernelGGL((logz_posterior_kernel<NB, CH, true, false>), grid, block, lds, stream, scores, grad,
+                                   (int)T, (int)N, Npad, ws, status, nt_load);
+                return hipGetLastError() == hipSuccess ? 0 : 4;
+            }
+        }
+        hipLaunchKernelGGL((logz_posterior_kernel<NB, CH, false, LOGZ_VL>), grid, block, lds, stream, scores, grad,
+                           (int)T, (int)N, Npad, ws, status, nt_load);
     }
     return hipGetLastError() == hipSuccess ? 0 : 4;
 }
@@ -1339,6 +1501,9 @@ static LogzWs logz_ws_from(const LogzWs &ws, size_t n0, size_t C) {
     o.Uout = ws.Uout + n0 * C * F::NS;
     if (ws.loss_acc != nullptr) o.loss_acc = ws.loss_acc + n0;
     if (ws.grad_scale_vec != nullptr) o.grad_scale_vec = ws.grad_scale_vec + n0;
+#ifdef TK_LOGZ_VARLEN
+    if (ws.lengths != nullptr) o.lengths = ws.lengths + n0;
+#endif
     return o;
 }
 
@@ -1395,10 +1560,13 @@ template <int NB>
 static int logz_launch(const float *scores, size_t T, size_t N, float *logz, float *grad,
                        void *workspace, size_t workspace_bytes, uint32_t *status,
                        hipStream_t stream, float *loss_acc, float acc_scale, float grad_scale,
-                       const float *grad_scale_vec) {
+                       const float *grad_scale_vec, const int32_t *lengths = nullptr) {
     LogzWs ws;
     const size_t need = logz_ws_layout<NB>(T, N, workspace, &ws);
     if (need > workspace_bytes) return 3;
+#ifdef TK_LOGZ_VARLEN
+    ws.lengths = lengths;
+#endif
     ws.loss_acc = loss_acc;
     ws.acc_scale = acc_scale;
     ws.grad_scale = grad_scale;
@@ -1458,7 +1626,7 @@ int logz_dispatch(const float *scores, size_t T, size_t N, size_t nbase, float *
                   float *grad, void *workspace, size_t workspace_bytes, uint32_t *status,
                   hipStream_t stream, float *loss_acc, float acc_scale, float grad_scale,
                   const float *grad_scale_vec) {
-    if (loss_acc != nullptr && grad == nullptr) return 1;
+    if (loss_acc != nullptr && (grad == nullptr || LOGZ_VL)) return 1;
     switch (nbase) {
         case 1: return logz_launch<1>(scores, T, N, logz, grad, workspace, workspace_bytes, status, stream, loss_acc, acc_scale, grad_scale, grad_scale_vec);
         case 2: return logz_launch<2>(scores, T, N, logz, grad, workspace, workspace_bytes, status, stream, loss_acc, acc_scale, grad_scale, grad_scale_vec);
@@ -1467,5 +1635,32 @@ int logz_dispatch(const float *scores, size_t T, size_t N, size_t nbase, float *
         default: return 2;
     }
 }
+
+#ifdef TK_LOGZ_VARLEN
+// libtaiyaki_amd_logz_varlen.so (logz_varlen_api.hip defines the C entries): the same three launches with a length per
+// column; chunk length, transfer form and super from (T, N) through logz_plan_nb, as for the call without lengths
+bool logz_varlen_supported(size_t T, size_t N, size_t nbase) {
+    LogzPlan p;
+    if (T == 0 || N == 0) return false;
+    switch (nbase) {
+        case 1: return logz_plan_nb<1>(T, N, T * N * FF<1>::S * sizeof(float), &p);
+        case 2: return logz_plan_nb<2>(T, N, T * N * FF<2>::S * sizeof(float), &p);
+        case 3: return logz_plan_nb<3>(T, N, T * N * FF<3>::S * sizeof(float), &p);
+        case 4: return logz_plan_nb<4>(T, N, T * N * FF<4>::S * sizeof(float), &p);
+        default: return false;
+    }
+}
+
+int logz_varlen_dispatch(const float *scores, const int32_t *lengths, size_t T, size_t N, size_t nbase, float *logz,
+                         float *grad, void *workspace, size_t workspace_bytes, uint32_t *status, hipStream_t stream) {
+    switch (nbase) {
+        case 1: return logz_launch<1>(scores, T, N, logz, grad, workspace, workspace_bytes, status, stream, nullptr, 0.f, 1.f, nullptr, lengths);
+        case 2: return logz_launch<2>(scores, T, N, logz, grad, workspace, workspace_bytes, status, stream, nullptr, 0.f, 1.f, nullptr, lengths);
+        case 3: return logz_launch<3>(scores, T, N, logz, grad, workspace, workspace_bytes, status, stream, nullptr, 0.f, 1.f, nullptr, lengths);
+        case 4: return logz_launch<4>(scores, T, N, logz, grad, workspace, workspace_bytes, status, stream, nullptr, 0.f, 1.f, nullptr, lengths);
+        default: return 2;
+    }
+}
+#endif
 
 }  // namespace tk

@@ -401,6 +401,16 @@ def cat_mod_flipflop_loss(logprob, seqs, seqlen, mod_cats, can_mods_offsets, mod
 # ---------------------------------------------------------------------------------------------
 # fused train-step loss: (A) + (B) / nblk in one operator, one gradient tensor
 # ---------------------------------------------------------------------------------------------
+def _fused_varlen_entry(blocks):
+    """The fused loss with lengths: (library, entry point, its query for the log-partition workspace (which 1) and the
+    compact buffers (which 0)) -- `blocks`: include/taiyaki_amd_logz_varlen.h, else include/taiyaki_amd_loss_varlen.h."""
+    if blocks:
+        V = _lib.logz_varlen_lib()
+        return V, "tk_flipflop_loss_fused_varlen_blocks_labels_dev", V.tk_flipflop_loss_varlen_blocks_aux_bytes
+    V = _lib.loss_varlen_lib()
+    return V, "tk_flipflop_loss_fused_varlen_labels_dev", V.tk_flipflop_loss_varlen_aux_bytes
+
+
 def _run_fused(outputs, seqs, seqlen, sharpfact, want_grad, grad_scale=1.0, grad_scale_per_read=None,
                mod_cats=None, can_mods_offsets=None, mod_cat_weights=None, lengths=None):
     lengths = _time_lengths(lengths, outputs, "flip-flop loss")
@@ -425,10 +435,13 @@ def _run_fused(outputs, seqs, seqlen, sharpfact, want_grad, grad_scale=1.0, grad
         grad = torch.empty_like(lp)
         wsa = L.tk_crf_flipflop_workspace_bytes_sharp(ntrans, nblk, nbatch, maxlen, 1, float(sharpfact))
         if lengths is not None:
-            # the log-partition half with lengths (one wave per column) and its compact buffers, then kernel A: one stream
-            V = _lib.loss_varlen_lib()
-            wsb = V.tk_flipflop_loss_varlen_aux_bytes(nblk, nbatch, nbase, ntrans, 1)
-            wsx = V.tk_flipflop_loss_varlen_aux_bytes(nblk, nbatch, nbase, ntrans, 0)
+            # the log-partition half with lengths and its compact buffers, then kernel A: one stream.  The half is the
+            # transfer-matrix kernels with lengths (layers.USE_HIP_LOGZ_VARLEN) or the one-wave posterior
+            from taiyaki_amd import layers
+            blocks = layers.USE_HIP_LOGZ_VARLEN
+            V, fused_name, aux_bytes = _fused_varlen_entry(blocks)
+            wsb = aux_bytes(nblk, nbatch, nbase, ntrans, 1)
+            wsx = aux_bytes(nblk, nbatch, nbase, ntrans, 0)
             if wsb == 0:
                 raise RuntimeError("flip-flop loss with lengths: nbase=%d is not built" % nbase)
         else:
@@ -452,13 +465,24 @@ def _run_fused(outputs, seqs, seqlen, sharpfact, want_grad, grad_scale=1.0, grad
             _lib.check(rc, "tk_flipflop_loss_fused_dev")
         elif lengths is not None:
             lens_d = lengths.to(dev)
-            rc = V.tk_flipflop_loss_fused_varlen_labels_dev(
-                _lib.ptr(lp), nblk, nbatch, ntrans, ctypes.byref(res[7]), _lib.ptr(seqlen_d), _lib.ptr(seqoff),
-                _lib.ptr(stay), _lib.ptr(move), _lib.ptr(mod), _lib.ptr(fact), maxlen, float(sharpfact),
-                float(grad_scale), _lib.ptr(gvec), _lib.ptr(lossvector), _lib.ptr(grad), _lib.ptr(logz),
-                _lib.ptr(ws_a), wsa, _lib.ptr(ws_b), wsb, _lib.ptr(ws_x), wsx, _lib.ptr(status), _lib.stream_ptr(),
-                _lib.ptr(lens_d))
-            _lib.check(rc, "tk_flipflop_loss_fused_varlen_labels_dev")
+
+            def fused_varlen():
+                return getattr(V, fused_name)(
+                    _lib.ptr(lp), nblk, nbatch, ntrans, ctypes.byref(res[7]), _lib.ptr(seqlen_d), _lib.ptr(seqoff),
+                    _lib.ptr(stay), _lib.ptr(move), _lib.ptr(mod), _lib.ptr(fact), maxlen, float(sharpfact),
+                    float(grad_scale), _lib.ptr(gvec), _lib.ptr(lossvector), _lib.ptr(grad), _lib.ptr(logz),
+                    _lib.ptr(ws_a), wsa, _lib.ptr(ws_b), wsb, _lib.ptr(ws_x), wsx, _lib.ptr(status), _lib.stream_ptr(),
+                    _lib.ptr(lens_d))
+            rc = fused_varlen()
+            if blocks and rc == _lib.DEFINES["TK_ERR_UNSUPPORTED"]:
+                # a shape the transfer-matrix launcher refuses (nothing was launched): the one-wave kernel, its workspace
+                V, fused_name, aux_bytes = _fused_varlen_entry(False)
+                wsb = aux_bytes(nblk, nbatch, nbase, ntrans, 1)
+                ws_b, blocks = _workspace(wsb, dev, "logz"), False
+                rc = fused_varlen()
+            _lib.check(rc, fused_name)
+            if blocks:
+                layers.logz_varlen_calls["loss"] += 1
             keep = keep + (lens_d,)
         else:
             # (the index build rides in kernel A's first launch: one launch less in the captured step)

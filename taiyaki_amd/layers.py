@@ -23,6 +23,7 @@ that feeds them.
   (include/taiyaki_amd_rnn_wide.h; USE_HIP_RNN_WIDE).
 """
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -75,14 +76,64 @@ class LogZ(torch.autograd.Function):
         return trans * g[:, None]
 
 
+# True: the log-partition with a time length per column -- `flipflop_logpartition(x, lengths=)` and the log-partition half
+# of the fused `ctc.flipflop_loss` / `flipflop_mean_loss(..., lengths=)`, through them `train.calculate_loss(..., lengths=)`
+# -- runs on the transfer-matrix kernels with lengths (include/taiyaki_amd_logz_varlen.h) wherever their launcher takes the
+# shape.  False: on the one-wave posterior with lengths (include/taiyaki_amd_decode_varlen.h), as before there were such
+# kernels.  `decode.flipflop_make_trans(..., lengths=)` and the basecaller keep the one-wave kernel either way.
+USE_HIP_LOGZ_VARLEN = os.environ.get("TK_HIP_LOGZ_VARLEN", "1") != "0"
+# calls that went through include/taiyaki_amd_logz_varlen.h: "logz" the operator, "loss" the fused loss
+logz_varlen_calls = {"logz": 0, "loss": 0}
+
+
+def _logz_varlen_blocks(scores, lengths, want_grad):
+    """tk_flipflop_logz_varlen_dev on `scores` (T, N, S) with `lengths`: (logz, trans or None), or None where its launcher
+    refuses the shape (too many chunks for the middle kernel: the caller keeps the one-wave kernel)."""
+    from taiyaki_amd import decode
+    T, N, S = scores.shape
+    lens = decode._column_lengths(lengths, T, N, "flipflop_logpartition")
+    _lib.require_gpu(scores, "flipflop_logpartition")
+    if T == 0 or N == 0:
+        return None
+    sc = scores.detach().float().contiguous()
+    if sc.data_ptr() % 16 != 0:
+        sc = sc.clone()
+    nbase, dev = flipflopfings.nbase_flipflop(S), sc.device
+    V = _lib.logz_varlen_lib()
+    wsb = V.tk_flipflop_logz_varlen_workspace_bytes(T, N, nbase)
+    if wsb == 0:
+        raise RuntimeError("flipflop_logpartition: nbase=%d is not built" % nbase)
+    with torch.cuda.device(dev):
+        lens = lens.to(dev)
+        logz = torch.empty(N, dtype=torch.float32, device=dev)
+        trans = torch.empty_like(sc) if want_grad else None
+        ws = _lib.workspace(wsb, dev, "logz")
+        status = _lib.status_word(dev)
+        rc = V.tk_flipflop_logz_varlen_dev(_lib.ptr(sc), _lib.ptr(lens), T, N, nbase, _lib.ptr(trans), _lib.ptr(logz),
+                                           _lib.ptr(ws), wsb, _lib.ptr(status), _lib.stream_ptr())
+        if rc == _lib.DEFINES["TK_ERR_UNSUPPORTED"]:
+            return None
+        _lib.check(rc, "tk_flipflop_logz_varlen_dev")
+        _lib.finish(status)
+    logz_varlen_calls["logz"] += 1
+    return logz, trans
+
+
 class LogZVarlen(torch.autograd.Function):
-    """logZ of every column on its own rows, (N,): the posterior with lengths of include/taiyaki_amd_decode_varlen.h (one
-    wave per column; `decode.flipflop_make_trans(..., lengths=)` is the same launch).  backward = the posterior transition
-    probabilities * g[:, None], rows at or beyond a column's length exactly 0."""
+    """logZ of every column on its own rows, (N,).  USE_HIP_LOGZ_VARLEN: the transfer-matrix kernels with lengths of
+    include/taiyaki_amd_logz_varlen.h; otherwise, and for a shape they refuse, the posterior with lengths of
+    include/taiyaki_amd_decode_varlen.h (one wave per column; `decode.flipflop_make_trans(..., lengths=)` is that launch).
+    backward = the posterior transition probabilities * g[:, None], rows at or beyond a column's length exactly 0."""
 
     @staticmethod
     def forward(ctx, scores, lengths):
         from taiyaki_amd import decode
+        if USE_HIP_LOGZ_VARLEN:
+            res = _logz_varlen_blocks(scores, lengths, ctx.needs_input_grad[0])
+            if res is not None:
+                if ctx.needs_input_grad[0]:
+                    ctx.save_for_backward(res[1])
+                return res[0]
         V, sc, lens, nbase, wsb = decode._varlen_args(scores, lengths, "flipflop_logpartition")
         T, N, _ = sc.shape
         with torch.cuda.device(sc.device):

@@ -2,12 +2,14 @@
 """The fused flip-flop loss with a time length per column, timed against the fixed-length operator (run it under
 rocprofv3 --kernel-trace --stats for the per-kernel split).
 
-    python tools/lossvarlenbench.py [--reps 40] [--only a|b|c|d] [--out profiles/r38_loss_varlen.txt]
-Shape: T 800 x N 128, configs[1]'s lengths (synth.realistic_seqlens at chunk_len 4000, 9 samples per base), plain CRF.
+    python tools/lossvarlenbench.py [--reps 40] [--batch 128] [--only a|b|c|d|B|C] [--skip-d] [--out profiles/r38_loss_varlen.txt]
+Shape: T 800 x N 128 (--batch: another N), configs[1]'s lengths (synth.realistic_seqlens at chunk_len 4000, 9 samples per base), plain CRF.
   (a) the existing fused call (ctc.flipflop_mean_loss without lengths)
   (b) the call with lengths = [T] * N: kernel A's VL instantiations, and the one-wave-per-column posterior with lengths in
       kernel B's place
   (c) lengths spread evenly over T/4 .. T, labels of 0.5 T_n bases
+  (B), (C) are (b) and (c) with layers.USE_HIP_LOGZ_VARLEN on: the transfer-matrix kernels with lengths in kernel B's place
+      (include/taiyaki_amd_logz_varlen.h); (b), (c) run with it off.  The turn-by-turn medians of the two pairs are printed.
   (d) the only route to (c) without the feature: N calls of the existing operator, one per column, on scores[:T_n, n:n+1]
 The variants are timed in turns of five calls each, so that clock and thermal drift fall on all of them alike; (d) in turns
 of one (a turn of it is N calls).  With each variant: the reads retried and redone in the log domain by one call.
@@ -24,7 +26,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from taiyaki_amd import _lib, ctc, synth  # noqa: E402
+from taiyaki_amd import _lib, ctc, layers, synth  # noqa: E402
 
 
 def long_reads(args, dev):
@@ -72,13 +74,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=40, help="timed calls per variant, taken in turns of five")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", default=None, help="a | b | c | d: that variant alone (for a per-kernel trace of it)")
+    ap.add_argument("--only", default=None, help="a | b | c | d | B | C: that variant alone (for a per-kernel trace of it)")
+    ap.add_argument("--batch", type=int, default=128, help="N, the columns of the batch")
+    ap.add_argument("--skip-d", action="store_true", help="leave out (d), N calls per turn")
     ap.add_argument("--long", action="store_true", help="kernel A at four cells per lane without a row maker, with and without lengths")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if args.long:
         return long_reads(args, dev)
-    T, N = 800, 128
+    T, N = 800, args.batch
     inp = synth.crf_case(T, N, 1, seqlens=synth.realistic_seqlens(T, N, 17000, 4000, 9.0))
     x = torch.from_numpy(inp["scores"]).to(dev)
     seqs, seqlens = torch.from_numpy(inp["seqs"]), torch.from_numpy(inp["seqlens"])
@@ -95,13 +99,19 @@ def main():
     def per_column():
         for xc, sc, lc in cols:
             ctc._run_fused(xc, sc, lc, 1.0, True, grad_scale=1.0 / N)
+    def with_lengths(blocks, *call, **kw):
+        layers.USE_HIP_LOGZ_VARLEN = blocks
+        return ctc._run_fused(*call, 1.0, True, grad_scale=1.0 / N, **kw)
     variants = [
         ("a", "existing fused call", 5, lambda: ctc._run_fused(x, seqs, seqlens, 1.0, True, grad_scale=1.0 / N)),
-        ("b", "lengths = [T] * N", 5, lambda: ctc._run_fused(x, seqs, seqlens, 1.0, True, grad_scale=1.0 / N, lengths=full)),
-        ("c", "T_n over T/4 .. T, labels 0.5 T_n", 5,
-         lambda: ctc._run_fused(x, seqs_c, seqlens_c, 1.0, True, grad_scale=1.0 / N, lengths=lens_c_dev)),
+        ("b", "lengths = [T] * N", 5, lambda: with_lengths(False, x, seqs, seqlens, lengths=full)),
+        ("B", "lengths = [T] * N, transfer-matrix", 5, lambda: with_lengths(True, x, seqs, seqlens, lengths=full)),
+        ("c", "T_n over T/4 .. T, labels 0.5 T_n", 5, lambda: with_lengths(False, x, seqs_c, seqlens_c, lengths=lens_c_dev)),
+        ("C", "T_n over T/4 .. T, transfer-matrix", 5, lambda: with_lengths(True, x, seqs_c, seqlens_c, lengths=lens_c_dev)),
         ("d", "N per-column existing calls for (c)", 1, per_column),
     ]
+    if args.skip_d:
+        variants = [v for v in variants if v[0] != "d"]
     if args.only:
         variants = [v for v in variants if v[0] == args.only]
     counts = {}
@@ -144,7 +154,15 @@ def main():
         lines.append("(%s) %-38s calls %3d  median %9.1f us  mean %9.1f  min %9.1f  max %9.1f   retried %d, redone %d per call" % (
             key, label, len(us), np.median(us), us.mean(), us.min(), us.max(), counts[key][0], counts[key][1]))
     if not args.only:
-        lines.append("(b) / (a) = %.3f    (d) / (c) = %.1f" % (stat["b"] / stat["a"], stat["d"] / stat["c"]))
+        lines.append("(b) / (a) = %.3f    (B) / (a) = %.3f    (C) / (a) = %.3f" % (stat["b"] / stat["a"], stat["B"] / stat["a"], stat["C"] / stat["a"])
+                     + ("" if args.skip_d else "    (d) / (c) = %.1f" % (stat["d"] / stat["c"])))
+        # the two paths turn by turn (five calls each): the median of every turn
+        turn = {k: np.array([a.elapsed_time(b) for a, b in times[k]]).reshape(-1, 5) * 1e3 for k in "bBcC"}
+        for old, new in ("bB", "cC"):
+            mo, mn = np.median(turn[old], axis=1), np.median(turn[new], axis=1)
+            lines.append("turns (%s) %s" % (old, " ".join("%.0f" % v for v in mo)))
+            lines.append("turns (%s) %s   below (%s) in every turn: %s" % (new, " ".join("%.0f" % v for v in mn), old, bool((mn < mo).all())))
+        lines.append("logz_varlen_calls %s" % layers.logz_varlen_calls)
     text = "\n".join(lines)
     print(text)
     if args.out:
