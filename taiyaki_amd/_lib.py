@@ -59,6 +59,9 @@ CONV_WINDOW_LIBNAME = "libtaiyaki_amd_conv_window.so"       # csrc/conv_strided.
 CONV_WINDOW_LAB_LIBNAME = "libtaiyaki_amd_conv_window_lab.so"       # ... and its lab build (tk_lab_conv_window_*)
 CHUNKS_SEQLEN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_chunks_seqlen.h")
 CHUNKS_SEQLEN_LIBNAME = "libtaiyaki_amd_chunks_seqlen.so"       # csrc/chunk_seqlen.hip: chunks of a fixed number of bases (the squiggle trainer's batches), header and library of its own
+LSTM_MATRIX_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_lstm_matrix.h")
+LSTM_MATRIX_LIBNAME = "libtaiyaki_amd_lstm_matrix.so"       # csrc/lstm_matrix.hip: the LSTM forward that saves nothing at size 96 on the matrix cores, header and library of its own
+LSTM_MATRIX_LAB_LIBNAME = "libtaiyaki_amd_lstm_matrix_lab.so"       # ... and its lab build (no hook)
 OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_optim.h")
 OPTIM_LIBNAME = "libtaiyaki_amd_optim.so"       # csrc/optim.hip: the optimiser step (scale, maxima, clamp, norm cap, AdamW, zero fill), header and library of its own
 
@@ -229,6 +232,10 @@ LSTM_LARGE_SIGNATURES, LSTM_LARGE_LAB_SIGNATURES = _read_wgrad_header(LSTM_LARGE
 LOGZ_VARLEN_SIGNATURES = {n: (r, a) for n, (r, a, _) in
                           parse_prototypes(_blank_comments(open(LOGZ_VARLEN_HEADER).read())).items()}
 
+# the twenty-fourth: include/taiyaki_amd_lstm_matrix.h (libtaiyaki_amd_lstm_matrix.so); its lab build adds no hook
+LSTM_MATRIX_SIGNATURES = {n: (r, a) for n, (r, a, _) in
+                          parse_prototypes(_blank_comments(open(LSTM_MATRIX_HEADER).read())).items()}
+
 
 class SeqLabels(ctypes.Structure):
     """include/taiyaki_amd_flipflop.h: tk_seq_labels (what tk_flipflop_build_indices_dev takes, for the entry points
@@ -374,6 +381,13 @@ def lstm_large_lib():
         return _load(os.path.join(CSRC, LSTM_LARGE_LAB_LIBNAME),
                      dict(LSTM_LARGE_SIGNATURES, **LSTM_LARGE_LAB_SIGNATURES))
     return _load(os.path.join(CSRC, LSTM_LARGE_LIBNAME), LSTM_LARGE_SIGNATURES)
+
+
+def lstm_matrix_lib():
+    """The LSTM forward that saves nothing at size 96 on the matrix cores (include/taiyaki_amd_lstm_matrix.h): the lab
+    build of that library while the process runs on the lab build (`use_lab`), the release one otherwise.  No fallback:
+    a missing library raises."""
+    return _load(os.path.join(CSRC, LSTM_MATRIX_LAB_LIBNAME if is_lab() else LSTM_MATRIX_LIBNAME), LSTM_MATRIX_SIGNATURES)
 
 
 def align_lib():

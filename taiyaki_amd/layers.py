@@ -9,7 +9,7 @@ that feeds them.
   (BASELINE.json north_star) and only produce the (T, N, S) score tensor.
   ``Lstm`` and ``GruMod`` keep their nn.LSTM / nn.GRU parameters, but on the GPU their
   recurrences run as the persistent HIP kernels of csrc/lstm_kernels.hip
-  (`LstmRecurrence`; size 96: csrc/lstm_local.hip; size 512: the same kernels from
+  (`LstmRecurrence`; size 96: csrc/lstm_local.hip, wide batches that save nothing csrc/lstm_matrix.hip; size 512: the same kernels from
   libtaiyaki_amd_lstm_large.so, include/taiyaki_amd_lstm_large.h, USE_HIP_LSTM_LARGE) and csrc/gru_kernels.hip (`GruRecurrence`):
   one Function per cell, on the launch of the first library that admits the call, in the order that `_rnn_route`
   states.  A narrow
@@ -608,11 +608,13 @@ class _Rnn(nn.Module):
     def forward(self, x, reverse=False, lengths=None):
         if lengths is not None:
             return _rnn_forward_varlen(self, x, reverse, lengths)
-        route = _rnn_route(self, x, False, False)
+        needs = _needs_grad(x, self)
+        route = _rnn_route(self, x, False, needs)
         if route:
             # The LSTM has no launch without lengths that saves nothing, so its main row saves whatever the grad mode,
             # and its slabs of columns do as that row does; every other row saves only where something needs a gradient
-            save = (isinstance(self.rnn, nn.LSTM) and route[0] in (False, "wide")) or _needs_grad(x, self)
+            # (the "matrix" row is chosen only where nothing does)
+            save = (isinstance(self.rnn, nn.LSTM) and route[0] in (False, "wide")) or needs
             return _rnn_apply(self, x, reverse, *route, None, save)
         if reverse:
             return torch.flip(self.rnn(torch.flip(x, (0,)))[0], (0,))
@@ -724,6 +726,27 @@ def hip_lstm_local_takes(rnn, x):
                 and _lib.lstm_local_lib().tk_lstm_local_supported(rnn.hidden_size))
 
 
+# True (also TK_HIP_LSTM_MATRIX=1 / 0 in the environment): an Lstm call at size 96 that saves nothing, on a batch of at
+# least LSTM_MATRIX_MIN_COLUMNS columns, runs on the matrix cores (include/taiyaki_amd_lstm_matrix.h: 16 columns per
+# workgroup) instead of the kernels of include/taiyaki_amd_lstm_local.h (2 columns per workgroup at such a width)
+USE_HIP_LSTM_MATRIX = os.environ.get("TK_HIP_LSTM_MATRIX", "1") != "0"
+# The narrowest batch that takes it: the smallest measured width from which the matrix kernel was ahead of the local one in
+# every turn, there and at every wider batch measured (tools/lstmmatrixbench.py, profiles/r51_lstm_matrix.txt).  Never below
+# 2 * 256 + 1: up to two columns per CU the local kernel runs one round of workgroups, and nothing changes there
+LSTM_MATRIX_MIN_COLUMNS = 2048
+# calls of `Lstm` that went through include/taiyaki_amd_lstm_matrix.h (all of them "inference": the entry saves nothing)
+lstm_matrix_calls = {"inference": 0}
+
+
+def hip_lstm_matrix_takes(rnn, x, save):
+    """True where the entry of include/taiyaki_amd_lstm_matrix.h runs this nn.LSTM on this input: nothing is saved, the
+    batch has at least LSTM_MATRIX_MIN_COLUMNS columns and at least one step, `_hip_lstm_takes` admits the layer and the
+    library supports its size (`tk_lstm_matrix_supported`: 96).  With or without lengths; no workspace to ask for."""
+    return bool(USE_HIP_LSTM_MATRIX and not save and x.dim() == 3 and x.shape[0] and x.shape[1]
+                and x.shape[1] >= LSTM_MATRIX_MIN_COLUMNS and _hip_lstm_takes(rnn, x)
+                and _lib.lstm_matrix_lib().tk_lstm_matrix_supported(rnn.hidden_size))
+
+
 def _hip_lstm_takes(rnn, x):
     if not (USE_HIP_LSTM and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
             and rnn.weight_hh_l0.is_cuda and rnn.weight_hh_l0.dtype == torch.float32):
@@ -766,6 +789,10 @@ _RNN_LAUNCHES = {
 # The rows whose entries take neither workspace, workspace size nor status word (csrc/lstm_local.hip: one workgroup owns
 # every unit of its columns)
 _RNN_BARE_ROWS = frozenset({"local"})
+# The row of include/taiyaki_amd_lstm_matrix.h ("matrix"; `_rnn_launch` looks a row up here too).  It stands beside the
+# table above, whose rows tests/test_rnn_routes.py pins with those of _RNN_BARE_ROWS and _RNN_CALLS: forward only and
+# nothing saved, a bare entry that takes no CU count either, and a counter of its own (lstm_matrix_calls)
+_RNN_MATRIX_LAUNCHES = {("matrix", False): ("lstm_matrix_lib", "tk_%s_matrix_forward_dev", None, None)}
 # The counter a call on a row moves, by "saved" / "inference"; the main row has none (the GRU: gru_forward_calls)
 _RNN_CALLS = {True: rnn_varlen_calls, "wide": rnn_wide_calls, "local": lstm_local_calls, "large": lstm_large_calls}
 
@@ -776,10 +803,12 @@ def _rnn_route(layer, x, lengths_given, save):
     column alone).  The order, for both cells, with and without lengths:
       1. the main library (`hip_lstm_workspace_bytes` / `hip_gru_workspace_bytes`, row False); with lengths the library
          with lengths in its place (row True): the training pair where `save`, the inference launch otherwise, neither
-         asked on a tensor without steps or columns.  `save` is read for nothing else;
+         asked on a tensor without steps or columns;
       2. slabs of columns ("wide"), not asked on a tensor without steps or columns;
-      3. the LSTM alone: size 96 ("local"), which has no workspace (0 bytes), then
-      4. size 512 ("large").
+      3. the LSTM alone: size 96 on the matrix cores ("matrix", `hip_lstm_matrix_takes`), which reads `save` too: only
+         a call that saves nothing, on a batch of LSTM_MATRIX_MIN_COLUMNS columns or more; no workspace (0 bytes);
+      4. size 96 ("local"), which has no workspace either, then
+      5. size 512 ("large").
     Every query is looked up when it is asked and none is asked behind the first that admits, so a call costs the host
     no more than the queries in front of its row."""
     rnn = layer.rnn
@@ -790,10 +819,11 @@ def _rnn_route(layer, x, lengths_given, save):
     else:
         first = (True, hip_rnn_varlen_train_workspace_bytes if save else hip_rnn_varlen_workspace_bytes, full)
     for row, query, asked in (first, ("wide", hip_rnn_wide_workspace_bytes, full),
+                              ("matrix", lambda r, v: hip_lstm_matrix_takes(r, v, save), lstm),
                               ("local", hip_lstm_local_takes, lstm), ("large", hip_lstm_large_workspace_bytes, lstm)):
         wsb = asked and query(rnn, x)
         if wsb:
-            return row, 0 if row in _RNN_BARE_ROWS else wsb
+            return row, 0 if row in _RNN_BARE_ROWS or row == "matrix" else wsb
     return None
 
 
@@ -809,16 +839,18 @@ def _rnn_apply(layer, x, reverse, row, wsb, lens, save):
 def _rnn_launch(cell, row, lens, save, backward, ins, shape, reverse, outs, wsb, dev):
     """One launch of a recurrence, checked: the entry of _RNN_LAUNCHES[row, save] on `ins` (the lengths behind them where
     the entry takes them), T, N, H, the direction and the CU count, `outs`, then the workspace, its size and the status
-    word (all three or, on a row of _RNN_BARE_ROWS, none) and the stream."""
-    libname, fwd, bwd, tag = _RNN_LAUNCHES[row, bool(save)]
+    word (all three or, on a row of _RNN_BARE_ROWS, none) and the stream.  The "matrix" row (_RNN_MATRIX_LAUNCHES) is bare
+    and takes no CU count."""
+    matrix = (row, bool(save)) in _RNN_MATRIX_LAUNCHES
+    libname, fwd, bwd, tag = (_RNN_MATRIX_LAUNCHES if matrix else _RNN_LAUNCHES)[row, bool(save)]
     name = (bwd if backward else fwd) % cell
     checked = ()
-    if row not in _RNN_BARE_ROWS:
+    if row not in _RNN_BARE_ROWS and not matrix:
         ws = _lib.workspace(wsb, dev, tag or cell)
         status = _lib.status_word(dev)
         checked = (_lib.ptr(ws), wsb, _lib.ptr(status))
     ptrs = [_lib.ptr(t) for t in ins + ((lens,) if row else ())]
-    rc = getattr(getattr(_lib, libname)(), name)(*ptrs, *shape, int(reverse), _cu_count(dev),
+    rc = getattr(getattr(_lib, libname)(), name)(*ptrs, *shape, int(reverse), *(() if matrix else (_cu_count(dev),)),
                                                  *[_lib.ptr(t) for t in outs], *checked, _lib.stream_ptr())
     _lib.check(rc, name)
     if checked:
@@ -838,7 +870,8 @@ class LstmRecurrence(torch.autograd.Function):
     the call cannot be differentiated.  "wide": the entries of include/taiyaki_amd_rnn_wide.h; "large": those of
     include/taiyaki_amd_lstm_large.h (size 512); "local": those of include/taiyaki_amd_lstm_local.h (size 96).  These
     three take `lens` or None and `save` either way (not `save`: NULL for the activations, which are neither allocated
-    nor written), and admit every batch width."""
+    nor written), and admit every batch width.  "matrix": the entry of include/taiyaki_amd_lstm_matrix.h (size 96, wide
+    batches), `lens` or None, never `save`: y alone is allocated and written."""
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, row, wsb, lens, save):
@@ -851,12 +884,14 @@ class LstmRecurrence(torch.autograd.Function):
         w_hh = w_hh.contiguous()
         if row in _RNN_CALLS:
             _RNN_CALLS[row]["saved" if save else "inference"] += 1
+        elif row == "matrix":
+            lstm_matrix_calls["inference"] += 1
         gx = _rnn_proj(x.view(T * N, -1), w_ih, b_ih + b_hh, False)
         y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
         gates = torch.empty(T, N, 4 * H, dtype=torch.float32, device=dev) if save else None
         cell = torch.empty(T, N, H, dtype=torch.float32, device=dev) if save else None
         _rnn_launch("lstm", row, lens, save, False, (gx, w_hh), (T, N, H), reverse,
-                    (y,) if row is True and not save else (y, gates, cell), wsb, dev)
+                    (y,) if (row is True or row == "matrix") and not save else (y, gates, cell), wsb, dev)
         if save:
             ctx.save_for_backward(x, w_ih, w_hh, y, gates, cell, lens)
         ctx.reverse, ctx.wsb, ctx.row = reverse, wsb, row
@@ -1534,7 +1569,8 @@ def _varlen_batched(plan, x, lens):
         h = _zero_beyond(h, lens_dev)
     for layer, rnn_layer, rev in plan:
         if rnn_layer is not None:
-            if not (hip_rnn_varlen_workspace_bytes(rnn_layer.rnn, h) or hip_lstm_large_workspace_bytes(rnn_layer.rnn, h)):
+            if not (hip_rnn_varlen_workspace_bytes(rnn_layer.rnn, h) or hip_lstm_large_workspace_bytes(rnn_layer.rnn, h)
+                    or hip_lstm_matrix_takes(rnn_layer.rnn, h, _needs_grad(h, rnn_layer))):
                 return None
             h = rnn_layer(h, reverse=rev, lengths=lens_dev)
             continue

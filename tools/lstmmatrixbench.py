@@ -1,0 +1,140 @@
+#!/usr/bin/env python
+"""Times the LSTM forward that saves nothing at hidden size 96 on the matrix cores (csrc/lstm_matrix.hip, 16 columns per
+workgroup) against the recurrence one workgroup holds (csrc/lstm_local.hip with NULL for the activations, 2 columns per
+workgroup at these widths) on the same tensors.
+
+For every (T, N) of --shapes, with full lengths and with lengths spread evenly over T/4 ... T: tk_lstm_matrix_forward_dev
+and tk_lstm_local_forward_dev in turns in one process, each timed with device events after warm-up (median over --steps),
+--turns turns.  One JSON line per case: microseconds per call and turn, whether the matrix kernel was ahead in EVERY
+turn, and the largest difference of the two outputs.  Then one JSON line with the threshold the table sets: the smallest
+measured N from which the matrix kernel is ahead in every turn, there and at every larger N measured, at every T and
+with both kinds of lengths (null: there is none).
+
+--basecall: one whole `Basecaller.call` on a seeded mLstm_flipflop of size 96 at max_concurrent_chunks 4096, with
+layers.USE_HIP_LSTM_MATRIX off and on in turns (the threshold as shipped unless --min-columns), samples per second.
+
+    python tools/lstmmatrixbench.py [--shapes 200x512,...] [--steps 5] [--warmup 2] [--turns 3] [--basecall]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from taiyaki_amd import _lib, layers  # noqa: E402
+
+H = 96
+SHAPES = ",".join("%dx%d" % (T, N) for T in (200, 800) for N in (512, 1024, 2048, 4096, 8192))
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return float(np.median(times))
+
+
+def kernel_turns(T, N, spread, turns, steps, warmup, dev):
+    g = torch.Generator(device=dev).manual_seed(11)
+    w_hh = (torch.rand(4 * H, H, generator=g, device=dev) * 2 - 1).div_(H ** 0.5)
+    gx = torch.randn(T, N, 4 * H, generator=g, device=dev)
+    lens = None
+    if spread:
+        lens = torch.linspace(T // 4, T, N, device=dev).round().to(torch.int32)[torch.randperm(N, generator=g, device=dev)]
+        lens = lens.contiguous()
+    ys = {k: torch.full((T, N, H), float("nan"), device=dev) for k in ("matrix", "local")}
+    cus = layers._cu_count(dev)
+    M, L = _lib.lstm_matrix_lib(), _lib.lstm_local_lib()
+    p, stream = _lib.ptr, _lib.stream_ptr()
+    legs = {
+        "matrix": lambda: _lib.check(M.tk_lstm_matrix_forward_dev(p(gx), p(w_hh), p(lens), T, N, H, 0, p(ys["matrix"]),
+                                                                  stream), "tk_lstm_matrix_forward_dev"),
+        "local": lambda: _lib.check(L.tk_lstm_local_forward_dev(p(gx), p(w_hh), p(lens), T, N, H, 0, cus, p(ys["local"]),
+                                                                None, None, stream), "tk_lstm_local_forward_dev"),
+    }
+    out = {k: [] for k in legs}
+    for _ in range(turns):
+        for k, fn in legs.items():
+            out[k].append(round(1e3 * timed(fn, steps, warmup), 1))
+    diff = (ys["matrix"] - ys["local"]).abs().max().item()
+    return {"T": T, "N": N, "lengths": "spread" if spread else "full", "us_per_call": out,
+            "us_per_step_median": {k: round(float(np.median(v)) / T, 3) for k, v in out.items()},
+            "matrix_ahead_every_turn": all(m < loc for m, loc in zip(out["matrix"], out["local"])),
+            "max_abs_diff": diff}
+
+
+def basecall_turns(turns, min_columns, dev):
+    from taiyaki_amd import basecall, models, synth
+    rs = np.random.RandomState(9)
+    sigs = [(90 + 12 * rs.standard_normal(40000)).astype(np.float32) for _ in range(512)]
+    torch.manual_seed(17)
+    net = synth.excite_network(models.mLstm_flipflop(size=H)).to(dev).eval()
+    caller = basecall.Basecaller(net, fastq=True, max_concurrent_chunks=4096)
+    if min_columns:
+        layers.LSTM_MATRIX_MIN_COLUMNS = min_columns
+    nsamples = sum(len(s) for s in sigs)
+    out, calls, seqs = {"off": [], "on": []}, {}, {}
+    shipped = layers.USE_HIP_LSTM_MATRIX
+    try:
+        for turn in range(turns + 1):           # (the first turn is the warm-up at the timed shapes)
+            for side in out:
+                layers.USE_HIP_LSTM_MATRIX = side == "on"
+                before = layers.lstm_matrix_calls["inference"]
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = caller.call(sigs)         # (ends in its download)
+                dt = time.perf_counter() - t0
+                calls[side] = layers.lstm_matrix_calls["inference"] - before
+                seqs[side] = [r[0] for r in res]
+                if turn:
+                    out[side].append(round(nsamples / dt))
+    finally:
+        layers.USE_HIP_LSTM_MATRIX = shipped
+    same = sum(a == b for a, b in zip(seqs["off"], seqs["on"]))
+    return {"basecall": "mLstm_flipflop 96, 512 reads x 40000 samples, max_concurrent_chunks 4096",
+            "min_columns": layers.LSTM_MATRIX_MIN_COLUMNS, "samples_per_s": out, "matrix_launches_per_call": calls,
+            "reads_with_equal_calls": "%d / %d" % (same, len(sigs)), "bases": sum(len(s) for s in seqs["on"])}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default=SHAPES, help="T x N, comma separated")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--turns", type=int, default=3)
+    ap.add_argument("--basecall", action="store_true")
+    ap.add_argument("--min-columns", type=int, default=0)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("lstmmatrixbench needs a GPU (the recurrence has no CPU fallback)")
+    dev = torch.device("cuda:0")
+    if a.basecall:
+        print(json.dumps(basecall_turns(a.turns, a.min_columns, dev)), flush=True)
+        return
+    ahead = {}
+    for shape in a.shapes.split(","):
+        T, N = (int(v) for v in shape.split("x"))
+        for spread in (False, True):
+            row = kernel_turns(T, N, spread, a.turns, a.steps, a.warmup, dev)
+            ahead[N] = ahead.get(N, True) and row["matrix_ahead_every_turn"]
+            print(json.dumps(row), flush=True)
+    widths = sorted(ahead)
+    from_n = [n for i, n in enumerate(widths) if all(ahead[m] for m in widths[i:])]
+    print(json.dumps({"device": torch.cuda.get_device_name(dev), "cus": layers._cu_count(dev),
+                      "ahead_at_every_T_and_lengths": ahead, "threshold": from_n[0] if from_n else None}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
