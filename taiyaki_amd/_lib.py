@@ -62,6 +62,9 @@ CHUNKS_SEQLEN_LIBNAME = "libtaiyaki_amd_chunks_seqlen.so"       # csrc/chunk_seq
 LSTM_MATRIX_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_lstm_matrix.h")
 LSTM_MATRIX_LIBNAME = "libtaiyaki_amd_lstm_matrix.so"       # csrc/lstm_matrix.hip: the LSTM forward that saves nothing at size 96 on the matrix cores, header and library of its own
 LSTM_MATRIX_LAB_LIBNAME = "libtaiyaki_amd_lstm_matrix_lab.so"       # ... and its lab build (no hook)
+LSTM_MATRIX_GROUP_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_lstm_matrix_group.h")
+LSTM_MATRIX_GROUP_LIBNAME = "libtaiyaki_amd_lstm_matrix_group.so"       # csrc/lstm_matrix_group.hip: the LSTM forward that saves nothing at size 256 on the matrix cores, groups of 8 workgroups, header and library of its own
+LSTM_MATRIX_GROUP_LAB_LIBNAME = "libtaiyaki_amd_lstm_matrix_group_lab.so"       # ... and its lab build (no hook: TK_LAB_LSTM_MATRIX_GROUP_M in the environment sets the columns per group)
 OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_optim.h")
 OPTIM_LIBNAME = "libtaiyaki_amd_optim.so"       # csrc/optim.hip: the optimiser step (scale, maxima, clamp, norm cap, AdamW, zero fill), header and library of its own
 
@@ -236,6 +239,10 @@ LOGZ_VARLEN_SIGNATURES = {n: (r, a) for n, (r, a, _) in
 LSTM_MATRIX_SIGNATURES = {n: (r, a) for n, (r, a, _) in
                           parse_prototypes(_blank_comments(open(LSTM_MATRIX_HEADER).read())).items()}
 
+# the twenty-fifth: include/taiyaki_amd_lstm_matrix_group.h (libtaiyaki_amd_lstm_matrix_group.so); its lab build adds no hook
+LSTM_MATRIX_GROUP_SIGNATURES = {n: (r, a) for n, (r, a, _) in
+                                parse_prototypes(_blank_comments(open(LSTM_MATRIX_GROUP_HEADER).read())).items()}
+
 
 class SeqLabels(ctypes.Structure):
     """include/taiyaki_amd_flipflop.h: tk_seq_labels (what tk_flipflop_build_indices_dev takes, for the entry points
@@ -388,6 +395,14 @@ def lstm_matrix_lib():
     build of that library while the process runs on the lab build (`use_lab`), the release one otherwise.  No fallback:
     a missing library raises."""
     return _load(os.path.join(CSRC, LSTM_MATRIX_LAB_LIBNAME if is_lab() else LSTM_MATRIX_LIBNAME), LSTM_MATRIX_SIGNATURES)
+
+
+def lstm_matrix_group_lib():
+    """The LSTM forward that saves nothing at size 256 on the matrix cores (include/taiyaki_amd_lstm_matrix_group.h): the
+    lab build of that library while the process runs on the lab build (`use_lab`), the release one otherwise.  No
+    fallback: a missing library raises."""
+    return _load(os.path.join(CSRC, LSTM_MATRIX_GROUP_LAB_LIBNAME if is_lab() else LSTM_MATRIX_GROUP_LIBNAME),
+                 LSTM_MATRIX_GROUP_SIGNATURES)
 
 
 def align_lib():

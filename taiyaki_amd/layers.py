@@ -9,7 +9,7 @@ that feeds them.
   (BASELINE.json north_star) and only produce the (T, N, S) score tensor.
   ``Lstm`` and ``GruMod`` keep their nn.LSTM / nn.GRU parameters, but on the GPU their
   recurrences run as the persistent HIP kernels of csrc/lstm_kernels.hip
-  (`LstmRecurrence`; size 96: csrc/lstm_local.hip, wide batches that save nothing csrc/lstm_matrix.hip; size 512: the same kernels from
+  (`LstmRecurrence`; size 96: csrc/lstm_local.hip, wide batches that save nothing csrc/lstm_matrix.hip; size 256, wide batches that save nothing: csrc/lstm_matrix_group.hip; size 512: the same kernels from
   libtaiyaki_amd_lstm_large.so, include/taiyaki_amd_lstm_large.h, USE_HIP_LSTM_LARGE) and csrc/gru_kernels.hip (`GruRecurrence`):
   one Function per cell, on the launch of the first library that admits the call, in the order that `_rnn_route`
   states.  A narrow
@@ -613,7 +613,7 @@ class _Rnn(nn.Module):
         if route:
             # The LSTM has no launch without lengths that saves nothing, so its main row saves whatever the grad mode,
             # and its slabs of columns do as that row does; every other row saves only where something needs a gradient
-            # (the "matrix" row is chosen only where nothing does)
+            # (the "matrix" and "matrix_group" rows are chosen only where nothing does)
             save = (isinstance(self.rnn, nn.LSTM) and route[0] in (False, "wide")) or needs
             return _rnn_apply(self, x, reverse, *route, None, save)
         if reverse:
@@ -747,6 +747,34 @@ def hip_lstm_matrix_takes(rnn, x, save):
                 and _lib.lstm_matrix_lib().tk_lstm_matrix_supported(rnn.hidden_size))
 
 
+# True (also TK_HIP_LSTM_MATRIX_GROUP=1 / 0 in the environment): an Lstm call at size 256 that saves nothing, on a batch
+# of at least LSTM_MATRIX_GROUP_MIN_COLUMNS columns, runs on the matrix cores (include/taiyaki_amd_lstm_matrix_group.h:
+# groups of 8 workgroups, slabs inside the entry) instead of the saving forward of the main library and its slabs
+USE_HIP_LSTM_MATRIX_GROUP = os.environ.get("TK_HIP_LSTM_MATRIX_GROUP", "1") != "0"
+# The narrowest batch that takes it: the smallest measured width from which the kernel was ahead of the main library and
+# its slabs in every turn, there and at every wider batch measured (tools/lstmmatrixgroupbench.py,
+# profiles/r52_lstm_matrix_group.txt): it was ahead at every width measured, 512 ... 8192, so this is the floor.  Never
+# below 2 * 256 + 1: up to two slabs of the main library stay where they are
+LSTM_MATRIX_GROUP_MIN_COLUMNS = 513
+# calls of `Lstm` that went through include/taiyaki_amd_lstm_matrix_group.h (all "inference": the entry saves nothing)
+lstm_matrix_group_calls = {"inference": 0}
+
+
+def hip_lstm_matrix_group_workspace_bytes(rnn, x, save):
+    """Workspace of the entry of include/taiyaki_amd_lstm_matrix_group.h for this nn.LSTM and input, 0 where it does not
+    run: something is saved, the tensor is not on the GPU (tested here, in front of `_hip_lstm_takes`: the query needs
+    the device's CU count), it has no steps or fewer than LSTM_MATRIX_GROUP_MIN_COLUMNS columns, `_hip_lstm_takes`
+    refuses the layer, or the library does not support its size (`tk_lstm_matrix_group_supported`: 256).  With or without
+    lengths."""
+    if not (USE_HIP_LSTM_MATRIX_GROUP and not save and isinstance(rnn, nn.LSTM) and x.is_cuda and x.dim() == 3
+            and x.shape[0] and x.shape[1] and x.shape[1] >= LSTM_MATRIX_GROUP_MIN_COLUMNS and _hip_lstm_takes(rnn, x)):
+        return 0
+    L = _lib.lstm_matrix_group_lib()
+    if not L.tk_lstm_matrix_group_supported(rnn.hidden_size):
+        return 0
+    return L.tk_lstm_matrix_group_workspace_bytes(x.shape[1], rnn.hidden_size, _cu_count(x.device))
+
+
 def _hip_lstm_takes(rnn, x):
     if not (USE_HIP_LSTM and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
             and rnn.weight_hh_l0.is_cuda and rnn.weight_hh_l0.dtype == torch.float32):
@@ -792,7 +820,12 @@ _RNN_BARE_ROWS = frozenset({"local"})
 # The row of include/taiyaki_amd_lstm_matrix.h ("matrix"; `_rnn_launch` looks a row up here too).  It stands beside the
 # table above, whose rows tests/test_rnn_routes.py pins with those of _RNN_BARE_ROWS and _RNN_CALLS: forward only and
 # nothing saved, a bare entry that takes no CU count either, and a counter of its own (lstm_matrix_calls)
-_RNN_MATRIX_LAUNCHES = {("matrix", False): ("lstm_matrix_lib", "tk_%s_matrix_forward_dev", None, None)}
+# ... and the row of include/taiyaki_amd_lstm_matrix_group.h ("matrix_group": size 256): forward only and nothing saved
+# too, but not bare: the arguments of the wide forward less the two saved tensors, and a counter of its own
+# (lstm_matrix_group_calls)
+_RNN_MATRIX_LAUNCHES = {("matrix", False): ("lstm_matrix_lib", "tk_%s_matrix_forward_dev", None, None),
+                        ("matrix_group", False): ("lstm_matrix_group_lib", "tk_%s_matrix_group_forward_dev", None,
+                                                  "lstm_matrix_group")}
 # The counter a call on a row moves, by "saved" / "inference"; the main row has none (the GRU: gru_forward_calls)
 _RNN_CALLS = {True: rnn_varlen_calls, "wide": rnn_wide_calls, "local": lstm_local_calls, "large": lstm_large_calls}
 
@@ -801,6 +834,9 @@ def _rnn_route(layer, x, lengths_given, save):
     """Which launch runs the recurrence of `layer` (an `Lstm` or a `GruMod`) on x: (row of _RNN_LAUNCHES, workspace
     bytes) of the first candidate that admits the call, None where none does (nn.LSTM / nn.GRU; with lengths every
     column alone).  The order, for both cells, with and without lengths:
+      0. the LSTM alone: size 256 on the matrix cores ("matrix_group", `hip_lstm_matrix_group_workspace_bytes`), which
+         reads `save`: only a call that saves nothing, on a GPU tensor of LSTM_MATRIX_GROUP_MIN_COLUMNS columns or more.
+         In front of the main library, whose rows admit every width at that size;
       1. the main library (`hip_lstm_workspace_bytes` / `hip_gru_workspace_bytes`, row False); with lengths the library
          with lengths in its place (row True): the training pair where `save`, the inference launch otherwise, neither
          asked on a tensor without steps or columns;
@@ -818,7 +854,8 @@ def _rnn_route(layer, x, lengths_given, save):
         first = (False, hip_lstm_workspace_bytes if lstm else hip_gru_workspace_bytes, True)
     else:
         first = (True, hip_rnn_varlen_train_workspace_bytes if save else hip_rnn_varlen_workspace_bytes, full)
-    for row, query, asked in (first, ("wide", hip_rnn_wide_workspace_bytes, full),
+    for row, query, asked in (("matrix_group", lambda r, v: hip_lstm_matrix_group_workspace_bytes(r, v, save), lstm),
+                              first, ("wide", hip_rnn_wide_workspace_bytes, full),
                               ("matrix", lambda r, v: hip_lstm_matrix_takes(r, v, save), lstm),
                               ("local", hip_lstm_local_takes, lstm), ("large", hip_lstm_large_workspace_bytes, lstm)):
         wsb = asked and query(rnn, x)
@@ -839,10 +876,11 @@ def _rnn_apply(layer, x, reverse, row, wsb, lens, save):
 def _rnn_launch(cell, row, lens, save, backward, ins, shape, reverse, outs, wsb, dev):
     """One launch of a recurrence, checked: the entry of _RNN_LAUNCHES[row, save] on `ins` (the lengths behind them where
     the entry takes them), T, N, H, the direction and the CU count, `outs`, then the workspace, its size and the status
-    word (all three or, on a row of _RNN_BARE_ROWS, none) and the stream.  The "matrix" row (_RNN_MATRIX_LAUNCHES) is bare
-    and takes no CU count."""
-    matrix = (row, bool(save)) in _RNN_MATRIX_LAUNCHES
-    libname, fwd, bwd, tag = (_RNN_MATRIX_LAUNCHES if matrix else _RNN_LAUNCHES)[row, bool(save)]
+    word (all three or, on a row of _RNN_BARE_ROWS, none) and the stream.  Of the rows of _RNN_MATRIX_LAUNCHES "matrix" is
+    bare and takes no CU count; "matrix_group" takes all of them."""
+    aside = (row, bool(save)) in _RNN_MATRIX_LAUNCHES
+    matrix = row == "matrix"
+    libname, fwd, bwd, tag = (_RNN_MATRIX_LAUNCHES if aside else _RNN_LAUNCHES)[row, bool(save)]
     name = (bwd if backward else fwd) % cell
     checked = ()
     if row not in _RNN_BARE_ROWS and not matrix:
@@ -871,7 +909,8 @@ class LstmRecurrence(torch.autograd.Function):
     include/taiyaki_amd_lstm_large.h (size 512); "local": those of include/taiyaki_amd_lstm_local.h (size 96).  These
     three take `lens` or None and `save` either way (not `save`: NULL for the activations, which are neither allocated
     nor written), and admit every batch width.  "matrix": the entry of include/taiyaki_amd_lstm_matrix.h (size 96, wide
-    batches), `lens` or None, never `save`: y alone is allocated and written."""
+    batches), `lens` or None, never `save`: y alone is allocated and written; "matrix_group": the entry of
+    include/taiyaki_amd_lstm_matrix_group.h (size 256, wide batches), likewise."""
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, row, wsb, lens, save):
@@ -886,12 +925,14 @@ class LstmRecurrence(torch.autograd.Function):
             _RNN_CALLS[row]["saved" if save else "inference"] += 1
         elif row == "matrix":
             lstm_matrix_calls["inference"] += 1
+        elif row == "matrix_group":
+            lstm_matrix_group_calls["inference"] += 1
         gx = _rnn_proj(x.view(T * N, -1), w_ih, b_ih + b_hh, False)
         y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
         gates = torch.empty(T, N, 4 * H, dtype=torch.float32, device=dev) if save else None
         cell = torch.empty(T, N, H, dtype=torch.float32, device=dev) if save else None
         _rnn_launch("lstm", row, lens, save, False, (gx, w_hh), (T, N, H), reverse,
-                    (y,) if (row is True or row == "matrix") and not save else (y, gates, cell), wsb, dev)
+                    (y,) if (row is True or row in ("matrix", "matrix_group")) and not save else (y, gates, cell), wsb, dev)
         if save:
             ctx.save_for_backward(x, w_ih, w_hh, y, gates, cell, lens)
         ctx.reverse, ctx.wsb, ctx.row = reverse, wsb, row
@@ -1570,7 +1611,8 @@ def _varlen_batched(plan, x, lens):
     for layer, rnn_layer, rev in plan:
         if rnn_layer is not None:
             if not (hip_rnn_varlen_workspace_bytes(rnn_layer.rnn, h) or hip_lstm_large_workspace_bytes(rnn_layer.rnn, h)
-                    or hip_lstm_matrix_takes(rnn_layer.rnn, h, _needs_grad(h, rnn_layer))):
+                    or hip_lstm_matrix_takes(rnn_layer.rnn, h, _needs_grad(h, rnn_layer))
+                    or hip_lstm_matrix_group_workspace_bytes(rnn_layer.rnn, h, _needs_grad(h, rnn_layer))):
                 return None
             h = rnn_layer(h, reverse=rev, lengths=lens_dev)
             continue
