@@ -775,6 +775,29 @@ def hip_lstm_matrix_group_workspace_bytes(rnn, x, save):
     return L.tk_lstm_matrix_group_workspace_bytes(x.shape[1], rnn.hidden_size, _cu_count(x.device))
 
 
+# True (also TK_HIP_GRU_MATRIX=1 / 0 in the environment): a GruMod call at size 96 that saves nothing, on a batch of at
+# least GRU_MATRIX_MIN_COLUMNS columns, runs on the matrix cores (include/taiyaki_amd_gru_matrix.h: 16 columns per
+# workgroup) instead of the kernels of the main library (2 columns per workgroup at such a width)
+USE_HIP_GRU_MATRIX = os.environ.get("TK_HIP_GRU_MATRIX", "1") != "0"
+# The narrowest batch that takes it: the smallest measured width from which the matrix kernel was ahead of the main
+# library's in every turn, there and at every wider batch measured (tools/grumatrixbench.py, profiles/r53_gru_matrix.txt).
+# It was behind at 512 and 1024 columns and ahead from 2048 on.  Never below 2 * 256 + 1: up to two columns per CU the main
+# library's kernel runs one round of workgroups
+GRU_MATRIX_MIN_COLUMNS = 2048
+# calls of `GruMod` that went through include/taiyaki_amd_gru_matrix.h (all of them "inference": the entry saves nothing)
+gru_matrix_calls = {"inference": 0}
+
+
+def hip_gru_matrix_takes(rnn, x, save):
+    """True where the entry of include/taiyaki_amd_gru_matrix.h runs this nn.GRU on this input: nothing is saved,
+    `_hip_gru_takes` admits the layer and the tensor (a GPU tensor: asked in front of the library, so a CPU tensor never
+    loads it), the batch has at least GRU_MATRIX_MIN_COLUMNS columns and at least one step, and the library supports the
+    size (`tk_gru_matrix_supported`: 96).  With or without lengths; no workspace to ask for."""
+    return bool(USE_HIP_GRU_MATRIX and not save and isinstance(rnn, nn.GRU) and _hip_gru_takes(rnn, x)
+                and x.shape[0] and x.shape[1] and x.shape[1] >= GRU_MATRIX_MIN_COLUMNS
+                and _lib.gru_matrix_lib().tk_gru_matrix_supported(rnn.hidden_size))
+
+
 def _hip_lstm_takes(rnn, x):
     if not (USE_HIP_LSTM and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
             and rnn.weight_hh_l0.is_cuda and rnn.weight_hh_l0.dtype == torch.float32):
@@ -817,13 +840,18 @@ _RNN_LAUNCHES = {
 # The rows whose entries take neither workspace, workspace size nor status word (csrc/lstm_local.hip: one workgroup owns
 # every unit of its columns)
 _RNN_BARE_ROWS = frozenset({"local"})
+# ... and the rows of _RNN_MATRIX_LAUNCHES that are bare as well and take no CU count either
+_RNN_MATRIX_BARE_ROWS = frozenset({"matrix", "gru_matrix"})
 # The row of include/taiyaki_amd_lstm_matrix.h ("matrix"; `_rnn_launch` looks a row up here too).  It stands beside the
 # table above, whose rows tests/test_rnn_routes.py pins with those of _RNN_BARE_ROWS and _RNN_CALLS: forward only and
 # nothing saved, a bare entry that takes no CU count either, and a counter of its own (lstm_matrix_calls)
 # ... and the row of include/taiyaki_amd_lstm_matrix_group.h ("matrix_group": size 256): forward only and nothing saved
 # too, but not bare: the arguments of the wide forward less the two saved tensors, and a counter of its own
 # (lstm_matrix_group_calls)
+# ... and the row of include/taiyaki_amd_gru_matrix.h ("gru_matrix": the GRU at size 96): as "matrix", bare and without a
+# CU count, b_hh among its inputs, and a counter of its own (gru_matrix_calls)
 _RNN_MATRIX_LAUNCHES = {("matrix", False): ("lstm_matrix_lib", "tk_%s_matrix_forward_dev", None, None),
+                        ("gru_matrix", False): ("gru_matrix_lib", "tk_%s_matrix_forward_dev", None, None),
                         ("matrix_group", False): ("lstm_matrix_group_lib", "tk_%s_matrix_group_forward_dev", None,
                                                   "lstm_matrix_group")}
 # The counter a call on a row moves, by "saved" / "inference"; the main row has none (the GRU: gru_forward_calls)
@@ -837,6 +865,9 @@ def _rnn_route(layer, x, lengths_given, save):
       0. the LSTM alone: size 256 on the matrix cores ("matrix_group", `hip_lstm_matrix_group_workspace_bytes`), which
          reads `save`: only a call that saves nothing, on a GPU tensor of LSTM_MATRIX_GROUP_MIN_COLUMNS columns or more.
          In front of the main library, whose rows admit every width at that size;
+         the GRU alone: size 96 on the matrix cores ("gru_matrix", `hip_gru_matrix_takes`), which reads `save` too: only
+         a call that saves nothing, on a GPU tensor of GRU_MATRIX_MIN_COLUMNS columns or more; no workspace (0 bytes).
+         In front of the main library and the library with lengths, which both admit every width at that size;
       1. the main library (`hip_lstm_workspace_bytes` / `hip_gru_workspace_bytes`, row False); with lengths the library
          with lengths in its place (row True): the training pair where `save`, the inference launch otherwise, neither
          asked on a tensor without steps or columns;
@@ -855,12 +886,13 @@ def _rnn_route(layer, x, lengths_given, save):
     else:
         first = (True, hip_rnn_varlen_train_workspace_bytes if save else hip_rnn_varlen_workspace_bytes, full)
     for row, query, asked in (("matrix_group", lambda r, v: hip_lstm_matrix_group_workspace_bytes(r, v, save), lstm),
+                              ("gru_matrix", lambda r, v: hip_gru_matrix_takes(r, v, save), not lstm),
                               first, ("wide", hip_rnn_wide_workspace_bytes, full),
                               ("matrix", lambda r, v: hip_lstm_matrix_takes(r, v, save), lstm),
                               ("local", hip_lstm_local_takes, lstm), ("large", hip_lstm_large_workspace_bytes, lstm)):
         wsb = asked and query(rnn, x)
         if wsb:
-            return row, 0 if row in _RNN_BARE_ROWS or row == "matrix" else wsb
+            return row, 0 if row in _RNN_BARE_ROWS or row in _RNN_MATRIX_BARE_ROWS else wsb
     return None
 
 
@@ -876,10 +908,10 @@ def _rnn_apply(layer, x, reverse, row, wsb, lens, save):
 def _rnn_launch(cell, row, lens, save, backward, ins, shape, reverse, outs, wsb, dev):
     """One launch of a recurrence, checked: the entry of _RNN_LAUNCHES[row, save] on `ins` (the lengths behind them where
     the entry takes them), T, N, H, the direction and the CU count, `outs`, then the workspace, its size and the status
-    word (all three or, on a row of _RNN_BARE_ROWS, none) and the stream.  Of the rows of _RNN_MATRIX_LAUNCHES "matrix" is
-    bare and takes no CU count; "matrix_group" takes all of them."""
+    word (all three or, on a row of _RNN_BARE_ROWS, none) and the stream.  Of the rows of _RNN_MATRIX_LAUNCHES "matrix" and
+    "gru_matrix" are bare and take no CU count; "matrix_group" takes all of them."""
     aside = (row, bool(save)) in _RNN_MATRIX_LAUNCHES
-    matrix = row == "matrix"
+    matrix = row in _RNN_MATRIX_BARE_ROWS
     libname, fwd, bwd, tag = (_RNN_MATRIX_LAUNCHES if aside else _RNN_LAUNCHES)[row, bool(save)]
     name = (bwd if backward else fwd) % cell
     checked = ()
@@ -1057,7 +1089,11 @@ class GruRecurrence(torch.autograd.Function):
     `lens` (a device int32 tensor, one entry per column): column n has lens[n] steps, and the launches are those of
     include/taiyaki_amd_rnn_varlen_train.h (`save`) or include/taiyaki_amd_rnn_varlen.h (not `save`).  y, the
     activations, q, dG and dq are 0 at and beyond every length, so the input and parameter gradients are the same sums
-    over the whole padded tensors.  `row` and `wsb` are what `_rnn_route` chose, as for `LstmRecurrence`."""
+    over the whole padded tensors.  `row` and `wsb` are what `_rnn_route` chose, as for `LstmRecurrence`.
+    "gru_matrix": the entry of include/taiyaki_amd_gru_matrix.h (size 96, wide batches), `lens` or None, never `save`: y
+    alone is handed over.  Such a call moves gru_matrix_calls, and gru_forward_calls["inference"] as well where it has
+    no lengths: that counter goes on counting the forward launches without lengths by kind, whichever library runs
+    them, as it does for the "wide" row; gru_matrix_calls tells which of them took the matrix cores."""
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, row, wsb, lens, save):
@@ -1070,6 +1106,8 @@ class GruRecurrence(torch.autograd.Function):
         train = bool(save)
         if row in _RNN_CALLS:
             _RNN_CALLS[row]["saved" if train else "inference"] += 1
+        elif row == "gru_matrix":
+            gru_matrix_calls["inference"] += 1
         if lens is None or train:
             gru_forward_calls["saved" if train else "inference"] += 1
         gx = _rnn_proj(x.view(T * N, -1), w_ih, b_ih, False)
@@ -1077,7 +1115,7 @@ class GruRecurrence(torch.autograd.Function):
         gates = torch.empty(T, N, 3 * H, dtype=torch.float32, device=dev) if train else None
         q = torch.empty(T, N, H, dtype=torch.float32, device=dev) if train else None
         _rnn_launch("gru", row, lens, train, False, (gx, w_hh, b_hh), (T, N, H), reverse,
-                    (y,) if row is True and not train else (y, gates, q), wsb, dev)
+                    (y,) if (row is True or row == "gru_matrix") and not train else (y, gates, q), wsb, dev)
         if train:
             ctx.save_for_backward(x, w_ih, w_hh, y, gates, q, lens)
         ctx.reverse, ctx.wsb, ctx.row = reverse, wsb, row
@@ -1613,6 +1651,7 @@ def _varlen_batched(plan, x, lens):
             if not (hip_rnn_varlen_workspace_bytes(rnn_layer.rnn, h) or hip_lstm_large_workspace_bytes(rnn_layer.rnn, h)
                     or hip_lstm_matrix_takes(rnn_layer.rnn, h, _needs_grad(h, rnn_layer))
                     or hip_lstm_matrix_group_workspace_bytes(rnn_layer.rnn, h, _needs_grad(h, rnn_layer))):
+                # (a GRU at 96 on the matrix cores is admitted by the first query, which takes every width at that size)
                 return None
             h = rnn_layer(h, reverse=rev, lengths=lens_dev)
             continue
