@@ -68,6 +68,9 @@ LSTM_MATRIX_GROUP_LAB_LIBNAME = "libtaiyaki_amd_lstm_matrix_group_lab.so"       
 GRU_MATRIX_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_gru_matrix.h")
 GRU_MATRIX_LIBNAME = "libtaiyaki_amd_gru_matrix.so"       # csrc/gru_matrix.hip: the GRU forward that saves nothing at size 96 on the matrix cores, header and library of its own
 GRU_MATRIX_LAB_LIBNAME = "libtaiyaki_amd_gru_matrix_lab.so"       # ... and its lab build (no hook: TK_LAB_GRU_MATRIX_UT in the environment sets the unit tiles per wave)
+GRU_MATRIX_GROUP_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_gru_matrix_group.h")
+GRU_MATRIX_GROUP_LIBNAME = "libtaiyaki_amd_gru_matrix_group.so"       # csrc/gru_matrix_group.hip: the GRU forward that saves nothing at size 256 on the matrix cores, groups of 4 workgroups, header and library of its own
+GRU_MATRIX_GROUP_LAB_LIBNAME = "libtaiyaki_amd_gru_matrix_group_lab.so"       # ... and its lab build (no hook)
 OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_optim.h")
 OPTIM_LIBNAME = "libtaiyaki_amd_optim.so"       # csrc/optim.hip: the optimiser step (scale, maxima, clamp, norm cap, AdamW, zero fill), header and library of its own
 
@@ -250,6 +253,10 @@ LSTM_MATRIX_GROUP_SIGNATURES = {n: (r, a) for n, (r, a, _) in
 GRU_MATRIX_SIGNATURES = {n: (r, a) for n, (r, a, _) in
                          parse_prototypes(_blank_comments(open(GRU_MATRIX_HEADER).read())).items()}
 
+# the twenty-seventh: include/taiyaki_amd_gru_matrix_group.h (libtaiyaki_amd_gru_matrix_group.so); its lab build adds no hook
+GRU_MATRIX_GROUP_SIGNATURES = {n: (r, a) for n, (r, a, _) in
+                               parse_prototypes(_blank_comments(open(GRU_MATRIX_GROUP_HEADER).read())).items()}
+
 
 class SeqLabels(ctypes.Structure):
     """include/taiyaki_amd_flipflop.h: tk_seq_labels (what tk_flipflop_build_indices_dev takes, for the entry points
@@ -417,6 +424,14 @@ def gru_matrix_lib():
     build of that library while the process runs on the lab build (`use_lab`), the release one otherwise.  No fallback:
     a missing library raises."""
     return _load(os.path.join(CSRC, GRU_MATRIX_LAB_LIBNAME if is_lab() else GRU_MATRIX_LIBNAME), GRU_MATRIX_SIGNATURES)
+
+
+def gru_matrix_group_lib():
+    """The GRU forward that saves nothing at size 256 on the matrix cores (include/taiyaki_amd_gru_matrix_group.h): the
+    lab build of that library while the process runs on the lab build (`use_lab`), the release one otherwise.  No
+    fallback: a missing library raises."""
+    return _load(os.path.join(CSRC, GRU_MATRIX_GROUP_LAB_LIBNAME if is_lab() else GRU_MATRIX_GROUP_LIBNAME),
+                 GRU_MATRIX_GROUP_SIGNATURES)
 
 
 def align_lib():

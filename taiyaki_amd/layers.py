@@ -10,7 +10,7 @@ that feeds them.
   ``Lstm`` and ``GruMod`` keep their nn.LSTM / nn.GRU parameters, but on the GPU their
   recurrences run as the persistent HIP kernels of csrc/lstm_kernels.hip
   (`LstmRecurrence`; size 96: csrc/lstm_local.hip, wide batches that save nothing csrc/lstm_matrix.hip; size 256, wide batches that save nothing: csrc/lstm_matrix_group.hip; size 512: the same kernels from
-  libtaiyaki_amd_lstm_large.so, include/taiyaki_amd_lstm_large.h, USE_HIP_LSTM_LARGE) and csrc/gru_kernels.hip (`GruRecurrence`):
+  libtaiyaki_amd_lstm_large.so, include/taiyaki_amd_lstm_large.h, USE_HIP_LSTM_LARGE) and csrc/gru_kernels.hip (`GruRecurrence`; wide batches that save nothing at size 96: csrc/gru_matrix.hip, at size 256: csrc/gru_matrix_group.hip):
   one Function per cell, on the launch of the first library that admits the call, in the order that `_rnn_route`
   states.  A narrow
   ``Convolution`` with swish runs as the fused HIP kernels of csrc/conv_kernels.hip
@@ -798,6 +798,36 @@ def hip_gru_matrix_takes(rnn, x, save):
                 and _lib.gru_matrix_lib().tk_gru_matrix_supported(rnn.hidden_size))
 
 
+# True (also TK_HIP_GRU_MATRIX_GROUP=1 / 0 in the environment): a GruMod call at size 256 that saves nothing, on a batch
+# of at least GRU_MATRIX_GROUP_MIN_COLUMNS columns, runs on the matrix cores (include/taiyaki_amd_gru_matrix_group.h:
+# groups of 4 workgroups, slabs inside the entry) instead of the kernels of the main library and their slabs
+USE_HIP_GRU_MATRIX_GROUP = os.environ.get("TK_HIP_GRU_MATRIX_GROUP", "1") != "0"
+# The narrowest batch that takes it: the smallest measured width from which the kernel was ahead of the main library and
+# its slabs in every turn, there and at every wider batch measured (tools/grumatrixgroupbench.py,
+# profiles/r54_gru_matrix_group.txt): it was ahead at every width measured, 512 ... 8192 (one GruMod(256, 256) call with its
+# projection at T 800: 5.6, 9.3, 18.7, 39.4 and 78 us per step against 6.4, 12.6, 24.9, 51.5 and 103; a whole
+# Basecaller.call of mGru_flipflop 256: 35.8 M samples/s against 27.7 M at 2048 chunks, 34.5 M against 26.8 M at 4096), so
+# this is the floor.  Never below 2 * 256 + 1: up to two slabs of the main library stay where they are
+GRU_MATRIX_GROUP_MIN_COLUMNS = 513
+# calls of `GruMod` that went through include/taiyaki_amd_gru_matrix_group.h (all "inference": the entry saves nothing)
+gru_matrix_group_calls = {"inference": 0}
+
+
+def hip_gru_matrix_group_workspace_bytes(rnn, x, save):
+    """Workspace of the entry of include/taiyaki_amd_gru_matrix_group.h for this nn.GRU and input, 0 where it does not
+    run: something is saved, the tensor is not on the GPU (tested here, in front of `_hip_gru_takes`: the query needs
+    the device's CU count), it has no steps or fewer than GRU_MATRIX_GROUP_MIN_COLUMNS columns, `_hip_gru_takes` refuses
+    the layer, or the library does not support its size (`tk_gru_matrix_group_supported`: 256).  With or without
+    lengths."""
+    if not (USE_HIP_GRU_MATRIX_GROUP and not save and isinstance(rnn, nn.GRU) and x.is_cuda and x.dim() == 3
+            and x.shape[0] and x.shape[1] and x.shape[1] >= GRU_MATRIX_GROUP_MIN_COLUMNS and _hip_gru_takes(rnn, x)):
+        return 0
+    L = _lib.gru_matrix_group_lib()
+    if not L.tk_gru_matrix_group_supported(rnn.hidden_size):
+        return 0
+    return L.tk_gru_matrix_group_workspace_bytes(x.shape[1], rnn.hidden_size, _cu_count(x.device))
+
+
 def _hip_lstm_takes(rnn, x):
     if not (USE_HIP_LSTM and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
             and rnn.weight_hh_l0.is_cuda and rnn.weight_hh_l0.dtype == torch.float32):
@@ -850,10 +880,14 @@ _RNN_MATRIX_BARE_ROWS = frozenset({"matrix", "gru_matrix"})
 # (lstm_matrix_group_calls)
 # ... and the row of include/taiyaki_amd_gru_matrix.h ("gru_matrix": the GRU at size 96): as "matrix", bare and without a
 # CU count, b_hh among its inputs, and a counter of its own (gru_matrix_calls)
+# ... and the row of include/taiyaki_amd_gru_matrix_group.h ("gru_matrix_group": the GRU at size 256): as "matrix_group",
+# not bare, b_hh among its inputs, and a counter of its own (gru_matrix_group_calls)
 _RNN_MATRIX_LAUNCHES = {("matrix", False): ("lstm_matrix_lib", "tk_%s_matrix_forward_dev", None, None),
                         ("gru_matrix", False): ("gru_matrix_lib", "tk_%s_matrix_forward_dev", None, None),
                         ("matrix_group", False): ("lstm_matrix_group_lib", "tk_%s_matrix_group_forward_dev", None,
-                                                  "lstm_matrix_group")}
+                                                  "lstm_matrix_group"),
+                        ("gru_matrix_group", False): ("gru_matrix_group_lib", "tk_%s_matrix_group_forward_dev", None,
+                                                      "gru_matrix_group")}
 # The counter a call on a row moves, by "saved" / "inference"; the main row has none (the GRU: gru_forward_calls)
 _RNN_CALLS = {True: rnn_varlen_calls, "wide": rnn_wide_calls, "local": lstm_local_calls, "large": lstm_large_calls}
 
@@ -868,6 +902,8 @@ def _rnn_route(layer, x, lengths_given, save):
          the GRU alone: size 96 on the matrix cores ("gru_matrix", `hip_gru_matrix_takes`), which reads `save` too: only
          a call that saves nothing, on a GPU tensor of GRU_MATRIX_MIN_COLUMNS columns or more; no workspace (0 bytes).
          In front of the main library and the library with lengths, which both admit every width at that size;
+         the GRU alone: size 256 on the matrix cores ("gru_matrix_group", `hip_gru_matrix_group_workspace_bytes`),
+         likewise: a call that saves nothing, on a GPU tensor of GRU_MATRIX_GROUP_MIN_COLUMNS columns or more;
       1. the main library (`hip_lstm_workspace_bytes` / `hip_gru_workspace_bytes`, row False); with lengths the library
          with lengths in its place (row True): the training pair where `save`, the inference launch otherwise, neither
          asked on a tensor without steps or columns;
@@ -887,6 +923,8 @@ def _rnn_route(layer, x, lengths_given, save):
         first = (True, hip_rnn_varlen_train_workspace_bytes if save else hip_rnn_varlen_workspace_bytes, full)
     for row, query, asked in (("matrix_group", lambda r, v: hip_lstm_matrix_group_workspace_bytes(r, v, save), lstm),
                               ("gru_matrix", lambda r, v: hip_gru_matrix_takes(r, v, save), not lstm),
+                              ("gru_matrix_group", lambda r, v: hip_gru_matrix_group_workspace_bytes(r, v, save),
+                               not lstm),
                               first, ("wide", hip_rnn_wide_workspace_bytes, full),
                               ("matrix", lambda r, v: hip_lstm_matrix_takes(r, v, save), lstm),
                               ("local", hip_lstm_local_takes, lstm), ("large", hip_lstm_large_workspace_bytes, lstm)):
@@ -909,7 +947,7 @@ def _rnn_launch(cell, row, lens, save, backward, ins, shape, reverse, outs, wsb,
     """One launch of a recurrence, checked: the entry of _RNN_LAUNCHES[row, save] on `ins` (the lengths behind them where
     the entry takes them), T, N, H, the direction and the CU count, `outs`, then the workspace, its size and the status
     word (all three or, on a row of _RNN_BARE_ROWS, none) and the stream.  Of the rows of _RNN_MATRIX_LAUNCHES "matrix" and
-    "gru_matrix" are bare and take no CU count; "matrix_group" takes all of them."""
+    "gru_matrix" are bare and take no CU count; "matrix_group" and "gru_matrix_group" take all of them."""
     aside = (row, bool(save)) in _RNN_MATRIX_LAUNCHES
     matrix = row in _RNN_MATRIX_BARE_ROWS
     libname, fwd, bwd, tag = (_RNN_MATRIX_LAUNCHES if aside else _RNN_LAUNCHES)[row, bool(save)]
@@ -1093,7 +1131,9 @@ class GruRecurrence(torch.autograd.Function):
     "gru_matrix": the entry of include/taiyaki_amd_gru_matrix.h (size 96, wide batches), `lens` or None, never `save`: y
     alone is handed over.  Such a call moves gru_matrix_calls, and gru_forward_calls["inference"] as well where it has
     no lengths: that counter goes on counting the forward launches without lengths by kind, whichever library runs
-    them, as it does for the "wide" row; gru_matrix_calls tells which of them took the matrix cores."""
+    them, as it does for the "wide" row; gru_matrix_calls tells which of them took the matrix cores.
+    "gru_matrix_group": the entry of include/taiyaki_amd_gru_matrix_group.h (size 256, wide batches), likewise, with
+    gru_matrix_group_calls."""
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, row, wsb, lens, save):
@@ -1108,6 +1148,8 @@ class GruRecurrence(torch.autograd.Function):
             _RNN_CALLS[row]["saved" if train else "inference"] += 1
         elif row == "gru_matrix":
             gru_matrix_calls["inference"] += 1
+        elif row == "gru_matrix_group":
+            gru_matrix_group_calls["inference"] += 1
         if lens is None or train:
             gru_forward_calls["saved" if train else "inference"] += 1
         gx = _rnn_proj(x.view(T * N, -1), w_ih, b_ih, False)
@@ -1115,7 +1157,7 @@ class GruRecurrence(torch.autograd.Function):
         gates = torch.empty(T, N, 3 * H, dtype=torch.float32, device=dev) if train else None
         q = torch.empty(T, N, H, dtype=torch.float32, device=dev) if train else None
         _rnn_launch("gru", row, lens, train, False, (gx, w_hh, b_hh), (T, N, H), reverse,
-                    (y,) if (row is True or row == "gru_matrix") and not train else (y, gates, q), wsb, dev)
+                    (y,) if (row is True or row in ("gru_matrix", "gru_matrix_group")) and not train else (y, gates, q), wsb, dev)
         if train:
             ctx.save_for_backward(x, w_ih, w_hh, y, gates, q, lens)
         ctx.reverse, ctx.wsb, ctx.row = reverse, wsb, row
@@ -1651,7 +1693,8 @@ def _varlen_batched(plan, x, lens):
             if not (hip_rnn_varlen_workspace_bytes(rnn_layer.rnn, h) or hip_lstm_large_workspace_bytes(rnn_layer.rnn, h)
                     or hip_lstm_matrix_takes(rnn_layer.rnn, h, _needs_grad(h, rnn_layer))
                     or hip_lstm_matrix_group_workspace_bytes(rnn_layer.rnn, h, _needs_grad(h, rnn_layer))):
-                # (a GRU at 96 on the matrix cores is admitted by the first query, which takes every width at that size)
+                # (a GRU at 96 or 256 on the matrix cores is admitted by the first query, which takes every width at those
+                # sizes)
                 return None
             h = rnn_layer(h, reverse=rev, lengths=lens_dev)
             continue
