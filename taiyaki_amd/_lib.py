@@ -71,6 +71,9 @@ GRU_MATRIX_LAB_LIBNAME = "libtaiyaki_amd_gru_matrix_lab.so"       # ... and its 
 GRU_MATRIX_GROUP_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_gru_matrix_group.h")
 GRU_MATRIX_GROUP_LIBNAME = "libtaiyaki_amd_gru_matrix_group.so"       # csrc/gru_matrix_group.hip: the GRU forward that saves nothing at size 256 on the matrix cores, groups of 4 workgroups, header and library of its own
 GRU_MATRIX_GROUP_LAB_LIBNAME = "libtaiyaki_amd_gru_matrix_group_lab.so"       # ... and its lab build (no hook)
+LSTM_MATRIX_SIZES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_lstm_matrix_sizes.h")
+LSTM_MATRIX_SIZES_LIBNAME = "libtaiyaki_amd_lstm_matrix_sizes.so"       # csrc/lstm_matrix_sizes.hip: the LSTM forward that saves nothing at sizes 384 and 192 on the matrix cores, groups of size / 32 workgroups, header and library of its own
+LSTM_MATRIX_SIZES_LAB_LIBNAME = "libtaiyaki_amd_lstm_matrix_sizes_lab.so"       # ... and its lab build (no hook: TK_LAB_LSTM_MATRIX_SIZES_M in the environment sets the column sets per group)
 OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "taiyaki_amd_optim.h")
 OPTIM_LIBNAME = "libtaiyaki_amd_optim.so"       # csrc/optim.hip: the optimiser step (scale, maxima, clamp, norm cap, AdamW, zero fill), header and library of its own
 
@@ -257,6 +260,10 @@ GRU_MATRIX_SIGNATURES = {n: (r, a) for n, (r, a, _) in
 GRU_MATRIX_GROUP_SIGNATURES = {n: (r, a) for n, (r, a, _) in
                                parse_prototypes(_blank_comments(open(GRU_MATRIX_GROUP_HEADER).read())).items()}
 
+# the twenty-eighth: include/taiyaki_amd_lstm_matrix_sizes.h (libtaiyaki_amd_lstm_matrix_sizes.so); its lab build adds no hook
+LSTM_MATRIX_SIZES_SIGNATURES = {n: (r, a) for n, (r, a, _) in
+                                parse_prototypes(_blank_comments(open(LSTM_MATRIX_SIZES_HEADER).read())).items()}
+
 
 class SeqLabels(ctypes.Structure):
     """include/taiyaki_amd_flipflop.h: tk_seq_labels (what tk_flipflop_build_indices_dev takes, for the entry points
@@ -432,6 +439,14 @@ def gru_matrix_group_lib():
     fallback: a missing library raises."""
     return _load(os.path.join(CSRC, GRU_MATRIX_GROUP_LAB_LIBNAME if is_lab() else GRU_MATRIX_GROUP_LIBNAME),
                  GRU_MATRIX_GROUP_SIGNATURES)
+
+
+def lstm_matrix_sizes_lib():
+    """The LSTM forward that saves nothing at sizes 384 and 192 on the matrix cores
+    (include/taiyaki_amd_lstm_matrix_sizes.h): the lab build of that library while the process runs on the lab build
+    (`use_lab`), the release one otherwise.  No fallback: a missing library raises."""
+    return _load(os.path.join(CSRC, LSTM_MATRIX_SIZES_LAB_LIBNAME if is_lab() else LSTM_MATRIX_SIZES_LIBNAME),
+                 LSTM_MATRIX_SIZES_SIGNATURES)
 
 
 def align_lib():

@@ -9,7 +9,7 @@ that feeds them.
   (BASELINE.json north_star) and only produce the (T, N, S) score tensor.
   ``Lstm`` and ``GruMod`` keep their nn.LSTM / nn.GRU parameters, but on the GPU their
   recurrences run as the persistent HIP kernels of csrc/lstm_kernels.hip
-  (`LstmRecurrence`; size 96: csrc/lstm_local.hip, wide batches that save nothing csrc/lstm_matrix.hip; size 256, wide batches that save nothing: csrc/lstm_matrix_group.hip; size 512: the same kernels from
+  (`LstmRecurrence`; size 96: csrc/lstm_local.hip, wide batches that save nothing csrc/lstm_matrix.hip; size 256, wide batches that save nothing: csrc/lstm_matrix_group.hip; sizes 384 and 192, likewise: csrc/lstm_matrix_sizes.hip; size 512: the same kernels from
   libtaiyaki_amd_lstm_large.so, include/taiyaki_amd_lstm_large.h, USE_HIP_LSTM_LARGE) and csrc/gru_kernels.hip (`GruRecurrence`; wide batches that save nothing at size 96: csrc/gru_matrix.hip, at size 256: csrc/gru_matrix_group.hip):
   one Function per cell, on the launch of the first library that admits the call, in the order that `_rnn_route`
   states.  A narrow
@@ -613,7 +613,7 @@ class _Rnn(nn.Module):
         if route:
             # The LSTM has no launch without lengths that saves nothing, so its main row saves whatever the grad mode,
             # and its slabs of columns do as that row does; every other row saves only where something needs a gradient
-            # (the "matrix" and "matrix_group" rows are chosen only where nothing does)
+            # (the "matrix", "matrix_group" and "matrix_sizes" rows are chosen only where nothing does)
             save = (isinstance(self.rnn, nn.LSTM) and route[0] in (False, "wide")) or needs
             return _rnn_apply(self, x, reverse, *route, None, save)
         if reverse:
@@ -775,6 +775,39 @@ def hip_lstm_matrix_group_workspace_bytes(rnn, x, save):
     return L.tk_lstm_matrix_group_workspace_bytes(x.shape[1], rnn.hidden_size, _cu_count(x.device))
 
 
+# True (also TK_HIP_LSTM_MATRIX_SIZES=1 / 0 in the environment): an Lstm call at size 384 or 192 that saves nothing, on a
+# batch of at least LSTM_MATRIX_SIZES_MIN_COLUMNS[size] columns, runs on the matrix cores
+# (include/taiyaki_amd_lstm_matrix_sizes.h: groups of size / 32 workgroups, slabs inside the entry) instead of the saving
+# forward of the main library and its slabs
+USE_HIP_LSTM_MATRIX_SIZES = os.environ.get("TK_HIP_LSTM_MATRIX_SIZES", "1") != "0"
+# The narrowest batch that takes it, by size; None: the size is built and tested but never taken.  The rule of
+# LSTM_MATRIX_GROUP_MIN_COLUMNS: the smallest measured width from which the kernel was ahead of the main library and its
+# slabs in every turn, there and at every wider batch measured (tools/lstmmatrixsizesbench.py,
+# profiles/r55_lstm_matrix_sizes.txt), and never below two slabs of the main library plus one: 2 * 128 + 1 at 384,
+# 2 * 512 + 1 at 192.  Both are that floor: at 384 the kernel was ahead at every width measured, 256 ... 8192, at 192
+# (two column sets per group) from 1024 on and behind at 256 and 512
+LSTM_MATRIX_SIZES_MIN_COLUMNS = {192: 1025, 384: 257}
+# calls of `Lstm` that went through include/taiyaki_amd_lstm_matrix_sizes.h (all "inference": the entry saves nothing)
+lstm_matrix_sizes_calls = {"inference": 0}
+
+
+def hip_lstm_matrix_sizes_workspace_bytes(rnn, x, save):
+    """Workspace of the entry of include/taiyaki_amd_lstm_matrix_sizes.h for this nn.LSTM and input, 0 where it does not
+    run: something is saved, the tensor is not on the GPU (tested here, in front of `_hip_lstm_takes`: the query needs
+    the device's CU count), its size has no threshold (LSTM_MATRIX_SIZES_MIN_COLUMNS: not a size of the library, or
+    None), it has no steps or fewer columns than the threshold, `_hip_lstm_takes` refuses the layer, or the library does
+    not support its size (`tk_lstm_matrix_sizes_supported`: 192, 384).  With or without lengths."""
+    if not (USE_HIP_LSTM_MATRIX_SIZES and not save and isinstance(rnn, nn.LSTM) and x.is_cuda and x.dim() == 3):
+        return 0
+    least = LSTM_MATRIX_SIZES_MIN_COLUMNS.get(rnn.hidden_size)
+    if not (least is not None and x.shape[0] and x.shape[1] and x.shape[1] >= least and _hip_lstm_takes(rnn, x)):
+        return 0
+    L = _lib.lstm_matrix_sizes_lib()
+    if not L.tk_lstm_matrix_sizes_supported(rnn.hidden_size):
+        return 0
+    return L.tk_lstm_matrix_sizes_workspace_bytes(x.shape[1], rnn.hidden_size, _cu_count(x.device))
+
+
 # True (also TK_HIP_GRU_MATRIX=1 / 0 in the environment): a GruMod call at size 96 that saves nothing, on a batch of at
 # least GRU_MATRIX_MIN_COLUMNS columns, runs on the matrix cores (include/taiyaki_amd_gru_matrix.h: 16 columns per
 # workgroup) instead of the kernels of the main library (2 columns per workgroup at such a width)
@@ -878,6 +911,8 @@ _RNN_MATRIX_BARE_ROWS = frozenset({"matrix", "gru_matrix"})
 # ... and the row of include/taiyaki_amd_lstm_matrix_group.h ("matrix_group": size 256): forward only and nothing saved
 # too, but not bare: the arguments of the wide forward less the two saved tensors, and a counter of its own
 # (lstm_matrix_group_calls)
+# ... and the row of include/taiyaki_amd_lstm_matrix_sizes.h ("matrix_sizes": sizes 384 and 192): as "matrix_group", with
+# a counter of its own (lstm_matrix_sizes_calls)
 # ... and the row of include/taiyaki_amd_gru_matrix.h ("gru_matrix": the GRU at size 96): as "matrix", bare and without a
 # CU count, b_hh among its inputs, and a counter of its own (gru_matrix_calls)
 # ... and the row of include/taiyaki_amd_gru_matrix_group.h ("gru_matrix_group": the GRU at size 256): as "matrix_group",
@@ -886,6 +921,8 @@ _RNN_MATRIX_LAUNCHES = {("matrix", False): ("lstm_matrix_lib", "tk_%s_matrix_for
                         ("gru_matrix", False): ("gru_matrix_lib", "tk_%s_matrix_forward_dev", None, None),
                         ("matrix_group", False): ("lstm_matrix_group_lib", "tk_%s_matrix_group_forward_dev", None,
                                                   "lstm_matrix_group"),
+                        ("matrix_sizes", False): ("lstm_matrix_sizes_lib", "tk_%s_matrix_sizes_forward_dev", None,
+                                                  "lstm_matrix_sizes"),
                         ("gru_matrix_group", False): ("gru_matrix_group_lib", "tk_%s_matrix_group_forward_dev", None,
                                                       "gru_matrix_group")}
 # The counter a call on a row moves, by "saved" / "inference"; the main row has none (the GRU: gru_forward_calls)
@@ -899,6 +936,9 @@ def _rnn_route(layer, x, lengths_given, save):
       0. the LSTM alone: size 256 on the matrix cores ("matrix_group", `hip_lstm_matrix_group_workspace_bytes`), which
          reads `save`: only a call that saves nothing, on a GPU tensor of LSTM_MATRIX_GROUP_MIN_COLUMNS columns or more.
          In front of the main library, whose rows admit every width at that size;
+         the LSTM alone: sizes 384 and 192 on the matrix cores ("matrix_sizes", `hip_lstm_matrix_sizes_workspace_bytes`),
+         likewise: a call that saves nothing, on a GPU tensor of LSTM_MATRIX_SIZES_MIN_COLUMNS[size] columns or more
+         (None: never);
          the GRU alone: size 96 on the matrix cores ("gru_matrix", `hip_gru_matrix_takes`), which reads `save` too: only
          a call that saves nothing, on a GPU tensor of GRU_MATRIX_MIN_COLUMNS columns or more; no workspace (0 bytes).
          In front of the main library and the library with lengths, which both admit every width at that size;
@@ -922,6 +962,7 @@ def _rnn_route(layer, x, lengths_given, save):
     else:
         first = (True, hip_rnn_varlen_train_workspace_bytes if save else hip_rnn_varlen_workspace_bytes, full)
     for row, query, asked in (("matrix_group", lambda r, v: hip_lstm_matrix_group_workspace_bytes(r, v, save), lstm),
+                              ("matrix_sizes", lambda r, v: hip_lstm_matrix_sizes_workspace_bytes(r, v, save), lstm),
                               ("gru_matrix", lambda r, v: hip_gru_matrix_takes(r, v, save), not lstm),
                               ("gru_matrix_group", lambda r, v: hip_gru_matrix_group_workspace_bytes(r, v, save),
                                not lstm),
@@ -947,7 +988,7 @@ def _rnn_launch(cell, row, lens, save, backward, ins, shape, reverse, outs, wsb,
     """One launch of a recurrence, checked: the entry of _RNN_LAUNCHES[row, save] on `ins` (the lengths behind them where
     the entry takes them), T, N, H, the direction and the CU count, `outs`, then the workspace, its size and the status
     word (all three or, on a row of _RNN_BARE_ROWS, none) and the stream.  Of the rows of _RNN_MATRIX_LAUNCHES "matrix" and
-    "gru_matrix" are bare and take no CU count; "matrix_group" and "gru_matrix_group" take all of them."""
+    "gru_matrix" are bare and take no CU count; "matrix_group", "matrix_sizes" and "gru_matrix_group" take all of them."""
     aside = (row, bool(save)) in _RNN_MATRIX_LAUNCHES
     matrix = row in _RNN_MATRIX_BARE_ROWS
     libname, fwd, bwd, tag = (_RNN_MATRIX_LAUNCHES if aside else _RNN_LAUNCHES)[row, bool(save)]
@@ -980,7 +1021,8 @@ class LstmRecurrence(torch.autograd.Function):
     three take `lens` or None and `save` either way (not `save`: NULL for the activations, which are neither allocated
     nor written), and admit every batch width.  "matrix": the entry of include/taiyaki_amd_lstm_matrix.h (size 96, wide
     batches), `lens` or None, never `save`: y alone is allocated and written; "matrix_group": the entry of
-    include/taiyaki_amd_lstm_matrix_group.h (size 256, wide batches), likewise."""
+    include/taiyaki_amd_lstm_matrix_group.h (size 256, wide batches), likewise; "matrix_sizes": the entry of
+    include/taiyaki_amd_lstm_matrix_sizes.h (sizes 384 and 192, wide batches), likewise."""
 
     @staticmethod
     def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, reverse, row, wsb, lens, save):
@@ -997,12 +1039,14 @@ class LstmRecurrence(torch.autograd.Function):
             lstm_matrix_calls["inference"] += 1
         elif row == "matrix_group":
             lstm_matrix_group_calls["inference"] += 1
+        elif row == "matrix_sizes":
+            lstm_matrix_sizes_calls["inference"] += 1
         gx = _rnn_proj(x.view(T * N, -1), w_ih, b_ih + b_hh, False)
         y = torch.empty(T, N, H, dtype=torch.float32, device=dev)
         gates = torch.empty(T, N, 4 * H, dtype=torch.float32, device=dev) if save else None
         cell = torch.empty(T, N, H, dtype=torch.float32, device=dev) if save else None
         _rnn_launch("lstm", row, lens, save, False, (gx, w_hh), (T, N, H), reverse,
-                    (y,) if (row is True or row in ("matrix", "matrix_group")) and not save else (y, gates, cell), wsb, dev)
+                    (y,) if (row is True or row in ("matrix", "matrix_group", "matrix_sizes")) and not save else (y, gates, cell), wsb, dev)
         if save:
             ctx.save_for_backward(x, w_ih, w_hh, y, gates, cell, lens)
         ctx.reverse, ctx.wsb, ctx.row = reverse, wsb, row
@@ -1692,7 +1736,8 @@ def _varlen_batched(plan, x, lens):
         if rnn_layer is not None:
             if not (hip_rnn_varlen_workspace_bytes(rnn_layer.rnn, h) or hip_lstm_large_workspace_bytes(rnn_layer.rnn, h)
                     or hip_lstm_matrix_takes(rnn_layer.rnn, h, _needs_grad(h, rnn_layer))
-                    or hip_lstm_matrix_group_workspace_bytes(rnn_layer.rnn, h, _needs_grad(h, rnn_layer))):
+                    or hip_lstm_matrix_group_workspace_bytes(rnn_layer.rnn, h, _needs_grad(h, rnn_layer))
+                    or hip_lstm_matrix_sizes_workspace_bytes(rnn_layer.rnn, h, _needs_grad(h, rnn_layer))):
                 # (a GRU at 96 or 256 on the matrix cores is admitted by the first query, which takes every width at those
                 # sizes)
                 return None
